@@ -10,13 +10,19 @@ N>1: one rank per GPU under torch.distributed.run — either the driver launches
 The (trial, image) pairs of the step are sharded over the ranks, one RCCL all-gather of the error slab per step
 (dist.py).  Default: the global batch grows with N (per-GPU work fixed -> "scaling": "weak"); `--global-batch B`
 fixes the total instead ("strong": what north_star quotes for CheXpert-256 1->8 GPUs).
-Prints ONE JSON line (rank 0).  `roofline` = the dominant kernel family (MFMA implicit GEMM)
-timed with HIP events on the launch stream inside the last timed step; `cpu_baseline` = the
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes `--dump-outputs` if asked and prints
+the line: `value` / `ms_per_step` and the workload's `config`, nothing else.
+`--dump-outputs DIR` (rank 0, after the timed region): what the last timed `classify` call computed — `labels.npy` (float64 [B])
+and `errors.npy` (float32 [B, classes, trials], +inf where a pruning stage skipped a cell) — for output-for-output comparison of two
+builds; the same arguments give the same inputs (seeded weights, batch and draws).
+`--full` adds everything else the benchmark measures or checks (all after the headline's timed region unless noted):
+`roofline` / `kernels` = per kernel family HIP-event timings (the last timed step carries an event pair around every op, as
+`--breakdown` does), with the dominant family (MFMA implicit GEMM) against the dense peak; `cpu_baseline` = the
 oracle's reference-structured loop on the host cores (N=1 only, bounded sample); `parity` = a small sub-grid of
-the same workload scored by the HIP path and by the CPU oracle (N=1 only, outside the timed region).
+the same workload scored by the HIP path and by the CPU oracle (N=1 only); the Haar DWT micro-measurement (`kernels.haar_dwt2`).
 The batch x sits in PINNED host memory and is copied to HBM inside every timed step (SURVEY §8d counts the H2D of x in the metric:
 196 KB per cfg2 step, 3 MB per CheXpert step — enqueued on the launch stream in front of the step's first kernel).
-`other_workloads` (default flags only, after the headline's timed region): a few timed steps each of BASELINE configs 3, 5 and 4
+`other_workloads` (`--full` with default flags, or `--other-workloads`): a few timed steps each of BASELINE configs 3, 5 and 4
 (CheXpert-DWT UNet, DiT-B/4 f16, IPMSA-5 UNet) with value / ms_per_step / dominant-kernel roofline fraction, so that the driver's
 record covers them; at N > 1 the CheXpert-DWT UNet runs there under STRONG scaling (fixed global batch: what north_star quotes).
 `--simulate-rank r/N` (one GPU, no process group): run exactly rank r's share of an N-rank grid-sharded step of `--global-batch B`
@@ -76,6 +82,28 @@ def relaunch_under_torchrun(n, argv):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, dc, labels, n_img, classes, trials):
+    """--dump-outputs: what the last timed `classify` call computed, as its caller receives it with `return_errors=True`:
+    labels.npy (float64 [B], class ids) and errors.npy (float32 [B, classes, trials]).  Read after the timed region: the errors
+    from the call's most recently used score plan, whose buffer holds the last stage's (gathered) errors.  A batch whose arrays
+    would pass 64 MB is cut to a seeded sample of images, listed in image_index.npy."""
+    import numpy as np
+    sp = next(reversed(dc._score_plans.values()))
+    err = sp["score"]["errors"][:-1].view(n_img, classes, trials).cpu().numpy()
+    lab = labels.cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    per_img = err[0].nbytes + lab.itemsize
+    if n_img * per_img > DUMP_BYTES_MAX:
+        keep = np.sort(np.random.default_rng(0).permutation(n_img)[:DUMP_BYTES_MAX // (per_img + 8)])
+        err, lab = err[keep], lab[keep]
+        np.save(os.path.join(out_dir, "image_index.npy"), keep.astype(np.float64))
+    np.save(os.path.join(out_dir, "labels.npy"), lab)
+    np.save(os.path.join(out_dir, "errors.npy"), err)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -96,9 +124,14 @@ def main():
     ap.add_argument("--simulate-rank", default=None, metavar="r/N",
                     help="one GPU, no process group: run rank r's share of an N-rank grid-sharded step (use with --global-batch); a projection")
     ap.add_argument("--other-workloads", dest="other_workloads", action="store_true", default=None,
-                    help="after the headline: a few timed steps of BASELINE configs 3 / 5 / 4 (default: on with default flags)")
+                    help="after the headline: a few timed steps of BASELINE configs 3 / 5 / 4 (default: on with --full and default flags)")
     ap.add_argument("--no-other-workloads", dest="other_workloads", action="store_false")
     ap.add_argument("--no-haar", action="store_true", help="skip the Haar DWT micro-measurement (2 x 201 MB of HBM, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel / roofline figures, the other BASELINE configs, parity against the CPU oracle, the CPU "
+                         "baseline and the Haar DWT micro-measurement (the --no-* flags above deselect parts of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/labels.npy and DIR/errors.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -165,10 +198,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(dc_, xs_, steps, warmup, tag=""):
+    def timed(dc_, xs_, steps, warmup, tag="", per_op=True):
         """W untimed steps, then exactly K steps between barrier + synchronize fences; MAX over ranks.  Every step starts with the
-        H2D copy of its batch (pinned host memory -> the resident device buffer, on the launch stream).  The last timed step
-        carries a HIP-event pair around every op (on the launch stream)."""
+        H2D copy of its batch (pinned host memory -> the resident device buffer, on the launch stream).  With `per_op` the last
+        timed step carries a HIP-event pair around every op (on the launch stream).  Returns (seconds, per-op sink or None,
+        labels of the last timed step)."""
         x_, xh_ = xs_
         torch.manual_seed(1234)
         for i in range(warmup):
@@ -179,17 +213,17 @@ def main():
         fence()
         t0 = time.perf_counter()
         for i in range(steps):
-            if i == steps - 1:
+            if per_op and i == steps - 1:
                 dc_._timed_sink = []           # HIP-event pair around every op of this step, on the launch stream
             x_.copy_(xh_, non_blocking=True)   # the H2D of x is part of the step
-            dc_.classify(x_, rng="philox", seed=1234 + warmup + i)
+            lab_ = dc_.classify(x_, rng="philox", seed=1234 + warmup + i)
         fence()
         dt_ = time.perf_counter() - t0
         sink_, dc_._timed_sink = dc_._timed_sink, None
         tt = torch.tensor([dt_], dtype=torch.float64, device="cpu" if rehearse else dev)
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        return tt.item(), sink_
+        return tt.item(), sink_, lab_
 
     def families(sink_):
         fam_ = {}
@@ -211,7 +245,10 @@ def main():
     x = xs[0]
     kw, cfg, size, cin, dwt = info["kw"], info["cfg"], info["size"], info["cin"], info["dwt"]
     T = info["T"]
-    dt, sink = timed(dc, xs, args.steps, args.warmup)
+    dt, sink, labels = timed(dc, xs, args.steps, args.warmup, per_op=args.full or bool(args.breakdown))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dc, labels, B, classes, T)
+    del labels
     bd_first = (sink[0][0].pb.meta, sink[0][1]) if (args.breakdown and sink) else None
 
     # ---- roofline of the dominant kernel family, from the event timings of the last timed step ----
@@ -222,9 +259,6 @@ def main():
         achieved = d["flops"] / (d["ms"] * 1e-3) / 1e12
         return dom_, d, peak, achieved
 
-    fam = families(sink)
-    del sink
-    dom, d, peak, achieved = roofline_of(fam, args.dtype, args.workload)
     # HBM traffic of that kernel from rocprofv3 PMC passes of this same command (FETCH_SIZE doubled for the
     # gfx950 half-count of wide streaming reads + WRITE_SIZE, per launch), recorded under profiles/
     tf = os.path.join(ROOT, "profiles", "pmc_traffic.json")
@@ -241,19 +275,24 @@ def main():
         rec_t = (allt.get("workloads", {}).get(key) or (allt if key == "cifar10-unet-10x50" else {})).get(kernel)
         return round((2.0 * rec_t["fetch_kb_per_launch"] + rec_t["write_kb_per_launch"]) * 1024.0) if rec_t else None
 
-    traffic = stored_traffic(args.workload, args.dtype, dom)
-    roofline = dict(bound="mfma", kernel=dom, achieved=round(achieved, 2), peak=peak, unit="TFLOP/s",
-                    frac=round(achieved / peak, 4), traffic=traffic, traffic_unit=TRAFFIC_UNIT,
-                    alg_bytes_per_launch=round(d["bytes"] / d["launches"]), launches=d["launches"],
-                    avg_launch_ms=round(d["ms"] / d["launches"], 5),
-                    alg_gflop_per_launch=round(d["flops"] / d["launches"] / 1e9, 4),
-                    note="peak = dense spec at 2.4 GHz (MI355X_MICROARCH.md); the clock this kernel actually holds is not sampled in this run — "
-                         "see profiles/README.md (in-kernel s_memtime / s_memrealtime stamps of a diagnostic build)")
-    total_ms = sum(v["ms"] for v in fam.values())
-    kernels = {k: dict(ms=round(v["ms"], 3), share=round(v["ms"] / total_ms, 4), launches=v["launches"],
-                       tflops=round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1) if v["flops"] else None,
-                       gbps=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)) for k, v in sorted(fam.items())}
-    if rank == 0 and world == 1 and not args.no_haar and (dwt or headline_cfg):
+    roofline = kernels = None
+    if sink:      # --full / --breakdown: the per-op event timings of the last timed step
+        fam = families(sink)
+        dom, d, peak, achieved = roofline_of(fam, args.dtype, args.workload)
+        traffic = stored_traffic(args.workload, args.dtype, dom)
+        roofline = dict(bound="mfma", kernel=dom, achieved=round(achieved, 2), peak=peak, unit="TFLOP/s",
+                        frac=round(achieved / peak, 4), traffic=traffic, traffic_unit=TRAFFIC_UNIT,
+                        alg_bytes_per_launch=round(d["bytes"] / d["launches"]), launches=d["launches"],
+                        avg_launch_ms=round(d["ms"] / d["launches"], 5),
+                        alg_gflop_per_launch=round(d["flops"] / d["launches"] / 1e9, 4),
+                        note="peak = dense MFMA spec of the MI355X at 2.4 GHz; the clock this kernel actually holds is not sampled in this run — "
+                             "see profiles/README.md (in-kernel s_memtime / s_memrealtime stamps of a diagnostic build)")
+        total_ms = sum(v["ms"] for v in fam.values())
+        kernels = {k: dict(ms=round(v["ms"], 3), share=round(v["ms"] / total_ms, 4), launches=v["launches"],
+                           tflops=round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 1) if v["flops"] else None,
+                           gbps=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)) for k, v in sorted(fam.items())}
+    del sink
+    if args.full and rank == 0 and world == 1 and not args.no_haar and (dwt or headline_cfg):
         # the Haar lifting kernel (utils/wavelet.py:4-35 replacement) on a CheXpert-shaped batch: HBM-bound, 8 bytes per input value
         # (rank 0 of single-GPU runs of the DWT workloads and of the headline only: 2 x 201 MB of HBM)
         hx = torch.rand(256, 3, 256, 256, device=dev) * 2 - 1
@@ -289,15 +328,16 @@ def main():
                            forwards_per_image=classes * T, share_trunk=not args.no_share_trunk,
                            stages=args.stages, input="haar_dwt2(x0)/2 (HIP kernel)" if dwt else "uniform [-1,1]",
                            h2d=f"x ({x.numel() * x.element_size()} bytes) copied from pinned host memory to HBM inside every timed step (in value)",
-                           parallelism=par_mode),
-               roofline=roofline, kernels=kernels)
+                           parallelism=par_mode))
+    if roofline is not None:
+        rec.update(roofline=roofline, kernels=kernels)
     if flop_fwd:
         rec["ref_equiv_tflops"] = round(value * classes * T * flop_fwd / 1e12, 1)     # reference-equivalent FLOPs
 
     # ---- the other BASELINE configurations, a few timed steps each (after the headline's timed region) ----
     default_flags = (headline_cfg and not args.stages and not sim and not args.no_share_trunk and args.units_per_launch is None
                      and not args.images_per_gpu and (world > 1 or not args.global_batch))
-    do_other = default_flags if args.other_workloads is None else args.other_workloads
+    do_other = (args.full and default_flags) if args.other_workloads is None else args.other_workloads
     if do_other and not sim:
         dc._score_plans.clear()
         torch.cuda.empty_cache()
@@ -313,7 +353,7 @@ def main():
             if rank == 0:
                 print(f"[bench] other workload {wl} ({dt_o}, {B_o} images per step) ...", file=sys.stderr, flush=True)
             dco, xo, io = build(wl, dt_o, B_o)
-            dto, sko = timed(dco, xo, st_o, wu_o, tag=wl + " ")
+            dto, sko, _ = timed(dco, xo, st_o, wu_o, tag=wl + " ")
             fo = families(sko)
             domo, do_, pko, aco = roofline_of(fo, dt_o, wl)
             val_o = B_o * st_o / dto
@@ -337,8 +377,8 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- CPU oracle legs (N=1 only, after the timed region): parity sub-grid, then the timed CPU baseline ----
-    if world == 1 and not (args.no_cpu_baseline and args.no_parity):
+    # ---- CPU oracle legs (--full, N=1 only, after the timed region): parity sub-grid, then the timed CPU baseline ----
+    if args.full and world == 1 and not (args.no_cpu_baseline and args.no_parity):
         import oracle
         cores = usable_cores()
         torch.set_num_threads(cores)
@@ -355,7 +395,7 @@ def main():
                 oc_.encoder.load_state_dict(dc.encoder.state_dict())
             return oc_
 
-    if world == 1 and not args.no_parity:
+    if args.full and world == 1 and not args.no_parity:
         # SURVEY §8d "parity gates reported with every number": the same weights and inputs, a sub-grid of the workload
         # (pb images x pt trials x ALL classes, draws injected), HIP f32 vs the fp32 oracle (bar 1e-4) and the HIP
         # compute dtype vs the oracle with the kernels' storage rounding / under torch autocast / in fp32.  Two quantities:
@@ -435,7 +475,7 @@ def main():
         del o32
 
     # ---- CPU baseline: the oracle's reference-structured loop on the host cores (N=1 only) ----
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         oc = make_oracle(False, T)
         print(f"[bench] cpu baseline on {cores} host threads ...", file=sys.stderr, flush=True)
         bs_c = 2 if size <= 32 else 1

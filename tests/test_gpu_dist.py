@@ -59,12 +59,12 @@ def test_bench_harness_with_three_ranks_rehearsed_on_one_gpu(tmp_path):
     """`python bench.py --gpus 3` exactly as typed by hand — the parent starts torch.distributed.run as a child, the ranks rendezvous on
     127.0.0.1, shard the grid, take the max time over ranks, rank 0 prints ONE JSON line — rehearsed with DCAMD_BENCH_REHEARSE=1 (ranks
     share cuda:0 and talk over gloo, since RCCL refuses two ranks on one device).  The line must carry the contract's fields and say
-    that it is a rehearsal."""
+    that it is a rehearsal; with --full it carries the per-kernel roofline too."""
     import json
     root = os.path.dirname(HERE)
     env = dict(os.environ, DCAMD_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--workload", "small-unet-2x8"],
-                       env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--workload", "small-unet-2x8",
+                        "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1000:]

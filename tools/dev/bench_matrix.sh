@@ -1,7 +1,7 @@
 #!/bin/bash
 # developer tool: run bench.py through its option matrix with short runs and report value / errors (catches paths the default run never takes)
 out=gpurun_out/${1:-matrix}; mkdir -p $out
-run() { name=$1; shift; python bench.py "$@" > $out/$name.json 2> $out/$name.err; rc=$?; v=$(python - <<PY
+run() { name=$1; shift; python bench.py --full "$@" > $out/$name.json 2> $out/$name.err; rc=$?; v=$(python - <<PY
 import json
 try:
     d=json.loads(open("$out/$name.json").read().strip().splitlines()[-1]); print(d["value"], d["ms_per_step"], (d.get("parity") or {}).get("f32_max_rel_eps_mse"))

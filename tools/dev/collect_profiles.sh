@@ -6,7 +6,7 @@ out=gpurun_out/${1:-prof}
 mkdir -p $out
 root=$(pwd)
 export TMPDIR=/tmp
-python3 bench.py --breakdown $out/breakdown.json > $out/bench.json 2> $out/bench.err || exit 1
+python3 bench.py --full --breakdown $out/breakdown.json > $out/bench.json 2> $out/bench.err || exit 1
 echo "bench done"; tail -c 400 $out/bench.json | head -c 200; echo
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof -- python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-other-workloads --no-haar > $root/$out/prof.log 2>&1 || exit 2

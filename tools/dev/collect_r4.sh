@@ -12,7 +12,7 @@ if has suite; then
   timeout -k 10 1000 python3 -m pytest tests -m gpu -q > $o/pytest.log 2>&1; echo "pytest rc=$?" | tee $o/pytest.rc; tail -3 $o/pytest.log
 fi
 if has bench; then
-  timeout -k 10 600 python3 bench.py --breakdown $o/breakdown.json > $o/bench.json 2> $o/bench.err || exit 1
+  timeout -k 10 600 python3 bench.py --full --breakdown $o/breakdown.json > $o/bench.json 2> $o/bench.err || exit 1
   echo "bench done"; tail -c 300 $o/bench.json; echo
 fi
 if has ab; then       # same session, same box: the producer-side GroupNorm on / off
