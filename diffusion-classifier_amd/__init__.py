@@ -68,6 +68,62 @@ def ipmsa5_unet_kwargs():
                 cross_attention_dim=512)
 
 
+# The reference's other UNet backbones: 768-channel levels (attention head dim 96 with 8 heads), GroupNorm groups of 24 / 40 / 48
+# channels, odd input / output channel counts.  image_channels / image_size come from experiment configs the reference does not
+# ship: the DWT form (4 x image_channels at image_size / 2) is restated here.
+def ipmsa5_dwt_unet_kwargs():
+    # models/ipmsa-5-dwt-unet.py:4-27
+    return dict(sample_size=128, in_channels=40, out_channels=40, layers_per_block=(2, 2, 2, 4, 2),
+                block_out_channels=(128, 128, 256, 512, 768),
+                down_block_types=("DownBlock2D", "DownBlock2D", "DownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+                up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "UpBlock2D", "UpBlock2D", "UpBlock2D"),
+                mid_block_type="UNetMidBlock2DCrossAttn", encoder_hid_dim=512, encoder_hid_dim_type="text_proj",
+                cross_attention_dim=512)
+
+
+def unet128_kwargs(image_channels=3, image_size=256, wavelet_transform=True):
+    # models/unet-128.py:4-27
+    ch, size = (4 * image_channels, image_size // 2) if wavelet_transform else (image_channels, image_size)
+    return dict(sample_size=size, in_channels=ch, out_channels=ch, layers_per_block=2,
+                block_out_channels=(128, 128, 256, 512, 1024),
+                down_block_types=("DownBlock2D", "DownBlock2D", "DownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+                up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "UpBlock2D", "UpBlock2D", "UpBlock2D"),
+                mid_block_type="UNetMidBlock2DCrossAttn", encoder_hid_dim=512, encoder_hid_dim_type="text_proj",
+                cross_attention_dim=512)
+
+
+def unet256_kwargs(image_channels=3, image_size=256, wavelet_transform=True):
+    # models/unet-256.py:4-29
+    ch, size = (4 * image_channels, image_size // 2) if wavelet_transform else (image_channels, image_size)
+    return dict(sample_size=size, in_channels=ch, out_channels=ch, layers_per_block=2,
+                block_out_channels=(128, 128, 256, 256, 512, 1024),
+                down_block_types=("DownBlock2D",) * 4 + ("CrossAttnDownBlock2D", "DownBlock2D"),
+                up_block_types=("UpBlock2D", "CrossAttnUpBlock2D") + ("UpBlock2D",) * 4,
+                mid_block_type="UNetMidBlock2DCrossAttn", encoder_hid_dim=512, encoder_hid_dim_type="text_proj",
+                cross_attention_dim=512)
+
+
+def chexpert_experiment_unet_kwargs(image_channels=1, image_size=256, wavelet_transform=True):
+    # experiments/chexpert-unet/inference.py:118-138
+    ch, size = (4 * image_channels, image_size // 2) if wavelet_transform else (image_channels, image_size)
+    return dict(sample_size=size, in_channels=ch, out_channels=ch, layers_per_block=2, block_out_channels=(256, 512, 768),
+                down_block_types=("DownBlock2D", "DownBlock2D", "CrossAttnDownBlock2D"),
+                up_block_types=("CrossAttnUpBlock2D", "UpBlock2D", "UpBlock2D"),
+                mid_block_type="UNetMidBlock2DCrossAttn", encoder_hid_dim=256, encoder_hid_dim_type="text_proj",
+                cross_attention_dim=256)
+
+
+def ipmsa_experiment_unet_kwargs(image_channels=10, image_size=256, wavelet_transform=True):
+    # experiments/ipmsa/inference.py:187-211
+    ch, size = (4 * image_channels, image_size // 2) if wavelet_transform else (image_channels, image_size)
+    return dict(sample_size=size, in_channels=ch, out_channels=ch, layers_per_block=(2, 2, 4, 4, 4),
+                block_out_channels=(128, 256, 256, 512, 768),
+                down_block_types=("DownBlock2D",) * 3 + ("CrossAttnDownBlock2D",) * 2,
+                up_block_types=("CrossAttnUpBlock2D",) * 2 + ("UpBlock2D",) * 3,
+                mid_block_type="UNetMidBlock2DCrossAttn", encoder_hid_dim=256, encoder_hid_dim_type="text_proj",
+                cross_attention_dim=256)
+
+
 def chexpert_dit_b4_kwargs(wavelet_transform=True):
     # models/chexpert-256-dit-b4.py:4-21 (image_size 256, 3 channels, patch 4)
     ch, size = (12, 128) if wavelet_transform else (3, 256)

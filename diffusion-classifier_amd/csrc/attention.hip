@@ -4,11 +4,12 @@
 // BasicTransformerBlock) reached through reference nets/unet.py:186.  (Cross-attention over
 // the single class token needs no kernel: softmax over one key is 1, see DESIGN.md.)
 //
-// UNet shapes are tiny (L<=256 tokens, d<=128; <0.5 % of the forward's FLOPs), so this kernel
+// UNet shapes are tiny (L<=1024 tokens, d<=128; <0.5 % of the forward's FLOPs), so this kernel
 // keeps everything on-chip and exact in fp32: K and V of one (sample, head) live in LDS as f32
 // (longer sequences — the fp32 parity path of the DiTs — stream them through LDS in blocks),
-// each query is owned by d/16 adjacent lanes holding a 16-wide slice of q and of the output,
-// scores are reduced across those lanes with xor-shuffles, softmax is online (running max / sum).
+// each query is owned by d/SW adjacent lanes holding an SW-wide slice of q and of the output (SW = 16; 24 for d = 96, so that
+// the lane count stays a power of two: 4 lanes, not 6), scores are reduced across those lanes with xor-shuffles, softmax is
+// online (running max / sum).
 #include <stdlib.h>
 #include "common.h"
 
@@ -18,11 +19,11 @@ struct AttnArgs {
   int KB;     // keys per LDS block: L when the whole sequence fits (the UNets), else 8192 / d (the fp32 parity path of the DiTs)
 };
 
-template <typename T>
+template <typename T, int SW>        // SW: slice width (16: d = 16/32/64/128; 24: d = 96)
 __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float kv[];  // K[L][d], V[L][d]
   const int t = threadIdx.x;
-  const int DS = a.d >> 4;            // lanes per query (1,2,4,8)
+  const int DS = a.d / SW;            // lanes per query (1,2,4,8): a power of two, the xor-shuffle ladder below needs one
   const int QT = 256 / DS;            // queries per workgroup
   const int qtiles = (a.L + QT - 1) / QT;
   int b = blockIdx.x;
@@ -31,13 +32,13 @@ __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs a) {
   float* Ks = kv; float* Vs = kv + a.KB * a.d;
   const T* kb = reinterpret_cast<const T*>(a.k) + (size_t)n * a.L * a.ld_qkv + h * a.d;
   const T* vb = reinterpret_cast<const T*>(a.v) + (size_t)n * a.L * a.ld_qkv + h * a.d;
-  const int sl = t % DS;                         // my 16-wide slice of d
+  const int sl = t % DS;                         // my SW-wide slice of d
   const int qi = qt * QT + t / DS;               // my query
   const bool live = qi < a.L;
-  float qv[16], o[16];
-  const T* qp = reinterpret_cast<const T*>(a.q) + ((size_t)n * a.L + (live ? qi : 0)) * a.ld_qkv + h * a.d + sl * 16;
+  float qv[SW], o[SW];
+  const T* qp = reinterpret_cast<const T*>(a.q) + ((size_t)n * a.L + (live ? qi : 0)) * a.ld_qkv + h * a.d + sl * SW;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) { qv[e] = Elem<T>::to_f(qp[e]) * a.scale; o[e] = 0.f; }
+  for (int e = 0; e < SW; ++e) { qv[e] = Elem<T>::to_f(qp[e]) * a.scale; o[e] = 0.f; }
   float m = -INFINITY, l = 0.f;
   // keys stream through LDS in blocks of KB (one block = the whole sequence for the UNets' token counts): the online softmax
   // does not care where a block ends, so long sequences (DiT-B/4: 1024 / 4096 tokens) take the same fp32-exact path
@@ -51,30 +52,30 @@ __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs a) {
     }
     __syncthreads();
     for (int j = 0; j < nk; ++j) {
-      const float* kj = Ks + j * a.d + sl * 16;
+      const float* kj = Ks + j * a.d + sl * SW;
       float s = 0.f;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) s += qv[e] * kj[e];
+      for (int e = 0; e < SW; ++e) s += qv[e] * kj[e];
       for (int off = 1; off < DS; off <<= 1) s += __shfl_xor(s, off, 64);
       const float mn = fmaxf(m, s);
       const float corr = expf(m - mn);
       const float p = expf(s - mn);
       l = l * corr + p;
-      const float* vj = Vs + j * a.d + sl * 16;
+      const float* vj = Vs + j * a.d + sl * SW;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) o[e] = o[e] * corr + p * vj[e];
+      for (int e = 0; e < SW; ++e) o[e] = o[e] * corr + p * vj[e];
       m = mn;
     }
   }
   if (live) {
     const float inv = 1.0f / l;
-    T* op = reinterpret_cast<T*>(a.out) + ((size_t)n * a.L + qi) * a.ld_out + h * a.d + sl * 16;
+    T* op = reinterpret_cast<T*>(a.out) + ((size_t)n * a.L + qi) * a.ld_out + h * a.d + sl * SW;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) op[e] = Elem<T>::from_f(o[e] * inv);
+    for (int e = 0; e < SW; ++e) op[e] = Elem<T>::from_f(o[e] * inv);
   }
 }
 
-// attention_mfma.hip: matrix-core kernel for 16-bit dtypes, L % 16 == 0, d % 32 == 0
+// attention_mfma.hip: matrix-core kernel for 16-bit dtypes, L % 16 == 0, d % 32 == 0 (d = 96 included)
 bool dc_attn_mfma_applicable(int dtype, int L, int d);
 int dc_attn_mfma_launch(const dc_attention_params* p, hipStream_t s);
 bool dc_attn_wave_applicable(const dc_attention_params* p);  // L <= 64: one wave per (sample, head) pair
@@ -84,13 +85,14 @@ int dc_attn_flash_launch(const dc_attention_params* p, hipStream_t s);
 
 extern "C" int dc_attention(const dc_attention_params* p, dc_stream stream) {
   DC_REQUIRE(p && p->q && p->k && p->v && p->out, DC_ERR_ARG, "dc_attention: null pointer");
-  DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 128, DC_ERR_SHAPE, "dc_attention: head dim %d (16/32/64/128)", p->d);
+  DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128, DC_ERR_SHAPE, "dc_attention: head dim %d (16/32/64/96/128)", p->d);
   DC_REQUIRE(p->n > 0 && p->L > 0 && p->heads > 0, DC_ERR_SHAPE, "dc_attention: n/L/heads");
   DC_REQUIRE(p->ld_qkv >= p->heads * p->d && p->ld_out >= p->heads * p->d, DC_ERR_SHAPE, "dc_attention: ld");
   // the matrix-core kernels keep the running max of the RAW scores and fold the scale into the exponent's FMA: valid for scale > 0 only
   DC_REQUIRE(p->scale > 0.f, DC_ERR_ARG, "dc_attention: scale must be positive (got %g)", (double)p->scale);
   // L <= 64: one wave per pair (attn_wave_kernel); up to 128: the whole-sequence matrix-core kernel; beyond: the flash kernel, which
   // also wins at 256 tokens (CheXpert 16x16 level, d = 64: 2.37 -> 0.71 ms per step; IPMSA: 13.2 -> 4.8 ms)
+  // (d = 96 — 768 channels, 8 heads — has no wave / flash instance: the whole-sequence kernel up to 128 tokens, else the fp32 kernel)
   constexpr int mfma_maxl = 128;
   if (dc_attn_wave_applicable(p)) return dc_attn_wave_launch(p, reinterpret_cast<hipStream_t>(stream));
   if (p->L <= mfma_maxl && dc_attn_mfma_applicable(p->dtype, p->L, p->d)) return dc_attn_mfma_launch(p, reinterpret_cast<hipStream_t>(stream));
@@ -102,25 +104,27 @@ extern "C" int dc_attention(const dc_attention_params* p, dc_stream stream) {
   const int KB = lds_all <= 160 * 1024 ? p->L : 8192 / p->d;
   const size_t lds = (size_t)2 * KB * p->d * sizeof(float);
   AttnArgs a{p->q, p->k, p->v, p->out, p->n, p->L, p->heads, p->d, p->ld_qkv, p->ld_out, p->scale, KB};
-  const int DS = p->d / 16, QT = 256 / DS, qtiles = (p->L + QT - 1) / QT;
+  const int SW = p->d == 96 ? 24 : 16, DS = p->d / SW, QT = 256 / DS, qtiles = (p->L + QT - 1) / QT;
   const long long nb = (long long)p->n * p->heads * qtiles;
   DC_REQUIRE(nb < (1LL << 31), DC_ERR_SHAPE, "dc_attention: grid too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)nb), blk(256);
-#define DC_ATTN_LAUNCH(T)                                                                                  \
+#define DC_ATTN_LAUNCH1(T, W)                                                                              \
   do {                                                                                                     \
     static bool done = false;                                                                              \
     if (!done) {                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_small_kernel<T>),                             \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_small_kernel<T, W>),                    \
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
       done = true;                                                                                         \
     }                                                                                                      \
-    hipLaunchKernelGGL((attn_small_kernel<T>), grid, blk, lds, s, a);                                      \
+    hipLaunchKernelGGL((attn_small_kernel<T, W>), grid, blk, lds, s, a);                                   \
   } while (0)
+#define DC_ATTN_LAUNCH(T) do { if (SW == 24) DC_ATTN_LAUNCH1(T, 24); else DC_ATTN_LAUNCH1(T, 16); } while (0)
   if (p->dtype == DC_F32) DC_ATTN_LAUNCH(float);
   else if (p->dtype == DC_BF16) DC_ATTN_LAUNCH(__bf16);
   else if (p->dtype == DC_F16) DC_ATTN_LAUNCH(_Float16);
   else { dc_set_error("dc_attention: dtype %d", p->dtype); return DC_ERR_DTYPE; }
 #undef DC_ATTN_LAUNCH
+#undef DC_ATTN_LAUNCH1
   return dc_check_launch("dc_attention");
 }

@@ -231,7 +231,8 @@ int64_t dc_workspace_bytes_layernorm(const dc_layernorm_params* p);
 /* ---------------------------------------------------------------- attention ------ */
 /* softmax(q k^T * scale) v per (sample, head).  q/k/v: [n, L, heads, d] with row stride
  * ld (elements) so a fused QKV GEMM output can be passed as three offset pointers.
- * scale must be > 0 (DC_ERR_ARG otherwise): the kernels take the running max on the raw scores. */
+ * scale must be > 0 (DC_ERR_ARG otherwise): the kernels take the running max on the raw scores.
+ * Head dims d = 16, 32, 64, 96, 128 (DC_ERR_SHAPE otherwise); 96 is the UNets' 768-channel level with 8 heads. */
 typedef struct {
   const void* q; const void* k; const void* v; void* out;
   int32_t dtype, n, L, heads, d, ld_qkv, ld_out; float scale;
