@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs a) {
   }
 }
 
-// attention_mfma.hip: matrix-core kernel for 16-bit dtypes, L % 16 == 0, d % 32 == 0 (d = 96 included)
+// attention_mfma.hip: matrix-core kernels for 16-bit dtypes (whole-sequence: L % 16 == 0, d % 32 == 0; flash: d = 32 / 64 / 96 / 128)
 bool dc_attn_mfma_applicable(int dtype, int L, int d);
 int dc_attn_mfma_launch(const dc_attention_params* p, hipStream_t s);
 bool dc_attn_wave_applicable(const dc_attention_params* p);  // L <= 64: one wave per (sample, head) pair
@@ -83,24 +83,50 @@ int dc_attn_wave_launch(const dc_attention_params* p, hipStream_t s);
 bool dc_attn_flash_applicable(const dc_attention_params* p);   // long sequences (DiT), online softmax
 int dc_attn_flash_launch(const dc_attention_params* p, hipStream_t s);
 
-extern "C" int dc_attention(const dc_attention_params* p, dc_stream stream) {
+static int attn_validate(const dc_attention_params* p) {
   DC_REQUIRE(p && p->q && p->k && p->v && p->out, DC_ERR_ARG, "dc_attention: null pointer");
   DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128, DC_ERR_SHAPE, "dc_attention: head dim %d (16/32/64/96/128)", p->d);
   DC_REQUIRE(p->n > 0 && p->L > 0 && p->heads > 0, DC_ERR_SHAPE, "dc_attention: n/L/heads");
   DC_REQUIRE(p->ld_qkv >= p->heads * p->d && p->ld_out >= p->heads * p->d, DC_ERR_SHAPE, "dc_attention: ld");
   // the matrix-core kernels keep the running max of the RAW scores and fold the scale into the exponent's FMA: valid for scale > 0 only
   DC_REQUIRE(p->scale > 0.f, DC_ERR_ARG, "dc_attention: scale must be positive (got %g)", (double)p->scale);
-  // L <= 64: one wave per pair (attn_wave_kernel); up to 128: the whole-sequence matrix-core kernel; beyond: the flash kernel, which
-  // also wins at 256 tokens (CheXpert 16x16 level, d = 64: 2.37 -> 0.71 ms per step; IPMSA: 13.2 -> 4.8 ms)
-  // (d = 96 — 768 channels, 8 heads — has no wave / flash instance: the whole-sequence kernel up to 128 tokens, else the fp32 kernel)
+  return DC_OK;
+}
+
+enum AttnRoute { ATTN_WAVE, ATTN_MFMA, ATTN_FLASH, ATTN_FP32 };
+
+// The kernel a valid problem dispatches to (dc_attention launches it, dc_attention_variant names it).
+// L <= 64: one wave per pair (attn_wave_kernel); up to 128: the whole-sequence matrix-core kernel; beyond: the flash kernel, which
+// also wins at 256 tokens (CheXpert 16x16 level, d = 64: 2.37 -> 0.71 ms per step; IPMSA: 13.2 -> 4.8 ms).  d = 96 (768 channels,
+// 8 heads; 72 / 80 padded in the packed weights) has no wave instance: the whole-sequence kernel up to 128 tokens, the flash kernel beyond.
+// fp32 (the parity path) and shapes the matrix-core kernels do not take: the exact fp32 kernel.
+static AttnRoute attn_route(const dc_attention_params* p) {
   constexpr int mfma_maxl = 128;
-  if (dc_attn_wave_applicable(p)) return dc_attn_wave_launch(p, reinterpret_cast<hipStream_t>(stream));
-  if (p->L <= mfma_maxl && dc_attn_mfma_applicable(p->dtype, p->L, p->d)) return dc_attn_mfma_launch(p, reinterpret_cast<hipStream_t>(stream));
+  if (dc_attn_wave_applicable(p)) return ATTN_WAVE;
+  if (p->L <= mfma_maxl && dc_attn_mfma_applicable(p->dtype, p->L, p->d)) return ATTN_MFMA;
   const size_t lds_all = (size_t)2 * p->L * p->d * sizeof(float);
-  if ((lds_all > 160 * 1024 || p->L > mfma_maxl) && dc_attn_flash_applicable(p))
-    return dc_attn_flash_launch(p, reinterpret_cast<hipStream_t>(stream));
-  // fp32 (the parity path) and shapes the matrix-core kernels do not take: exact fp32 kernel; K / V stay whole in LDS when they
-  // fit 160 KiB (one block: the order of operations of the UNet parity path is unchanged), else stream in 64 KiB blocks
+  if ((lds_all > 160 * 1024 || p->L > mfma_maxl) && dc_attn_flash_applicable(p)) return ATTN_FLASH;
+  return ATTN_FP32;
+}
+
+extern "C" const char* dc_attention_variant(const dc_attention_params* p) {
+  if (attn_validate(p) != DC_OK) return "invalid";
+  static const char* const names[] = {"wave", "mfma", "flash", "fp32"};
+  return names[attn_route(p)];
+}
+
+extern "C" int dc_attention(const dc_attention_params* p, dc_stream stream) {
+  const int rc = attn_validate(p);
+  if (rc != DC_OK) return rc;
+  switch (attn_route(p)) {
+    case ATTN_WAVE: return dc_attn_wave_launch(p, reinterpret_cast<hipStream_t>(stream));
+    case ATTN_MFMA: return dc_attn_mfma_launch(p, reinterpret_cast<hipStream_t>(stream));
+    case ATTN_FLASH: return dc_attn_flash_launch(p, reinterpret_cast<hipStream_t>(stream));
+    case ATTN_FP32: break;
+  }
+  // exact fp32 kernel: K / V stay whole in LDS when they fit 160 KiB (one block: the order of operations of the UNet parity path is
+  // unchanged), else stream in 64 KiB blocks
+  const size_t lds_all = (size_t)2 * p->L * p->d * sizeof(float);
   const int KB = lds_all <= 160 * 1024 ? p->L : 8192 / p->d;
   const size_t lds = (size_t)2 * KB * p->d * sizeof(float);
   AttnArgs a{p->q, p->k, p->v, p->out, p->n, p->L, p->heads, p->d, p->ld_qkv, p->ld_out, p->scale, KB};

@@ -179,7 +179,7 @@ struct FlashArgs {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Flash forward, transposed-score form (head dims 32 / 64 / 128): no transposed V image, no LDS round trip for P.
+// Flash forward, transposed-score form (head dims 32 / 64 / 96 / 128): no transposed V image, no LDS round trip for P.
 //   S^T = K Q^T     16x16x32 MFMA, A = K rows straight from a row-major LDS image, B = Q fragments held in registers;
 //                   the D fragment gives a lane 4 consecutive KEYS of ONE query (column lane&15)
 //   softmax         per query = per lane column: running max / sum live in every lane of the column, the cross-lane part
@@ -187,7 +187,7 @@ struct FlashArgs {
 //   O^T += V^T P^T  16x16x32 MFMA over PAIRS of key tiles: the two packed P^T D-fragments a lane holds ARE its B operand
 //                   (the k order inside an MFMA is free as long as A agrees), and the matching A operand (4 + 4
 //                   consecutive keys of one d column) is two ds_read_b64_tr_b16 of the ROW-MAJOR V image
-// K / V blocks of 128 / 64 / 32 keys (d = 32 / 64 / 128) are register-staged (global loads of block i+1 issued before the MFMAs of block i, written to
+// K / V blocks of 128 / 64 / 64 / 32 keys (d = 32 / 64 / 96 / 128) are register-staged (global loads of block i+1 issued before the MFMAs of block i, written to
 // the other LDS buffer after them), one barrier per block.  (The first version — transposed V staged with 2-byte LDS writes, P through
 // LDS, no prefetch — ran DiT-B/4 attention at 0.2 PF and was removed in round 4.)
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -233,13 +233,18 @@ static __device__ __forceinline__ float col4_sum(float x) {
   return a + b;
 }
 
+// Keys per block: sized so that scores + staged K/V fit the register file.  D = 96 takes 64, not 32 as D = 128 does: 32 rows of 12
+// chunks are 1.5 staging chunks per thread; 64 rows are 3, and 2 x 2 buffers x 64 x 104 x 2 B = 52 KiB of LDS keep two workgroups per CU.
+static constexpr int flash_kb(int D) { return D <= 32 ? 128 : (D <= 64 || D == 96 ? 64 : 32); }
+
 template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void attn_flash_t_kernel(const FlashArgs a) {
-  constexpr int KB = D <= 32 ? 128 : (D <= 64 ? 64 : 32);     // keys per block: sized so that scores + staged K/V fit the register file
+  constexpr int KB = flash_kb(D);
   constexpr int NKT = KB / 16, NQT = 2, NDT = D / 16, NKB = D / 32;
   constexpr int PITCH = D + 8;                                // LDS row pitch in elements (+16 B)
   constexpr int CPR = D / 8;                                  // 16-byte chunks per row
   constexpr int NST = KB * CPR / 256;                         // staging chunks per thread and operand
+  static_assert(KB * CPR % 256 == 0 && NKT % 2 == 0 && D % 32 == 0, "whole staging chunks, key tiles in pairs, 32-wide k-chunks");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* const Kl = reinterpret_cast<T*>(smem);                   // [2][KB][PITCH]
   T* const Vl = Kl + 2 * KB * PITCH;                          // [2][KB][PITCH]
@@ -400,8 +405,7 @@ __global__ __launch_bounds__(256, 2) void attn_flash_t_kernel(const FlashArgs a)
 
 template <typename T, int D>
 static int launch_flash_t(const FlashArgs& a, long long nb, hipStream_t s) {
-  constexpr int KB = D <= 32 ? 128 : (D <= 64 ? 64 : 32);
-  constexpr size_t lds = (size_t)4 * KB * (D + 8) * 2;
+  constexpr size_t lds = (size_t)4 * flash_kb(D) * (D + 8) * 2;
   static bool done = false;
   if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_flash_t_kernel<T, D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
   hipLaunchKernelGGL((attn_flash_t_kernel<T, D>), dim3((unsigned)nb), dim3(256), lds, s, a);
@@ -573,7 +577,7 @@ int dc_attn_wave_launch(const dc_attention_params* p, hipStream_t s) {
 }
 
 bool dc_attn_flash_applicable(const dc_attention_params* p) {
-  return p->dtype != DC_F32 && (p->d == 32 || p->d == 64 || p->d == 128) && p->L >= 1 && p->ld_out % 4 == 0 && (((uintptr_t)p->out) & 7) == 0 &&
+  return p->dtype != DC_F32 && (p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128) && p->L >= 1 && p->ld_out % 4 == 0 && (((uintptr_t)p->out) & 7) == 0 &&
          ((((uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v) & 15) == 0) && p->ld_qkv % 8 == 0;
 }
 
@@ -584,5 +588,6 @@ int dc_attn_flash_launch(const dc_attention_params* p, hipStream_t s) {
   const bool bf = p->dtype == DC_BF16;
   if (p->d == 32) return bf ? launch_flash_t<__bf16, 32>(a, nb, s) : launch_flash_t<_Float16, 32>(a, nb, s);
   if (p->d == 64) return bf ? launch_flash_t<__bf16, 64>(a, nb, s) : launch_flash_t<_Float16, 64>(a, nb, s);
+  if (p->d == 96) return bf ? launch_flash_t<__bf16, 96>(a, nb, s) : launch_flash_t<_Float16, 96>(a, nb, s);
   return bf ? launch_flash_t<__bf16, 128>(a, nb, s) : launch_flash_t<_Float16, 128>(a, nb, s);
 }

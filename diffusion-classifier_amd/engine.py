@@ -322,14 +322,18 @@ class PlanBuilder:
                    dict(name=name, family="layernorm", flops=0.0, bytes=2.0 * f["rows"] * x.C * DT_SIZE[x.dt]))
         return out
 
-    def attention(self, name, q, k, v, heads):
+    def attention(self, name, q, k, v, heads, d):
+        """softmax(q k^T / sqrt(d)) v per head, for heads of true width d.  q / k / v hold q.C // heads channels per head: d, or
+        padded_head_dim(d) with the pad channels zero (pad_head_rows), which add nothing to the scores and give zero output
+        columns.  The scale is that of the true d; the FLOP count is what executes, at the padded width."""
         out = self.tensor(name, q.dom, q.H, q.W, q.C, q.dt)
-        d = q.C // heads
-        f = dict(q=q, k=k, v=v, out=out, dtype=q.dt, n=self.n[q.dom], L=q.H * q.W, heads=heads, d=d,
+        dp = q.C // heads
+        assert d <= dp and dp * heads == q.C, (d, dp, heads, q.C)
+        f = dict(q=q, k=k, v=v, out=out, dtype=q.dt, n=self.n[q.dom], L=q.H * q.W, heads=heads, d=dp,
                  ld_qkv=q.ld, ld_out=out.ld, scale=float(d) ** -0.5)
         Lq = q.H * q.W
         self._emit(L.OP_ATTENTION, L.AttentionParams, f, [q, k, v], [out],
-                   dict(name=name, family="attention", flops=4.0 * self.n[q.dom] * heads * Lq * Lq * d,
+                   dict(name=name, family="attention", flops=4.0 * self.n[q.dom] * heads * Lq * Lq * dp,
                         bytes=4.0 * self.n[q.dom] * Lq * q.C * DT_SIZE[q.dt]))
         return out
 
@@ -460,6 +464,8 @@ class PlanBuilder:
             self.structs.append(s)
             if kind == L.OP_IGEMM:      # the kernel libdcamd picks for this shape (bench.py groups timings by it)
                 self.meta[i]["family"] = L.lib().dc_igemm_variant(s).decode()
+            elif kind == L.OP_ATTENTION:
+                self.meta[i]["variant"] = L.lib().dc_attention_variant(s).decode()
             arr[i].kind = kind
             arr[i].params = C.cast(C.pointer(s), C.c_void_p)
         self.op_array = arr
@@ -584,6 +590,41 @@ def pad_vec(v, rows):
     return out
 
 
+# Head widths dc_attention serves.  Heads of another width d <= 128 (DiT-XL/2: 72; UNet levels of 384 / 640 channels in 8 heads:
+# 48 / 80) run their attention at dp = padded_head_dim(d): the packed q/k/v weights give each head dp - d zero rows and to_out zero
+# input columns at the same positions, so the scores and the real output columns are the same sums.
+HEAD_DIMS = (16, 32, 64, 96, 128)
+
+
+def padded_head_dim(d):
+    """The smallest served head width >= d.  Wider heads are refused (NotImplementedError naming the width)."""
+    for dp in HEAD_DIMS:
+        if dp >= d:
+            return dp
+    raise NotImplementedError(f"attention head width {d} is not supported (at most {HEAD_DIMS[-1]})")
+
+
+def pad_head_rows(w, d, dp):
+    """[m*d(, K)] rows in consecutive heads of d (q | k | v stacked are 3 * heads of them; a bias too) -> [m*dp(, K)]: head i's row j
+    at i*dp + j, rows i*dp + d ... (i+1)*dp - 1 zero."""
+    if dp == d:
+        return w
+    x = w.reshape((-1, d) + tuple(w.shape[1:]))
+    out = w.new_zeros((x.shape[0], dp) + tuple(w.shape[1:]))
+    out[:, :d] = x
+    return out.reshape((-1,) + tuple(w.shape[1:]))
+
+
+def pad_head_cols(w, d, dp):
+    """[N, heads*d] (to_out's weight) -> [N, heads*dp]: zero input columns where pad_head_rows put zero rows."""
+    if dp == d:
+        return w
+    x = w.reshape(w.shape[0], -1, d)
+    out = w.new_zeros(w.shape[0], x.shape[1], dp)
+    out[..., :d] = x
+    return out.reshape(w.shape[0], -1)
+
+
 class UNetWeights:
     """Device-resident packed weights of a UNetCondition2D for one compute dtype."""
 
@@ -642,9 +683,12 @@ class UNetWeights:
             norm(key + ".norm"); conv1(key + ".proj_in"); conv1(key + ".proj_out")
             tb_ = key + ".transformer_blocks.0"
             norm(tb_ + ".norm1"); norm(tb_ + ".norm3")
-            qkv = torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0)
+            d = sd[key + ".proj_in.weight"].shape[0] // cfg.attention_head_dim
+            dp = padded_head_dim(d)
+            qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0), d, dp)
             P[tb_ + ".qkv.w"] = pack_matrix(qkv, dt, device)
-            lin(tb_ + ".attn1.to_out.0")
+            P[tb_ + ".attn1.to_out.0.w"] = pack_matrix(pad_head_cols(sd[tb_ + ".attn1.to_out.0.weight"], d, dp), dt, device)
+            P[tb_ + ".attn1.to_out.0.b"] = f32c(sd[tb_ + ".attn1.to_out.0.bias"], device)
             P[tb_ + ".ff.net.0.proj.w"], P[tb_ + ".ff.net.0.proj.b"] = pack_geglu(
                 sd[tb_ + ".ff.net.0.proj.weight"], sd[tb_ + ".ff.net.0.proj.bias"], dt, device)
             lin(tb_ + ".ff.net.2")
@@ -659,6 +703,7 @@ class UNetWeights:
         P["attn2v.w"] = pack_matrix(vw, L.DC_F32, device)
         self.P = P
         self._sd = sd              # references only (no copy): split packing of skip-connection convs is lazy
+        self.heads = cfg.attention_head_dim
 
     def split_resnet(self, key, C0):
         """Packed halves of a skip-connection ResNet's input convs: `.conv1.wa/.wb` ([Cout, 9*C0] / [Cout, 9*C1], same
@@ -689,7 +734,8 @@ class UNetWeights:
         P, sd = self.P, self._sd
         if tb_ + ".qkv.wf" in P:
             return P
-        qkv = torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0).float()
+        d = sd[tb_ + ".norm1.weight"].shape[0] // self.heads
+        qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0).float(), d, padded_head_dim(d))
         P[tb_ + ".qkv.wf"] = pack_matrix(qkv, self.dt, self.dev, col_scale=sd[tb_ + ".norm1.weight"])
         P[tb_ + ".qkv.bf"] = fold_layernorm_bias(qkv, None, sd[tb_ + ".norm1.bias"], self.dev)
         P[tb_ + ".ff.net.0.proj.wf"], P[tb_ + ".ff.net.0.proj.bf"] = pack_geglu(
@@ -885,11 +931,14 @@ class UNetPlan:
         def transformer(key, x):
             Cc = x.C
             tbk = key + ".transformer_blocks.0"
+            d = Cc // heads
+            Cq = heads * padded_head_dim(d)    # q / k / v / attention width: heads of d channels padded to a served width
             h = pb.pn_claim(x, pb.const(P[key + ".norm.g"]), pb.const(P[key + ".norm.b"]), G, 1e-6, False)
             if h is None:
                 h = pb.groupnorm(key + ".gn", x, pb.const(P[key + ".norm.g"]), pb.const(P[key + ".norm.b"]), G, 1e-6, False)
             if fuse_tb and h.dom == pb._dom(h, cvec[key]) and pb.tblock_front_ok(h, heads):
                 # proj_in -> LayerNorm -> q/k/v -> attention -> to_out + class vector + residual in ONE launch, the sample on chip
+                assert Cq == Cc, "dc_tblock_front takes unpadded heads only"
                 h = pb.tblock_front(tbk + ".front", h, pb.const(P[key + ".proj_in.w"]), pb.const(P[key + ".proj_in.b"]),
                                     pb.const(P[tbk + ".norm1.g"]), pb.const(P[tbk + ".norm1.b"]), pb.const(P[tbk + ".qkv.w"]),
                                     pb.const(P[tbk + ".attn1.to_out.0.w"]), pb.const(P[tbk + ".attn1.to_out.0.b"]), cvec[key], heads, 1e-5)
@@ -899,8 +948,8 @@ class UNetPlan:
             # (gamma into W's columns, beta into the bias: UNetWeights.fold_layernorms): no LayerNorm launch, no normalised tensor
             # (q/k/v keeps its LayerNorm launch: measured faster on the 256x256 tile + LayerNorm than on the row-standardising GEMM)
             hn = pb.layernorm(tbk + ".ln1", h, pb.const(P[tbk + ".norm1.g"]), pb.const(P[tbk + ".norm1.b"]), 1e-5)
-            qkv = pb.igemm(tbk + ".qkv", hn, pb.const(P[tbk + ".qkv.w"]), 3 * Cc)
-            o = pb.attention(tbk + ".attn1", qkv.view(0, Cc), qkv.view(Cc, Cc), qkv.view(2 * Cc, Cc), heads)
+            qkv = pb.igemm(tbk + ".qkv", hn, pb.const(P[tbk + ".qkv.w"]), 3 * Cq)
+            o = pb.attention(tbk + ".attn1", qkv.view(0, Cq), qkv.view(Cq, Cq), qkv.view(2 * Cq, Cq), heads, d)
             h = pb.igemm(tbk + ".attn_out", o, pb.const(P[tbk + ".attn1.to_out.0.w"]), Cc,
                          bias=pb.const(P[tbk + ".attn1.to_out.0.b"]), rowvec=cvec[key], residual=h)
             return transformer_back(key, tbk, x, h, Cc)

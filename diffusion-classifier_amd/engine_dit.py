@@ -8,7 +8,7 @@ the per-class part of the conditioning is a table row added in a GEMM epilogue.
 import torch
 
 from . import _lib as L
-from .engine import PlanBuilder, TORCH_DT, bke, f32c, pack_matrix, round_up
+from .engine import PlanBuilder, TORCH_DT, bke, f32c, pack_matrix, pad_head_cols, pad_head_rows, padded_head_dim, round_up
 
 
 class DiTWeights:
@@ -25,6 +25,8 @@ class DiTWeights:
         P["pos"] = model.pos_embed.pos_embed.detach().to(device=device, dtype=TORCH_DT[dt]).reshape(-1, model.D).contiguous()
         nl = cfg.num_layers
         self.nl = nl
+        d = cfg.attention_head_dim
+        dp = padded_head_dim(d)               # heads of 72 (DiT-XL/2) run at 96: zero rows / columns in q/k/v and to_out
         t1w = torch.cat([sd[f"transformer_blocks.{i}.norm1.emb.timestep_embedder.linear_1.weight"] for i in range(nl)], 0)
         t1b = torch.cat([sd[f"transformer_blocks.{i}.norm1.emb.timestep_embedder.linear_1.bias"] for i in range(nl)], 0)
         P["t1.w"], P["t1.b"] = pack_matrix(t1w, L.DC_F32, device), f32c(t1b, device)
@@ -36,10 +38,10 @@ class DiTWeights:
             P[k + ".table"] = f32c(sd[e + ".class_embedder.embedding_table.weight"], device)
             P[k + ".mod.w"] = pack_matrix(sd[k + ".norm1.linear.weight"], L.DC_F32, device)
             P[k + ".mod.b"] = f32c(sd[k + ".norm1.linear.bias"], device)
-            qkv_w = torch.cat([sd[k + f".attn1.to_{n}.weight"] for n in "qkv"], 0)
-            qkv_b = torch.cat([sd[k + f".attn1.to_{n}.bias"] for n in "qkv"], 0)
+            qkv_w = pad_head_rows(torch.cat([sd[k + f".attn1.to_{n}.weight"] for n in "qkv"], 0), d, dp)
+            qkv_b = pad_head_rows(torch.cat([sd[k + f".attn1.to_{n}.bias"] for n in "qkv"], 0), d, dp)
             P[k + ".qkv.w"], P[k + ".qkv.b"] = pack_matrix(qkv_w, dt, device), f32c(qkv_b, device)
-            P[k + ".out.w"] = pack_matrix(sd[k + ".attn1.to_out.0.weight"], dt, device)
+            P[k + ".out.w"] = pack_matrix(pad_head_cols(sd[k + ".attn1.to_out.0.weight"], d, dp), dt, device)
             P[k + ".out.b"] = f32c(sd[k + ".attn1.to_out.0.bias"], device)
             P[k + ".ff1.w"] = pack_matrix(sd[k + ".ff.net.0.proj.weight"], dt, device)
             P[k + ".ff1.b"] = f32c(sd[k + ".ff.net.0.proj.bias"], device)
@@ -61,6 +63,8 @@ class DiTPlan:
         dt = weights.dt
         P = weights.P
         D, heads, p = model.D, cfg.num_attention_heads, cfg.patch_size
+        d = cfg.attention_head_dim
+        Dq = heads * padded_head_dim(d)       # q / k / v / attention width (= D unless the heads are padded)
         H = W = cfg.sample_size
         g = H // p
         U = n_bj * n_cls
@@ -107,8 +111,8 @@ class DiTPlan:
             k = f"transformer_blocks.{i}"
             m = mods[i]
             hn = pb.layernorm(k + ".ln1", h, None, None, 1e-6, scale=m.view(D, D), shift=m.view(0, D))
-            qkv = pb.igemm(k + ".qkv", hn, pb.const(P[k + ".qkv.w"]), 3 * D, bias=pb.const(P[k + ".qkv.b"]))
-            o = pb.attention(k + ".attn", qkv.view(0, D), qkv.view(D, D), qkv.view(2 * D, D), heads)
+            qkv = pb.igemm(k + ".qkv", hn, pb.const(P[k + ".qkv.w"]), 3 * Dq, bias=pb.const(P[k + ".qkv.b"]))
+            o = pb.attention(k + ".attn", qkv.view(0, Dq), qkv.view(Dq, Dq), qkv.view(2 * Dq, Dq), heads, d)
             h = pb.igemm(k + ".attn_out", o, pb.const(P[k + ".out.w"]), D, bias=pb.const(P[k + ".out.b"]),
                          gate=m.view(2 * D, D), residual=h)
             hn = pb.layernorm(k + ".ln2", h, None, None, cfg.norm_eps, scale=m.view(4 * D, D), shift=m.view(3 * D, D))

@@ -190,6 +190,15 @@ class UNetCondition2D(_HipBackbone):
         lpb = (layers_per_block,) * nb if isinstance(layers_per_block, int) else tuple(layers_per_block)
         assert len(down_block_types) == nb and len(up_block_types) == nb and len(lpb) == nb
         G, eps, xdim = norm_num_groups, norm_eps, cross_attention_dim
+        # self-attention heads of C / attention_head_dim channels run zero-padded to a width dc_attention serves (engine.padded_head_dim):
+        # a level whose heads are wider than 128 is refused here, not at its first launch
+        rboc = boc[::-1]
+        for C in {boc[-1]} | {boc[i] for i, k in enumerate(down_block_types) if k == "CrossAttnDownBlock2D"} \
+                | {rboc[i] for i, k in enumerate(up_block_types) if k == "CrossAttnUpBlock2D"}:
+            try:
+                E.padded_head_dim(C // attention_head_dim)
+            except NotImplementedError as e:
+                raise NotImplementedError(f"UNetCondition2D: a {C}-channel attention level in {attention_head_dim} heads: {e}") from None
         self.config = SimpleNamespace(
             sample_size=sample_size, in_channels=in_channels, out_channels=out_channels,
             down_block_types=tuple(down_block_types), up_block_types=tuple(up_block_types), mid_block_type=mid_block_type,
@@ -219,7 +228,7 @@ class UNetCondition2D(_HipBackbone):
         self.mid_block.attentions = nn.ModuleList([_transformer2d(boc[-1], xdim, G)])
         self.mid_block.resnets = nn.ModuleList([_resnet(boc[-1], boc[-1], temb, G, eps) for _ in range(2)])
         self.up_blocks = nn.ModuleList()
-        rboc, rlpb = boc[::-1], lpb[::-1]
+        rlpb = lpb[::-1]
         out = rboc[0]
         for i, kind in enumerate(up_block_types):
             if kind not in ("UpBlock2D", "CrossAttnUpBlock2D"):

@@ -232,12 +232,19 @@ int64_t dc_workspace_bytes_layernorm(const dc_layernorm_params* p);
 /* softmax(q k^T * scale) v per (sample, head).  q/k/v: [n, L, heads, d] with row stride
  * ld (elements) so a fused QKV GEMM output can be passed as three offset pointers.
  * scale must be > 0 (DC_ERR_ARG otherwise): the kernels take the running max on the raw scores.
- * Head dims d = 16, 32, 64, 96, 128 (DC_ERR_SHAPE otherwise); 96 is the UNets' 768-channel level with 8 heads. */
+ * Head dims d = 16, 32, 64, 96, 128 (DC_ERR_SHAPE otherwise); 96 is the UNets' 768-channel level with 8 heads.  Other widths
+ * up to 128 run as the next of these with zero pad channels in q/k/v (the scale stays that of the true width): the pad adds
+ * nothing to the scores and its output columns are zero.
+ * Routes in 16-bit: L <= 64 one wave per (sample, head) (d = 32 / 64 / 128), L <= 128 the whole-sequence matrix-core kernel,
+ * longer sequences the flash kernel (d = 32 / 64 / 96 / 128); fp32 and the shapes those do not take: the exact fp32 kernel. */
 typedef struct {
   const void* q; const void* k; const void* v; void* out;
   int32_t dtype, n, L, heads, d, ld_qkv, ld_out; float scale;
 } dc_attention_params;
 int dc_attention(const dc_attention_params* p, dc_stream s);
+/* Name of the kernel dc_attention would launch for these parameters: "wave", "mfma" (whole sequence), "flash" or "fp32";
+ * "invalid" when dc_attention would refuse them (measurement / tests only; static string). */
+const char* dc_attention_variant(const dc_attention_params* p);
 int64_t dc_workspace_bytes_attention(const dc_attention_params* p);
 
 /* ---------------------------------------------------------------- transformer block, attention half --- */

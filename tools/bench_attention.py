@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of dc_attention on the DiT-B/4 shape (1024 tokens, 12 heads x 64, f16 / bf16) and a 4096-token one (developer tool;
-DCAMD_LIB selects the library, so A/B builds can be timed in one gpurun session).
+"""Micro-benchmark of dc_attention on the DiT-B/4 shape (1024 tokens, 12 heads x 64, f16 / bf16), a 4096-token one, and head dim 96:
+the CheXpert experiment UNet's 768-channel level (1024 / 4096 tokens x 8 heads) and DiT-XL/2 (256 tokens x 16 heads of 72, padded to 96)
+(developer tool; DCAMD_LIB selects the library, so A/B builds can be timed in one session).
 
   python tools/bench_attention.py [n_samples]
 """
@@ -11,7 +12,8 @@ from diffusion_classifier_amd import _lib as L
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 for dt, td in ((L.DC_F16, torch.float16), (L.DC_BF16, torch.bfloat16)):
-    for Lq, heads, d, nn in ((1024, 12, 64, n), (4096, 12, 64, max(1, n // 16))):
+    for Lq, heads, d, nn in ((1024, 12, 64, n), (4096, 12, 64, max(1, n // 16)),
+                             (1024, 8, 96, n), (4096, 8, 96, max(1, n // 16)), (256, 16, 96, 4 * n)):
         Cc = heads * d
         torch.manual_seed(1)
         qkv = (torch.randn(nn, Lq, 3 * Cc, device="cuda") * 1.2).to(td)
@@ -30,4 +32,7 @@ for dt, td in ((L.DC_F16, torch.float16), (L.DC_BF16, torch.bfloat16)):
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / reps
         fl = 4.0 * nn * heads * Lq * Lq * d
-        print(f"{'f16' if dt == L.DC_F16 else 'bf16'} L={Lq} n={nn}: {ms:.3f} ms  {fl / ms / 1e9:.0f} TFLOP/s  checksum {out.float().abs().mean().item():.6f}")
+        vf = getattr(L.lib(), "dc_attention_variant", None)      # (absent from libraries older than this tool)
+        kern = vf(p).decode() if vf is not None else "?"
+        print(f"{'f16' if dt == L.DC_F16 else 'bf16'} L={Lq} heads={heads} d={d} n={nn} [{kern}]: {ms:.3f} ms  {fl / ms / 1e9:.0f} TFLOP/s  "
+              f"checksum {out.float().abs().mean().item():.6f}")
