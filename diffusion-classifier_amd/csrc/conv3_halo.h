@@ -39,6 +39,11 @@ struct HaloGeom {
 
 constexpr int HALO_WST = 128 * 64;                      // bytes per W tap tile
 
+// Waves per workgroup of the halo kernels, from the extents the kernel walks (the four-phase upsample form walks the low-resolution
+// image).  8x8 images and smaller: deep layers (Cout >= 256) are weight-traffic bound, so they take the 512-pixel patch (half the
+// weight bytes per pixel); the 256-pixel patch would also need 4 x 100 halo rows = 7 loads per lane
+inline int dc_conv3_halo_waves(int H, int W) { return (H <= 8 || W <= 8) ? 8 : 4; }
+
 template <int NW> struct HaloCfg {
   static constexpr int NT = NW * 64;                    // threads
   static constexpr int PIX = NW * 64;                   // output pixels per workgroup

@@ -1002,8 +1002,7 @@ int dc_conv3_up4_launch(const IgemmArgs& a0, int dtype, int n_img, hipStream_t s
   a.Ktot = 4 * (a.C0 + a.C1);
   a.tiles_n = 4 * a0.tiles_n;                                    // phase-major N tiles
   a.n_fast = 0;
-  const int nw = (a.Hin <= 8 || a.Win <= 8) ? 8 : 4;
-  if (nw == 8) {
+  if (dc_conv3_halo_waves(a.Hin, a.Win) == 8) {
     if (dtype == DC_BF16) return launch_halo<__bf16, 8>(a, n_img, s, true);
     if (dtype == DC_F16) return launch_halo<_Float16, 8>(a, n_img, s, true);
     return launch_halo<float, 8>(a, n_img, s, true);
@@ -1014,10 +1013,7 @@ int dc_conv3_up4_launch(const IgemmArgs& a0, int dtype, int n_img, hipStream_t s
 }
 
 int dc_conv3_halo_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) {
-  // 8x8 images: deep layers (Cout >= 256) are weight-traffic bound, so they take the 512-pixel patch (half the
-  // weight bytes per pixel); the 256-pixel patch would also need 4 x 100 halo rows = 7 loads per lane
-  const int nw = (a.Hin <= 8 || a.Win <= 8) ? 8 : 4;
-  if (nw == 8) {
+  if (dc_conv3_halo_waves(a.Hin, a.Win) == 8) {
     if (dtype == DC_BF16) return launch_halo<__bf16, 8>(a, n_img, s);
     if (dtype == DC_F16) return launch_halo<_Float16, 8>(a, n_img, s);
     return launch_halo<float, 8>(a, n_img, s);

@@ -22,7 +22,7 @@
 // same weight panel.
 #include <stdio.h>
 #include <stdlib.h>
-#include "igemm_common.h"
+#include "conv3_halo.h"
 
 template <typename T, int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
@@ -160,80 +160,11 @@ extern "C" int32_t dc_igemm_cout_pad(int32_t cout, int32_t tile_n) {
   return (cout + tn - 1) / tn * tn;
 }
 
-static int igemm_run(const dc_igemm_params* p, dc_stream stream, const char** variant);
+// ---- dispatch ---------------------------------------------------------------------------------------------------------------------
+// dc_igemm, dc_igemm_variant and the dc_igemm_*_ok probes all go the same way: igemm_validate_and_fill, then igemm_choose — the one
+// place that picks a kernel or refuses — and then igemm_launch, igemm_name or a look at the choice.
 
-extern "C" int dc_igemm(const dc_igemm_params* p, dc_stream stream) { return igemm_run(p, stream, nullptr); }
-
-extern "C" int32_t dc_igemm_gn_fusable(const dc_igemm_params* p) {
-  if (!p) return 0;
-  dc_igemm_params q = *p;
-  static const float dummy = 0.f;
-  q.gn_scale = &dummy; q.gn_shift = &dummy;
-  const char* v = nullptr;
-  return igemm_run(&q, nullptr, &v) == DC_OK ? 1 : 0;
-}
-
-extern "C" int32_t dc_igemm_ln_ok(const dc_igemm_params* p) {
-  if (!p) return 0;
-  dc_igemm_params q = *p;
-  if (!(q.ln_eps > 0.f)) q.ln_eps = 1e-5f;
-  const char* v = nullptr;
-  return igemm_run(&q, nullptr, &v) == DC_OK ? 1 : 0;
-}
-
-extern "C" int32_t dc_igemm_qstats_parts(const dc_igemm_params* p) {
-  if (!p) return 0;
-  dc_igemm_params q = *p;
-  alignas(16) static float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  if (!q.qstats) q.qstats = dummy;
-  const char* v = nullptr;
-  if (igemm_run(&q, nullptr, &v) != DC_OK) return 0;
-  const int hw = p->Hout * p->Wout;
-  if (p->up4) { const int lo = hw >> 2; return 4 * (lo >= 128 ? lo / 128 : 1); }     // per phase, on the low-resolution image
-  return hw >= 128 ? hw / 128 : 1;          // one part per wave-sized run of 128 pixels (64-pixel images: one)
-}
-
-extern "C" int32_t dc_igemm_pn_ok(const dc_igemm_params* p) {
-  if (!p || p->pn_groups <= 0) return 0;
-  dc_igemm_params q = *p;
-  alignas(16) static float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  if (!q.pn_out) q.pn_out = dummy;
-  if (!q.qstats && !(q.Hin == 4 && q.Win == 4)) q.qstats = dummy;      // (4x4 mosaic patches form no quad records: their GroupNorm needs none)
-  if (!q.pn_gamma) q.pn_gamma = dummy;
-  if (!q.pn_beta) q.pn_beta = dummy;
-  if (!q.pn_cnt) q.pn_cnt = reinterpret_cast<uint32_t*>(dummy);
-  if (!(q.pn_eps > 0.f)) q.pn_eps = 1e-5f;
-  const char* v = nullptr;
-  return igemm_run(&q, nullptr, &v) == DC_OK ? 1 : 0;
-}
-
-extern "C" int32_t dc_pn_timeouts(void) { return (int32_t)dc_conv3_halo_pn_timeouts(); }
-
-extern "C" int32_t dc_igemm_up4_ok(const dc_igemm_params* p) {
-  if (!p) return 0;
-  dc_igemm_params q = *p;
-  q.up4 = 1;
-  const char* v = nullptr;
-  return igemm_run(&q, nullptr, &v) == DC_OK ? 1 : 0;
-}
-
-extern "C" int32_t dc_igemm_side_ok(const dc_igemm_params* p) {
-  if (!p) return 0;
-  dc_igemm_params q = *p;
-  alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  if (!q.src2) { q.src2 = dummy; q.W2 = dummy; }
-  const char* v = nullptr;
-  return igemm_run(&q, nullptr, &v) == DC_OK ? 1 : 0;
-}
-
-extern "C" const char* dc_igemm_variant(const dc_igemm_params* p) {
-  const char* v = "invalid";
-  (void)igemm_run(p, nullptr, &v);
-  return v;
-}
-
-// variant != nullptr: dry run — validate, pick the kernel, report its name, launch nothing.
-static int igemm_run(const dc_igemm_params* p, dc_stream stream, const char** variant) {
+static int igemm_validate_and_fill(const dc_igemm_params* p, IgemmArgs& a) {
   DC_REQUIRE(p, DC_ERR_ARG, "dc_igemm: null params");
   DC_REQUIRE(p->dtype == DC_F32 || p->dtype == DC_BF16 || p->dtype == DC_F16, DC_ERR_DTYPE, "dc_igemm: dtype %d", p->dtype);
   DC_REQUIRE(p->taps == 1 || p->taps == 9, DC_ERR_ARG, "dc_igemm: taps must be 1 or 9 (got %d)", p->taps);
@@ -269,7 +200,6 @@ static int igemm_run(const dc_igemm_params* p, dc_stream stream, const char** va
   if (p->rowvec) DC_REQUIRE(p->rowvec_ld >= cout_out, DC_ERR_SHAPE, "dc_igemm: rowvec_ld");
   if (p->gate) DC_REQUIRE(p->gate_ld >= cout_out, DC_ERR_SHAPE, "dc_igemm: gate_ld");
 
-  IgemmArgs a;
   a.src0 = p->src0; a.map0 = p->map0; a.src1 = p->src1; a.map1 = p->map1; a.W = p->W; a.bias = p->bias;
   a.rowvec = p->rowvec; a.rowvec_map = p->rowvec_map; a.gate = p->gate; a.gate_map = p->gate_map;
   a.residual = p->residual; a.res_map = p->res_map; a.out = p->out;
@@ -291,14 +221,36 @@ static int igemm_run(const dc_igemm_params* p, dc_stream stream, const char** va
   a.tiles_n = dc_igemm_cout_pad(p->Cout, bn) / bn;
   {
     // N fastest when the whole weight matrix can stay in an XCD's L2 next to the activation stream (<= 2 MiB), and for 1-tap GEMMs
-    // up to DCAMD_NFAST_GEMM_BYTES (default 16 MiB): there the activation panel of an M tile (rows x K) is the big operand — with
+    // up to gemm_cap (16 MiB, a compile-time constant): there the activation panel of an M tile (rows x K) is the big operand — with
     // M fastest it is re-fetched from HBM once per N panel (DiT-B/4 qkv: 9 x 786 MB per launch, the GEMM ran HBM-bound), with N
     // fastest the N tiles of an M tile run side by side on one XCD and share it in L2, while the weights come back from L2 / MALL
     constexpr long long gemm_cap = 16LL << 20;
     const long long wbytes = (long long)dc_igemm_cout_pad(p->Cout, bn) * a.Ktot * dc_dtype_size(p->dtype);
     a.n_fast = (a.tiles_n > 1 && (wbytes <= (2 << 20) || (p->taps == 1 && wbytes <= gemm_cap))) ? 1 : 0;
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return DC_OK;
+}
+
+enum IgemmKernel { IG_THIN, IG_WS, IG_HALO, IG_UP4_HALO, IG_UP4_PIPE, IG_XREG, IG_PIPE, IG_REG128, IG_REG32 };
+
+// What dc_igemm does with a valid problem: the kernel, or (status != DC_OK) the opted-in feature it cannot serve
+struct IgemmChoice {
+  IgemmKernel kernel = IG_REG32;
+  int waves = 0;                   // IG_HALO / IG_UP4_HALO: dc_conv3_halo_waves of the extents the kernel walks
+  int shape = 0;                   // IG_PIPE: dc_igemm_pipe_shape
+  bool gn = false, pn = false;     // IG_WS: GroupNorm prologue; IG_HALO / IG_UP4_HALO: producer-side GroupNorm
+  int status = DC_OK;
+  const char* tag = nullptr;       // refusal: what dc_igemm_variant reports ...
+  const char* message = nullptr;   // ... and what dc_last_error reports after dc_igemm
+};
+
+// the caller opted in to a feature (src2, gn_scale, qstats, pn_out, up4, ln_eps), so a problem that cannot take it is an error
+static IgemmChoice refuse(const char* tag, const char* message) { return IgemmChoice{IG_REG32, 0, 0, false, false, DC_ERR_UNSUPPORTED, tag, message}; }
+
+// p, a: after igemm_validate_and_fill.  No launch, no formatting, no dc_set_error: dc_run_plan comes through here for every op of every step
+static IgemmChoice igemm_choose(const dc_igemm_params* p, const IgemmArgs& a) {
+  const int dt = p->dtype, bn = p->tile_n, epc = 16 / dc_dtype_size(dt);
+  const int cout_out = p->act == DC_ACT_GEGLU ? p->Cout / 2 : p->Cout;
   // tile_n 128: the LDS-DMA kernels (igemm_pipe.hip, igemm_wide.hip, igemm_xreg.hip, conv3_*.hip).
   // the LDS-DMA kernels finish with the lane-resident epilogue (igemm_epilogue.h): whole 16-byte runs of 8 channels in
   // and out.  Anything else (channel counts / leading dimensions that are not multiples of 8, unaligned side
@@ -308,128 +260,177 @@ static int igemm_run(const dc_igemm_params* p, dc_stream stream, const char** va
                            (!p->bias || ((uintptr_t)p->bias & 15) == 0) &&
                            (!p->rowvec || (((uintptr_t)p->rowvec & 15) == 0 && p->rowvec_ld % 4 == 0)) &&
                            (!p->gate || (((uintptr_t)p->gate & 15) == 0 && p->gate_ld % 4 == 0 && p->act == DC_ACT_NONE)) &&
-                           (!p->residual || p->res_dtype == p->dtype) && (p->out_dtype == p->dtype || p->out_dtype == DC_F32);
-  const bool use_v1 = !lane_epi_ok;
+                           (!p->residual || p->res_dtype == dt) && (p->out_dtype == dt || p->out_dtype == DC_F32);
+  const bool lds_dma = bn == 128 && lane_epi_ok;
   static const bool no_halo = getenv("DCAMD_NO_HALO") != nullptr;
-  const char* dn = p->dtype == DC_BF16 ? "bf16" : (p->dtype == DC_F16 ? "f16" : "f32");
-  const bool halo_ok = bn == 128 && !use_v1 && !no_halo && dc_conv3_halo_applicable(a, p->dtype);
-  // four-phase upsample conv (W in the phase-summed form): the caller opted in, so anything else is an error
-  if (p->up4) {
-    const bool up4_halo = bn == 128 && !use_v1 && !no_halo && !a.src1 && dc_conv3_up4_applicable(a, p->dtype) &&
-                          (!a.qstats || (p->out_dtype == p->dtype && p->Cout % 8 == 0 && ((uintptr_t)a.qstats & 15) == 0 &&
-                                         (a.Hin >> 1) >= 8 && (a.Win >> 1) >= 8));      // no quad statistics from mosaic (< 8x8) patches
+  const bool halo_ok = lds_dma && !no_halo && dc_conv3_halo_applicable(a, dt);
+  // quad statistics / producer-side GroupNorm: what the plain and the four-phase form both ask of the operands
+  const bool qs_args_ok = p->out_dtype == dt && p->Cout % 8 == 0 && ((uintptr_t)a.qstats & 15) == 0;
+  const bool pn_args_ok = a.pn_gamma && a.pn_beta && a.pn_cnt && p->out_dtype == dt && a.pn_ld % 8 == 0 && a.pn_ld >= p->Cout &&
+                          (((uintptr_t)a.pn_out | (uintptr_t)a.qstats) & 15) == 0 && ((uintptr_t)a.pn_cnt & 3) == 0 && a.pn_eps > 0.f;
+  const bool use_pn = a.pn_out != nullptr;
+
+  if (p->up4) {      // four-phase upsample conv (W in the phase-summed form)
+    const bool up4_halo = lds_dma && !no_halo && !a.src1 && dc_conv3_up4_applicable(a, dt) &&
+                          (!a.qstats || (qs_args_ok && (a.Hin >> 1) >= 8 && (a.Win >> 1) >= 8));      // no quad statistics from mosaic (< 8x8) patches
     // sources smaller than 8x8 (4x4 -> 8x8): the same four phases on the tap-gather kernel (no quad statistics there)
-    const bool up4_pipe = !up4_halo && bn == 128 && !use_v1 && !a.src1 && !a.qstats && p->taps == 9 && p->stride == 1 &&
+    const bool up4_pipe = !up4_halo && lds_dma && !a.src1 && !a.qstats && p->taps == 9 && p->stride == 1 &&
                           p->upsample && p->act == DC_ACT_NONE && !p->gate && !p->residual && !a.gn_scale && !a.src2 &&
                           p->Hin >= 4 && p->Win >= 4 && p->Hin % 2 == 0 && p->Win % 2 == 0 && (p->Hin < 16 || p->Win < 16);
-    if (p->pn_out) {      // producer-side GroupNorm on the four-phase form: the 4-wave one-image-per-patch kernel only (sources of 16x16 and more)
-      const bool pn_ok = up4_halo && a.Hin > 16 && a.Win > 16 && dc_conv3_halo_pn_ok(a, p->dtype, true) && a.qstats && a.pn_gamma && a.pn_beta && a.pn_cnt &&
-                         p->out_dtype == p->dtype && a.pn_ld % 8 == 0 && a.pn_ld >= p->Cout && (((uintptr_t)a.pn_out | (uintptr_t)a.qstats) & 15) == 0 &&
-                         ((uintptr_t)a.pn_cnt & 3) == 0 && a.pn_eps > 0.f;
-      if (!pn_ok) {
-        if (variant) { *variant = "producer-groupnorm-unsupported"; return DC_ERR_UNSUPPORTED; }
-        dc_set_error("dc_igemm: pn_out given but this upsample conv cannot normalise its own output (see dc_igemm_pn_ok)");
-        return DC_ERR_UNSUPPORTED;
-      }
-    }
-    if (!up4_halo && !up4_pipe) {
-      if (variant) { *variant = "up4-unsupported"; return DC_ERR_UNSUPPORTED; }
-      dc_set_error("dc_igemm: up4 given but this problem cannot take the four-phase upsample conv (see dc_igemm_up4_ok)");
-      return DC_ERR_UNSUPPORTED;
-    }
-    if (variant) {
-      static thread_local char name4[64];
-      if (up4_halo) snprintf(name4, sizeof(name4), p->pn_out ? "conv3_up4<%s,%dw,pn>" : "conv3_up4<%s,%dw>", dn, (a.Hin <= 16 || a.Win <= 16) ? 8 : 4);
-      else snprintf(name4, sizeof(name4), "igemm_pipe_up4<%s,256x128,3st>", dn);
-      *variant = name4;
-      return DC_OK;
-    }
-    if (up4_halo) return dc_conv3_up4_launch(a, p->dtype, p->n_img, s);
-    return dc_igemm_launch_pipe_up4(a, p->dtype, s);
+    // producer-side GroupNorm on the four-phase form: the 4-wave one-image-per-patch kernel only (sources of 16x16 and more)
+    if (use_pn && !(up4_halo && a.Hin > 16 && a.Win > 16 && dc_conv3_halo_pn_ok(a, dt, true) && a.qstats && pn_args_ok))
+      return refuse("producer-groupnorm-unsupported", "dc_igemm: pn_out given but this upsample conv cannot normalise its own output (see dc_igemm_pn_ok)");
+    if (!up4_halo && !up4_pipe)
+      return refuse("up4-unsupported", "dc_igemm: up4 given but this problem cannot take the four-phase upsample conv (see dc_igemm_up4_ok)");
+    if (up4_halo) return IgemmChoice{IG_UP4_HALO, dc_conv3_halo_waves(a.Hin >> 1, a.Win >> 1), 0, false, use_pn};
+    return IgemmChoice{IG_UP4_PIPE};
   }
+
+  const bool thin_app = dc_conv3_thin_applicable(a, dt);
+  const bool thin = thin_app && ((uintptr_t)p->out & 3) == 0;       // (with gn_scale: conv_out, normalised in the halo)
   // wave-specialised halo conv: takes the fused GroupNorm prologue (also together with the 1x1 side source / a residual); DCAMD_WS_PLAIN
   // routes the plain one-image-per-patch convs there too (A/B of the structure alone)
   static const bool ws_plain = getenv("DCAMD_WS_PLAIN") != nullptr;
-  const bool ws_ok = halo_ok && dc_conv3_ws_ok(a, p->dtype) && !dc_conv3_thin_applicable(a, p->dtype);
+  const bool ws_ok = halo_ok && dc_conv3_ws_ok(a, dt) && !thin_app;
   const bool use_ws = ws_ok && (a.gn_scale || ws_plain);
-  if (a.src2) {
-    const int bke64 = 64 / dc_dtype_size(p->dtype);
-    const bool side_ok = halo_ok && (!a.gn_scale || ws_ok) && !a.upsample && a.W2 && a.C2 >= 2 * bke64 && a.C2 % bke64 == 0 && a.ld2 % epc == 0 &&
-                         (((uintptr_t)a.src2 | (uintptr_t)a.W2) & 15) == 0 && lane_epi_ok;
-    if (!side_ok) {
-      if (variant) { *variant = "side-source-unsupported"; return DC_ERR_UNSUPPORTED; }
-      dc_set_error("dc_igemm: src2/W2 given but this problem cannot take the 1x1 side source (see dc_igemm_side_ok)");
-      return DC_ERR_UNSUPPORTED;
-    }
-  }
-  const bool thin_gn = a.gn_scale && dc_conv3_thin_applicable(a, p->dtype) && ((uintptr_t)p->out & 3) == 0;   // conv_out: normalised in the halo
-  if (a.gn_scale && !thin_gn && !ws_ok) {
-    if (variant) { *variant = "gn-not-fusable"; return DC_ERR_UNSUPPORTED; }
-    dc_set_error("dc_igemm: gn_scale/gn_shift given but this problem cannot take the fused GroupNorm prologue (see dc_igemm_gn_fusable)");
-    return DC_ERR_UNSUPPORTED;
-  }
-  if (a.qstats) {
-    const bool thin_q = dc_conv3_thin_applicable(a, p->dtype);
-    const bool qs_ok = halo_ok && !thin_q && p->out_dtype == p->dtype && p->Cout % 8 == 0 && ((uintptr_t)a.qstats & 15) == 0 &&
-                       a.Hin >= 8 && a.Win >= 8;          // mosaic patches (images below 8x8) emit none: a wave's half holds four images
-    if (!qs_ok) {
-      if (variant) { *variant = "qstats-unsupported"; return DC_ERR_UNSUPPORTED; }
-      dc_set_error("dc_igemm: qstats given but this problem cannot emit quad statistics (see dc_igemm_qstats_parts)");
-      return DC_ERR_UNSUPPORTED;
-    }
-  }
-  // producer-side GroupNorm: the caller opted in (dc_igemm_pn_ok), anything that cannot take it is an error
-  const bool use_pn = a.pn_out != nullptr;
-  if (use_pn) {
-    const bool pn_ok = halo_ok && !use_ws && !a.gn_scale && !dc_conv3_thin_applicable(a, p->dtype) && dc_conv3_halo_pn_ok(a, p->dtype, false) &&
-                       (a.qstats || (a.Hin == 4 && a.Win == 4)) && a.pn_gamma && a.pn_beta && a.pn_cnt && p->out_dtype == p->dtype && a.pn_ld % 8 == 0 &&
-                       a.pn_ld >= p->Cout && (((uintptr_t)a.pn_out | (uintptr_t)a.qstats) & 15) == 0 && ((uintptr_t)a.pn_cnt & 3) == 0 && a.pn_eps > 0.f;
-    if (!pn_ok) {
-      if (variant) { *variant = "producer-groupnorm-unsupported"; return DC_ERR_UNSUPPORTED; }
-      dc_set_error("dc_igemm: pn_out given but this problem cannot normalise its own output (see dc_igemm_pn_ok)");
-      return DC_ERR_UNSUPPORTED;
-    }
-  } else {
-    DC_REQUIRE(p->out, DC_ERR_ARG, "dc_igemm: null out");
-  }
+  const int bke64 = 64 / dc_dtype_size(dt);
+  if (a.src2 && !(halo_ok && (!a.gn_scale || ws_ok) && !a.upsample && a.W2 && a.C2 >= 2 * bke64 && a.C2 % bke64 == 0 && a.ld2 % epc == 0 &&
+                  (((uintptr_t)a.src2 | (uintptr_t)a.W2) & 15) == 0))
+    return refuse("side-source-unsupported", "dc_igemm: src2/W2 given but this problem cannot take the 1x1 side source (see dc_igemm_side_ok)");
+  if (a.gn_scale && !thin && !ws_ok)
+    return refuse("gn-not-fusable", "dc_igemm: gn_scale/gn_shift given but this problem cannot take the fused GroupNorm prologue (see dc_igemm_gn_fusable)");
+  if (a.qstats && !(halo_ok && !thin_app && qs_args_ok && a.Hin >= 8 && a.Win >= 8))      // mosaic patches (images below 8x8) emit none: a wave's half holds four images
+    return refuse("qstats-unsupported", "dc_igemm: qstats given but this problem cannot emit quad statistics (see dc_igemm_qstats_parts)");
+  if (use_pn && !(halo_ok && !use_ws && !a.gn_scale && !thin_app && dc_conv3_halo_pn_ok(a, dt, false) &&
+                  (a.qstats || (a.Hin == 4 && a.Win == 4)) && pn_args_ok))
+    return refuse("producer-groupnorm-unsupported", "dc_igemm: pn_out given but this problem cannot normalise its own output (see dc_igemm_pn_ok)");
+  const bool xreg_app = dc_igemm_xreg_applicable(a, dt);
+  if (a.ln_eps > 0.f && !(lds_dma && !a.src1 && xreg_app))
+    return refuse("row-layernorm-unsupported", "dc_igemm: ln_eps given but this problem cannot take the fused row LayerNorm (see dc_igemm_ln_ok)");
+
+  if (thin) return IgemmChoice{IG_THIN};
+  if (use_ws) return IgemmChoice{IG_WS, 0, 0, a.gn_scale != nullptr};
+  if (halo_ok) return IgemmChoice{IG_HALO, dc_conv3_halo_waves(a.Hin, a.Win), 0, false, use_pn};
+  if (!lds_dma) return IgemmChoice{bn == 128 ? IG_REG128 : IG_REG32};
   // short-K GEMMs: the activation-stationary kernel wins for GEGLU (448 vs 376 TFLOP/s at K = 256, 584 vs 544 at K = 512);
   // for plain epilogues the 256x256 tile is faster where it applies (q/k/v 505-709 vs 478-556), xreg elsewhere
-  const bool ln_ok = bn == 128 && !use_v1 && !a.src1 && dc_igemm_xreg_applicable(a, p->dtype);
-  if (a.ln_eps > 0.f && !ln_ok) {
-    if (variant) { *variant = "row-layernorm-unsupported"; return DC_ERR_UNSUPPORTED; }
-    dc_set_error("dc_igemm: ln_eps given but this problem cannot take the fused row LayerNorm (see dc_igemm_ln_ok)");
-    return DC_ERR_UNSUPPORTED;
+  const int shape = dc_igemm_pipe_shape(a);
+  if (xreg_app && (p->act == DC_ACT_GEGLU || a.ln_eps > 0.f || shape != 2)) return IgemmChoice{IG_XREG};
+  return IgemmChoice{IG_PIPE, 0, shape};
+}
+
+static const char* igemm_name(const IgemmChoice& c, int dtype) {
+  // by dc_igemm_pipe_shape, as dc_igemm_launch_pipe switches
+  static const char* const pipe_fmt[3] = {"igemm_pipe<%s,128x128,2st>", "igemm_pipe<%s,256x128,3st>", "igemm_wide8<%s,256x256>"};
+  static thread_local char name[64];
+  const char* dn = dtype == DC_BF16 ? "bf16" : (dtype == DC_F16 ? "f16" : "f32");
+  switch (c.kernel) {
+    case IG_THIN: snprintf(name, sizeof(name), "conv3_thin<%s>", dn); break;
+    case IG_WS: snprintf(name, sizeof(name), c.gn ? "conv3_ws<%s,gn>" : "conv3_ws<%s>", dn); break;
+    case IG_HALO: snprintf(name, sizeof(name), c.pn ? "conv3_halo<%s,%dw,pn>" : "conv3_halo<%s,%dw>", dn, c.waves); break;
+    case IG_UP4_HALO: snprintf(name, sizeof(name), c.pn ? "conv3_up4<%s,%dw,pn>" : "conv3_up4<%s,%dw>", dn, c.waves); break;
+    case IG_UP4_PIPE: snprintf(name, sizeof(name), "igemm_pipe_up4<%s,256x128,3st>", dn); break;
+    case IG_XREG: snprintf(name, sizeof(name), "igemm_xreg<%s,96xN>", dn); break;
+    case IG_PIPE: snprintf(name, sizeof(name), pipe_fmt[c.shape], dn); break;
+    case IG_REG128: snprintf(name, sizeof(name), "igemm<%s,128x128>", dn); break;
+    case IG_REG32: snprintf(name, sizeof(name), "igemm<%s,128x32>", dn); break;
   }
-  const bool use_xreg = bn == 128 && dc_igemm_xreg_applicable(a, p->dtype) && (p->act == DC_ACT_GEGLU || a.ln_eps > 0.f || dc_igemm_pipe_shape(a) != 2);
-  const bool thin = dc_conv3_thin_applicable(a, p->dtype) && ((uintptr_t)p->out & 3) == 0;
-  if (variant) {
-    static thread_local char name[64];
-    if (thin) { snprintf(name, sizeof(name), "conv3_thin<%s>", dn); *variant = name; return DC_OK; }
-    if (use_ws) snprintf(name, sizeof(name), a.gn_scale ? "conv3_ws<%s,gn>" : "conv3_ws<%s>", dn);
-    else if (use_pn) snprintf(name, sizeof(name), "conv3_halo<%s,%dw,pn>", dn, (a.Hin <= 8 || a.Win <= 8) ? 8 : 4);
-    else if (bn == 128 && !use_v1 && !no_halo && dc_conv3_halo_applicable(a, p->dtype)) snprintf(name, sizeof(name), "conv3_halo<%s,%dw>", dn, (a.Hin <= 8 || a.Win <= 8) ? 8 : 4);
-    else if (bn == 128 && !use_v1 && use_xreg) snprintf(name, sizeof(name), "igemm_xreg<%s,96xN>", dn);
-    else if (bn == 128 && !use_v1) {
-      static const char* const shapes[4] = {"igemm_pipe<%s,128x128,2st>", "igemm_pipe<%s,256x128,3st>", "igemm_pipe<%s,256x256,2st>",
-                                            "igemm_wide8<%s,256x256>"};
-      const int shp = dc_igemm_pipe_shape(a);
-      snprintf(name, sizeof(name), shapes[shp == 2 ? 3 : shp], dn);
-    }
-    else snprintf(name, sizeof(name), "igemm<%s,128x%d>", dn, bn);
-    *variant = name;
-    return DC_OK;
+  return name;
+}
+
+static int igemm_launch(const IgemmChoice& c, const IgemmArgs& a, const dc_igemm_params* p, dc_stream stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  switch (c.kernel) {
+    case IG_THIN: return dc_conv3_thin_launch(a, p->dtype, p->n_img, s);
+    case IG_WS: return dc_conv3_ws_launch(a, p->dtype, p->n_img, s);
+    case IG_HALO: return dc_conv3_halo_launch(a, p->dtype, p->n_img, s);
+    case IG_UP4_HALO: return dc_conv3_up4_launch(a, p->dtype, p->n_img, s);
+    case IG_UP4_PIPE: return dc_igemm_launch_pipe_up4(a, p->dtype, s);
+    case IG_XREG: return dc_igemm_xreg_launch(a, p->dtype, s);
+    case IG_PIPE: return dc_igemm_launch_pipe(a, p->dtype, c.shape, s);
+    case IG_REG128:
+      if (p->dtype == DC_BF16) return launch<__bf16, 128, 128, 2, 2>(a, s);
+      if (p->dtype == DC_F16) return launch<_Float16, 128, 128, 2, 2>(a, s);
+      return launch<float, 128, 128, 2, 2>(a, s);
+    case IG_REG32:
+      if (p->dtype == DC_BF16) return launch<__bf16, 128, 32, 4, 1>(a, s);
+      if (p->dtype == DC_F16) return launch<_Float16, 128, 32, 4, 1>(a, s);
+      return launch<float, 128, 32, 4, 1>(a, s);
   }
-  if (thin) return dc_conv3_thin_launch(a, p->dtype, p->n_img, s);
-  if (use_ws) return dc_conv3_ws_launch(a, p->dtype, p->n_img, s);
-  if (bn == 128 && !use_v1 && !no_halo && dc_conv3_halo_applicable(a, p->dtype)) return dc_conv3_halo_launch(a, p->dtype, p->n_img, s);
-  if (bn == 128 && !use_v1 && use_xreg) return dc_igemm_xreg_launch(a, p->dtype, s);
-  if (bn == 128 && !use_v1) return dc_igemm_launch_pipe(a, p->dtype, s);
-  if (bn == 128) {
-    if (p->dtype == DC_BF16) return launch<__bf16, 128, 128, 2, 2>(a, s);
-    if (p->dtype == DC_F16) return launch<_Float16, 128, 128, 2, 2>(a, s);
-    return launch<float, 128, 128, 2, 2>(a, s);
-  }
-  if (p->dtype == DC_BF16) return launch<__bf16, 128, 32, 4, 1>(a, s);
-  if (p->dtype == DC_F16) return launch<_Float16, 128, 32, 4, 1>(a, s);
-  return launch<float, 128, 32, 4, 1>(a, s);
+  return DC_ERR_ARG;
+}
+
+extern "C" int dc_igemm(const dc_igemm_params* p, dc_stream stream) {
+  IgemmArgs a;
+  const int rc = igemm_validate_and_fill(p, a);
+  if (rc != DC_OK) return rc;
+  const IgemmChoice c = igemm_choose(p, a);
+  if (c.status != DC_OK) { dc_set_error("%s", c.message); return c.status; }
+  return igemm_launch(c, a, p, stream);
+}
+
+extern "C" const char* dc_igemm_variant(const dc_igemm_params* p) {
+  IgemmArgs a;
+  if (igemm_validate_and_fill(p, a) != DC_OK) return "invalid";
+  const IgemmChoice c = igemm_choose(p, a);
+  return c.status == DC_OK ? igemm_name(c, p->dtype) : c.tag;
+}
+
+// ---- probes: plant what the feature needs where the caller left it out, choose, test ---------------------------------------------
+static int32_t igemm_accepts(const dc_igemm_params& q) {
+  IgemmArgs a;
+  return igemm_validate_and_fill(&q, a) == DC_OK && igemm_choose(&q, a).status == DC_OK ? 1 : 0;
+}
+alignas(16) static float g_probe_dummy[4] = {0.f, 0.f, 0.f, 0.f};
+
+extern "C" int32_t dc_igemm_gn_fusable(const dc_igemm_params* p) {
+  if (!p) return 0;
+  dc_igemm_params q = *p;
+  q.gn_scale = g_probe_dummy; q.gn_shift = g_probe_dummy;
+  return igemm_accepts(q);
+}
+
+extern "C" int32_t dc_igemm_ln_ok(const dc_igemm_params* p) {
+  if (!p) return 0;
+  dc_igemm_params q = *p;
+  if (!(q.ln_eps > 0.f)) q.ln_eps = 1e-5f;
+  return igemm_accepts(q);
+}
+
+extern "C" int32_t dc_igemm_qstats_parts(const dc_igemm_params* p) {
+  if (!p) return 0;
+  dc_igemm_params q = *p;
+  if (!q.qstats) q.qstats = g_probe_dummy;
+  if (!igemm_accepts(q)) return 0;
+  const int hw = p->Hout * p->Wout;
+  if (p->up4) { const int lo = hw >> 2; return 4 * (lo >= 128 ? lo / 128 : 1); }     // per phase, on the low-resolution image
+  return hw >= 128 ? hw / 128 : 1;          // one part per wave-sized run of 128 pixels (64-pixel images: one)
+}
+
+extern "C" int32_t dc_igemm_pn_ok(const dc_igemm_params* p) {
+  if (!p || p->pn_groups <= 0) return 0;
+  dc_igemm_params q = *p;
+  if (!q.pn_out) q.pn_out = g_probe_dummy;
+  if (!q.qstats && !(q.Hin == 4 && q.Win == 4)) q.qstats = g_probe_dummy;      // (4x4 mosaic patches form no quad records: their GroupNorm needs none)
+  if (!q.pn_gamma) q.pn_gamma = g_probe_dummy;
+  if (!q.pn_beta) q.pn_beta = g_probe_dummy;
+  if (!q.pn_cnt) q.pn_cnt = reinterpret_cast<uint32_t*>(g_probe_dummy);
+  if (!(q.pn_eps > 0.f)) q.pn_eps = 1e-5f;
+  return igemm_accepts(q);
+}
+
+extern "C" int32_t dc_pn_timeouts(void) { return (int32_t)dc_conv3_halo_pn_timeouts(); }
+
+extern "C" int32_t dc_igemm_up4_ok(const dc_igemm_params* p) {
+  if (!p) return 0;
+  dc_igemm_params q = *p;
+  q.up4 = 1;
+  return igemm_accepts(q);
+}
+
+extern "C" int32_t dc_igemm_side_ok(const dc_igemm_params* p) {
+  if (!p) return 0;
+  dc_igemm_params q = *p;
+  if (!q.src2) { q.src2 = g_probe_dummy; q.W2 = g_probe_dummy; }
+  return igemm_accepts(q);
 }

@@ -142,8 +142,8 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
 }
 
 // defined in igemm_pipe.hip; returns DC_ERR_UNSUPPORTED-free status (always handles tile_n == 128)
-int dc_igemm_launch_pipe(const IgemmArgs& a, int dtype, hipStream_t s);
 int dc_igemm_pipe_shape(const IgemmArgs& a);   // 0: 128x128, 1: 256x128, 2: 256x256 tile
+int dc_igemm_launch_pipe(const IgemmArgs& a, int dtype, int shape, hipStream_t s);
 // igemm_wide.hip: the 256 x 256 tile on the 8-phase main loop
 int dc_igemm_launch_wide8(const IgemmArgs& a, int dtype, hipStream_t s);
 // hipcc expands the integer divisions of tile_of_block on the VECTOR unit, so tile_m / tile_n (and everything derived from them: weight

@@ -315,8 +315,8 @@ int dc_igemm_launch_pipe_up4(const IgemmArgs& a0, int dtype, hipStream_t s) {
   return launch_pipe<float, 256, 3, 1, 5, false>(a, s);
 }
 
-int dc_igemm_launch_pipe(const IgemmArgs& a, int dtype, hipStream_t s) {
-  const int shape = dc_igemm_pipe_shape(a);
+// shape: dc_igemm_pipe_shape(a)
+int dc_igemm_launch_pipe(const IgemmArgs& a, int dtype, int shape, hipStream_t s) {
   const bool slim = a.taps == 1;
   if (shape == 0) {
     if (slim) {

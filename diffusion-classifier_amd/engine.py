@@ -27,6 +27,7 @@ DT = {"f32": L.DC_F32, "fp32": L.DC_F32, "float32": L.DC_F32, "bf16": L.DC_BF16,
       "f16": L.DC_F16, "fp16": L.DC_F16, "float16": L.DC_F16}
 TORCH_DT = {L.DC_F32: torch.float32, L.DC_BF16: torch.bfloat16, L.DC_F16: torch.float16}
 DT_SIZE = {L.DC_F32: 4, L.DC_BF16: 2, L.DC_F16: 2}
+FAKE_PTR = 1 << 20      # non-null and 16-byte aligned, for the questions to the library that only look at a pointer (PlanBuilder._probe)
 
 
 def bke(dt):
@@ -154,12 +155,10 @@ class PlanBuilder:
         if src1 is not None:
             assert src1.dt == src0.dt and (src1.H, src1.W) == (src0.H, src0.W)
         qs = None
-        if qstats and L.lib().dc_igemm_qstats_parts is not None:
+        if qstats:
             # the conv also writes (mean, M2) per (sample, part, channel quad) of its output: the GroupNorm that consumes the
             # tensor then streams it once (read + write) instead of sweeping it twice
-            fake = 1 << 20
-            probe = L.IgemmParams(**{k: (fake if isinstance(v, TRef) else v) for k, v in f.items() if v is not None})
-            parts = int(L.lib().dc_igemm_qstats_parts(probe))
+            parts = int(L.lib().dc_igemm_qstats_parts(self._probe(**f)))
             if parts > 0:
                 qs = TRef(name + ".qs", dom, 1, 1, 1, L.DC_F32, nbytes=round_up(self.n[dom] * parts * (Cout // 4) * 2 * 4, 256))
                 f.update(qstats=qs)
@@ -181,15 +180,20 @@ class PlanBuilder:
             out.prod = len(self.ops) - 1       # (4x4 images: no quad records, but the conv can still normalise its output inside the wave)
         return out
 
+    def _probe(self, x=None, **fields):
+        """dc_igemm_params for a question to the library (dc_igemm_*_ok, dc_igemm_variant; none of them touches memory): FAKE_PTR for
+        every plan tensor, and, given x, a plain 3x3 stride-1 conv of x with Cout channels on the 128-wide tile unless `fields` says
+        otherwise."""
+        if x is not None:
+            fields = dict(dict(dtype=x.dt, taps=9, stride=1, upsample=0, n_img=self.n[x.dom], Hin=x.H, Win=x.W, Hout=x.H, Wout=x.W,
+                               src0=x, C0=x.C, ld0=x.ld, W=FAKE_PTR, tile_n=128, out=FAKE_PTR, out_dtype=x.dt, out_ld=fields["Cout"]), **fields)
+        return L.IgemmParams(**{k: (FAKE_PTR if isinstance(v, TRef) else v) for k, v in fields.items() if v is not None})
+
     def pn_capable(self, x, Cout, dom):
         """Would a plain 3x3 stride-1 conv of x (single source) be able to normalise its own output (dc_igemm_pn_ok)?"""
-        if self.pn_off or L.lib().dc_igemm_pn_ok is None or Cout % 32:
+        if self.pn_off or Cout % 32:
             return False
-        fake = 1 << 20
-        p = L.IgemmParams(dtype=x.dt, taps=9, stride=1, upsample=0, n_img=self.n[dom], Hin=x.H, Win=x.W, Hout=x.H, Wout=x.W,
-                          src0=fake, C0=x.C, ld0=x.ld, W=fake, Cout=Cout, tile_n=128, out=fake, out_dtype=x.dt, out_ld=Cout,
-                          pn_groups=32, pn_eps=1e-5)
-        return bool(L.lib().dc_igemm_pn_ok(p))
+        return bool(L.lib().dc_igemm_pn_ok(self._probe(x, Cout=Cout, n_img=self.n[dom], pn_groups=32, pn_eps=1e-5)))
 
     def pn_claim(self, x, gamma, beta, groups, eps, silu):
         """Producer-side GroupNorm (dc_igemm_params.pn_*; csrc/epi_pn.h): ask the 3x3 conv that produced x to ALSO store
@@ -197,15 +201,13 @@ class PlanBuilder:
         this GroupNorm reads a finished tensor with a plain conv / GEMM and no GroupNorm pass (nor a normalising loader) runs.
         Returns the normalised tensor, or None when the producer cannot (then the caller takes the GroupNorm pass / the fused loader).
         One claim per tensor; whether the raw x is still stored is decided in finalize() (only if something reads it)."""
-        if x is None or x.prod is None or x.base is not x or self.pn_off or L.lib().dc_igemm_pn_ok is None:
+        if x is None or x.prod is None or x.base is not x or self.pn_off:
             return None
         idx = x.prod
         kind, cls, f = self.ops[idx]
         if f.get("pn_out") is not None or f["Cout"] % groups:
             return None
-        fake = 1 << 20
-        probe = L.IgemmParams(**{k: (fake if isinstance(v, TRef) else v) for k, v in f.items() if v is not None}, pn_groups=groups, pn_eps=float(eps))
-        if not L.lib().dc_igemm_pn_ok(probe):
+        if not L.lib().dc_igemm_pn_ok(self._probe(**f, pn_groups=groups, pn_eps=float(eps))):
             return None
         dom = x.dom
         y = self.tensor(x.name + ".pn", dom, x.H, x.W, x.C, x.dt)
@@ -220,49 +222,29 @@ class PlanBuilder:
 
     def up4_ok(self, src0, Cout):
         """Can the upsample conv of src0 run as four 2x2-tap phases on the low-resolution image (dc_igemm_up4_ok)?"""
-        fake = 1 << 20
-        p = L.IgemmParams(dtype=src0.dt, taps=9, stride=1, upsample=1, n_img=self.n[src0.dom], Hin=2 * src0.H, Win=2 * src0.W,
-                          Hout=2 * src0.H, Wout=2 * src0.W, src0=fake, C0=src0.C, ld0=src0.ld, W=fake, Cout=Cout, tile_n=128,
-                          bias=fake, out=fake, out_dtype=src0.dt, out_ld=Cout, up4=1)
-        return bool(L.lib().dc_igemm_up4_ok(p))
+        H2, W2 = 2 * src0.H, 2 * src0.W
+        return bool(L.lib().dc_igemm_up4_ok(self._probe(src0, Cout=Cout, upsample=1, Hin=H2, Win=W2, Hout=H2, Wout=W2, bias=FAKE_PTR, up4=1)))
 
     def ln_ok(self, src0, Cout, act=L.ACT_NONE):
         """Can this 1-tap GEMM normalise its input rows itself (dc_igemm_ln_ok)?"""
-        fake = 1 << 20
         cout_out = Cout // 2 if act == L.ACT_GEGLU else Cout
-        p = L.IgemmParams(dtype=src0.dt, taps=1, stride=1, upsample=0, n_img=self.n[src0.dom], Hin=src0.H, Win=src0.W,
-                          Hout=src0.H, Wout=src0.W, src0=fake, C0=src0.C, ld0=src0.ld, W=fake, Cout=Cout, tile_n=128, act=act,
-                          out=fake, out_dtype=src0.dt, out_ld=cout_out, ln_eps=1e-5)
-        return bool(L.lib().dc_igemm_ln_ok(p))
+        return bool(L.lib().dc_igemm_ln_ok(self._probe(src0, Cout=Cout, taps=1, act=act, out_ld=cout_out, ln_eps=1e-5)))
 
     def side_ok(self, src0, s2, Cout, residual=None):
         """Can a 3x3 stride-1 conv of src0 take the 1x1 side source s2 (dc_igemm_side_ok)?"""
-        fake = 1 << 20
-        dom = self._dom(src0, s2, residual)
-        p = L.IgemmParams(dtype=src0.dt, taps=9, stride=1, upsample=0, n_img=self.n[dom], Hin=src0.H, Win=src0.W,
-                          Hout=src0.H, Wout=src0.W, src0=fake, C0=src0.C, ld0=src0.ld, W=fake, Cout=Cout, tile_n=128,
-                          residual=fake if residual is not None else None, res_dtype=src0.dt, res_ld=Cout,
-                          out=fake, out_dtype=src0.dt, out_ld=Cout, src2=fake, W2=fake, C2=s2.C, ld2=s2.ld)
-        return bool(L.lib().dc_igemm_side_ok(p))
+        return bool(L.lib().dc_igemm_side_ok(self._probe(src0, Cout=Cout, n_img=self.n[self._dom(src0, s2, residual)], residual=residual,
+                                                         res_dtype=src0.dt, res_ld=Cout, src2=s2, W2=FAKE_PTR, C2=s2.C, ld2=s2.ld)))
 
     def gn_fusable(self, src0, src1, Cout, tile_n=128, out_dt=None):
         """Can a 3x3 stride-1 conv of these sources take the GroupNorm prologue (dc_igemm_gn_fusable)?"""
-        if L.lib().dc_igemm_gn_fusable is None:
-            return False
-        fake = 1 << 20
-        p = L.IgemmParams(dtype=src0.dt, taps=9, stride=1, upsample=0, n_img=self.n[self._dom(src0, src1)], Hin=src0.H, Win=src0.W,
-                          Hout=src0.H, Wout=src0.W, src0=fake, C0=src0.C, ld0=src0.ld, src1=fake if src1 is not None else None,
-                          C1=src1.C if src1 is not None else 0, ld1=src1.ld if src1 is not None else 0, W=fake, Cout=Cout,
-                          tile_n=tile_n, out=fake, out_dtype=src0.dt if out_dt is None else out_dt, out_ld=Cout)
-        return bool(L.lib().dc_igemm_gn_fusable(p))
+        return bool(L.lib().dc_igemm_gn_fusable(self._probe(src0, Cout=Cout, n_img=self.n[self._dom(src0, src1)], src1=src1,
+                                                            C1=src1.C if src1 is not None else 0, ld1=src1.ld if src1 is not None else 0,
+                                                            tile_n=tile_n, out_dtype=src0.dt if out_dt is None else out_dt)))
 
     def gn_ws_ok(self, x, Cout):
         """Would a 3x3 stride-1 conv of x with a fused GroupNorm prologue run on the wave-specialised halo kernel (conv3_ws.hip: the
         transform is done by loader waves, not in the MFMA waves' stream)?  Asked through dc_igemm_variant."""
-        fake = 1 << 20
-        p = L.IgemmParams(dtype=x.dt, taps=9, stride=1, upsample=0, n_img=self.n[x.dom], Hin=x.H, Win=x.W, Hout=x.H, Wout=x.W,
-                          src0=fake, C0=x.C, ld0=x.ld, W=fake, Cout=Cout, tile_n=128, out=fake, out_dtype=x.dt, out_ld=Cout,
-                          gn_scale=fake, gn_shift=fake, gn_silu=1)
+        p = self._probe(x, Cout=Cout, gn_scale=FAKE_PTR, gn_shift=FAKE_PTR, gn_silu=1)
         return L.lib().dc_igemm_variant(p).decode().startswith("conv3_ws")
 
     def groupnorm_stats(self, name, x0, gamma, beta, groups, eps, x1=None):
