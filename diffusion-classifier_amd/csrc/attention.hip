@@ -135,22 +135,12 @@ extern "C" int dc_attention(const dc_attention_params* p, dc_stream stream) {
   DC_REQUIRE(nb < (1LL << 31), DC_ERR_SHAPE, "dc_attention: grid too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)nb), blk(256);
-#define DC_ATTN_LAUNCH1(T, W)                                                                              \
-  do {                                                                                                     \
-    static bool done = false;                                                                              \
-    if (!done) {                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_small_kernel<T, W>),                    \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-      done = true;                                                                                         \
-    }                                                                                                      \
-    hipLaunchKernelGGL((attn_small_kernel<T, W>), grid, blk, lds, s, a);                                   \
-  } while (0)
-#define DC_ATTN_LAUNCH(T) do { if (SW == 24) DC_ATTN_LAUNCH1(T, 24); else DC_ATTN_LAUNCH1(T, 16); } while (0)
-  if (p->dtype == DC_F32) DC_ATTN_LAUNCH(float);
-  else if (p->dtype == DC_BF16) DC_ATTN_LAUNCH(__bf16);
-  else if (p->dtype == DC_F16) DC_ATTN_LAUNCH(_Float16);
-  else { dc_set_error("dc_attention: dtype %d", p->dtype); return DC_ERR_DTYPE; }
-#undef DC_ATTN_LAUNCH
-#undef DC_ATTN_LAUNCH1
-  return dc_check_launch("dc_attention");
+  return dc_by_dtype(p->dtype, "dc_attention: dtype", [&](auto t) {
+    using T = decltype(t);
+    void (*kern)(const AttnArgs) = SW == 24 ? attn_small_kernel<T, 24> : attn_small_kernel<T, 16>;
+    static bool done[2] = {};
+    if (!done[SW == 24]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done[SW == 24] = true; }
+    hipLaunchKernelGGL(kern, grid, blk, lds, s, a);
+    return dc_check_launch("dc_attention");
+  });
 }

@@ -160,15 +160,13 @@ int dc_attn_mfma_launch(const dc_attention_params* p, hipStream_t s) {
     dc_set_error("dc_attention: q/k/v must be 16-byte aligned with ld %% 8 == 0");
     return DC_ERR_ALIGN;
   }
-  static bool done_b = false, done_h = false;
-  if (p->dtype == DC_BF16) {
-    if (!done_b) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done_b = true; }
-    hipLaunchKernelGGL((attn_mfma_kernel<__bf16>), dim3((unsigned)nb), dim3(256), lds, s, a);
-  } else {
-    if (!done_h) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done_h = true; }
-    hipLaunchKernelGGL((attn_mfma_kernel<_Float16>), dim3((unsigned)nb), dim3(256), lds, s, a);
-  }
-  return dc_check_launch("dc_attention(mfma)");
+  return dc_by_dtype16(p->dtype, "dc_attention: dtype", [&](auto t) {
+    using T = decltype(t);
+    static bool done = false;
+    if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done = true; }
+    hipLaunchKernelGGL((attn_mfma_kernel<T>), dim3((unsigned)nb), dim3(256), lds, s, a);
+    return dc_check_launch("dc_attention(mfma)");
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -566,14 +564,13 @@ bool dc_attn_wave_applicable(const dc_attention_params* p) {
 
 int dc_attn_wave_launch(const dc_attention_params* p, hipStream_t s) {
   FlashArgs a{p->q, p->k, p->v, p->out, p->n, p->L, p->heads, p->d, p->ld_qkv, p->ld_out, p->scale};
-  const bool bf = p->dtype == DC_BF16;
   const bool two = p->L <= 32;                                 // 2 or 4 key tiles (an even count: the P.V MFMAs take key tiles in pairs)
-#define DC_AW(D) (two ? (bf ? launch_attn_wave<__bf16, D, 2>(a, s) : launch_attn_wave<_Float16, D, 2>(a, s)) \
-                      : (bf ? launch_attn_wave<__bf16, D, 4>(a, s) : launch_attn_wave<_Float16, D, 4>(a, s)))
-  if (p->d == 32) return DC_AW(32);
-  if (p->d == 64) return DC_AW(64);
-  return DC_AW(128);
-#undef DC_AW
+  return dc_by_dtype16(p->dtype, "dc_attention: dtype", [&](auto t) {
+    using T = decltype(t);
+    if (p->d == 32) return two ? launch_attn_wave<T, 32, 2>(a, s) : launch_attn_wave<T, 32, 4>(a, s);
+    if (p->d == 64) return two ? launch_attn_wave<T, 64, 2>(a, s) : launch_attn_wave<T, 64, 4>(a, s);
+    return two ? launch_attn_wave<T, 128, 2>(a, s) : launch_attn_wave<T, 128, 4>(a, s);
+  });
 }
 
 bool dc_attn_flash_applicable(const dc_attention_params* p) {
@@ -585,9 +582,11 @@ int dc_attn_flash_launch(const dc_attention_params* p, hipStream_t s) {
   FlashArgs a{p->q, p->k, p->v, p->out, p->n, p->L, p->heads, p->d, p->ld_qkv, p->ld_out, p->scale};
   const long long nb = (long long)p->n * p->heads * ((p->L + 127) / 128);
   if (nb >= (1LL << 31)) { dc_set_error("dc_attention: grid too large"); return DC_ERR_SHAPE; }
-  const bool bf = p->dtype == DC_BF16;
-  if (p->d == 32) return bf ? launch_flash_t<__bf16, 32>(a, nb, s) : launch_flash_t<_Float16, 32>(a, nb, s);
-  if (p->d == 64) return bf ? launch_flash_t<__bf16, 64>(a, nb, s) : launch_flash_t<_Float16, 64>(a, nb, s);
-  if (p->d == 96) return bf ? launch_flash_t<__bf16, 96>(a, nb, s) : launch_flash_t<_Float16, 96>(a, nb, s);
-  return bf ? launch_flash_t<__bf16, 128>(a, nb, s) : launch_flash_t<_Float16, 128>(a, nb, s);
+  return dc_by_dtype16(p->dtype, "dc_attention: dtype", [&](auto t) {
+    using T = decltype(t);
+    if (p->d == 32) return launch_flash_t<T, 32>(a, nb, s);
+    if (p->d == 64) return launch_flash_t<T, 64>(a, nb, s);
+    if (p->d == 96) return launch_flash_t<T, 96>(a, nb, s);
+    return launch_flash_t<T, 128>(a, nb, s);
+  });
 }

@@ -136,6 +136,20 @@ __device__ __forceinline__ float load_as(const void* base, size_t idx, int dtype
 
 static inline int dc_dtype_size(int dt) { return dt == DC_F32 ? 4 : 2; }
 
+// ---- the one runtime-dtype switch of the host side ---------------------------------------------------------------------------
+// dc_by_dtype(dtype, "dc_groupnorm: dtype", [&](auto t) { using T = decltype(t); ...launch<T>...; return DC_OK; }) calls f with a value of
+// the element type and returns its status; any other dtype: DC_ERR_DTYPE, "<what> <dtype>".  dc_by_dtype16: kernels with no fp32 instance.
+template <typename F> static inline int dc_by_dtype16(int dtype, const char* what, F&& f) {
+  if (dtype == DC_BF16) return f(__bf16{});
+  if (dtype == DC_F16) return f(_Float16{});
+  dc_set_error("%s %d", what, dtype);
+  return DC_ERR_DTYPE;
+}
+template <typename F> static inline int dc_by_dtype(int dtype, const char* what, F&& f) {
+  if (dtype == DC_F32) return f(float{});
+  return dc_by_dtype16(dtype, what, f);
+}
+
 // ---- asynchronous LDS fragment reads with hand-counted waits -------------------------------------------------
 // hipcc waits lgkmcnt(0) in front of the first MFMA that uses a ds_read result, and under register pressure it
 // even re-serialises "read, wait, 4 MFMA" (seen in the ISA of both GEMM kernels).  These helpers issue the reads

@@ -996,32 +996,24 @@ bool dc_conv3_up4_applicable(const IgemmArgs& a, int dtype) {
   return dc_conv3_halo_applicable(lo, dtype);
 }
 
+// a: the extents the kernel walks (8 or 4 waves by them)
+static int launch_halo_by_dtype(const IgemmArgs& a, int dtype, int n_img, hipStream_t s, bool up4) {
+  const bool w8 = dc_conv3_halo_waves(a.Hin, a.Win) == 8;
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) {
+    return w8 ? launch_halo<decltype(t), 8>(a, n_img, s, up4) : launch_halo<decltype(t), 4>(a, n_img, s, up4);
+  });
+}
+
 int dc_conv3_up4_launch(const IgemmArgs& a0, int dtype, int n_img, hipStream_t s) {
   IgemmArgs a = a0;
   a.upsample = 0; a.Hin = a0.Hin >> 1; a.Win = a0.Win >> 1;      // the kernel walks the LOW-resolution image
   a.Ktot = 4 * (a.C0 + a.C1);
   a.tiles_n = 4 * a0.tiles_n;                                    // phase-major N tiles
   a.n_fast = 0;
-  if (dc_conv3_halo_waves(a.Hin, a.Win) == 8) {
-    if (dtype == DC_BF16) return launch_halo<__bf16, 8>(a, n_img, s, true);
-    if (dtype == DC_F16) return launch_halo<_Float16, 8>(a, n_img, s, true);
-    return launch_halo<float, 8>(a, n_img, s, true);
-  }
-  if (dtype == DC_BF16) return launch_halo<__bf16, 4>(a, n_img, s, true);
-  if (dtype == DC_F16) return launch_halo<_Float16, 4>(a, n_img, s, true);
-  return launch_halo<float, 4>(a, n_img, s, true);
+  return launch_halo_by_dtype(a, dtype, n_img, s, true);
 }
 
-int dc_conv3_halo_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) {
-  if (dc_conv3_halo_waves(a.Hin, a.Win) == 8) {
-    if (dtype == DC_BF16) return launch_halo<__bf16, 8>(a, n_img, s);
-    if (dtype == DC_F16) return launch_halo<_Float16, 8>(a, n_img, s);
-    return launch_halo<float, 8>(a, n_img, s);
-  }
-  if (dtype == DC_BF16) return launch_halo<__bf16, 4>(a, n_img, s);
-  if (dtype == DC_F16) return launch_halo<_Float16, 4>(a, n_img, s);
-  return launch_halo<float, 4>(a, n_img, s);
-}
+int dc_conv3_halo_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) { return launch_halo_by_dtype(a, dtype, n_img, s, false); }
 
 template <typename T>
 static int launch_thin(const IgemmArgs& a0, int n_img, hipStream_t s) {
@@ -1055,7 +1047,5 @@ static int launch_thin(const IgemmArgs& a0, int n_img, hipStream_t s) {
 }
 
 int dc_conv3_thin_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) {
-  if (dtype == DC_BF16) return launch_thin<__bf16>(a, n_img, s);
-  if (dtype == DC_F16) return launch_thin<_Float16>(a, n_img, s);
-  return launch_thin<float>(a, n_img, s);
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_thin<decltype(t)>(a, n_img, s); });
 }

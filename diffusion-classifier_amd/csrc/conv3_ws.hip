@@ -420,7 +420,5 @@ static int launch_ws(const IgemmArgs& a0, int n_img, hipStream_t s) {
 }
 
 int dc_conv3_ws_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) {
-  if (dtype == DC_BF16) return launch_ws<__bf16>(a, n_img, s);
-  if (dtype == DC_F16) return launch_ws<_Float16>(a, n_img, s);
-  return launch_ws<float>(a, n_img, s);
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_ws<decltype(t)>(a, n_img, s); });
 }

@@ -74,11 +74,10 @@ extern "C" int dc_qsample(const dc_qsample_params* p, dc_stream stream) {
   const long long total = (long long)p->n_bj * (p->H / pp) * (p->W / pp) * (p->ld / epc);
   const unsigned grid = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (p->out_dtype == DC_F32) hipLaunchKernelGGL((qsample_kernel<float>), dim3(grid), dim3(256), 0, s, a);
-  else if (p->out_dtype == DC_BF16) hipLaunchKernelGGL((qsample_kernel<__bf16>), dim3(grid), dim3(256), 0, s, a);
-  else if (p->out_dtype == DC_F16) hipLaunchKernelGGL((qsample_kernel<_Float16>), dim3(grid), dim3(256), 0, s, a);
-  else { dc_set_error("dc_qsample: out_dtype %d", p->out_dtype); return DC_ERR_DTYPE; }
-  return dc_check_launch("dc_qsample");
+  return dc_by_dtype(p->out_dtype, "dc_qsample: out_dtype", [&](auto t) {
+    hipLaunchKernelGGL((qsample_kernel<decltype(t)>), dim3(grid), dim3(256), 0, s, a);
+    return dc_check_launch("dc_qsample");
+  });
 }
 
 // ------------------------------------------------------------------ Philox normal --

@@ -348,14 +348,8 @@ static int igemm_launch(const IgemmChoice& c, const IgemmArgs& a, const dc_igemm
     case IG_UP4_PIPE: return dc_igemm_launch_pipe_up4(a, p->dtype, s);
     case IG_XREG: return dc_igemm_xreg_launch(a, p->dtype, s);
     case IG_PIPE: return dc_igemm_launch_pipe(a, p->dtype, c.shape, s);
-    case IG_REG128:
-      if (p->dtype == DC_BF16) return launch<__bf16, 128, 128, 2, 2>(a, s);
-      if (p->dtype == DC_F16) return launch<_Float16, 128, 128, 2, 2>(a, s);
-      return launch<float, 128, 128, 2, 2>(a, s);
-    case IG_REG32:
-      if (p->dtype == DC_BF16) return launch<__bf16, 128, 32, 4, 1>(a, s);
-      if (p->dtype == DC_F16) return launch<_Float16, 128, 32, 4, 1>(a, s);
-      return launch<float, 128, 32, 4, 1>(a, s);
+    case IG_REG128: return dc_by_dtype(p->dtype, "dc_igemm: dtype", [&](auto t) { return launch<decltype(t), 128, 128, 2, 2>(a, s); });
+    case IG_REG32: return dc_by_dtype(p->dtype, "dc_igemm: dtype", [&](auto t) { return launch<decltype(t), 128, 32, 4, 1>(a, s); });
   }
   return DC_ERR_ARG;
 }

@@ -310,31 +310,16 @@ int dc_igemm_launch_pipe_up4(const IgemmArgs& a0, int dtype, hipStream_t s) {
   a.nk = 4 * a.cpt;
   a.tiles_n = 4 * a0.tiles_n;
   a.n_fast = 0;
-  if (dtype == DC_BF16) return launch_pipe<__bf16, 256, 3, 1, 5, false>(a, s);
-  if (dtype == DC_F16) return launch_pipe<_Float16, 256, 3, 1, 5, false>(a, s);
-  return launch_pipe<float, 256, 3, 1, 5, false>(a, s);
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_pipe<decltype(t), 256, 3, 1, 5, false>(a, s); });
 }
 
 // shape: dc_igemm_pipe_shape(a)
 int dc_igemm_launch_pipe(const IgemmArgs& a, int dtype, int shape, hipStream_t s) {
-  const bool slim = a.taps == 1;
-  if (shape == 0) {
-    if (slim) {
-      if (dtype == DC_BF16) return launch_pipe<__bf16, 128, 2, 1, -1, true>(a, s);
-      if (dtype == DC_F16) return launch_pipe<_Float16, 128, 2, 1, -1, true>(a, s);
-      return launch_pipe<float, 128, 2, 1, -1, true>(a, s);
-    }
-    if (dtype == DC_BF16) return launch_pipe<__bf16, 128, 2, 1, -1, false>(a, s);
-    if (dtype == DC_F16) return launch_pipe<_Float16, 128, 2, 1, -1, false>(a, s);
-    return launch_pipe<float, 128, 2, 1, -1, false>(a, s);
-  }
   if (shape == 2) return dc_igemm_launch_wide8(a, dtype, s);     // the 256 x 256 tile lives in igemm_wide.hip (8-phase loop)
-  if (slim) {
-    if (dtype == DC_BF16) return launch_pipe<__bf16, 256, 3, 1, -1, true>(a, s);
-    if (dtype == DC_F16) return launch_pipe<_Float16, 256, 3, 1, -1, true>(a, s);
-    return launch_pipe<float, 256, 3, 1, -1, true>(a, s);
-  }
-  if (dtype == DC_BF16) return launch_pipe<__bf16, 256, 3, 1, -1, false>(a, s);
-  if (dtype == DC_F16) return launch_pipe<_Float16, 256, 3, 1, -1, false>(a, s);
-  return launch_pipe<float, 256, 3, 1, -1, false>(a, s);
+  const bool slim = a.taps == 1;
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) {
+    using T = decltype(t);
+    if (shape == 0) return slim ? launch_pipe<T, 128, 2, 1, -1, true>(a, s) : launch_pipe<T, 128, 2, 1, -1, false>(a, s);
+    return slim ? launch_pipe<T, 256, 3, 1, -1, true>(a, s) : launch_pipe<T, 256, 3, 1, -1, false>(a, s);
+  });
 }

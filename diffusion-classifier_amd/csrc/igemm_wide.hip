@@ -265,7 +265,5 @@ static int launch_wide8_t(const IgemmArgs& a, hipStream_t s) {
 
 // 1-tap GEMM on the 256 x 256 tile (dc_igemm_pipe_shape(a) == 2 decides; same epilogue variants as the 2-stage loop it replaces)
 int dc_igemm_launch_wide8(const IgemmArgs& a, int dtype, hipStream_t s) {
-  if (dtype == DC_BF16) return launch_wide8_t<__bf16>(a, s);
-  if (dtype == DC_F16) return launch_wide8_t<_Float16>(a, s);
-  return launch_wide8_t<float>(a, s);
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_wide8_t<decltype(t)>(a, s); });
 }

@@ -302,6 +302,7 @@ static int xreg_launch_t(const IgemmArgs& a0, hipStream_t s) {
 int dc_igemm_xreg_launch(const IgemmArgs& a, int dtype, hipStream_t s) {
   // K <= 256: 96 rows per workgroup (3 fragments x 8 chunks = 96 activation registers per wave);
   // K <= 512: 64 rows (2 x 16 = 128 registers)
-  if (a.Ktot <= 256) return dtype == DC_BF16 ? xreg_launch_t<__bf16, 3, 8>(a, s) : xreg_launch_t<_Float16, 3, 8>(a, s);
-  return dtype == DC_BF16 ? xreg_launch_t<__bf16, 2, 16>(a, s) : xreg_launch_t<_Float16, 2, 16>(a, s);
+  return dc_by_dtype16(dtype, "dc_igemm: dtype", [&](auto t) {
+    return a.Ktot <= 256 ? xreg_launch_t<decltype(t), 3, 8>(a, s) : xreg_launch_t<decltype(t), 2, 16>(a, s);
+  });
 }

@@ -6,6 +6,7 @@
 // HBM-bound: every transfer is a 16-byte chunk per lane, statistics in fp32, deterministic
 // (fixed-order) reductions — no float atomics.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 #include "gn_fold.h"
 
@@ -494,15 +495,6 @@ __global__ __launch_bounds__(256) void gn_wave_kernel(const GnArgs a, const int 
   }
 }
 
-template <typename T>
-static void launch_gn_wave(const GnArgs& a, int n, int nch, size_t lds, hipStream_t s) {
-  dim3 g((unsigned)((n + 3) / 4)), b(256);
-  if (nch <= 4) hipLaunchKernelGGL((gn_wave_kernel<T, 4>), g, b, lds, s, a, n);
-  else if (nch <= 8) hipLaunchKernelGGL((gn_wave_kernel<T, 8>), g, b, lds, s, a, n);
-  else if (nch <= 16) hipLaunchKernelGGL((gn_wave_kernel<T, 16>), g, b, lds, s, a, n);
-  else hipLaunchKernelGGL((gn_wave_kernel<T, 32>), g, b, lds, s, a, n);
-}
-
 // statistics-only mode: fold the split partials and emit the per-(sample, channel) affine for dc_igemm's fused prologue
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const GnArgs a, float* out_scale, float* out_shift) {
   __shared__ float st[2 * 64];
@@ -555,7 +547,31 @@ extern "C" int32_t dc_groupnorm_splits(int32_t n, int32_t HW, int32_t C) {
   return s < 1 ? 1 : (s > 64 ? 64 : s);
 }
 
-extern "C" int dc_groupnorm(const dc_groupnorm_params* p, dc_stream stream) {
+// ---- dispatch ---------------------------------------------------------------------------------------------------------------------
+// dc_groupnorm and dc_groupnorm_variant go the same way: gn_validate, then gn_choose — the one place that picks among the eight
+// launch sequences — and then gn_launch or the name of the choice.
+enum GnRoute { GN_QAFFINE, GN_STATS, GN_WAVE, GN_SPAN, GN_QFOLD_SPAN, GN_IMAGE, GN_STATS_APPLY, GN_QFOLD_APPLY };
+
+// What dc_groupnorm does with a valid problem.  block / lds / grid: the route's last kernel (GN_STATS: the statistics sweep, which
+// gn_finalize_kernel follows); lds_pre: the kernel in front of it (the statistics sweep of GN_STATS_APPLY, gn_qfold_kernel)
+struct GnChoice {
+  GnRoute route;
+  unsigned block;
+  size_t lds, lds_pre = 0;
+  int spans = 0, nch = 0;          // GN_SPAN / GN_QFOLD_SPAN: 16 KiB spans per sample; GN_WAVE: chunks per lane
+  unsigned grid = 0;
+  bool fold() const { return route == GN_QFOLD_SPAN || route == GN_QFOLD_APPLY; }      // the quad records folded once per sample first
+};
+
+// everything a route may depend on: dtype, statistics source, mode and the extents of ONE sample — no n
+struct GnShape { int dtype, HW, C, C1, groups, qparts; bool qstats, stats_only; };
+static int gn_tpr(int CP) { int t = 1; while (t < CP) t <<= 1; return t; }      // lanes per pixel: 16-byte chunks per pixel, rounded up to 2^k
+static size_t gn_stats_lds(int dtype, int C) {
+  const int tpr = gn_tpr(C / (16 / dc_dtype_size(dtype)));
+  return (size_t)2 * (256 / (tpr < 256 ? tpr : 256)) * C * sizeof(float);
+}
+
+static int gn_validate(const dc_groupnorm_params* p) {
   DC_REQUIRE(p && p->x && p->gamma && p->beta && p->ws, DC_ERR_ARG, "dc_groupnorm: null pointer");
   const bool stats_only = p->y == nullptr;
   if (stats_only) DC_REQUIRE(p->out_scale && p->out_shift && (p->groups <= 64 || p->qstats), DC_ERR_ARG, "dc_groupnorm: statistics-only mode needs out_scale/out_shift and groups <= 64");
@@ -568,63 +584,41 @@ extern "C" int dc_groupnorm(const dc_groupnorm_params* p, dc_stream stream) {
   DC_REQUIRE(p->n > 0 && p->HW > 0 && p->splits > 0 && p->splits <= p->HW, DC_ERR_SHAPE, "dc_groupnorm: n/HW/splits");
   DC_REQUIRE((C1 > 0) == (p->x1 != nullptr), DC_ERR_ARG, "dc_groupnorm: x1/C1 mismatch");
   DC_REQUIRE(p->dtype == p->out_dtype, DC_ERR_DTYPE, "dc_groupnorm: in/out dtype must match");
-  GnArgs a;
-  a.x0 = p->x; a.map0 = p->map0; a.x1 = p->x1; a.map1 = p->map1; a.y = p->y; a.gamma = p->gamma; a.beta = p->beta; a.ws = p->ws;
-  a.C0 = p->C; a.C1 = C1; a.HW = p->HW; a.groups = p->groups; a.silu = p->silu; a.splits = p->splits;
-  a.out_dtype = p->out_dtype; a.eps = p->eps;
-  a.qstats = nullptr; a.qparts = 0; a.wsplits = p->splits;
   if (p->qstats) {
     DC_REQUIRE(C1 == 0 && p->qparts > 0 && p->HW % p->qparts == 0 && (C / p->groups) % 4 == 0 && ((uintptr_t)p->qstats & 7) == 0, DC_ERR_ARG,
                "dc_groupnorm: qstats needs one source, qparts > 0 dividing HW and (C/groups) %% 4 == 0 (C=%d groups=%d C1=%d HW=%d qparts=%d)", C, p->groups, C1, p->HW, p->qparts);
   }
-  const int CP = C / epc;
-  int TPR = 1; while (TPR < CP && TPR < 256) TPR <<= 1;
-  const int PL = 256 / TPR;
-  const size_t lds_stats = (size_t)2 * PL * C * sizeof(float);
-  DC_REQUIRE(lds_stats <= 64 * 1024, DC_ERR_SHAPE, "dc_groupnorm: C=%d too large", C);
-  const size_t lds_apply = (size_t)2 * p->groups * sizeof(float);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const long long nb = (long long)p->splits * p->n;
-  DC_REQUIRE(nb < (1LL << 31), DC_ERR_SHAPE, "dc_groupnorm: grid too large");
-  dim3 grid((unsigned)nb), blk(256);
-  if (stats_only && p->qstats) {
-    DC_REQUIRE(p->groups <= 4096, DC_ERR_SHAPE, "dc_groupnorm: groups=%d", p->groups);
-    a.qstats = p->qstats; a.qparts = p->qparts;
-    hipLaunchKernelGGL(gn_qaffine_kernel, dim3((unsigned)p->n), blk, lds_apply, s, a, p->out_scale, p->out_shift);
-    return dc_check_launch("dc_groupnorm(qaffine)");
-  }
-  if (stats_only) {
-    if (p->dtype == DC_F32) hipLaunchKernelGGL((gn_stats_kernel<float>), grid, blk, lds_stats, s, a);
-    else if (p->dtype == DC_BF16) hipLaunchKernelGGL((gn_stats_kernel<__bf16>), grid, blk, lds_stats, s, a);
-    else if (p->dtype == DC_F16) hipLaunchKernelGGL((gn_stats_kernel<_Float16>), grid, blk, lds_stats, s, a);
-    else { dc_set_error("dc_groupnorm: dtype %d", p->dtype); return DC_ERR_DTYPE; }
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(p->n), blk, 0, s, a, p->out_scale, p->out_shift);
-    return dc_check_launch("dc_groupnorm(stats)");
-  }
-  // samples of up to 4 MiB: one workgroup per sample (gn_image_kernel).  The choice depends on (HW, C) only, never
-  // on n, so a score does not depend on how many samples share a launch.
-  const size_t img_bytes = (size_t)p->HW * C * dc_dtype_size(p->dtype);
-  constexpr size_t img_cap = 4u << 20;
+  DC_REQUIRE(gn_stats_lds(p->dtype, C) <= 64 * 1024, DC_ERR_SHAPE, "dc_groupnorm: C=%d too large", C);
+  DC_REQUIRE((long long)p->splits * p->n < (1LL << 31), DC_ERR_SHAPE, "dc_groupnorm: grid too large");      // a grid-size guard, see gn_grid
+  if (stats_only && p->qstats) DC_REQUIRE(p->groups <= 4096, DC_ERR_SHAPE, "dc_groupnorm: groups=%d", p->groups);
+  return DC_OK;
+}
+
+// The launch sequence a valid problem prefers among those not in `barred` (a bit per GnRoute), with the geometry that does not depend
+// on n.  A function of (dtype, HW, C, groups, statistics source) and the two environment switches only, never of n: the routes sum in
+// different orders, and a score must not depend on how many samples share a launch (micro-batch size, world size).
+static GnChoice gn_route(const GnShape& k, unsigned barred) {
+  const auto open = [barred](GnRoute r) { return !(barred >> r & 1); };
+  const int C = k.C, CP = C / (16 / dc_dtype_size(k.dtype)), tpr = gn_tpr(CP), CQ = C >> 2;
+  const size_t lds_stats = gn_stats_lds(k.dtype, C), lds_apply = (size_t)2 * k.groups * sizeof(float);
+  const size_t lds_fold = (size_t)(256 / (CQ < 256 ? CQ : 256)) * CQ * 3 * sizeof(float);
+  // statistics-only mode: the per-(sample, channel) affine for dc_igemm's fused prologue, from the producer's quad records or a sweep
+  if (k.stats_only) return k.qstats ? GnChoice{GN_QAFFINE, 256, lds_apply} : GnChoice{GN_STATS, 256, lds_stats};
   // tiny samples without producer statistics: one wave per sample, register resident (gn_wave_kernel)
   static const bool no_wave = getenv("DCAMD_GN_NO_WAVE") != nullptr;
-  if (!no_wave && !p->qstats && CP <= 64 && p->n < (1 << 30)) {
-    int tpr = 1; while (tpr < CP) tpr <<= 1;
-    const int plw = 64 / tpr, nch = (p->HW + plw - 1) / plw;
-    const size_t lds_w = (size_t)4 * (2 * C + 2 * p->groups) * sizeof(float);
-    if (nch <= 32 && lds_w <= 64 * 1024) {
-      if (p->dtype == DC_F32) launch_gn_wave<float>(a, p->n, nch, lds_w, s);
-      else if (p->dtype == DC_BF16) launch_gn_wave<__bf16>(a, p->n, nch, lds_w, s);
-      else if (p->dtype == DC_F16) launch_gn_wave<_Float16>(a, p->n, nch, lds_w, s);
-      else { dc_set_error("dc_groupnorm: dtype %d", p->dtype); return DC_ERR_DTYPE; }
-      return dc_check_launch("dc_groupnorm(wave)");
-    }
+  if (open(GN_WAVE) && !no_wave && !k.qstats && CP <= 64) {
+    const int plw = 64 / tpr, nch = (k.HW + plw - 1) / plw;
+    const size_t lds_w = (size_t)4 * (2 * C + 2 * k.groups) * sizeof(float);
+    if (nch <= 32 && lds_w <= 64 * 1024) return GnChoice{GN_WAVE, 256, lds_w, 0, 0, nch};
   }
+  const size_t img_bytes = (size_t)k.HW * C * dc_dtype_size(k.dtype);
+  constexpr size_t img_cap = 4u << 20;
   // With the producer's statistics the normalise sweep needs no reduction across a sample, so a big sample is better spread
   // over many workgroups (gn_qfold_kernel + gn_apply_kernel, HW/256 splits) than streamed by ONE: the CheXpert / IPMSA plans
-  // put only a few hundred 1-4 MiB samples into a launch (cfg3: 4.3 -> 5.x TB/s).  The threshold is a function of (HW, C) only.
+  // put only a few hundred 1-4 MiB samples into a launch (cfg3: 4.3 -> 5.x TB/s).
   constexpr size_t qsplit_min = 1u << 20;
-  const bool qsplit = p->qstats != nullptr && img_bytes >= qsplit_min;
-  // producer statistics + a sample that divides into whole 16 KiB spans of one column set: gn_span_kernel (a function of (HW, C) only).
+  const bool qsplit = k.qstats && img_bytes >= qsplit_min;
+  // producer statistics + a sample that divides into whole 16 KiB spans of one column set: gn_span_kernel.
   // Default for samples of 1 MiB and more (the CheXpert / IPMSA plans, where it replaces gn_apply_kernel's split sweep: cfg3 +0.8 %,
   // cfg4 +1.7 % per step); DCAMD_GN_SPAN forces it for every size (tests/test_gpu_ops.py).  For the small samples of cfg2 it
   // is NOT the default: alone it streams 5.9-6.4 TB/s against gn_image_kernel's 5.2-5.6, and inside the scoring step GroupNorm drops
@@ -632,60 +626,95 @@ extern "C" int dc_groupnorm(const dc_groupnorm_params* p, dc_stream stream) {
   // that step runs at the socket's power cap (~1.37 kW, 2.08-2.18 GHz by rocm-smi), so a phase that moves the same bytes in less
   // time only hands a hotter chip to the next phase.  DESIGN.md §6c.
   static const bool span_all = getenv("DCAMD_GN_SPAN") != nullptr;
-  const bool no_span = !(span_all || qsplit);      // default: only the samples of 1 MiB and more, which had the split apply sweep
-  const long long chunks = (long long)p->HW * CP;
-  if (!no_span && p->qstats && C1 == 0 && CP <= 256 && (CP & (CP - 1)) == 0 && chunks % 1024 == 0 && p->groups <= 2048 &&
-      (long long)p->n * (chunks / 1024) < (1LL << 31)) {
-    a.qstats = p->qstats; a.qparts = p->qparts;
-    const bool fold = qsplit || (long long)p->qparts * (C >> 2) > 8 * 256;
-    if (fold) {                                // many quad records per sample: fold them once per sample, not once per span
-      const int CQ = C >> 2, cols = CQ < 256 ? CQ : 256;
-      hipLaunchKernelGGL(gn_qfold_kernel, dim3((unsigned)p->n), blk, (size_t)(256 / cols) * CQ * 3 * sizeof(float), s, a);
-      a.qstats = nullptr; a.wsplits = 1;
-    }
-    const int spans = (int)(chunks / 1024);
-    const size_t lds_span = lds_apply + (size_t)(fold ? p->groups : p->qparts * (C >> 2)) * sizeof(float2);
-    dim3 gs((unsigned)((long long)p->n * spans));
-    if (p->dtype == DC_F32) hipLaunchKernelGGL((gn_span_kernel<float, false>), gs, blk, lds_span, s, a, spans);
-    else if (p->dtype == DC_BF16) hipLaunchKernelGGL((gn_span_kernel<__bf16, true>), gs, blk, lds_span, s, a, spans);
-    else if (p->dtype == DC_F16) hipLaunchKernelGGL((gn_span_kernel<_Float16, false>), gs, blk, lds_span, s, a, spans);
-    else { dc_set_error("dc_groupnorm: dtype %d", p->dtype); return DC_ERR_DTYPE; }
-    return dc_check_launch("dc_groupnorm(span)");
+  const long long chunks = (long long)k.HW * CP;
+  if ((span_all || qsplit) && k.qstats && k.C1 == 0 && CP <= 256 && (CP & (CP - 1)) == 0 && chunks % 1024 == 0 && k.groups <= 2048) {
+    const bool fold = qsplit || (long long)k.qparts * CQ > 8 * 256;      // many quad records per sample: fold them once per sample, not once per span
+    const GnRoute r = fold ? GN_QFOLD_SPAN : GN_SPAN;
+    const size_t lds_span = lds_apply + (size_t)(fold ? k.groups : k.qparts * CQ) * sizeof(float2);
+    if (open(r)) return GnChoice{r, 256, lds_span, fold ? lds_fold : 0, (int)(chunks / 1024)};
   }
-  if (!qsplit && img_bytes <= img_cap && CP <= 512 && p->groups <= 512 && p->n < (1 << 30)) {
-    a.qstats = p->qstats; a.qparts = p->qparts;
-    int tpr = 1; while (tpr < CP) tpr <<= 1;
-    const size_t lds_img = (size_t)2 * (512 / tpr) * C * sizeof(float);
-    dim3 g1((unsigned)p->n), b1(512);
-    if (p->dtype == DC_F32) hipLaunchKernelGGL((gn_image_kernel<float>), g1, b1, lds_img, s, a);
-    else if (p->dtype == DC_BF16) hipLaunchKernelGGL((gn_image_kernel<__bf16>), g1, b1, lds_img, s, a);
-    else if (p->dtype == DC_F16) hipLaunchKernelGGL((gn_image_kernel<_Float16>), g1, b1, lds_img, s, a);
-    else { dc_set_error("dc_groupnorm: dtype %d", p->dtype); return DC_ERR_DTYPE; }
-    return dc_check_launch("dc_groupnorm(image)");
-  }
+  // samples of up to 4 MiB: one workgroup per sample (gn_image_kernel)
+  if (open(GN_IMAGE) && !qsplit && img_bytes <= img_cap && CP <= 512 && k.groups <= 512)
+    return GnChoice{GN_IMAGE, 512, (size_t)2 * (512 / tpr) * C * sizeof(float)};
   // large samples: split scheme; with the producer's quad statistics a small fold launch replaces the statistics sweep
   // (the tensor is read once, not twice)
-  const bool sweep = p->qstats == nullptr;
-  if (!sweep) {
-    a.qstats = p->qstats; a.qparts = p->qparts;
-    const int CQ = C >> 2, cols = CQ < 256 ? CQ : 256;
-    hipLaunchKernelGGL(gn_qfold_kernel, dim3((unsigned)p->n), blk, (size_t)(256 / cols) * CQ * 3 * sizeof(float), s, a);
-    a.qstats = nullptr; a.wsplits = 1;
+  return k.qstats ? GnChoice{GN_QFOLD_APPLY, 256, lds_apply, lds_fold} : GnChoice{GN_STATS_APPLY, 256, lds_apply, lds_stats};
+}
+
+// The only place where n meets the choice: the grid of a route's kernels.  One of 2^31 workgroups or more (wave, image: from 2^30
+// samples on) is a grid-size guard, not a preference: gn_choose bars that route and the problem takes the next one gn_route offers.
+// The split routes' splits * n < 2^31 is refused up front by gn_validate, so the last route always fits.
+static long long gn_grid(const GnChoice& c, int n, int splits) {
+  constexpr long long over = 1LL << 31;
+  switch (c.route) {
+    case GN_QAFFINE: return n;
+    case GN_WAVE: return n < (1 << 30) ? (n + 3) / 4 : over;
+    case GN_IMAGE: return n < (1 << 30) ? n : over;
+    case GN_SPAN: case GN_QFOLD_SPAN: return (long long)n * c.spans;
+    default: return (long long)splits * n;
   }
-  if (p->dtype == DC_F32) {
-    if (sweep) hipLaunchKernelGGL((gn_stats_kernel<float>), grid, blk, lds_stats, s, a);
-    hipLaunchKernelGGL((gn_apply_kernel<float, float>), grid, blk, lds_apply, s, a);
-  } else if (p->dtype == DC_BF16) {
-    if (sweep) hipLaunchKernelGGL((gn_stats_kernel<__bf16>), grid, blk, lds_stats, s, a);
-    hipLaunchKernelGGL((gn_apply_kernel<__bf16, __bf16>), grid, blk, lds_apply, s, a);
-  } else if (p->dtype == DC_F16) {
-    if (sweep) hipLaunchKernelGGL((gn_stats_kernel<_Float16>), grid, blk, lds_stats, s, a);
-    hipLaunchKernelGGL((gn_apply_kernel<_Float16, _Float16>), grid, blk, lds_apply, s, a);
-  } else {
-    dc_set_error("dc_groupnorm: dtype %d", p->dtype);
-    return DC_ERR_DTYPE;
+}
+
+// p: after gn_validate.  No launch, no dc_set_error, no GnArgs
+static GnChoice gn_choose(const dc_groupnorm_params* p) {
+  const GnShape k{p->dtype, p->HW, p->C + p->C1, p->C1, p->groups, p->qparts, p->qstats != nullptr, p->y == nullptr};
+  GnChoice c = gn_route(k, 0);
+  for (unsigned barred = 0; gn_grid(c, p->n, p->splits) >= (1LL << 31); c = gn_route(k, barred)) barred |= 1u << c.route;
+  c.grid = (unsigned)gn_grid(c, p->n, p->splits);
+  return c;
+}
+
+static int gn_launch(const GnChoice& c, const dc_groupnorm_params* p, hipStream_t s) {
+  GnArgs a;
+  a.x0 = p->x; a.map0 = p->map0; a.x1 = p->x1; a.map1 = p->map1; a.y = p->y; a.gamma = p->gamma; a.beta = p->beta; a.ws = p->ws;
+  a.C0 = p->C; a.C1 = p->C1; a.HW = p->HW; a.groups = p->groups; a.silu = p->silu; a.splits = p->splits;
+  a.out_dtype = p->out_dtype; a.eps = p->eps;
+  a.qstats = p->qstats; a.qparts = p->qstats ? p->qparts : 0; a.wsplits = p->splits;
+  const dim3 grid(c.grid), blk(c.block), per_sample((unsigned)p->n);
+  static const char* const what[] = {"dc_groupnorm(qaffine)", "dc_groupnorm(stats)", "dc_groupnorm(wave)", "dc_groupnorm(span)",
+                                     "dc_groupnorm(span)", "dc_groupnorm(image)", "dc_groupnorm", "dc_groupnorm"};
+  if (c.route == GN_QAFFINE) {      // reads the records only: no instance per dtype
+    hipLaunchKernelGGL(gn_qaffine_kernel, grid, blk, c.lds, s, a, p->out_scale, p->out_shift);
+    return dc_check_launch(what[c.route]);
   }
-  return dc_check_launch("dc_groupnorm");
+  return dc_by_dtype(p->dtype, "dc_groupnorm: dtype", [&](auto t) {
+    using T = decltype(t);
+    if (c.fold()) {                 // the kernels behind it read the folded statistics from ws: one record per (sample, group)
+      hipLaunchKernelGGL(gn_qfold_kernel, per_sample, dim3(256), c.lds_pre, s, a);
+      a.qstats = nullptr; a.wsplits = 1;
+    }
+    switch (c.route) {
+      case GN_STATS:
+        hipLaunchKernelGGL((gn_stats_kernel<T>), grid, blk, c.lds, s, a);
+        hipLaunchKernelGGL(gn_finalize_kernel, per_sample, blk, 0, s, a, p->out_scale, p->out_shift);
+        break;
+      case GN_WAVE:
+        if (c.nch <= 4) hipLaunchKernelGGL((gn_wave_kernel<T, 4>), grid, blk, c.lds, s, a, p->n);
+        else if (c.nch <= 8) hipLaunchKernelGGL((gn_wave_kernel<T, 8>), grid, blk, c.lds, s, a, p->n);
+        else if (c.nch <= 16) hipLaunchKernelGGL((gn_wave_kernel<T, 16>), grid, blk, c.lds, s, a, p->n);
+        else hipLaunchKernelGGL((gn_wave_kernel<T, 32>), grid, blk, c.lds, s, a, p->n);
+        break;
+      case GN_SPAN: case GN_QFOLD_SPAN: hipLaunchKernelGGL((gn_span_kernel<T, std::is_same<T, __bf16>::value>), grid, blk, c.lds, s, a, c.spans); break;
+      case GN_IMAGE: hipLaunchKernelGGL((gn_image_kernel<T>), grid, blk, c.lds, s, a); break;
+      case GN_STATS_APPLY: hipLaunchKernelGGL((gn_stats_kernel<T>), grid, blk, c.lds_pre, s, a); [[fallthrough]];
+      default: hipLaunchKernelGGL((gn_apply_kernel<T, T>), grid, blk, c.lds, s, a);      // GN_QFOLD_APPLY
+    }
+    return dc_check_launch(what[c.route]);
+  });
+}
+
+extern "C" int dc_groupnorm(const dc_groupnorm_params* p, dc_stream stream) {
+  const int rc = gn_validate(p);
+  if (rc != DC_OK) return rc;
+  return gn_launch(gn_choose(p), p, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" const char* dc_groupnorm_variant(const dc_groupnorm_params* p) {
+  if (gn_validate(p) != DC_OK) return "invalid";
+  const GnRoute r = gn_choose(p).route;
+  if (r != GN_QAFFINE && dc_by_dtype(p->dtype, "dc_groupnorm: dtype", [](auto) { return (int)DC_OK; }) != DC_OK) return "invalid";
+  static const char* const names[] = {"qaffine", "stats", "wave", "span", "qfold+span", "image", "stats+apply", "qfold+apply"};
+  return names[r];
 }
 
 // ------------------------------------------------------------------ LayerNorm -----
@@ -828,8 +857,7 @@ __global__ __launch_bounds__(256) void ln16_kernel(const LnArgs a) {
 
 // Two rows per 16-lane group (round 4): the one-row kernel above keeps 2-6 loads per lane in flight (C = 256 ... 768 in 16-bit) and reduces with
 // ds_bpermute shuffles; it moved 3.6-4.3 TB/s.  Here every lane holds its chunks of TWO rows (twice the loads in flight) and the row reductions are
-// DPP butterflies (xor 1, xor 2, half-row mirror, row mirror: no LDS crossbar).  Chosen by (dtype, C) only — never by the row count — so a row's
-// result does not depend on how many rows share the launch.
+// DPP butterflies (xor 1, xor 2, half-row mirror, row mirror: no LDS crossbar).  (Chosen by ln_route.)
 template <typename T>
 __global__ __launch_bounds__(256) void ln16x2_kernel(const LnArgs a) {
   constexpr int EPC = Elem<T>::EPC, RPG = 2, KMAX = 6;         // C <= 96 chunks of 16 bytes
@@ -919,7 +947,7 @@ __global__ __launch_bounds__(256) void ln16x2_kernel(const LnArgs a) {
   }
 }
 
-extern "C" int dc_layernorm(const dc_layernorm_params* p, dc_stream stream) {
+static int ln_validate(const dc_layernorm_params* p) {
   DC_REQUIRE(p && p->x && p->y, DC_ERR_ARG, "dc_layernorm: null pointer");
   DC_REQUIRE(p->dtype == p->out_dtype, DC_ERR_DTYPE, "dc_layernorm: in/out dtype must match");
   const int epc = 16 / dc_dtype_size(p->dtype);
@@ -927,29 +955,46 @@ extern "C" int dc_layernorm(const dc_layernorm_params* p, dc_stream stream) {
   DC_REQUIRE((p->gamma == nullptr) == (p->beta == nullptr), DC_ERR_ARG, "dc_layernorm: gamma/beta must both be set or null");
   DC_REQUIRE((p->scale == nullptr) == (p->shift == nullptr), DC_ERR_ARG, "dc_layernorm: scale/shift must both be set or null");
   if (p->scale) DC_REQUIRE(p->rows_per_sample > 0 && p->mod_ld >= p->C, DC_ERR_SHAPE, "dc_layernorm: rows_per_sample/mod_ld");
+  // every kernel has an instance per dtype it is chosen for; the launch's dc_by_dtype refuses the rest with the same words
+  return dc_by_dtype(p->dtype, "dc_layernorm: dtype", [](auto) -> int { return DC_OK; });
+}
+
+enum LnRoute { LN_16X2, LN_16, LN_ROW };
+
+// The kernel a valid problem dispatches to: a function of (dtype, C) and pointer alignment only — a row never depends on the
+// launch's row count.  Rows of up to 128 chunks with 16-byte aligned parameter vectors: ln16_kernel; of those, 16-bit rows of up
+// to 96 chunks (C <= 768): two rows per lane group (ln16x2_kernel); everything else: one wave per row (ln_kernel).
+static LnRoute ln_route(const dc_layernorm_params* p) {
+  const int CP = p->C / (16 / dc_dtype_size(p->dtype));
+  const bool vec16 = CP <= 128 && (((uintptr_t)p->gamma | (uintptr_t)p->beta | (uintptr_t)p->scale | (uintptr_t)p->shift) & 15) == 0 &&
+                     (p->mod_ld % 4 == 0);
+  if (vec16 && p->dtype != DC_F32 && CP <= 96) return LN_16X2;
+  return vec16 ? LN_16 : LN_ROW;
+}
+
+extern "C" const char* dc_layernorm_variant(const dc_layernorm_params* p) {
+  if (ln_validate(p) != DC_OK) return "invalid";
+  static const char* const names[] = {"ln16x2", "ln16", "ln"};
+  return names[ln_route(p)];
+}
+
+extern "C" int dc_layernorm(const dc_layernorm_params* p, dc_stream stream) {
+  const int rc = ln_validate(p);
+  if (rc != DC_OK) return rc;
   LnArgs a{p->x, p->y, p->gamma, p->beta, p->scale, p->shift, p->mod_map, p->rows, p->C, p->rows_per_sample, p->mod_ld, p->eps};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool vec16 = p->C / epc <= 128 && (((uintptr_t)p->gamma | (uintptr_t)p->beta | (uintptr_t)p->scale | (uintptr_t)p->shift) & 15) == 0 &&
-                     (p->mod_ld % 4 == 0);
-  // 16-bit rows of up to 96 chunks (C <= 768): two rows per lane group (a function of dtype and C only)
-  if (vec16 && p->dtype != DC_F32 && p->C / epc <= 96) {
-    dim3 g32((p->rows + 31) / 32), b32(256);
-    if (p->dtype == DC_BF16) hipLaunchKernelGGL((ln16x2_kernel<__bf16>), g32, b32, 0, s, a);
-    else hipLaunchKernelGGL((ln16x2_kernel<_Float16>), g32, b32, 0, s, a);
+  const LnRoute r = ln_route(p);
+  const int rpw = r == LN_16X2 ? 32 : (r == LN_16 ? 16 : 4);      // rows per workgroup
+  const dim3 grid((p->rows + rpw - 1) / rpw), blk(256);
+  return dc_by_dtype(p->dtype, "dc_layernorm: dtype", [&](auto t) {
+    using T = decltype(t);
+    switch (r) {
+      case LN_16X2:
+        if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((ln16x2_kernel<T>), grid, blk, 0, s, a);      // (ln_route: never fp32)
+        break;
+      case LN_16: hipLaunchKernelGGL((ln16_kernel<T>), grid, blk, 0, s, a); break;
+      case LN_ROW: hipLaunchKernelGGL((ln_kernel<T>), grid, blk, 0, s, a); break;
+    }
     return dc_check_launch("dc_layernorm");
-  }
-  if (vec16) {
-    dim3 g16((p->rows + 15) / 16), b16(256);
-    if (p->dtype == DC_F32) hipLaunchKernelGGL((ln16_kernel<float>), g16, b16, 0, s, a);
-    else if (p->dtype == DC_BF16) hipLaunchKernelGGL((ln16_kernel<__bf16>), g16, b16, 0, s, a);
-    else if (p->dtype == DC_F16) hipLaunchKernelGGL((ln16_kernel<_Float16>), g16, b16, 0, s, a);
-    else { dc_set_error("dc_layernorm: dtype %d", p->dtype); return DC_ERR_DTYPE; }
-    return dc_check_launch("dc_layernorm");
-  }
-  dim3 grid((p->rows + 3) / 4), blk(256);
-  if (p->dtype == DC_F32) hipLaunchKernelGGL((ln_kernel<float>), grid, blk, 0, s, a);
-  else if (p->dtype == DC_BF16) hipLaunchKernelGGL((ln_kernel<__bf16>), grid, blk, 0, s, a);
-  else if (p->dtype == DC_F16) hipLaunchKernelGGL((ln_kernel<_Float16>), grid, blk, 0, s, a);
-  else { dc_set_error("dc_layernorm: dtype %d", p->dtype); return DC_ERR_DTYPE; }
-  return dc_check_launch("dc_layernorm");
+  });
 }

@@ -365,12 +365,13 @@ extern "C" int dc_tblock_front(const dc_tblock_front_params* p, dc_stream stream
   a.n = p->n; a.ldx = p->ldx; a.ld_out = p->ld_out; a.rowvec_ld = p->rowvec_ld; a.ln_eps = p->ln_eps; a.scale = p->scale;
   constexpr int lds = 2 * 64 * (256 * 2 + 16) + 5 * 256 * 4;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool bf = p->dtype == DC_BF16, h4 = p->heads == 4;
-  void (*kern)(const TbArgs) = bf ? (h4 ? tblock_front_kernel<__bf16, 64> : tblock_front_kernel<__bf16, 32>)
-                                  : (h4 ? tblock_front_kernel<_Float16, 64> : tblock_front_kernel<_Float16, 32>);
-  static bool done[2][2] = {};
-  bool& d = done[bf ? 0 : 1][h4 ? 0 : 1];
-  if (!d) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); d = true; }
-  hipLaunchKernelGGL(kern, dim3((unsigned)p->n), dim3(256), lds, s, a);
-  return dc_check_launch("dc_tblock_front");
+  const bool h4 = p->heads == 4;
+  return dc_by_dtype16(p->dtype, "dc_tblock_front: dtype", [&](auto t) {
+    using T = decltype(t);
+    void (*kern)(const TbArgs) = h4 ? tblock_front_kernel<T, 64> : tblock_front_kernel<T, 32>;
+    static bool done[2] = {};
+    if (!done[h4]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); done[h4] = true; }
+    hipLaunchKernelGGL(kern, dim3((unsigned)p->n), dim3(256), lds, s, a);
+    return dc_check_launch("dc_tblock_front");
+  });
 }

@@ -448,6 +448,10 @@ class PlanBuilder:
                 self.meta[i]["family"] = L.lib().dc_igemm_variant(s).decode()
             elif kind == L.OP_ATTENTION:
                 self.meta[i]["variant"] = L.lib().dc_attention_variant(s).decode()
+            elif kind == L.OP_GROUPNORM:
+                self.meta[i]["variant"] = L.lib().dc_groupnorm_variant(s).decode()
+            elif kind == L.OP_LAYERNORM:
+                self.meta[i]["variant"] = L.lib().dc_layernorm_variant(s).decode()
             arr[i].kind = kind
             arr[i].params = C.cast(C.pointer(s), C.c_void_p)
         self.op_array = arr

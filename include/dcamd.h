@@ -211,6 +211,10 @@ typedef struct {
   const float* qstats; int32_t qparts, pad_;
 } dc_groupnorm_params;
 int dc_groupnorm(const dc_groupnorm_params* p, dc_stream s);
+/* Name of the launch sequence dc_groupnorm would run for these parameters: "qaffine", "stats", "wave", "span", "qfold+span", "image",
+ * "stats+apply" or "qfold+apply"; "invalid" when dc_groupnorm would refuse them (measurement / tests only; static string; touches no
+ * memory). */
+const char* dc_groupnorm_variant(const dc_groupnorm_params* p);
 int64_t dc_groupnorm_ws_floats(int32_t n, int32_t groups, int32_t splits);
 int32_t dc_groupnorm_splits(int32_t n, int32_t HW, int32_t C);
 /* Workspace bytes per op (only GroupNorm needs one; the others keep everything in registers / LDS and return 0). */
@@ -226,6 +230,9 @@ typedef struct {
   const float* scale; const float* shift; const int32_t* mod_map;
 } dc_layernorm_params;
 int dc_layernorm(const dc_layernorm_params* p, dc_stream s);
+/* Name of the kernel dc_layernorm would launch for these parameters: "ln16x2", "ln16" or "ln"; "invalid" when dc_layernorm would
+ * refuse them (measurement / tests only; static string; touches no memory). */
+const char* dc_layernorm_variant(const dc_layernorm_params* p);
 int64_t dc_workspace_bytes_layernorm(const dc_layernorm_params* p);
 
 /* ---------------------------------------------------------------- attention ------ */

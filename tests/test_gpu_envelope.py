@@ -161,6 +161,10 @@ def test_groupnorm_wide_groups(dt, hw, case):
     sc, sh = torch.full((n, Cc), float("nan"), device=DEV), torch.full((n, Cc), float("nan"), device=DEV)
     gk = dict(x=ptr(x0d), x1=ptr(x1d), map1=ptr(m1d) if C1 else None, dtype=dt, out_dtype=dt, n=n, HW=HW, C=C0, C1=C1, groups=groups,
               splits=splits, eps=1e-5, gamma=ptr(gd), beta=ptr(bd), ws=ptr(ws))
+    # the sweep kernels: one workgroup per sample up to 4 MiB, the split sweep beyond (fp32 at 32x32 from 1280 channels on)
+    sweep = "image" if HW * Cc * (4 if dt == L.DC_F32 else 2) <= 4 << 20 else "stats+apply"
+    assert lib.dc_groupnorm_variant(L.GroupnormParams(y=ptr(y), silu=1, **gk)).decode() == sweep
+    assert lib.dc_groupnorm_variant(L.GroupnormParams(y=None, silu=0, out_scale=ptr(sc), out_shift=ptr(sh), **gk)) == b"stats"
     L.check(lib.dc_groupnorm(L.GroupnormParams(y=ptr(y), silu=1, **gk), L.stream_ptr()), "gn")
     L.check(lib.dc_groupnorm(L.GroupnormParams(y=None, silu=0, out_scale=ptr(sc), out_shift=ptr(sh), **gk), L.stream_ptr()), "gn stats")
     torch.cuda.synchronize()
@@ -207,6 +211,10 @@ def test_groupnorm_from_quad_records_wide_groups(dt, hw, Cout):
     ya, yb = torch.empty_like(out), torch.empty_like(out)
     gk = dict(x=ptr(out), dtype=dt, out_dtype=dt, n=n, HW=H * W, C=Cout, C1=0, groups=32, silu=1, splits=splits, eps=1e-5,
               gamma=ptr(gamma), beta=ptr(beta), ws=ptr(ws))
+    # the records folded inside gn_image_kernel (gn_fold_rec) below 1 MiB per sample, by gn_qfold_kernel in front of the split apply sweep
+    # from there on (96 ... 384 chunks per pixel: no span kernel, whatever DCAMD_GN_SPAN says)
+    folded = "image" if H * W * Cout * (4 if dt == L.DC_F32 else 2) < 1 << 20 else "qfold+apply"
+    assert lib.dc_groupnorm_variant(L.GroupnormParams(y=ptr(yb), qstats=ptr(qs), qparts=parts, **gk)).decode() == folded
     L.check(lib.dc_groupnorm(L.GroupnormParams(y=ptr(ya), **gk), L.stream_ptr()), "gn")
     L.check(lib.dc_groupnorm(L.GroupnormParams(y=ptr(yb), qstats=ptr(qs), qparts=parts, **gk), L.stream_ptr()), "gn qstats")
     torch.cuda.synchronize()

@@ -310,12 +310,14 @@ def test_igemm_rejects_bad_arguments():
 
 
 @pytest.mark.parametrize("dt", [L.DC_F32, L.DC_BF16])
-@pytest.mark.parametrize("shape", [(5, 64, 128, 0, True), (3, 16, 384, 0, False), (4, 256, 256, 128, True),
-                                   (2, 4096, 128, 0, True), (3, 16, 1024, 1024, True),
-                                   # tiny samples: one wave per sample, register resident (gn_wave_kernel)
-                                   (6, 16, 512, 0, True), (7, 16, 256, 256, True), (5, 64, 256, 0, False), (9, 10, 64, 0, True)])
+@pytest.mark.parametrize("shape", [(5, 64, 128, 0, True, "wave", "wave"), (3, 16, 384, 0, False, "image", "wave"), (4, 256, 256, 128, True, "image", "image"),
+                                   (2, 4096, 128, 0, True, "image", "image"), (3, 16, 1024, 1024, True, "image", "image"),
+                                   # tiny samples: one wave per sample, register resident (gn_wave_kernel) — up to 64 chunks per pixel, so in
+                                   # fp32 the 256- and 512-channel ones take one workgroup per sample (gn_image_kernel)
+                                   (6, 16, 512, 0, True, "image", "wave"), (7, 16, 256, 256, True, "image", "wave"), (5, 64, 256, 0, False, "image", "wave"),
+                                   (9, 10, 64, 0, True, "wave", "wave")])
 def test_groupnorm(dt, shape):
-    n, HW, C0, C1, silu = shape
+    n, HW, C0, C1, silu, route_f32, route_bf16 = shape
     torch.manual_seed(4)
     q = lambda t: t.to(TD[dt]).float()
     Cc = C0 + C1
@@ -339,19 +341,21 @@ def test_groupnorm(dt, shape):
     p = L.GroupnormParams(x=ptr(x0d), map0=None, x1=ptr(x1d), map1=ptr(m1d) if C1 else None, y=ptr(y), dtype=dt, out_dtype=dt,
                           n=n, HW=HW, C=C0, C1=C1, groups=32, silu=int(silu), splits=splits, eps=1e-5,
                           gamma=ptr(gd), beta=ptr(bd), ws=ptr(ws))
+    assert lib.dc_groupnorm_variant(p).decode() == (route_f32 if dt == L.DC_F32 else route_bf16)
     L.check(lib.dc_groupnorm(p, L.stream_ptr()), "gn")
     torch.cuda.synchronize()
     err = (y.float().cpu() - ref).abs().max().item()
     assert err < (2e-4 if dt == L.DC_F32 else 6e-2), err     # outputs are O(1..8); bf16 rounding 2^-8 relative
 
 
-@pytest.mark.parametrize("shape", [(3, 16, 256, 0), (2, 64, 128, 128), (3, 1024, 128, 0), (2, 4096, 128, 0), (2, 65536, 64, 0)])
+@pytest.mark.parametrize("shape", [(3, 16, 256, 0, "wave"), (2, 64, 128, 128, "image"), (3, 1024, 128, 0, "image"), (2, 4096, 128, 0, "image"),
+                                   (2, 65536, 64, 0, "stats+apply")])
 def test_groupnorm_with_large_offsets_f32(shape):
     """|mean| >> std: group means of ~1e3 standard deviations.  The sum / sum-of-squares
     form loses the variance to cancellation there (fp32: relative error ~1e-7 * mean^2 / var = 10 %); the (mean, M2) form with
-    shifted sums must stay at torch's own accuracy.  Paths: one wave per sample, one workgroup per sample, split sweep, 16 MiB
-    samples."""
-    n, HW, C0, C1 = shape
+    shifted sums must stay at torch's own accuracy.  Paths: one wave per sample, one workgroup per sample (one and two sources, up
+    to 2 MiB), the split sweep on 16 MiB samples."""
+    n, HW, C0, C1, route = shape
     torch.manual_seed(44)
     Cc = C0 + C1
     off = (torch.randn(1, 1, 32, 1) * 300 + 1000).expand(1, 1, 32, Cc // 32).reshape(1, 1, Cc)   # one offset of ~1e3 std per GROUP
@@ -367,6 +371,7 @@ def test_groupnorm_with_large_offsets_f32(shape):
     y = torch.full((n, HW, Cc), float("nan"), device=DEV)
     p = L.GroupnormParams(x=ptr(x0d), x1=ptr(x1d), y=ptr(y), dtype=L.DC_F32, out_dtype=L.DC_F32, n=n, HW=HW, C=C0, C1=C1, groups=32, silu=1,
                           splits=splits, eps=1e-5, gamma=ptr(gd), beta=ptr(bd), ws=ptr(ws))
+    assert lib.dc_groupnorm_variant(p).decode() == route
     L.check(lib.dc_groupnorm(p, L.stream_ptr()), "gn")
     torch.cuda.synchronize()
     err = (y.cpu() - ref).abs().max().item()
@@ -1151,7 +1156,8 @@ def test_a_wait_that_cannot_complete_times_out_counts_and_poisons_its_outputs():
 
 def test_groupnorm_span_kernel_opt_in():
     """DCAMD_GN_SPAN=1 (read once per process): the short-span normalise sweep must pass the same quad-statistics GroupNorm
-    test in ONE child interpreter — spans of 16 KiB, statistics folded from the records or from gn_qfold_kernel's output."""
+    test in ONE child interpreter — spans of 16 KiB, statistics folded from the records or from gn_qfold_kernel's output (that test
+    asserts the "span" / "qfold+span" route there)."""
     import subprocess
     import sys
     if os.environ.get("DCAMD_GN_SPAN") is not None:
@@ -1164,8 +1170,10 @@ def test_groupnorm_span_kernel_opt_in():
 
 
 @pytest.mark.parametrize("dt", [L.DC_F32, L.DC_BF16, L.DC_F16])
-@pytest.mark.parametrize("shape", [(3, 8, 8, 128), (5, 16, 16, 256), (3, 32, 32, 128), (2, 64, 32, 384), (3, 8, 16, 128),
-                                   (2, 256, 128, 128)])       # > 4 MiB per sample: split GroupNorm, quad records folded by gn_qfold_kernel
+@pytest.mark.parametrize("shape", [(3, 8, 8, 128), (5, 16, 16, 256), (3, 32, 32, 128),
+                                   (2, 64, 32, 384),          # >= 1 MiB per sample, 48 / 96 chunks per pixel: quad records folded by gn_qfold_kernel, split apply sweep
+                                   (3, 8, 16, 128),
+                                   (2, 256, 128, 128)])       # > 4 MiB per sample: quad records folded by gn_qfold_kernel, span sweep; without them the split GroupNorm
 def test_conv3x3_quad_statistics_feed_groupnorm(dt, shape):
     """dc_igemm qstats: per (sample, part, channel quad) sum / sumsq of the STORED output; a GroupNorm given them skips its
     statistics sweep and must match the GroupNorm that sweeps the tensor itself."""
@@ -1208,6 +1216,13 @@ def test_conv3x3_quad_statistics_feed_groupnorm(dt, shape):
     ya, yb = torch.empty_like(out), torch.empty_like(out)
     gk = dict(x=ptr(out), dtype=dt, out_dtype=dt, n=n, HW=H * W, C=Cout, C1=0, groups=32, silu=1, splits=splits, eps=1e-5,
               gamma=ptr(gamma), beta=ptr(beta), ws=ptr(ws))
+    route = lib.dc_groupnorm_variant(L.GroupnormParams(y=ptr(yb), qstats=ptr(qs), qparts=parts, **gk)).decode()
+    if shape == (2, 64, 32, 384):
+        assert route == "qfold+apply"
+    elif shape == (2, 256, 128, 128):
+        assert route == "qfold+span" and lib.dc_groupnorm_variant(L.GroupnormParams(y=ptr(ya), **gk)) == b"stats+apply"
+    else:       # below 1 MiB per sample: one workgroup per sample, or the span kernel where DCAMD_GN_SPAN asks for it
+        assert route == ("span" if os.environ.get("DCAMD_GN_SPAN") is not None else "image")
     L.check(lib.dc_groupnorm(L.GroupnormParams(y=ptr(ya), **gk), L.stream_ptr()), "gn")
     L.check(lib.dc_groupnorm(L.GroupnormParams(y=ptr(yb), qstats=ptr(qs), qparts=parts, **gk), L.stream_ptr()), "gn qstats")
     torch.cuda.synchronize()
