@@ -189,6 +189,9 @@ static int igemm_validate_and_fill(const dc_igemm_params* p, IgemmArgs& a) {
   DC_REQUIRE(M < (1LL << 31), DC_ERR_SHAPE, "dc_igemm: M=%lld too large", M);
   DC_REQUIRE(p->act >= 0 && p->act <= 3, DC_ERR_ARG, "dc_igemm: act %d", p->act);
   if (p->act == DC_ACT_GEGLU) DC_REQUIRE(p->Cout % 32 == 0 && p->tile_n == 128, DC_ERR_SHAPE, "dc_igemm: GEGLU needs Cout%%32==0, tile_n 128");
+  // no GEGLU epilogue (igemm_common.h, igemm_epilogue.h) applies a per-sample row vector or gate: refuse them instead of dropping them
+  if (p->act == DC_ACT_GEGLU) DC_REQUIRE(!p->rowvec, DC_ERR_ARG, "dc_igemm: rowvec cannot be combined with DC_ACT_GEGLU");
+  if (p->act == DC_ACT_GEGLU) DC_REQUIRE(!p->gate, DC_ERR_ARG, "dc_igemm: gate cannot be combined with DC_ACT_GEGLU");
   DC_REQUIRE(((uintptr_t)p->src0 & 15) == 0 && ((uintptr_t)p->W & 15) == 0 && ((uintptr_t)p->src1 & 15) == 0, DC_ERR_ALIGN,
              "dc_igemm: src/W must be 16-byte aligned");
   const int epc = 16 / dc_dtype_size(p->dtype);

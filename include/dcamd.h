@@ -87,6 +87,7 @@ int dc_sinusoid(const dc_sinusoid_params* p, dc_stream s);
  * (taps = 1).  Activations are NHWC: rows = n_img*Hout*Wout, K = taps*(C0+C1).
  *   out[row, co] = epilogue( sum_k A[row,k] * Wp[co,k] )
  * epilogue: (+bias[co]) (+rowvec[vmap[n]][co]) -> act -> (*gate[gmap[n]][co]) (+residual[row,co])
+ * DC_ACT_GEGLU takes bias and residual only: with rowvec or gate set dc_igemm returns DC_ERR_ARG (the text names the field).
  * A/W dtype = dtype (f32 uses v_mfma_f32_16x16x4_f32; bf16/f16 use 16x16x32).
  * W is packed [Cout_pad][K] (K contiguous, k = tap*(C0+C1) + c), Cout_pad = multiple of the
  * kernel's N tile (dc_igemm_cout_pad), zero filled.  For DC_ACT_GEGLU the packed rows
