@@ -26,18 +26,23 @@ struct GnArgs {
 
 // merge of many (count, mean, M2) sets in ONE pass without a division per set: shifted by the first set's mean,
 // N = sum n, S1 = sum n d, S3 = sum n d^2 (d = mean - pivot), S2 = sum M2  ->  mean = pivot + S1/N, M2 = S2 + S3 - S1^2/N
+// The four sums run in fp64 (full rate on this chip; one thread per group walks up to pixel lanes x cpg sets one after the other, thousands
+// for one-chunk rows or wide groups).  In fp32 the rounding of S1 and S3 grew with the number of sets — and not as a random walk when the
+// set means carry few mantissa bits (16-bit inputs, four or five pixels per lane): 2100 pixels of 8 bf16 channels in one group gave a mean
+// off by 4e-5 and a variance off by 2.5e-5 relative, 300 and 200 times what the per-lane sums in front of it lose.
 struct GnMerge {
-  float piv = 0.f, N = 0.f, S1 = 0.f, S2 = 0.f, S3 = 0.f;
+  float piv = 0.f;
+  double N = 0., S1 = 0., S2 = 0., S3 = 0.;
   bool have = false;
   __device__ __forceinline__ void add(float n, float mean, float m2) {
     if (n <= 0.f) return;
     if (!have) { piv = mean; have = true; }
-    const float d = mean - piv;
-    N += n; S1 += n * d; S3 += n * d * d; S2 += m2;
+    const double d = (double)(mean - piv), nn = (double)n;
+    N += nn; S1 += nn * d; S3 += nn * d * d; S2 += (double)m2;
   }
   __device__ __forceinline__ GnAcc result() const {
     GnAcc A;
-    if (N > 0.f) { const float iN = 1.0f / N; A.n = N; A.mean = piv + S1 * iN; A.m2 = S2 + fmaxf(S3 - S1 * S1 * iN, 0.f); }
+    if (N > 0.) { const double m = S1 / N; A.n = (float)N; A.mean = (float)((double)piv + m); A.m2 = (float)(S2 + fmax(S3 - S1 * m, 0.)); }
     return A;
   }
 };

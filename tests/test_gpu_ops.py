@@ -425,6 +425,9 @@ def test_layernorm_plain_and_adaln(dt, C_):
     gd, bd = gamma.to(DEV), beta.to(DEV)
     p = L.LayernormParams(x=ptr(xd), y=ptr(y), dtype=dt, out_dtype=dt, rows=n * L_, C=C_, rows_per_sample=L_, mod_ld=0,
                           eps=1e-5, gamma=ptr(gd), beta=ptr(bd))
+    chunks = C_ // (4 if dt == L.DC_F32 else 8)      # ln_route: 16-byte chunks per row, and whether two rows fit a 16-bit lane group
+    route = "ln" if chunks > 128 else ("ln16" if dt == L.DC_F32 or chunks > 96 else "ln16x2")
+    assert lib.dc_layernorm_variant(p).decode() == route
     L.check(lib.dc_layernorm(p, L.stream_ptr()), "ln")
     ref = F.layer_norm(x, (C_,), gamma, beta, 1e-5)
     tol = {L.DC_F32: 2e-5, L.DC_BF16: 5e-2, L.DC_F16: 8e-3}[dt]
@@ -434,6 +437,7 @@ def test_layernorm_plain_and_adaln(dt, C_):
     modd, mmd = mod.to(DEV), mm.to(DEV)
     p = L.LayernormParams(x=ptr(xd), y=ptr(y), dtype=dt, out_dtype=dt, rows=n * L_, C=C_, rows_per_sample=L_, mod_ld=6 * C_,
                           eps=1e-6, scale=modd.data_ptr() + C_ * 4, shift=modd.data_ptr(), mod_map=ptr(mmd))
+    assert lib.dc_layernorm_variant(p).decode() == route
     L.check(lib.dc_layernorm(p, L.stream_ptr()), "ln")
     sel = mod[mm.long()].repeat_interleave(L_, 0)
     ref = F.layer_norm(x, (C_,), eps=1e-6) * (1 + sel[:, C_:2 * C_]) + sel[:, :C_]
