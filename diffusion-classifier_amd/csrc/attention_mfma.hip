@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "igemm_common.h"
+#include "attn_lanes.h"
 
 struct AttnMArgs {
   const void* q; const void* k; const void* v; void* out;
@@ -203,34 +204,6 @@ template <> struct Mma16<_Float16> {
 
 // (two workgroups per CU.  Three — launch bounds of 168 registers — were measured slower for D = 64: 10 spilled registers, 442 against
 //  507 TFLOP/s on the DiT-B/4 shape, tools/bench_attention.py)
-// Reductions over the four lanes that share a query column in the transposed-score form (lanes lr, lr + 16, lr + 32, lr + 48) on the
-// VALU: v_permlane16_swap_b32 exchanges the odd 16-lane rows of one operand with the even rows of the other, v_permlane32_swap_b32 the
-// upper half of one with the lower half of the other — with both operands the same register the two results are "rows 0 0 2 2" /
-// "rows 1 1 3 3" and "lower lower" / "upper upper", so an op over each pair is the xor-16 / xor-32 butterfly.  The ds_bpermute shuffles
-// these replace were four LDS round trips per query tile and key block in front of the exponentials.
-// (as instructions, not through __builtin_amdgcn_permlane{16,32}_swap: hipcc 7.2 folds the builtin's two results into one once they meet in
-//  an add or a max — it emitted v_add_f32 v, a0, a0 for a0 + a1, with the same or with different operands — which the hardware does not
-//  do: tools/dev/permlane_probe.hip prints what the instruction returns.  The two wait states in front cover a VALU write of the
-//  operands, as the compiler places them in front of its own.)
-template <bool WIDE> static __device__ __forceinline__ void lane_swap(float x, float& lo, float& hi) {
-  unsigned u = __builtin_bit_cast(unsigned, x), v = u;
-  if constexpr (WIDE) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(u), "+v"(v));
-  else asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(u), "+v"(v));
-  lo = __builtin_bit_cast(float, u); hi = __builtin_bit_cast(float, v);
-}
-static __device__ __forceinline__ float col4_max(float x) {
-  float a, b;
-  lane_swap<false>(x, a, b);
-  lane_swap<true>(fmaxf(a, b), a, b);
-  return fmaxf(a, b);
-}
-static __device__ __forceinline__ float col4_sum(float x) {
-  float a, b;
-  lane_swap<false>(x, a, b);
-  lane_swap<true>(a + b, a, b);
-  return a + b;
-}
-
 // Keys per block: sized so that scores + staged K/V fit the register file.  D = 96 takes 64, not 32 as D = 128 does: 32 rows of 12
 // chunks are 1.5 staging chunks per thread; 64 rows are 3, and 2 x 2 buffers x 64 x 104 x 2 B = 52 KiB of LDS keep two workgroups per CU.
 static constexpr int flash_kb(int D) { return D <= 32 ? 128 : (D <= 64 || D == 96 ? 64 : 32); }

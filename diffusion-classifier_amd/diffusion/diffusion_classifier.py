@@ -5,6 +5,8 @@ Kept surface (same names, argument meaning, assertions and return types):
   .classify(x, text=None, fast=False) -> LongTensor[BS]         reference :657-725
   .evaluate(val_dataloader, stop_idx, metrics, classification)  reference :532-578
   .encode_text_prompt / .diffuse / .logsnr_schedule_cosine(_shifted)  :83-161
+`config.encoder_type`: 'nn' and 'DiT' as in the reference; 'prompt' (additive, with `config.prompt_tokens = S`) conditions on a table of
+per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text encoder hands to the backbone (:93-98), without fetching one.
 `config` is the reference's attribute bag (missing keys read as None).  Additive keys read
 here: `compute_dtype` ("bf16" default | "f16" | "f32"), `units_per_launch`, `score_plan_cache` (launch plans kept, LRU;
 default 6), `dwt_on_device` (True: `inference` applies `wavelet_dec_2(images) / 2` on the device to the batches its loader yields, on the
@@ -53,6 +55,19 @@ def log(t, eps=1e-20):
     return torch.log(t.clamp(min=eps))
 
 
+class PromptTable(nn.Module):
+    """encoder_type='prompt': one prompt of S token embeddings per class, `weight` [classes + 1, S, encoder_hid_dim] (the last row is the
+    null prompt, as for 'nn').  The place for per-class text embeddings computed offline (T5, CLIP, a learned soft prompt): copy them
+    into `weight`; the parameter keeps the name `weight`, so a checkpoint carries it as `model_2.safetensors` like nn.Embedding's."""
+
+    def __init__(self, rows, tokens, dim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.randn(rows, tokens, dim))
+
+    def forward(self, ids):
+        return self.weight[ids]
+
+
 class DiffusionClassifier(nn.Module):
     def __init__(self, backbone: nn.Module, config):
         super().__init__()
@@ -72,7 +87,18 @@ class DiffusionClassifier(nn.Module):
                        update_every=config.ema_update_freq)
         self.encoder_type = self.config.encoder_type
         if self.encoder_type == 't5':
-            raise NotImplementedError("encoder_type='t5' fetches t5-base over the network; not part of the scoring path")
+            raise NotImplementedError("encoder_type='t5' fetches t5-base over the network; not part of the scoring path. Text embeddings "
+                                      "computed offline run through encoder_type='prompt' (config.prompt_tokens = S; copy them into "
+                                      "encoder.weight [classes + 1, S, encoder_hid_dim])")
+        elif self.encoder_type == 'prompt':
+            S = self.config.prompt_tokens
+            assert isinstance(S, int) and S >= 1, "encoder_type='prompt' needs config.prompt_tokens = S >= 1"
+            hid = getattr(backbone.config, "encoder_hid_dim", None)
+            if hid is None:
+                raise NotImplementedError("encoder_type='prompt' needs a backbone with a projected context (config.encoder_hid_dim: UNetCondition2D)")
+            self.encoder = PromptTable(self.config.classes + 1, S, hid)
+            self.tokenizer = None
+            self.null_token = self.config.classes
         elif self.encoder_type == 'nn':
             self.encoder = nn.Embedding(self.config.classes + 1, backbone.config.encoder_hid_dim)
             self.tokenizer = None
@@ -90,6 +116,8 @@ class DiffusionClassifier(nn.Module):
         if self.encoder_type == 'nn':
             embeddings = self.encoder(text)
             embeddings.unsqueeze_(1)
+        elif self.encoder_type == 'prompt':
+            embeddings = self.encoder(text)              # [B, S, hid], what the reference's text encoder returns (:93-98)
         elif self.encoder_type == 'DiT':
             embeddings = text
         else:
@@ -525,8 +553,9 @@ class _HipRunner:
         cfg = dc.config
         BS, Cc, H, W = self.x.shape
         wver = getattr(self.bb, "_wver", 0)
+        S = int(dc.encoder.weight.shape[1]) if dc.encoder_type == 'prompt' else 1      # tokens per context
         key = (BS, n_bj, k, self.dt, str(dev), (Cc, H, W), bool(getattr(self.bb, "share_trunk", True)), id(self.bb),
-               self.T, cfg.classes, wver)
+               self.T, cfg.classes, wver, S)
         sp = dc._score_plans.get(key)
         if sp is not None:
             dc._score_plans[key] = dc._score_plans.pop(key)      # most recently used last
@@ -554,7 +583,7 @@ class _HipRunner:
             errors=torch.full((BS * cfg.classes * T + 1,), float("inf"), dtype=torch.float32, device=dev),
             lam=lam, alpha=alpha, sigma=sigma, img_of_bj=img_of_bj, ctx_of_unit=ctx_of_unit, out_index=out_index,
             v_param=dc.pred_param == 'v')
-        plan = self.bb.make_plan(n_bj, k, cfg.classes, dev, score=score)
+        plan = self.bb.make_plan(n_bj, k, cfg.classes, dev, score=score, **({"S": S} if S > 1 else {}))
         sp = dict(plan=plan, score=score, ctl=ctl, pair_id=pair_id, words=words, n_bj=n_bj, k=k, U=U)
         dc._score_plans[key] = sp
         # each entry owns an arena, a workspace and an errors buffer in HBM, and n_bj follows the pair count (per rank, per stage, per
@@ -607,7 +636,7 @@ class _HipRunner:
         self.err_dev = score["errors"]
         score["x"].copy_(self.x_dev)
         if dc.encoder is not None:
-            plan.ctx.copy_(dc.encoder.weight[:ncls].detach().to(dev, torch.float32))
+            plan.ctx.copy_(dc.encoder.weight[:ncls].detach().to(dev, torch.float32).reshape(plan.ctx.shape))
         plan.run_ctx()                                   # per-class vectors: once per stage, not per micro-batch
         n_mb = -(-len(pairs) // n_bj)
         host = sp.get("host")                            # pinned staging, reused across calls (pin_memory() is slow)

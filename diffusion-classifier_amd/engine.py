@@ -319,6 +319,23 @@ class PlanBuilder:
                         bytes=4.0 * self.n[q.dom] * Lq * q.C * DT_SIZE[q.dt]))
         return out
 
+    def cross_attention(self, name, q, k, v, heads, d):
+        """softmax(q k^T / sqrt(d)) v per head with keys / values from the 'ctx' domain (k.W tokens per context, picked per unit through
+        ctx_of_unit) and queries of q's domain read through its map (bj_of_unit for the class-shared trunk): dc_cross_attention.  Head
+        widths as in `attention` (q.C // heads channels per head, the scale of the true d).  The output is per unit."""
+        dom = self._dom(q, k)
+        out = self.tensor(name, dom, q.H, q.W, q.C, q.dt)
+        dp = q.C // heads
+        assert d <= dp and dp * heads == q.C and k.C == q.C and v.C == q.C and k.dom == v.dom and k.ld == v.ld, (d, dp, heads, q.C, k.C)
+        assert k.dt == q.dt and v.dt == q.dt and k.H == 1
+        n, Lq, S = self.n[dom], q.H * q.W, k.W
+        f = dict(q=q, k=k, v=v, out=out, q_map=self._map(q, dom), kv_map=self._map(k, dom), dtype=q.dt, n=n, Lq=Lq, S=S, heads=heads,
+                 d=dp, ld_q=q.ld, ld_kv=k.ld, ld_out=out.ld, scale=float(d) ** -0.5)
+        self._emit(L.OP_CROSS_ATTENTION, L.CrossAttentionParams, f, [q, k, v], [out],
+                   dict(name=name, family="cross_attention", flops=4.0 * n * heads * Lq * S * dp,
+                        bytes=2.0 * n * Lq * q.C * DT_SIZE[q.dt]))
+        return out
+
     def tblock_front_ok(self, x, heads):
         """Can ONE launch take proj_in -> LayerNorm -> q/k/v -> attention -> to_out of this block input (dc_tblock_front_ok)?"""
         fn = getattr(L.lib(), "dc_tblock_front_ok", None)
@@ -448,6 +465,8 @@ class PlanBuilder:
                 self.meta[i]["family"] = L.lib().dc_igemm_variant(s).decode()
             elif kind == L.OP_ATTENTION:
                 self.meta[i]["variant"] = L.lib().dc_attention_variant(s).decode()
+            elif kind == L.OP_CROSS_ATTENTION:
+                self.meta[i]["variant"] = L.lib().dc_cross_attention_variant(s).decode()
             elif kind == L.OP_GROUPNORM:
                 self.meta[i]["variant"] = L.lib().dc_groupnorm_variant(s).decode()
             elif kind == L.OP_LAYERNORM:
@@ -729,6 +748,38 @@ class UNetWeights:
             ln_gamma=sd[tb_ + ".norm3.weight"], ln_beta=sd[tb_ + ".norm3.bias"])
         return P
 
+    def pack_cross(self, fold_ln):
+        """attn2 as attention (a context of several tokens; the one-token plan never needs these): per transformer `<tb>.norm2.g/.b`,
+        `<tb>.attn2.to_q.w` and `<tb>.attn2.to_out.0.wc` in the compute dtype with attn1's head padding, and ONE fp32 matrix
+        `attn2kv.w` that stacks [to_k ; to_v] of every site (rows `ckv_off[key]` ... + 2 Cq: K | V of that site), so the context side
+        path produces K | V of all sites with one GEMM, as `attn2v.w` stacks to_v for the one-token plan.  fold_ln: also
+        `<tb>.attn2.to_q.wf/.bf`, norm2 folded into to_q for the row-standardising GEMM."""
+        P, sd = self.P, self._sd
+        if "attn2kv.w" not in P:
+            kv, self.ckv_off, o = [], {}, 0
+            for key in self.attns:
+                tb_ = key + ".transformer_blocks.0"
+                d = sd[key + ".proj_in.weight"].shape[0] // self.heads
+                dp = padded_head_dim(d)
+                P[tb_ + ".norm2.g"], P[tb_ + ".norm2.b"] = f32c(sd[tb_ + ".norm2.weight"], self.dev), f32c(sd[tb_ + ".norm2.bias"], self.dev)
+                P[tb_ + ".attn2.to_q.w"] = pack_matrix(pad_head_rows(sd[tb_ + ".attn2.to_q.weight"], d, dp), self.dt, self.dev)
+                P[tb_ + ".attn2.to_out.0.wc"] = pack_matrix(pad_head_cols(sd[tb_ + ".attn2.to_out.0.weight"], d, dp), self.dt, self.dev)
+                P[tb_ + ".attn2.to_out.0.bc"] = f32c(sd[tb_ + ".attn2.to_out.0.bias"], self.dev)
+                kv += [pad_head_rows(sd[tb_ + ".attn2.to_k.weight"], d, dp), pad_head_rows(sd[tb_ + ".attn2.to_v.weight"], d, dp)]
+                self.ckv_off[key] = o
+                o += 2 * self.heads * dp
+            self.ckv_total = o
+            P["attn2kv.w"] = pack_matrix(torch.cat(kv, 0), L.DC_F32, self.dev)
+        if fold_ln:
+            for key in self.attns:
+                tb_ = key + ".transformer_blocks.0"
+                if tb_ + ".attn2.to_q.wf" not in P:
+                    d = sd[key + ".proj_in.weight"].shape[0] // self.heads
+                    wq = pad_head_rows(sd[tb_ + ".attn2.to_q.weight"].float(), d, padded_head_dim(d))
+                    P[tb_ + ".attn2.to_q.wf"] = pack_matrix(wq, self.dt, self.dev, col_scale=sd[tb_ + ".norm2.weight"])
+                    P[tb_ + ".attn2.to_q.bf"] = fold_layernorm_bias(wq, None, sd[tb_ + ".norm2.bias"], self.dev)
+        return P
+
     def fold_proj_out(self, key):
         """proj_out folded into the feed-forward's second linear: with h3 = W2 f + b2 + h2 (ff.net.2 + residual) the block's output
         x + Wpo h3 + bpo equals x + [Wpo W2 | Wpo] [f ; h2] + (Wpo b2 + bpo) — ONE GEMM over K = 4C + C with x as its residual instead of
@@ -755,14 +806,15 @@ class UNetPlan:
     """Static launch plan of one UNetCondition2D scoring step.
 
     inputs (plan-owned device buffers, refreshed per micro-batch by the caller):
-      lam [n_bj] f32;  ctx [n_ctx, hid] f32;  a0 = conv_in GEMM operand [n_bj, H, W, kin]
+      lam [n_bj] f32;  ctx [n_ctx, hid] f32 (S = 1: one class token per context) or [n_ctx, S, hid] (S > 1: a prompt of S tokens);  a0 = conv_in GEMM operand [n_bj, H, W, kin]
       (written by the q_sample op when `score=True`, else by the caller through `a0_view`);
       maps bj_of_unit / ctx_of_unit [U] int32.
     output: pred [U, H, W, out_channels] f32 (NHWC); with score=True also err -> errors buffer.
     """
 
-    def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, share_trunk=True, score=None, device=None):
+    def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, share_trunk=True, score=None, device=None, S=1):
         import os
+        assert S >= 1, S
         fuse_gn_out = os.environ.get("DCAMD_NO_GN_OUT_FUSION") is None
         split_skips = os.environ.get("DCAMD_NO_SKIP_SPLIT") is None
         fold_short = os.environ.get("DCAMD_NO_SHORT_FOLD") is None
@@ -780,7 +832,7 @@ class UNetPlan:
         cfg = model.config
         dev = device or weights.dev
         dt = weights.dt
-        self.dt, self.n_bj, self.n_cls, self.n_ctx = dt, n_bj, n_cls, n_ctx
+        self.dt, self.n_bj, self.n_cls, self.n_ctx, self.S = dt, n_bj, n_cls, n_ctx, S
         U = n_bj * n_cls
         pb = PlanBuilder(dev, n_bj, n_cls, n_ctx)
         self.pb = pb
@@ -793,7 +845,7 @@ class UNetPlan:
         f32 = dict(dtype=torch.float32, device=dev)
         # ---- inputs ----
         self.lam = score["lam"] if score is not None and "lam" in score else torch.zeros(n_bj, **f32)
-        self.ctx = torch.zeros(n_ctx, cfg.encoder_hid_dim, **f32)
+        self.ctx = torch.zeros((n_ctx, cfg.encoder_hid_dim) if S == 1 else (n_ctx, S, cfg.encoder_hid_dim), **f32)
         self.bj_of_unit = (torch.arange(U, **i32) // n_cls).contiguous()
         if score is not None and "ctx_of_unit" in score:
             self.ctx_of_unit = score["ctx_of_unit"]
@@ -802,7 +854,7 @@ class UNetPlan:
         pb.set_map("bj", "unit", self.bj_of_unit)
         pb.set_map("ctx", "unit", self.ctx_of_unit)
         lam = pb.external("lam", self.lam, "bj", 1, 1, 1, L.DC_F32)
-        ctx = pb.external("ctx", self.ctx, "ctx", 1, 1, cfg.encoder_hid_dim, L.DC_F32)
+        pb.external("ctx", self.ctx, "ctx", 1, S, cfg.encoder_hid_dim, L.DC_F32)
         kin = weights.kin
         if score is not None:
             # score = dict(x=[B,C,H,W] f32 buffer, eps=[n_bj,C,H,W], alpha, sigma, img_of_bj, out_index, errors, v_param)
@@ -825,18 +877,31 @@ class UNetPlan:
         # class-token vectors: their own small plan (run_ctx), executed once per classify call / forward and
         # NOT once per micro-batch: they depend only on the weights and on `ctx`
         pc = self.ctx_pb = PlanBuilder(dev, 1, 1, n_ctx)
-        cctx = pc.external("ctx", self.ctx, "ctx", 1, 1, cfg.encoder_hid_dim, L.DC_F32)
+        cctx = pc.external("ctx", self.ctx, "ctx", 1, S, cfg.encoder_hid_dim, L.DC_F32)
         hp = pc.igemm("ctx.hid_proj", cctx, pc.const(P["encoder_hid_proj.w"]), cfg.cross_attention_dim,
                       bias=pc.const(P["encoder_hid_proj.b"]))
-        vall = pc.igemm("ctx.to_v", hp, pc.const(P["attn2v.w"]), weights.cv_total)
-        cv_t = {}
-        for k in weights.attns:
-            tbk = k + ".transformer_blocks.0"
-            Ck = P[k + ".norm.g"].shape[0]
-            cv_t[k] = pc.igemm(k + ".cvec", vall.view(weights.cv_off[k], Ck), pc.const(P[tbk + ".attn2.to_out.0.w"]), Ck,
-                               bias=pc.const(P[tbk + ".attn2.to_out.0.b"]))
-        pc.finalize(keep_alive=list(cv_t.values()))
-        cvec = {k: pb.external(k + ".cvec", pc.tensor_view(t).view(n_ctx, -1), "ctx", 1, 1, t.C, L.DC_F32) for k, t in cv_t.items()}
+        cvec, ckv = {}, {}
+        if S == 1:
+            # one key: softmax = 1, attn2 is to_out(to_v(ctx)), a row vector of the attn1.to_out epilogue
+            vall = pc.igemm("ctx.to_v", hp, pc.const(P["attn2v.w"]), weights.cv_total)
+            cv_t = {}
+            for k in weights.attns:
+                tbk = k + ".transformer_blocks.0"
+                Ck = P[k + ".norm.g"].shape[0]
+                cv_t[k] = pc.igemm(k + ".cvec", vall.view(weights.cv_off[k], Ck), pc.const(P[tbk + ".attn2.to_out.0.w"]), Ck,
+                                   bias=pc.const(P[tbk + ".attn2.to_out.0.b"]))
+            pc.finalize(keep_alive=list(cv_t.values()))
+            cvec = {k: pb.external(k + ".cvec", pc.tensor_view(t).view(n_ctx, -1), "ctx", 1, 1, t.C, L.DC_F32) for k, t in cv_t.items()}
+        else:
+            # a prompt of S tokens: K | V of every site from ONE stacked GEMM over the n_ctx * S projected rows (fp32 side path, stored in
+            # the compute dtype); the main plan reads them as 'ctx'-domain tensors of 1 x S tokens
+            weights.pack_cross(fold_ln)
+            kvall = pc.igemm("ctx.to_kv", hp, pc.const(P["attn2kv.w"]), weights.ckv_total, out_dt=dt)
+            pc.finalize(keep_alive=[kvall])
+            kvx = pb.external("ctx.kv", pc.tensor_view(kvall), "ctx", 1, S, weights.ckv_total, dt)
+            for k in weights.attns:
+                Cq = heads * padded_head_dim(P[k + ".norm.g"].shape[0] // heads)
+                ckv[k] = (kvx.view(weights.ckv_off[k], Cq), kvx.view(weights.ckv_off[k] + Cq, Cq))
 
         def gn_conv3(gname, cname, x, gamma, beta, groups, Wp, Cout, **kw):
             """GroupNorm + SiLU of the single-source tensor x, then a 3x3 conv of it (bias / row vector / residual / side source
@@ -922,6 +987,8 @@ class UNetPlan:
             h = pb.pn_claim(x, pb.const(P[key + ".norm.g"]), pb.const(P[key + ".norm.b"]), G, 1e-6, False)
             if h is None:
                 h = pb.groupnorm(key + ".gn", x, pb.const(P[key + ".norm.g"]), pb.const(P[key + ".norm.b"]), G, 1e-6, False)
+            if S > 1:
+                return transformer_prompt(key, tbk, x, h, Cc, d, Cq)
             if fuse_tb and h.dom == pb._dom(h, cvec[key]) and pb.tblock_front_ok(h, heads):
                 # proj_in -> LayerNorm -> q/k/v -> attention -> to_out + class vector + residual in ONE launch, the sample on chip
                 assert Cq == Cc, "dc_tblock_front takes unpadded heads only"
@@ -938,6 +1005,28 @@ class UNetPlan:
             o = pb.attention(tbk + ".attn1", qkv.view(0, Cq), qkv.view(Cq, Cq), qkv.view(2 * Cq, Cq), heads, d)
             h = pb.igemm(tbk + ".attn_out", o, pb.const(P[tbk + ".attn1.to_out.0.w"]), Cc,
                          bias=pb.const(P[tbk + ".attn1.to_out.0.b"]), rowvec=cvec[key], residual=h)
+            return transformer_back(key, tbk, x, h, Cc)
+
+        def transformer_prompt(key, tbk, x, h, Cc, d, Cq):
+            """A transformer block whose attn2 attends S > 1 prompt tokens.  The self-attention half runs as the chain of launches without
+            a class vector (the one-launch front, dc_tblock_front, is built around that vector's epilogue and is not used here), then
+            norm2 -> to_q -> dc_cross_attention against this site's K | V of the context plan -> attn2.to_out + bias + residual.
+            Everything in front of the cross-attention is class-independent: in the first block of a class-shared trunk it stays in the
+            'bj' domain, and the cross-attention, reading q through bj_of_unit, is the first per-unit op."""
+            h = pb.igemm(key + ".proj_in", h, pb.const(P[key + ".proj_in.w"]), Cc, bias=pb.const(P[key + ".proj_in.b"]))
+            hn = pb.layernorm(tbk + ".ln1", h, pb.const(P[tbk + ".norm1.g"]), pb.const(P[tbk + ".norm1.b"]), 1e-5)
+            qkv = pb.igemm(tbk + ".qkv", hn, pb.const(P[tbk + ".qkv.w"]), 3 * Cq)
+            o = pb.attention(tbk + ".attn1", qkv.view(0, Cq), qkv.view(Cq, Cq), qkv.view(2 * Cq, Cq), heads, d)
+            h = pb.igemm(tbk + ".attn_out", o, pb.const(P[tbk + ".attn1.to_out.0.w"]), Cc,
+                         bias=pb.const(P[tbk + ".attn1.to_out.0.b"]), residual=h)
+            if fold_ln and pb.ln_ok(h, Cq):
+                q2 = pb.igemm(tbk + ".attn2.to_q", h, pb.const(P[tbk + ".attn2.to_q.wf"]), Cq, bias=pb.const(P[tbk + ".attn2.to_q.bf"]), ln_eps=1e-5)
+            else:
+                hn = pb.layernorm(tbk + ".ln2", h, pb.const(P[tbk + ".norm2.g"]), pb.const(P[tbk + ".norm2.b"]), 1e-5)
+                q2 = pb.igemm(tbk + ".attn2.to_q", hn, pb.const(P[tbk + ".attn2.to_q.w"]), Cq)
+            o2 = pb.cross_attention(tbk + ".attn2", q2, ckv[key][0], ckv[key][1], heads, d)
+            h = pb.igemm(tbk + ".attn2_out", o2, pb.const(P[tbk + ".attn2.to_out.0.wc"]), Cc,
+                         bias=pb.const(P[tbk + ".attn2.to_out.0.bc"]), residual=h)
             return transformer_back(key, tbk, x, h, Cc)
 
         def transformer_back(key, tbk, x, h, Cc):
@@ -1021,7 +1110,8 @@ class UNetPlan:
         self.pb.run()
 
     def run_ctx(self):
-        """Refresh the per-class cross-attention vectors from `self.ctx` (call after changing ctx / weights)."""
+        """Refresh the per-class cross-attention vectors (S = 1) or the per-site K | V of every prompt (S > 1) from `self.ctx` (call
+        after changing ctx / weights)."""
         self.ctx_pb.run()
 
     def pred_view(self):

@@ -255,11 +255,22 @@ class UNetCondition2D(_HipBackbone):
             self._packed[key] = E.UNetWeights(self, dt, device)
         return self._packed[key]
 
-    def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None):
+    def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None, S=1):
+        """S: tokens per context (1: the class token; more: a prompt, attended by dc_cross_attention)."""
         dt = E.DT[self.compute_dtype]
         w = self.packed_weights(dt, device)
         return E.UNetPlan(self, w, n_bj, n_cls, n_ctx, share_trunk=self.share_trunk if share_trunk is None else share_trunk,
-                          score=score, device=device)
+                          score=score, device=device, S=S)
+
+    def _context_tokens(self, *ts):
+        """Token count S of the context tensors [N, S, hid] of one call (all the same S; any S >= 1)."""
+        for t in ts:
+            if t is None or t.dim() != 3 or t.shape[1] < 1 or t.shape[2] != self.config.encoder_hid_dim:
+                raise L.DcamdError(f"the context must be [N, S, {self.config.encoder_hid_dim}] with S >= 1 tokens, got "
+                                   f"{None if t is None else tuple(t.shape)}")
+        if len({int(t.shape[1]) for t in ts}) != 1:
+            raise L.DcamdError(f"the contexts of one call must have the same token count, got {[int(t.shape[1]) for t in ts]}")
+        return int(ts[0].shape[1])
 
     @torch.no_grad()
     def forward(self, x, noise_labels, downblock_additional_residuals=None, midblock_additional_residuals=None,
@@ -271,14 +282,13 @@ class UNetCondition2D(_HipBackbone):
             raise L.DcamdError("UNetCondition2D.forward needs CUDA/HIP tensors (no CPU fallback)")
         dev = x.device
         N, Cin, H, W = x.shape
-        assert encoder_hidden_states is not None and encoder_hidden_states.shape[1] == 1, \
-            "the scoring path conditions on exactly one class token [N,1,hid]"
-        key = ("fwd", N, str(dev), self.compute_dtype, self.share_trunk)
+        S = self._context_tokens(encoder_hidden_states)
+        key = ("fwd", N, str(dev), self.compute_dtype, self.share_trunk, S)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 1, N, dev)
+            plan = self._plans[key] = self.make_plan(N, 1, N, dev, S=S)
         self._feed(plan, x, noise_labels)
-        plan.ctx.copy_(encoder_hidden_states[:, 0].to(dev, torch.float32))
+        plan.ctx.copy_(encoder_hidden_states.to(dev, torch.float32).reshape(plan.ctx.shape))
         plan.run_ctx()
         plan.run()
         return plan.pred_view().permute(0, 3, 1, 2).contiguous().to(x.dtype)
@@ -287,7 +297,8 @@ class UNetCondition2D(_HipBackbone):
     @torch.no_grad()
     def forward_pair(self, x, noise_labels, cond, null):
         """Classifier-free-guidance pair as ONE batch-2 plan launch (reference `sample`, :255-266, calls the backbone twice per
-        step): unit 2b scores image b under its class token `cond[b]`, unit 2b+1 under the null token `null[b]`; every layer in
+        step): unit 2b scores image b under its class token (or prompt of S tokens) `cond[b]`, unit 2b+1 under the null one `null[b]`
+        (`cond` and `null` [N, S, hid] with the same S); every layer in
         front of the first cross-attention runs once per image (class-shared trunk).  Returns the plan's prediction buffer
         [2N, H, W, ld] fp32 NHWC (the layout `dc_ddpm_step` reads) — a view that the next call overwrites."""
         L.require_gpu()
@@ -295,13 +306,14 @@ class UNetCondition2D(_HipBackbone):
             raise L.DcamdError("UNetCondition2D.forward_pair needs CUDA/HIP tensors (no CPU fallback)")
         dev = x.device
         N, Cin, H, W = x.shape
-        key = ("pair", N, str(dev), self.compute_dtype, self.share_trunk)
+        S = self._context_tokens(cond, null)
+        key = ("pair", N, str(dev), self.compute_dtype, self.share_trunk, S)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 2, 2 * N, dev)        # ctx_of_unit = unit index: one context row per unit
+            plan = self._plans[key] = self.make_plan(N, 2, 2 * N, dev, S=S)   # ctx_of_unit = unit index: one context per unit
         self._feed(plan, x, noise_labels)
-        ctx = torch.stack([cond[:, 0], null[:, 0]], dim=1).reshape(2 * N, -1)
-        plan.ctx.copy_(ctx.to(dev, torch.float32))
+        ctx = torch.stack([cond, null], dim=1)                                # [N, 2, S, hid]: context 2b = cond[b], 2b + 1 = null[b]
+        plan.ctx.copy_(ctx.to(dev, torch.float32).reshape(plan.ctx.shape))
         plan.run_ctx()
         plan.run()
         return plan.pred_view()

@@ -13,6 +13,8 @@
  *   dc_groupnorm        GroupNorm(+SiLU) sites of ResnetBlock2D / Transformer2DModel
  *   dc_layernorm        LayerNorm sites of BasicTransformerBlock; adaLN-Zero modulate (DiT)
  *   dc_attention        F.scaled_dot_product_attention self-attention (attn1)
+ *   dc_cross_attention  F.scaled_dot_product_attention cross-attention (attn2) over a context of several tokens
+ *                       (encode_text_prompt's [B, S, hid], diffusion_classifier.py:93-98; one token needs no kernel)
  *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
@@ -37,7 +39,8 @@ extern "C" {
 #endif
 
 /* 2: qstats records are (mean, M2) sets (version 1: sum, sum of squares) and qparts must divide HW
- * 3: dc_ddpm_step_params.one_plus_w; dc_attention requires scale > 0; dc_igemm_params.pn_* (producer-side GroupNorm) */
+ * 3: dc_ddpm_step_params.one_plus_w; dc_attention requires scale > 0; dc_igemm_params.pn_* (producer-side GroupNorm)
+ * (dc_cross_attention, dc_cross_attention_variant and DC_OP_CROSS_ATTENTION are additive within 4: no existing struct or symbol changed) */
 #define DC_ABI_VERSION 4
 
 typedef void* dc_stream; /* hipStream_t */
@@ -255,6 +258,28 @@ int dc_attention(const dc_attention_params* p, dc_stream s);
 const char* dc_attention_variant(const dc_attention_params* p);
 int64_t dc_workspace_bytes_attention(const dc_attention_params* p);
 
+/* ---------------------------------------------------------------- cross-attention */
+/* out[i] = softmax(q[q_map[i]] k[kv_map[i]]^T * scale) v[kv_map[i]] per head, for i < n: attention whose keys and values come from
+ * another tensor with its own length (the prompt of a unit, picked through ctx_of_unit) and whose queries may be shared (the
+ * class-shared trunk keeps them once per (image, trial) pair: bj_of_unit).  A map of NULL is the identity.
+ * q [*, Lq, heads, d] with row stride ld_q, k / v [*, S, heads, d] with row stride ld_kv (a stacked K | V GEMM output is passed as two
+ * offset pointers), out [n, Lq, heads, d] with row stride ld_out; all in `dtype`.  Every one of the S keys is attended: there is no mask
+ * (the reference passes none, so padded prompt rows take part).  Rows behind the S-th of a context are never read.
+ * scale must be > 0 and S >= 1 (DC_ERR_ARG / DC_ERR_SHAPE); head dims d = 16, 32, 64, 96, 128, narrower heads zero-padded by the
+ * caller exactly as for dc_attention (scale of the true width; the pad columns of the output are zero).
+ * 16-bit with d = 32 / 64 / 96 / 128 and 16-byte aligned rows: the matrix-core kernel (one wave per 32 queries of a (sample, head),
+ * online softmax over key blocks, fp32 statistics); f32, d = 16 and unaligned operands: the exact fp32 kernel.  Fixed summation
+ * order, no atomics: the bits of out[i] depend on its own q rows and its own context only, not on n or on i. */
+typedef struct {
+  const void* q; const void* k; const void* v; void* out;
+  const int32_t* q_map; const int32_t* kv_map;          /* NULL = identity */
+  int32_t dtype, n, Lq, S, heads, d, ld_q, ld_kv, ld_out; float scale;
+} dc_cross_attention_params;
+int dc_cross_attention(const dc_cross_attention_params* p, dc_stream s);
+/* Name of the kernel dc_cross_attention would launch for these parameters: "mfma" or "fp32"; "invalid" when it would refuse them
+ * (measurement / tests only; static string; touches no memory). */
+const char* dc_cross_attention_variant(const dc_cross_attention_params* p);
+
 /* ---------------------------------------------------------------- transformer block, attention half --- */
 /* One launch for the self-attention half of a UNet transformer block (the backbone behind /root/reference/nets/unet.py:186-195:
  * Transformer2DModel.proj_in -> BasicTransformerBlock.norm1 -> attn1 (to_q/k/v, softmax, to_out) -> + attn2's class vector -> residual):
@@ -328,7 +353,8 @@ int dc_stage_maps(const int32_t* keep, int32_t BS, int32_t C, int32_t T, int32_t
 
 /* ---------------------------------------------------------------- plan ----------- */
 typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GROUPNORM = 4,
-               DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8 } dc_op_kind;
+               DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8,
+               DC_OP_CROSS_ATTENTION = 9 } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */
