@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs a) {
 }
 
 // attention_mfma.hip: matrix-core kernels for 16-bit dtypes (whole-sequence: L % 16 == 0, d % 32 == 0; flash: d = 32 / 64 / 96 / 128)
-bool dc_attn_mfma_applicable(int dtype, int L, int d);
+bool dc_attn_mfma_applicable(const dc_attention_params* p);
 int dc_attn_mfma_launch(const dc_attention_params* p, hipStream_t s);
 bool dc_attn_wave_applicable(const dc_attention_params* p);  // L <= 64: one wave per (sample, head) pair
 int dc_attn_wave_launch(const dc_attention_params* p, hipStream_t s);
@@ -103,7 +103,7 @@ enum AttnRoute { ATTN_WAVE, ATTN_MFMA, ATTN_FLASH, ATTN_FP32 };
 static AttnRoute attn_route(const dc_attention_params* p) {
   constexpr int mfma_maxl = 128;
   if (dc_attn_wave_applicable(p)) return ATTN_WAVE;
-  if (p->L <= mfma_maxl && dc_attn_mfma_applicable(p->dtype, p->L, p->d)) return ATTN_MFMA;
+  if (p->L <= mfma_maxl && dc_attn_mfma_applicable(p)) return ATTN_MFMA;
   const size_t lds_all = (size_t)2 * p->L * p->d * sizeof(float);
   if ((lds_all > 160 * 1024 || p->L > mfma_maxl) && dc_attn_flash_applicable(p)) return ATTN_FLASH;
   return ATTN_FP32;

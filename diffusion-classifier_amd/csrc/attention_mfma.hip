@@ -137,8 +137,11 @@ static int attn_pairs_per_wg(int L, int d) {
   return L >= 64 ? 1 : (L == 32 ? 2 : (L == 16 ? 4 : 0));
 }
 
-bool dc_attn_mfma_applicable(int dtype, int L, int d) {
+// whole sequence in LDS: 16-bit, L % 16 == 0, d % 32 == 0, q/k/v rows readable as 16-byte chunks (anything else: the exact fp32 kernel)
+bool dc_attn_mfma_applicable(const dc_attention_params* p) {
+  const int dtype = p->dtype, L = p->L, d = p->d;
   if (dtype == DC_F32) return false;
+  if ((((uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v) & 15) || (p->ld_qkv % 8)) return false;
   if (L % 16 || L > 256 || d % 32 || d > 128) return false;
   const int G = attn_pairs_per_wg(L, d);
   if (!G) return false;
@@ -157,7 +160,7 @@ int dc_attn_mfma_launch(const dc_attention_params* p, hipStream_t s) {
   const long long npairs = (long long)p->n * p->heads;
   const long long nb = (npairs + a.G - 1) / a.G;
   if (nb >= (1LL << 31)) { dc_set_error("dc_attention: grid too large"); return DC_ERR_SHAPE; }
-  if (((uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v) & 15 || (p->ld_qkv % 8)) {
+  if (((uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v) & 15 || (p->ld_qkv % 8)) {   // (attn_route asks dc_attn_mfma_applicable first: cannot fire)
     dc_set_error("dc_attention: q/k/v must be 16-byte aligned with ld %% 8 == 0");
     return DC_ERR_ALIGN;
   }

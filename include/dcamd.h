@@ -247,7 +247,8 @@ int64_t dc_workspace_bytes_layernorm(const dc_layernorm_params* p);
  * up to 128 run as the next of these with zero pad channels in q/k/v (the scale stays that of the true width): the pad adds
  * nothing to the scores and its output columns are zero.
  * Routes in 16-bit: L <= 64 one wave per (sample, head) (d = 32 / 64 / 128), L <= 128 the whole-sequence matrix-core kernel,
- * longer sequences the flash kernel (d = 32 / 64 / 96 / 128); fp32 and the shapes those do not take: the exact fp32 kernel. */
+ * longer sequences the flash kernel (d = 32 / 64 / 96 / 128); fp32 and the shapes those do not take: the exact fp32 kernel.
+ * Unaligned operands (16-bit q / k / v not 16-byte aligned, or ld_qkv % 8 != 0): the exact fp32 kernel. */
 typedef struct {
   const void* q; const void* k; const void* v; void* out;
   int32_t dtype, n, L, heads, d, ld_qkv, ld_out; float scale;
