@@ -14,6 +14,7 @@ DC_F32, DC_BF16, DC_F16 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU_TANH = 0, 1, 2, 3
 OP_QSAMPLE, OP_SINUSOID, OP_IGEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_EPS_MSE, OP_TBLOCK_FRONT = 1, 2, 3, 4, 5, 6, 7, 8
 OP_CROSS_ATTENTION = 9
+OP_CROSS_ATTENTION_LEN = 10
 
 i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -73,6 +74,12 @@ class CrossAttentionParams(C.Structure):
                 ("ld_q", i32), ("ld_kv", i32), ("ld_out", i32), ("scale", f32)]
 
 
+class CrossAttentionLenParams(C.Structure):
+    _fields_ = [("q", vp), ("k", vp), ("v", vp), ("out", vp), ("q_map", vp), ("kv_map", vp), ("kv_len", vp),
+                ("dtype", i32), ("n", i32), ("Lq", i32), ("S", i32), ("heads", i32), ("d", i32),
+                ("ld_q", i32), ("ld_kv", i32), ("ld_out", i32), ("scale", f32)]
+
+
 class TblockFrontParams(C.Structure):
     _fields_ = [("x", vp), ("Wp", vp), ("bp", vp), ("ln_g", vp), ("ln_b", vp), ("Wqkv", vp), ("Wo", vp), ("bo", vp),
                 ("rowvec", vp), ("rowvec_map", vp), ("out", vp),
@@ -99,7 +106,7 @@ class Op(C.Structure):
 # every symbol include/dcamd.h declares (tests check that the library exports all of them)
 EXPORTS = ["dc_abi_version", "dc_last_error", "dc_arch", "dc_qsample", "dc_philox_normal", "dc_sinusoid",
            "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
-           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_ddpm_step", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_run_plan", "dc_run_plan_timed",
+           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_ddpm_step", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_run_plan", "dc_run_plan_timed",
            "dc_packed_bytes", "dc_pack_weights_matrix", "dc_pack_weights_conv3x3", "dc_pack_weights_up4", "dc_pack_weights_geglu",
            "dc_fold_layernorm_bias", "dc_workspace_bytes_groupnorm", "dc_workspace_bytes_igemm", "dc_workspace_bytes_attention",
            "dc_workspace_bytes_layernorm"]
@@ -131,6 +138,7 @@ def lib():
                        ("dc_layernorm", [C.POINTER(LayernormParams), vp]),
                        ("dc_attention", [C.POINTER(AttentionParams), vp]),
                        ("dc_cross_attention", [C.POINTER(CrossAttentionParams), vp]),
+                       ("dc_cross_attention_len", [C.POINTER(CrossAttentionLenParams), vp]),
                        ("dc_tblock_front", [C.POINTER(TblockFrontParams), vp]),
                        ("dc_eps_mse", [C.POINTER(EpsMseParams), vp]),
                        ("dc_ddpm_step", [C.POINTER(DdpmStepParams), vp]),
@@ -170,6 +178,8 @@ def lib():
     L.dc_attention_variant.restype = C.c_char_p
     L.dc_cross_attention_variant.argtypes = [C.POINTER(CrossAttentionParams)]
     L.dc_cross_attention_variant.restype = C.c_char_p
+    L.dc_cross_attention_len_variant.argtypes = [C.POINTER(CrossAttentionLenParams)]
+    L.dc_cross_attention_len_variant.restype = C.c_char_p
     L.dc_groupnorm_variant.argtypes = [C.POINTER(GroupnormParams)]
     L.dc_groupnorm_variant.restype = C.c_char_p
     L.dc_layernorm_variant.argtypes = [C.POINTER(LayernormParams)]

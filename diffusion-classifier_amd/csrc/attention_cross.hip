@@ -15,8 +15,12 @@
 // query tile and the K / V block of the next step is fetched into registers under the MFMAs of the current one.  The last block is
 // ragged: keys >= S are staged as zeros and masked, never read (behind them lies the next context, or a gap).
 // A sample's bits depend on its own q rows and its own context only: no atomics, fixed order, no dependence on n or on the position.
+// LEN instantiations (dc_cross_attention_len): context c holds kv_len[c] <= S keys in its S rows; the length, uniform over the wave (over
+// the workgroup in the fp32 kernel), replaces S in the block count, the prefetch condition, the staging bound and the ragged mask, so
+// blocks wholly past it cost nothing and the surviving keys keep their blocks: the bits are those of a context of kv_len[c] rows.
 //
 // fp32 and d = 16: the exact kernel (FMA chain over the keys in order), as attention.hip's.
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 #include "igemm_common.h"
@@ -27,7 +31,15 @@ struct CrossArgs {
   const int32_t* q_map; const int32_t* kv_map;
   int n, Lq, S, heads, d, ld_q, ld_kv, ld_out; float scale;
   int KB;     // fp32 kernel: keys per LDS block
+  const int32_t* kv_len;   // LEN instantiations only: keys per context, clamped into [1, S] by the kernel
 };
+
+// keys of context cs that are attended (LEN): device data, so a bad value is clamped rather than trusted; uniform -> the scalar path
+template <bool LEN>
+__device__ __forceinline__ int cross_len(const CrossArgs& a, int cs) {
+  if constexpr (LEN) return __builtin_amdgcn_readfirstlane(min(max(a.kv_len[cs], 1), a.S));
+  else return a.S;
+}
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -35,7 +47,7 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;
 // keys per block: 8 staging chunks per lane and operand at most, and an LDS strip small enough for 2 - 4 workgroups per CU
 static constexpr int cross_kb(int D) { return D <= 32 ? 64 : 32; }
 
-template <typename T, int D>
+template <typename T, int D, bool LEN>
 __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
   constexpr int KB = cross_kb(D);
   constexpr int NKT = KB / 16, NQT = 2, NDT = D / 16, NKB = D / 32;
@@ -58,6 +70,7 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
   const T* qg = reinterpret_cast<const T*>(a.q) + (size_t)qs * Lq * a.ld_q + h * D;
   const T* kg = reinterpret_cast<const T*>(a.k) + (size_t)cs * S * a.ld_kv + h * D;
   const T* vg = reinterpret_cast<const T*>(a.v) + (size_t)cs * S * a.ld_kv + h * D;
+  const int len = cross_len<LEN>(a, cs);                      // keys of this context (S without LEN); the rows stay S apart
   const int q0 = qt_i * 16 * NQT;
   const int nqt = min(NQT, (Lq - q0 + 15) >> 4);              // 16-query tiles of this wave that hold a query (wave-uniform)
 
@@ -80,12 +93,12 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
   const float sc2 = a.scale * 1.4426950408889634f;            // scores in log2 units
 
   chunk16 ks[NCH], vs[NCH];
-  auto fetch = [&](int k0) {                                  // keys >= S: zeros, and no load (a masked key has P = 0, and 0 x garbage must not be a NaN)
+  auto fetch = [&](int k0) {                                  // keys >= len: zeros, and no load (a masked key has P = 0, and 0 x garbage must not be a NaN)
 #pragma unroll
     for (int u = 0; u < NCH; ++u) {
       const int idx = u * 64 + lane, r = idx / CPR, c = idx - r * CPR;
       ks[u] = chunk16{0u, 0u, 0u, 0u}; vs[u] = ks[u];
-      if (k0 + r < S) {
+      if (k0 + r < len) {
         ks[u] = *reinterpret_cast<const chunk16*>(kg + (size_t)(k0 + r) * a.ld_kv + c * 8);
         vs[u] = *reinterpret_cast<const chunk16*>(vg + (size_t)(k0 + r) * a.ld_kv + c * 8);
       }
@@ -107,8 +120,8 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   };
   typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
-  const int nblk = (S + KB - 1) / KB;
-  // one key block; RAGGED: it holds keys past S (only the last block of a context whose length is not a multiple of KB)
+  const int nblk = (len + KB - 1) / KB;
+  // one key block; RAGGED: it holds keys past len (only the last block of a context whose length is not a multiple of KB)
   auto run_block = [&](int ib, auto raggedc) {
     constexpr bool ragged = decltype(raggedc)::value;
     const int k0 = ib * KB;
@@ -129,7 +142,7 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
         if constexpr (ragged) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (k0 + kt * 16 + lq * 4 + r >= S) acc[r] = -INFINITY;     // keys past S never win the max nor add to the sum
+            if (k0 + kt * 16 + lq * 4 + r >= len) acc[r] = -INFINITY;   // keys past len never win the max nor add to the sum
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[r]);
@@ -183,7 +196,7 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
   fetch(0);
   stash();
   wave_sync();
-  const int nfull = S / KB;
+  const int nfull = len / KB;
   for (int ib = 0; ib < nfull; ++ib) run_block(ib, std::false_type{});
   if (nfull < nblk) run_block(nfull, std::true_type{});
 #pragma unroll
@@ -202,16 +215,16 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
   }
 }
 
-template <typename T, int D>
-static int launch_cross(const CrossArgs& a, hipStream_t s) {
+template <typename T, int D, bool LEN>
+static int launch_cross(const CrossArgs& a, hipStream_t s, const char* fn) {
   constexpr size_t lds = (size_t)4 * 2 * cross_kb(D) * (D + 8) * 2;
   static bool done = false;
-  if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_cross_kernel<T, D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
+  if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_cross_kernel<T, D, LEN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
   const long long items = (long long)a.n * a.heads * ((a.Lq + 31) / 32);
   const long long nb = (items + 3) / 4;
-  if (nb >= (1LL << 31)) { dc_set_error("dc_cross_attention: grid too large"); return DC_ERR_SHAPE; }
-  hipLaunchKernelGGL((attn_cross_kernel<T, D>), dim3((unsigned)nb), dim3(256), lds, s, a);
-  return dc_check_launch("dc_cross_attention(mfma)");
+  if (nb >= (1LL << 31)) { dc_set_error("%s: grid too large", fn); return DC_ERR_SHAPE; }
+  hipLaunchKernelGGL((attn_cross_kernel<T, D, LEN>), dim3((unsigned)nb), dim3(256), lds, s, a);
+  return dc_check_launch(LEN ? "dc_cross_attention_len(mfma)" : "dc_cross_attention(mfma)");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -219,7 +232,7 @@ static int launch_cross(const CrossArgs& a, hipStream_t s) {
 // through LDS as f32 in blocks, each query is owned by d / SW adjacent lanes holding an SW-wide slice of q and of the output (SW = 16;
 // 24 for d = 96), scores are reduced across those lanes with xor-shuffles, the softmax is online key by key — the order of operations
 // does not depend on where a block ends.
-template <typename T, int SW>
+template <typename T, int SW, bool LEN>
 __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) {
   extern __shared__ __attribute__((aligned(16))) float kv[];  // K[KB][d], V[KB][d]
   const int t = threadIdx.x;
@@ -230,6 +243,7 @@ __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) 
   const int qt = b % qtiles; b /= qtiles;
   const int h = b % a.heads; const int i = b / a.heads;
   const int qs = a.q_map ? a.q_map[i] : i, cs = a.kv_map ? a.kv_map[i] : i;
+  const int len = cross_len<LEN>(a, cs);         // keys of this context (S without LEN): uniform over the workgroup, as the barriers need
   float* Ks = kv; float* Vs = kv + a.KB * a.d;
   const T* kb = reinterpret_cast<const T*>(a.k) + (size_t)cs * a.S * a.ld_kv + h * a.d;
   const T* vb = reinterpret_cast<const T*>(a.v) + (size_t)cs * a.S * a.ld_kv + h * a.d;
@@ -241,8 +255,8 @@ __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) 
 #pragma unroll
   for (int e = 0; e < SW; ++e) { qv[e] = Elem<T>::to_f(qp[e]) * a.scale; o[e] = 0.f; }
   float m = -INFINITY, l = 0.f;
-  for (int j0 = 0; j0 < a.S; j0 += a.KB) {
-    const int nk = min(a.KB, a.S - j0);
+  for (int j0 = 0; j0 < len; j0 += a.KB) {
+    const int nk = min(a.KB, len - j0);
     if (j0) __syncthreads();                     // everyone is done with the previous block
     for (int e = t; e < nk * a.d; e += 256) {
       const int r = e / a.d, c = e - r * a.d;
@@ -274,15 +288,16 @@ __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) 
   }
 }
 
-static int cross_validate(const dc_cross_attention_params* p) {
-  DC_REQUIRE(p && p->q && p->k && p->v && p->out, DC_ERR_ARG, "dc_cross_attention: null pointer");
-  DC_REQUIRE(p->dtype == DC_F32 || p->dtype == DC_BF16 || p->dtype == DC_F16, DC_ERR_DTYPE, "dc_cross_attention: dtype %d", p->dtype);
-  DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128, DC_ERR_SHAPE, "dc_cross_attention: head dim %d (16/32/64/96/128)", p->d);
-  DC_REQUIRE(p->n > 0 && p->Lq > 0 && p->heads > 0, DC_ERR_SHAPE, "dc_cross_attention: n/Lq/heads");
-  DC_REQUIRE(p->S >= 1, DC_ERR_SHAPE, "dc_cross_attention: S=%d (at least one key)", p->S);
-  DC_REQUIRE(p->ld_q >= p->heads * p->d && p->ld_kv >= p->heads * p->d && p->ld_out >= p->heads * p->d, DC_ERR_SHAPE, "dc_cross_attention: ld");
+// `fn`: the entry point's name in front of every message (dc_cross_attention / dc_cross_attention_len validate alike)
+static int cross_validate(const dc_cross_attention_params* p, const char* fn) {
+  DC_REQUIRE(p && p->q && p->k && p->v && p->out, DC_ERR_ARG, "%s: null pointer", fn);
+  DC_REQUIRE(p->dtype == DC_F32 || p->dtype == DC_BF16 || p->dtype == DC_F16, DC_ERR_DTYPE, "%s: dtype %d", fn, p->dtype);
+  DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128, DC_ERR_SHAPE, "%s: head dim %d (16/32/64/96/128)", fn, p->d);
+  DC_REQUIRE(p->n > 0 && p->Lq > 0 && p->heads > 0, DC_ERR_SHAPE, "%s: n/Lq/heads", fn);
+  DC_REQUIRE(p->S >= 1, DC_ERR_SHAPE, "%s: S=%d (at least one key)", fn, p->S);
+  DC_REQUIRE(p->ld_q >= p->heads * p->d && p->ld_kv >= p->heads * p->d && p->ld_out >= p->heads * p->d, DC_ERR_SHAPE, "%s: ld", fn);
   // the matrix-core kernel keeps the running max of the RAW scores and folds the scale into the exponent's FMA: valid for scale > 0 only
-  DC_REQUIRE(p->scale > 0.f, DC_ERR_ARG, "dc_cross_attention: scale must be positive (got %g)", (double)p->scale);
+  DC_REQUIRE(p->scale > 0.f, DC_ERR_ARG, "%s: scale must be positive (got %g)", fn, (double)p->scale);
   return DC_OK;
 }
 
@@ -293,33 +308,64 @@ static bool cross_mfma_ok(const dc_cross_attention_params* p) {
   return p->ld_out % 4 == 0 && (((uintptr_t)p->out) & 7) == 0;
 }
 
-extern "C" const char* dc_cross_attention_variant(const dc_cross_attention_params* p) {
-  if (cross_validate(p) != DC_OK) return "invalid";
-  return cross_mfma_ok(p) ? "mfma" : "fp32";
-}
-
-extern "C" int dc_cross_attention(const dc_cross_attention_params* p, dc_stream stream) {
-  const int rc = cross_validate(p);
-  if (rc != DC_OK) return rc;
+// validated parameters -> the launch; LEN: the instantiations that read a.kv_len
+template <bool LEN>
+static int cross_launch(const dc_cross_attention_params* p, const int32_t* kv_len, dc_stream stream, const char* fn) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  CrossArgs a{p->q, p->k, p->v, p->out, p->q_map, p->kv_map, p->n, p->Lq, p->S, p->heads, p->d, p->ld_q, p->ld_kv, p->ld_out, p->scale, 0};
+  CrossArgs a{p->q, p->k, p->v, p->out, p->q_map, p->kv_map, p->n, p->Lq, p->S, p->heads, p->d, p->ld_q, p->ld_kv, p->ld_out, p->scale, 0, kv_len};
+  char what[40];
+  snprintf(what, sizeof(what), "%s: dtype", fn);
   if (cross_mfma_ok(p))
-    return dc_by_dtype16(p->dtype, "dc_cross_attention: dtype", [&](auto t) {
+    return dc_by_dtype16(p->dtype, what, [&](auto t) {
       using T = decltype(t);
-      if (p->d == 32) return launch_cross<T, 32>(a, s);
-      if (p->d == 64) return launch_cross<T, 64>(a, s);
-      if (p->d == 96) return launch_cross<T, 96>(a, s);
-      return launch_cross<T, 128>(a, s);
+      if (p->d == 32) return launch_cross<T, 32, LEN>(a, s, fn);
+      if (p->d == 64) return launch_cross<T, 64, LEN>(a, s, fn);
+      if (p->d == 96) return launch_cross<T, 96, LEN>(a, s, fn);
+      return launch_cross<T, 128, LEN>(a, s, fn);
     });
   a.KB = p->S < 4096 / p->d ? p->S : 4096 / p->d;                // at most 32 KiB of LDS
   const size_t lds = (size_t)2 * a.KB * p->d * sizeof(float);
   const int SW = p->d == 96 ? 24 : 16, DS = p->d / SW, QT = 256 / DS, qtiles = (p->Lq + QT - 1) / QT;
   const long long nb = (long long)p->n * p->heads * qtiles;
-  DC_REQUIRE(nb < (1LL << 31), DC_ERR_SHAPE, "dc_cross_attention: grid too large");
-  return dc_by_dtype(p->dtype, "dc_cross_attention: dtype", [&](auto t) {
+  DC_REQUIRE(nb < (1LL << 31), DC_ERR_SHAPE, "%s: grid too large", fn);
+  return dc_by_dtype(p->dtype, what, [&](auto t) {
     using T = decltype(t);
-    void (*kern)(const CrossArgs) = SW == 24 ? attn_cross_f32_kernel<T, 24> : attn_cross_f32_kernel<T, 16>;
+    void (*kern)(const CrossArgs) = SW == 24 ? attn_cross_f32_kernel<T, 24, LEN> : attn_cross_f32_kernel<T, 16, LEN>;
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(256), lds, s, a);
-    return dc_check_launch("dc_cross_attention");
+    return dc_check_launch(fn);
   });
+}
+
+extern "C" const char* dc_cross_attention_variant(const dc_cross_attention_params* p) {
+  if (cross_validate(p, "dc_cross_attention") != DC_OK) return "invalid";
+  return cross_mfma_ok(p) ? "mfma" : "fp32";
+}
+
+extern "C" int dc_cross_attention(const dc_cross_attention_params* p, dc_stream stream) {
+  const int rc = cross_validate(p, "dc_cross_attention");
+  if (rc != DC_OK) return rc;
+  return cross_launch<false>(p, nullptr, stream, "dc_cross_attention");
+}
+
+// dc_cross_attention_len: the same problem with kv_len keys per context.  Everything but kv_len is validated and routed as above.
+static dc_cross_attention_params cross_base(const dc_cross_attention_len_params* p) {
+  return dc_cross_attention_params{p->q, p->k, p->v, p->out, p->q_map, p->kv_map, p->dtype, p->n, p->Lq, p->S, p->heads, p->d,
+                                   p->ld_q, p->ld_kv, p->ld_out, p->scale};
+}
+
+extern "C" const char* dc_cross_attention_len_variant(const dc_cross_attention_len_params* p) {
+  if (!p) return "invalid";
+  const dc_cross_attention_params b = cross_base(p);
+  if (cross_validate(&b, "dc_cross_attention_len") != DC_OK) return "invalid";
+  return cross_mfma_ok(&b) ? "mfma" : "fp32";
+}
+
+extern "C" int dc_cross_attention_len(const dc_cross_attention_len_params* p, dc_stream stream) {
+  DC_REQUIRE(p, DC_ERR_ARG, "dc_cross_attention_len: null pointer");
+  const dc_cross_attention_params b = cross_base(p);
+  const int rc = cross_validate(&b, "dc_cross_attention_len");
+  if (rc != DC_OK) return rc;
+  // no lengths: every context has S keys, which is dc_cross_attention's launch
+  if (!p->kv_len) return cross_launch<false>(&b, nullptr, stream, "dc_cross_attention_len");
+  return cross_launch<true>(&b, p->kv_len, stream, "dc_cross_attention_len");
 }

@@ -58,11 +58,64 @@ def log(t, eps=1e-20):
 class PromptTable(nn.Module):
     """encoder_type='prompt': one prompt of S token embeddings per class, `weight` [classes + 1, S, encoder_hid_dim] (the last row is the
     null prompt, as for 'nn').  The place for per-class text embeddings computed offline (T5, CLIP, a learned soft prompt): copy them
-    into `weight`; the parameter keeps the name `weight`, so a checkpoint carries it as `model_2.safetensors` like nn.Embedding's."""
+    into `weight`; the parameter keeps the name `weight`, so a checkpoint carries it as `model_2.safetensors` like nn.Embedding's.
+
+    Prompts of different lengths: `lengths` [rows] int64 (a buffer; S everywhere by default) says how many of a row's S tokens are
+    attended, the rest being padding whose content is never read — `set_prompt(row, emb)` for one prompt, or copy a text encoder's
+    padded output into `weight` and hand the token counts to `set_lengths`.  A table whose lengths are all S saves exactly
+    `["weight"]`, as before; a ragged one adds `"lengths"`; loading takes both forms (no `"lengths"`: all S)."""
 
     def __init__(self, rows, tokens, dim):
         super().__init__()
         self.weight = nn.Parameter(torch.randn(rows, tokens, dim))
+        self.register_buffer("lengths", torch.full((rows,), tokens, dtype=torch.int64))
+        self._ragged = False         # host copy of `(lengths != S).any()`: asked per plan lookup, must not synchronise with the device
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        if not self._ragged:
+            destination.pop(prefix + "lengths", None)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args):
+        ln = state_dict.get(prefix + "lengths")
+        if ln is None:
+            ln = state_dict[prefix + "lengths"] = torch.full_like(self.lengths, self.weight.shape[1])
+        self._check(ln.cpu())
+        self._ragged = bool((ln != self.weight.shape[1]).any())
+        super()._load_from_state_dict(state_dict, prefix, *args)
+
+    def _check(self, ln):
+        rows, S = self.weight.shape[0], self.weight.shape[1]
+        if ln.dim() != 1 or ln.numel() != rows or ln.dtype.is_floating_point or ln.dtype == torch.bool:
+            raise ValueError(f"prompt lengths must be an int sequence of {rows} entries, got {ln.dtype} {tuple(ln.shape)}")
+        if int(ln.min()) < 1 or int(ln.max()) > S:
+            raise ValueError(f"prompt lengths must lie in [1, {S}], got {ln.tolist()}")
+
+    @property
+    def varlen(self):
+        """Does any prompt have fewer than S tokens (known on the host: no device read)?"""
+        return self._ragged
+
+    @torch.no_grad()
+    def set_lengths(self, seq):
+        """Token counts of all rows (1 <= len <= S), for a `weight` filled with padded text-encoder output."""
+        ln = torch.as_tensor(seq).detach().cpu()
+        self._check(ln)
+        self.lengths.copy_(ln.to(torch.int64))
+        self._ragged = bool((ln != self.weight.shape[1]).any())
+
+    @torch.no_grad()
+    def set_prompt(self, row, emb):
+        """Prompt `row` := emb [len, hid] with 1 <= len <= S: writes its tokens, zeroes the pad rows and records the length."""
+        S, hid = self.weight.shape[1], self.weight.shape[2]
+        emb = torch.as_tensor(emb)
+        if emb.dim() != 2 or emb.shape[1] != hid or not 1 <= emb.shape[0] <= S:
+            raise ValueError(f"a prompt must be [len, {hid}] with 1 <= len <= {S}, got {tuple(emb.shape)}")
+        n = int(emb.shape[0])
+        self.weight[row, :n] = emb.to(self.weight.device, self.weight.dtype)
+        self.weight[row, n:] = 0
+        self.lengths[row] = n
+        self._ragged = bool((self.lengths.cpu() != S).any())
 
     def forward(self, ids):
         return self.weight[ids]
@@ -123,6 +176,15 @@ class DiffusionClassifier(nn.Module):
         else:
             raise NotImplementedError(self.encoder_type)
         return embeddings
+
+    def _ragged_table(self):
+        return self.encoder_type == 'prompt' and self.encoder.varlen
+
+    def _refuse_ragged_on_foreign(self):
+        if self._ragged_table():
+            raise NotImplementedError("prompts of different lengths need a HIP backbone (UNetCondition2D): the reference's backbone "
+                                      "signature (x, noise_labels, encoder_hidden_states) has no mask argument, so a foreign nn.Module "
+                                      "would attend the pad rows")
 
     def diffuse(self, x, alpha_t, sigma_t):
         eps_t = torch.randn_like(x)
@@ -357,20 +419,26 @@ class DiffusionClassifier(nn.Module):
             null = self.encode_text_prompt(torch.full_like(text, self.null_token)).to(dev)
         backbone = self.ema.ema_model
         fused = hasattr(backbone, "forward_pair") and cond is not None and z_t.is_cuda
+        lens = {}                                                             # prompts of different lengths: the rows' token counts
+        if cond is not None and self._ragged_table():
+            if not hasattr(backbone, "make_plan"):
+                self._refuse_ragged_on_foreign()
+            ln = self.encoder.lengths.cpu()
+            lens = dict(cond=ln[text.detach().cpu()], null=ln[torch.full_like(text, self.null_token).cpu()])
         steps = torch.linspace(from_t, 0.0, self.config.sampling_steps + 1)
         n = len(steps) - 1
         for i in range(n + 1):                                                # the last pass repeats step n-1 and keeps the mean
             u_t, u_s = (steps[i], steps[i + 1]) if i < n else (steps[-2], steps[-1])
             lam_t, lam_s = self.schedule(u_t).to(dev).unsqueeze(0), self.schedule(u_s).to(dev).unsqueeze(0)
             if fused:
-                pair = backbone.forward_pair(z_t, lam_t, cond, null)
+                pair = backbone.forward_pair(z_t, lam_t, cond, null, **({"cond_lengths": lens["cond"], "null_lengths": lens["null"]} if lens else {}))
                 if i == n:
                     return self._fused_sampler_step(backbone, z_t, pair, lam_t, lam_s, None).to(z_t.dtype)
                 noise = torch.randn_like(z_t).to(torch.float32).contiguous()
                 z_t = self._fused_sampler_step(backbone, z_t, pair, lam_t, lam_s, noise).to(z_t.dtype)
                 continue
-            pred = self.ema(z_t, lam_t, encoder_hidden_states=cond)
-            u_pred = self.ema(z_t, lam_t, encoder_hidden_states=null)
+            pred = self.ema(z_t, lam_t, encoder_hidden_states=cond, **({"encoder_lengths": lens["cond"]} if lens else {}))
+            u_pred = self.ema(z_t, lam_t, encoder_hidden_states=null, **({"encoder_lengths": lens["null"]} if lens else {}))
             mu, var = self.ddpm_sampler_step(z_t, pred, u_pred, lam_t.clone().detach(), lam_s.clone().detach())
             if i == n:
                 return self.clip(mu)
@@ -487,6 +555,7 @@ class _ForeignRunner:
     def __init__(self, dc, backbone, x, T, draws):
         if draws["philox"]:
             raise L.DcamdError("rng='philox' needs a HIP backbone (UNetCondition2D / DiT)")
+        dc._refuse_ragged_on_foreign()
         self.dc, self.bb, self.x, self.T, self.d = dc, backbone, x, T, draws
         self.err = torch.full((x.shape[0], dc.config.classes, T), float("inf"), device=x.device)
 
@@ -554,8 +623,9 @@ class _HipRunner:
         BS, Cc, H, W = self.x.shape
         wver = getattr(self.bb, "_wver", 0)
         S = int(dc.encoder.weight.shape[1]) if dc.encoder_type == 'prompt' else 1      # tokens per context
+        varlen = dc.encoder_type == 'prompt' and dc.encoder.varlen                     # prompts of different lengths: a plan with ctx_len
         key = (BS, n_bj, k, self.dt, str(dev), (Cc, H, W), bool(getattr(self.bb, "share_trunk", True)), id(self.bb),
-               self.T, cfg.classes, wver, S)
+               self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ())
         sp = dc._score_plans.get(key)
         if sp is not None:
             dc._score_plans[key] = dc._score_plans.pop(key)      # most recently used last
@@ -583,7 +653,7 @@ class _HipRunner:
             errors=torch.full((BS * cfg.classes * T + 1,), float("inf"), dtype=torch.float32, device=dev),
             lam=lam, alpha=alpha, sigma=sigma, img_of_bj=img_of_bj, ctx_of_unit=ctx_of_unit, out_index=out_index,
             v_param=dc.pred_param == 'v')
-        plan = self.bb.make_plan(n_bj, k, cfg.classes, dev, score=score, **({"S": S} if S > 1 else {}))
+        plan = self.bb.make_plan(n_bj, k, cfg.classes, dev, score=score, **({"S": S} if S > 1 else {}), **({"varlen": True} if varlen else {}))
         sp = dict(plan=plan, score=score, ctl=ctl, pair_id=pair_id, words=words, n_bj=n_bj, k=k, U=U)
         dc._score_plans[key] = sp
         # each entry owns an arena, a workspace and an errors buffer in HBM, and n_bj follows the pair count (per rank, per stage, per
@@ -637,6 +707,8 @@ class _HipRunner:
         score["x"].copy_(self.x_dev)
         if dc.encoder is not None:
             plan.ctx.copy_(dc.encoder.weight[:ncls].detach().to(dev, torch.float32).reshape(plan.ctx.shape))
+            if plan.varlen:                              # the same on every rank: grid sharding needs nothing else
+                plan.ctx_len.copy_(dc.encoder.lengths[:ncls].to(dev, torch.int32))
         plan.run_ctx()                                   # per-class vectors: once per stage, not per micro-batch
         n_mb = -(-len(pairs) // n_bj)
         host = sp.get("host")                            # pinned staging, reused across calls (pin_memory() is slow)

@@ -319,10 +319,13 @@ class PlanBuilder:
                         bytes=4.0 * self.n[q.dom] * Lq * q.C * DT_SIZE[q.dt]))
         return out
 
-    def cross_attention(self, name, q, k, v, heads, d):
+    def cross_attention(self, name, q, k, v, heads, d, kv_len=None):
         """softmax(q k^T / sqrt(d)) v per head with keys / values from the 'ctx' domain (k.W tokens per context, picked per unit through
         ctx_of_unit) and queries of q's domain read through its map (bj_of_unit for the class-shared trunk): dc_cross_attention.  Head
-        widths as in `attention` (q.C // heads channels per head, the scale of the true d).  The output is per unit."""
+        widths as in `attention` (q.C // heads channels per head, the scale of the true d).  The output is per unit.
+        kv_len: device pointer (`const`) of an int32 tensor [n_ctx] of keys per context, indexed through the same map as k / v: dc_cross_attention_len
+        (only the first kv_len[c] of a context's k.W rows are attended).  The lengths are device data that change between runs, so
+        `flops` is computed with S = k.W: the upper bound.  `bytes` (q + out) does not depend on the length."""
         dom = self._dom(q, k)
         out = self.tensor(name, dom, q.H, q.W, q.C, q.dt)
         dp = q.C // heads
@@ -331,9 +334,12 @@ class PlanBuilder:
         n, Lq, S = self.n[dom], q.H * q.W, k.W
         f = dict(q=q, k=k, v=v, out=out, q_map=self._map(q, dom), kv_map=self._map(k, dom), dtype=q.dt, n=n, Lq=Lq, S=S, heads=heads,
                  d=dp, ld_q=q.ld, ld_kv=k.ld, ld_out=out.ld, scale=float(d) ** -0.5)
-        self._emit(L.OP_CROSS_ATTENTION, L.CrossAttentionParams, f, [q, k, v], [out],
-                   dict(name=name, family="cross_attention", flops=4.0 * n * heads * Lq * S * dp,
-                        bytes=2.0 * n * Lq * q.C * DT_SIZE[q.dt]))
+        meta = dict(name=name, family="cross_attention", flops=4.0 * n * heads * Lq * S * dp, bytes=2.0 * n * Lq * q.C * DT_SIZE[q.dt])
+        if kv_len is None:
+            self._emit(L.OP_CROSS_ATTENTION, L.CrossAttentionParams, f, [q, k, v], [out], meta)
+        else:
+            f["kv_len"] = kv_len
+            self._emit(L.OP_CROSS_ATTENTION_LEN, L.CrossAttentionLenParams, f, [q, k, v], [out], meta)
         return out
 
     def tblock_front_ok(self, x, heads):
@@ -467,6 +473,8 @@ class PlanBuilder:
                 self.meta[i]["variant"] = L.lib().dc_attention_variant(s).decode()
             elif kind == L.OP_CROSS_ATTENTION:
                 self.meta[i]["variant"] = L.lib().dc_cross_attention_variant(s).decode()
+            elif kind == L.OP_CROSS_ATTENTION_LEN:
+                self.meta[i]["variant"] = L.lib().dc_cross_attention_len_variant(s).decode()
             elif kind == L.OP_GROUPNORM:
                 self.meta[i]["variant"] = L.lib().dc_groupnorm_variant(s).decode()
             elif kind == L.OP_LAYERNORM:
@@ -806,15 +814,18 @@ class UNetPlan:
     """Static launch plan of one UNetCondition2D scoring step.
 
     inputs (plan-owned device buffers, refreshed per micro-batch by the caller):
-      lam [n_bj] f32;  ctx [n_ctx, hid] f32 (S = 1: one class token per context) or [n_ctx, S, hid] (S > 1: a prompt of S tokens);  a0 = conv_in GEMM operand [n_bj, H, W, kin]
+      lam [n_bj] f32;  ctx [n_ctx, hid] f32 (S = 1: one class token per context) or [n_ctx, S, hid] (S > 1: a prompt of S tokens);
+      varlen plans: ctx_len [n_ctx] int32, tokens of each prompt that are attended (1 ... S; S when built);  a0 = conv_in GEMM operand [n_bj, H, W, kin]
       (written by the q_sample op when `score=True`, else by the caller through `a0_view`);
       maps bj_of_unit / ctx_of_unit [U] int32.
     output: pred [U, H, W, out_channels] f32 (NHWC); with score=True also err -> errors buffer.
     """
 
-    def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, share_trunk=True, score=None, device=None, S=1):
+    def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, share_trunk=True, score=None, device=None, S=1, varlen=False):
         import os
         assert S >= 1, S
+        if varlen and S == 1:
+            raise L.DcamdError("a varlen plan needs prompts of S > 1 tokens: one token is always attended")
         fuse_gn_out = os.environ.get("DCAMD_NO_GN_OUT_FUSION") is None
         split_skips = os.environ.get("DCAMD_NO_SKIP_SPLIT") is None
         fold_short = os.environ.get("DCAMD_NO_SHORT_FOLD") is None
@@ -832,7 +843,7 @@ class UNetPlan:
         cfg = model.config
         dev = device or weights.dev
         dt = weights.dt
-        self.dt, self.n_bj, self.n_cls, self.n_ctx, self.S = dt, n_bj, n_cls, n_ctx, S
+        self.dt, self.n_bj, self.n_cls, self.n_ctx, self.S, self.varlen = dt, n_bj, n_cls, n_ctx, S, bool(varlen)
         U = n_bj * n_cls
         pb = PlanBuilder(dev, n_bj, n_cls, n_ctx)
         self.pb = pb
@@ -855,6 +866,10 @@ class UNetPlan:
         pb.set_map("ctx", "unit", self.ctx_of_unit)
         lam = pb.external("lam", self.lam, "bj", 1, 1, 1, L.DC_F32)
         pb.external("ctx", self.ctx, "ctx", 1, S, cfg.encoder_hid_dim, L.DC_F32)
+        # prompts of different lengths: every cross-attention site reads the key count of a unit's context through the same map as
+        # its K | V.  The context plan is the same: the pad rows of a prompt are projected and never read
+        self.ctx_len = torch.full((n_ctx,), S, **i32) if varlen else None
+        ctx_len = pb.const(self.ctx_len)
         kin = weights.kin
         if score is not None:
             # score = dict(x=[B,C,H,W] f32 buffer, eps=[n_bj,C,H,W], alpha, sigma, img_of_bj, out_index, errors, v_param)
@@ -1024,7 +1039,7 @@ class UNetPlan:
             else:
                 hn = pb.layernorm(tbk + ".ln2", h, pb.const(P[tbk + ".norm2.g"]), pb.const(P[tbk + ".norm2.b"]), 1e-5)
                 q2 = pb.igemm(tbk + ".attn2.to_q", hn, pb.const(P[tbk + ".attn2.to_q.w"]), Cq)
-            o2 = pb.cross_attention(tbk + ".attn2", q2, ckv[key][0], ckv[key][1], heads, d)
+            o2 = pb.cross_attention(tbk + ".attn2", q2, ckv[key][0], ckv[key][1], heads, d, kv_len=ctx_len)
             h = pb.igemm(tbk + ".attn2_out", o2, pb.const(P[tbk + ".attn2.to_out.0.wc"]), Cc,
                          bias=pb.const(P[tbk + ".attn2.to_out.0.bc"]), residual=h)
             return transformer_back(key, tbk, x, h, Cc)

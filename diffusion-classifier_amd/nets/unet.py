@@ -255,12 +255,14 @@ class UNetCondition2D(_HipBackbone):
             self._packed[key] = E.UNetWeights(self, dt, device)
         return self._packed[key]
 
-    def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None, S=1):
-        """S: tokens per context (1: the class token; more: a prompt, attended by dc_cross_attention)."""
+    def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None, S=1, varlen=False):
+        """S: tokens per context (1: the class token; more: a prompt, attended by dc_cross_attention).  varlen (S > 1 only): the
+        prompts are padded to S and the plan owns `ctx_len` [n_ctx] int32, the tokens of each that are attended
+        (dc_cross_attention_len)."""
         dt = E.DT[self.compute_dtype]
         w = self.packed_weights(dt, device)
         return E.UNetPlan(self, w, n_bj, n_cls, n_ctx, share_trunk=self.share_trunk if share_trunk is None else share_trunk,
-                          score=score, device=device, S=S)
+                          score=score, device=device, S=S, varlen=varlen)
 
     def _context_tokens(self, *ts):
         """Token count S of the context tensors [N, S, hid] of one call (all the same S; any S >= 1)."""
@@ -272,9 +274,26 @@ class UNetCondition2D(_HipBackbone):
             raise L.DcamdError(f"the contexts of one call must have the same token count, got {[int(t.shape[1]) for t in ts]}")
         return int(ts[0].shape[1])
 
+    @staticmethod
+    def _context_lengths(lengths, N, S):
+        """Token counts [N] of padded prompts, validated on the host (1 <= len <= S; the kernels only clamp) -> int32 on the CPU.
+        None: all S."""
+        if lengths is None:
+            return torch.full((N,), S, dtype=torch.int32)
+        ln = torch.as_tensor(lengths).detach().cpu()
+        if ln.dim() != 1 or ln.numel() != N or ln.dtype.is_floating_point or ln.dtype == torch.bool:
+            raise L.DcamdError(f"prompt lengths must be an int tensor [{N}], got {ln.dtype} {tuple(ln.shape)}")
+        if S == 1:
+            raise L.DcamdError("prompt lengths need prompts of S > 1 tokens: one token is always attended")
+        if int(ln.min()) < 1 or int(ln.max()) > S:
+            raise L.DcamdError(f"prompt lengths must lie in [1, {S}], got {ln.tolist()}")
+        return ln.to(torch.int32)
+
     @torch.no_grad()
     def forward(self, x, noise_labels, downblock_additional_residuals=None, midblock_additional_residuals=None,
-                encoder_hidden_states=None):
+                encoder_hidden_states=None, encoder_lengths=None):
+        """encoder_lengths: int tensor [N], the tokens of each padded prompt [N, S, hid] that are attended (what diffusers expresses as
+        `encoder_attention_mask`); the content of the pad rows is irrelevant.  None: all S, today's plan."""
         if downblock_additional_residuals is not None or midblock_additional_residuals is not None:
             raise NotImplementedError("ControlNet residuals are not on the scoring path")
         L.require_gpu()
@@ -284,23 +303,31 @@ class UNetCondition2D(_HipBackbone):
         N, Cin, H, W = x.shape
         S = self._context_tokens(encoder_hidden_states)
         key = ("fwd", N, str(dev), self.compute_dtype, self.share_trunk, S)
+        varlen = encoder_lengths is not None
+        if varlen:
+            lens = self._context_lengths(encoder_lengths, N, S)
+            key += ("varlen",)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 1, N, dev, S=S)
+            plan = self._plans[key] = self.make_plan(N, 1, N, dev, S=S, varlen=varlen)
         self._feed(plan, x, noise_labels)
         plan.ctx.copy_(encoder_hidden_states.to(dev, torch.float32).reshape(plan.ctx.shape))
+        if varlen:
+            plan.ctx_len.copy_(lens)
         plan.run_ctx()
         plan.run()
         return plan.pred_view().permute(0, 3, 1, 2).contiguous().to(x.dtype)
 
 
     @torch.no_grad()
-    def forward_pair(self, x, noise_labels, cond, null):
+    def forward_pair(self, x, noise_labels, cond, null, cond_lengths=None, null_lengths=None):
         """Classifier-free-guidance pair as ONE batch-2 plan launch (reference `sample`, :255-266, calls the backbone twice per
         step): unit 2b scores image b under its class token (or prompt of S tokens) `cond[b]`, unit 2b+1 under the null one `null[b]`
         (`cond` and `null` [N, S, hid] with the same S); every layer in
         front of the first cross-attention runs once per image (class-shared trunk).  Returns the plan's prediction buffer
-        [2N, H, W, ld] fp32 NHWC (the layout `dc_ddpm_step` reads) — a view that the next call overwrites."""
+        [2N, H, W, ld] fp32 NHWC (the layout `dc_ddpm_step` reads) — a view that the next call overwrites.
+        cond_lengths / null_lengths: int tensors [N], the attended tokens of each padded prompt (as `forward`'s encoder_lengths; one
+        of them None: all S on that side); both None: today's plan."""
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError("UNetCondition2D.forward_pair needs CUDA/HIP tensors (no CPU fallback)")
@@ -308,12 +335,18 @@ class UNetCondition2D(_HipBackbone):
         N, Cin, H, W = x.shape
         S = self._context_tokens(cond, null)
         key = ("pair", N, str(dev), self.compute_dtype, self.share_trunk, S)
+        varlen = cond_lengths is not None or null_lengths is not None
+        if varlen:
+            lens = torch.stack([self._context_lengths(cond_lengths, N, S), self._context_lengths(null_lengths, N, S)], dim=1)
+            key += ("varlen",)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 2, 2 * N, dev, S=S)   # ctx_of_unit = unit index: one context per unit
+            plan = self._plans[key] = self.make_plan(N, 2, 2 * N, dev, S=S, varlen=varlen)   # ctx_of_unit = unit index: one context per unit
         self._feed(plan, x, noise_labels)
         ctx = torch.stack([cond, null], dim=1)                                # [N, 2, S, hid]: context 2b = cond[b], 2b + 1 = null[b]
         plan.ctx.copy_(ctx.to(dev, torch.float32).reshape(plan.ctx.shape))
+        if varlen:
+            plan.ctx_len.copy_(lens.reshape(-1))                              # interleaved as the contexts: 2b = cond[b], 2b + 1 = null[b]
         plan.run_ctx()
         plan.run()
         return plan.pred_view()

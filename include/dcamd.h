@@ -15,6 +15,8 @@
  *   dc_attention        F.scaled_dot_product_attention self-attention (attn1)
  *   dc_cross_attention  F.scaled_dot_product_attention cross-attention (attn2) over a context of several tokens
  *                       (encode_text_prompt's [B, S, hid], diffusion_classifier.py:93-98; one token needs no kernel)
+ *   dc_cross_attention_len  the same over prompts of different lengths padded to S tokens: a key count per context, which is
+ *                       what diffusers' encoder_attention_mask expresses for a text encoder's padded output
  *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
@@ -40,7 +42,8 @@ extern "C" {
 
 /* 2: qstats records are (mean, M2) sets (version 1: sum, sum of squares) and qparts must divide HW
  * 3: dc_ddpm_step_params.one_plus_w; dc_attention requires scale > 0; dc_igemm_params.pn_* (producer-side GroupNorm)
- * (dc_cross_attention, dc_cross_attention_variant and DC_OP_CROSS_ATTENTION are additive within 4: no existing struct or symbol changed) */
+ * (dc_cross_attention, dc_cross_attention_variant and DC_OP_CROSS_ATTENTION are additive within 4: no existing struct or symbol changed)
+ * (dc_cross_attention_len, dc_cross_attention_len_variant, dc_cross_attention_len_params and DC_OP_CROSS_ATTENTION_LEN likewise) */
 #define DC_ABI_VERSION 4
 
 typedef void* dc_stream; /* hipStream_t */
@@ -264,8 +267,9 @@ int64_t dc_workspace_bytes_attention(const dc_attention_params* p);
  * another tensor with its own length (the prompt of a unit, picked through ctx_of_unit) and whose queries may be shared (the
  * class-shared trunk keeps them once per (image, trial) pair: bj_of_unit).  A map of NULL is the identity.
  * q [*, Lq, heads, d] with row stride ld_q, k / v [*, S, heads, d] with row stride ld_kv (a stacked K | V GEMM output is passed as two
- * offset pointers), out [n, Lq, heads, d] with row stride ld_out; all in `dtype`.  Every one of the S keys is attended: there is no mask
- * (the reference passes none, so padded prompt rows take part).  Rows behind the S-th of a context are never read.
+ * offset pointers), out [n, Lq, heads, d] with row stride ld_out; all in `dtype`.  Every one of the S keys is attended (the reference
+ * passes no mask, so padded prompt rows take part; dc_cross_attention_len below takes a key count per context).  Rows behind the S-th
+ * of a context are never read.
  * scale must be > 0 and S >= 1 (DC_ERR_ARG / DC_ERR_SHAPE); head dims d = 16, 32, 64, 96, 128, narrower heads zero-padded by the
  * caller exactly as for dc_attention (scale of the true width; the pad columns of the output are zero).
  * 16-bit with d = 32 / 64 / 96 / 128 and 16-byte aligned rows: the matrix-core kernel (one wave per 32 queries of a (sample, head),
@@ -280,6 +284,25 @@ int dc_cross_attention(const dc_cross_attention_params* p, dc_stream s);
 /* Name of the kernel dc_cross_attention would launch for these parameters: "mfma" or "fp32"; "invalid" when it would refuse them
  * (measurement / tests only; static string; touches no memory). */
 const char* dc_cross_attention_variant(const dc_cross_attention_params* p);
+
+/* dc_cross_attention over prompts of different lengths.  k / v keep the padded layout (context c starts at row c * S); output sample
+ * i, with context c = kv_map ? kv_map[i] : i, attends keys 0 .. kv_len[c] - 1 of it only: masking keys >= kv_len[c] out of the
+ * softmax, which is attending the prompt truncated to kv_len[c] tokens.  Rows kv_len[c] .. S - 1 of a context are never read, key
+ * blocks wholly past the length are skipped, and the surviving keys keep their blocks: the bits of out[i] are those dc_cross_attention
+ * gives for a context of S = kv_len[c] rows.  kv_len [number of contexts] int32 on the device; NULL: every context has S keys (the
+ * launch of dc_cross_attention).  A length is device data the host cannot see without a synchronisation: the kernels clamp it into
+ * [1, S] (no read outside the context's own rows, no empty softmax); validate lengths where they are produced.  Every other argument
+ * is validated and routed as for dc_cross_attention (same codes; messages under this function's name).  There is no mask with holes
+ * and no per-query mask. */
+typedef struct {
+  const void* q; const void* k; const void* v; void* out;
+  const int32_t* q_map; const int32_t* kv_map;          /* NULL = identity */
+  const int32_t* kv_len;                                /* keys per context; NULL = S everywhere */
+  int32_t dtype, n, Lq, S, heads, d, ld_q, ld_kv, ld_out; float scale;
+} dc_cross_attention_len_params;
+int dc_cross_attention_len(const dc_cross_attention_len_params* p, dc_stream s);
+/* As dc_cross_attention_variant: "mfma", "fp32" or "invalid" (the routing does not depend on kv_len). */
+const char* dc_cross_attention_len_variant(const dc_cross_attention_len_params* p);
 
 /* ---------------------------------------------------------------- transformer block, attention half --- */
 /* One launch for the self-attention half of a UNet transformer block (the backbone behind /root/reference/nets/unet.py:186-195:
@@ -355,7 +378,7 @@ int dc_stage_maps(const int32_t* keep, int32_t BS, int32_t C, int32_t T, int32_t
 /* ---------------------------------------------------------------- plan ----------- */
 typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GROUPNORM = 4,
                DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8,
-               DC_OP_CROSS_ATTENTION = 9 } dc_op_kind;
+               DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10 } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */

@@ -5,7 +5,11 @@ through a ctx_of_unit map (unit -> class), against F.scaled_dot_product_attentio
 the reference's stack would run; the gather itself is not timed).  Reports ms and TB/s of the q + out stream the kernel is bound by
 (developer tool; DCAMD_LIB selects the library, so A/B builds can be timed in one session).
 
-  python tools/bench_cross_attention.py [units] [S] [--json OUT.json]
+  python tools/bench_cross_attention.py [units] [S] [--json OUT.json] [--kv-len 8,20,77]
+
+--kv-len: also time dc_cross_attention_len with every context at each of the given key counts (of S rows per context), in rounds that
+alternate with dc_cross_attention on the same buffers (median, min and max of the rounds): what the skipped key blocks of short
+prompts save, and what the length costs at full length.  Without the option the output is what it was.
 """
 import json
 import os
@@ -17,8 +21,8 @@ from diffusion_classifier_amd import _lib as L
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 out_json = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
-if out_json:
-    args = [a for a in args if a != out_json]
+kv_lens = [int(v) for v in sys.argv[sys.argv.index("--kv-len") + 1].split(",")] if "--kv-len" in sys.argv else []
+args = [a for a in args if a != out_json and not (kv_lens and a == sys.argv[sys.argv.index("--kv-len") + 1])]
 units = int(args[0]) if len(args) > 0 else 8000
 S = int(args[1]) if len(args) > 1 else 77
 n_ctx, reps = 10, 200
@@ -37,7 +41,16 @@ def timed(fn):
     return e0.elapsed_time(e1) / reps
 
 
-rows = []
+def alternated(fns, rounds=5):
+    """Time the calls in alternating rounds -> per call (median, min, max) ms."""
+    ms = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            ms[i].append(timed(fn))
+    return [(sorted(m)[len(m) // 2], min(m), max(m)) for m in ms]
+
+
+rows, len_rows = [], []
 for dt, td, name in ((L.DC_F16, torch.float16, "f16"), (L.DC_BF16, torch.bfloat16, "bf16")):
     for site, Lq, heads, d, n in (("cfg2 8x8", 64, 8, 32, units), ("cfg2 4x4", 16, 8, 64, units), ("cfg3 16x16", 256, 8, 64, max(1, units // 10))):
         C = heads * d
@@ -66,6 +79,21 @@ for dt, td, name in ((L.DC_F16, torch.float16, "f16"), (L.DC_BF16, torch.bfloat1
         rows.append(row)
         print(f"{name} {site}: n={n} Lq={Lq} heads={heads} d={d} S={S} [{kern}]: {ms:.3f} ms  {row['tb_per_s']:.2f} TB/s (q + out)   "
               f"SDPA, K/V gathered: {ms_sdpa:.3f} ms  {row['sdpa_tb_per_s']:.2f} TB/s   max |diff| {diff:.2e}")
+        if kv_lens:
+            lens = [torch.full((n_ctx,), ln, dtype=torch.int32, device="cuda") for ln in kv_lens]
+            pl = [L.CrossAttentionLenParams(kv_len=t.data_ptr(), **{f: getattr(p, f) for f, _ in L.CrossAttentionParams._fields_}) for t in lens]
+            calls = [lambda: L.check(L.lib().dc_cross_attention(p, L.stream_ptr()), "dc_cross_attention")]
+            calls += [lambda x=x: L.check(L.lib().dc_cross_attention_len(x, L.stream_ptr()), "dc_cross_attention_len") for x in pl]
+            res = alternated(calls)
+            for ln, (med, lo, hi) in zip(["full"] + kv_lens, res):
+                lr = dict(dtype=name, site=site, n=n, Lq=Lq, heads=heads, d=d, S=S, kernel=kern,
+                          call="dc_cross_attention" if ln == "full" else "dc_cross_attention_len", kv_len=S if ln == "full" else ln,
+                          ms=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4), tb_per_s=round(stream / med / 1e9, 3))
+                len_rows.append(lr)
+                print(f"    {lr['call']} kv_len={lr['kv_len']}: {med:.3f} ms (min {lo:.3f}, max {hi:.3f})  {lr['tb_per_s']:.2f} TB/s (q + out)")
 if out_json:
     with open(out_json, "w") as fh:
-        json.dump(dict(tool="tools/bench_cross_attention.py", units=units, S=S, n_ctx=n_ctx, reps=reps, rows=rows), fh, indent=1)
+        rec = dict(tool="tools/bench_cross_attention.py", units=units, S=S, n_ctx=n_ctx, reps=reps, rows=rows)
+        if kv_lens:
+            rec.update(kv_lens=kv_lens, rounds=5, len_rows=len_rows)
+        json.dump(rec, fh, indent=1)
