@@ -15,6 +15,8 @@ ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU_TANH = 0, 1, 2, 3
 OP_QSAMPLE, OP_SINUSOID, OP_IGEMM, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_EPS_MSE, OP_TBLOCK_FRONT = 1, 2, 3, 4, 5, 6, 7, 8
 OP_CROSS_ATTENTION = 9
 OP_CROSS_ATTENTION_LEN = 10
+OP_ATTENTION_BIAS, OP_RMSNORM, OP_EMBED_ROWS, OP_RELU = 11, 12, 13, 14
+ATTENTION_BIAS_MAX_L = 512      # include/dcamd.h DC_ATTENTION_BIAS_MAX_L
 
 i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -80,6 +82,24 @@ class CrossAttentionLenParams(C.Structure):
                 ("ld_q", i32), ("ld_kv", i32), ("ld_out", i32), ("scale", f32)]
 
 
+class AttentionBiasParams(C.Structure):
+    _fields_ = [("q", vp), ("k", vp), ("v", vp), ("out", vp), ("bias", vp), ("kv_len", vp),
+                ("dtype", i32), ("n", i32), ("L", i32), ("heads", i32), ("d", i32), ("ld_qkv", i32), ("ld_out", i32), ("scale", f32)]
+
+
+class RmsnormParams(C.Structure):
+    _fields_ = [("x", vp), ("y", vp), ("weight", vp), ("row_len", vp),
+                ("dtype", i32), ("out_dtype", i32), ("rows", i32), ("C", i32), ("rows_per_sample", i32), ("eps", f32)]
+
+
+class EmbedRowsParams(C.Structure):
+    _fields_ = [("table", vp), ("ids", vp), ("out", vp), ("out_dtype", i32), ("rows", i32), ("C", i32), ("vocab", i32)]
+
+
+class ReluParams(C.Structure):
+    _fields_ = [("x", vp), ("n", i64), ("dtype", i32), ("pad_", i32)]
+
+
 class TblockFrontParams(C.Structure):
     _fields_ = [("x", vp), ("Wp", vp), ("bp", vp), ("ln_g", vp), ("ln_b", vp), ("Wqkv", vp), ("Wo", vp), ("bo", vp),
                 ("rowvec", vp), ("rowvec_map", vp), ("out", vp),
@@ -106,7 +126,7 @@ class Op(C.Structure):
 # every symbol include/dcamd.h declares (tests check that the library exports all of them)
 EXPORTS = ["dc_abi_version", "dc_last_error", "dc_arch", "dc_qsample", "dc_philox_normal", "dc_sinusoid",
            "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
-           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_ddpm_step", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_run_plan", "dc_run_plan_timed",
+           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_ddpm_step", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_run_plan", "dc_run_plan_timed",
            "dc_packed_bytes", "dc_pack_weights_matrix", "dc_pack_weights_conv3x3", "dc_pack_weights_up4", "dc_pack_weights_geglu",
            "dc_fold_layernorm_bias", "dc_workspace_bytes_groupnorm", "dc_workspace_bytes_igemm", "dc_workspace_bytes_attention",
            "dc_workspace_bytes_layernorm"]
@@ -139,6 +159,10 @@ def lib():
                        ("dc_attention", [C.POINTER(AttentionParams), vp]),
                        ("dc_cross_attention", [C.POINTER(CrossAttentionParams), vp]),
                        ("dc_cross_attention_len", [C.POINTER(CrossAttentionLenParams), vp]),
+                       ("dc_attention_bias", [C.POINTER(AttentionBiasParams), vp]),
+                       ("dc_rmsnorm", [C.POINTER(RmsnormParams), vp]),
+                       ("dc_embed_rows", [C.POINTER(EmbedRowsParams), vp]),
+                       ("dc_relu", [C.POINTER(ReluParams), vp]),
                        ("dc_tblock_front", [C.POINTER(TblockFrontParams), vp]),
                        ("dc_eps_mse", [C.POINTER(EpsMseParams), vp]),
                        ("dc_ddpm_step", [C.POINTER(DdpmStepParams), vp]),
@@ -180,6 +204,8 @@ def lib():
     L.dc_cross_attention_variant.restype = C.c_char_p
     L.dc_cross_attention_len_variant.argtypes = [C.POINTER(CrossAttentionLenParams)]
     L.dc_cross_attention_len_variant.restype = C.c_char_p
+    L.dc_attention_bias_variant.argtypes = [C.POINTER(AttentionBiasParams)]
+    L.dc_attention_bias_variant.restype = C.c_char_p
     L.dc_groupnorm_variant.argtypes = [C.POINTER(GroupnormParams)]
     L.dc_groupnorm_variant.restype = C.c_char_p
     L.dc_layernorm_variant.argtypes = [C.POINTER(LayernormParams)]

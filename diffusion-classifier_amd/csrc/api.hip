@@ -72,6 +72,10 @@ static int run_one(const dc_op* ops, int i, dc_stream s) {
       case DC_OP_ATTENTION: rc = dc_attention(static_cast<const dc_attention_params*>(ops[i].params), s); break;
       case DC_OP_CROSS_ATTENTION: rc = dc_cross_attention(static_cast<const dc_cross_attention_params*>(ops[i].params), s); break;
       case DC_OP_CROSS_ATTENTION_LEN: rc = dc_cross_attention_len(static_cast<const dc_cross_attention_len_params*>(ops[i].params), s); break;
+      case DC_OP_ATTENTION_BIAS: rc = dc_attention_bias(static_cast<const dc_attention_bias_params*>(ops[i].params), s); break;
+      case DC_OP_RMSNORM: rc = dc_rmsnorm(static_cast<const dc_rmsnorm_params*>(ops[i].params), s); break;
+      case DC_OP_EMBED_ROWS: rc = dc_embed_rows(static_cast<const dc_embed_rows_params*>(ops[i].params), s); break;
+      case DC_OP_RELU: rc = dc_relu(static_cast<const dc_relu_params*>(ops[i].params), s); break;
       case DC_OP_TBLOCK_FRONT: rc = dc_tblock_front(static_cast<const dc_tblock_front_params*>(ops[i].params), s); break;
       case DC_OP_EPS_MSE: rc = dc_eps_mse(static_cast<const dc_eps_mse_params*>(ops[i].params), s); break;
       default: dc_set_error("dc_run_plan: op %d has unknown kind %d", i, ops[i].kind); return DC_ERR_ARG;

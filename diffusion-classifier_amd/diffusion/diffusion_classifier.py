@@ -7,6 +7,8 @@ Kept surface (same names, argument meaning, assertions and return types):
   .encode_text_prompt / .diffuse / .logsnr_schedule_cosine(_shifted)  :83-161
 `config.encoder_type`: 'nn' and 'DiT' as in the reference; 'prompt' (additive, with `config.prompt_tokens = S`) conditions on a table of
 per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text encoder hands to the backbone (:93-98), without fetching one.
+'t5' (with `config.t5_path`, a LOCAL Hugging Face directory, and `config.prompt_tokens = S`) runs the T5 encoder on the device
+(nets/t5.py) and fills the same table: `set_class_prompts(input_ids, attention_mask)`, then everything is the 'prompt' path.
 `config` is the reference's attribute bag (missing keys read as None).  Additive keys read
 here: `compute_dtype` ("bf16" default | "f16" | "f32"), `units_per_launch`, `score_plan_cache` (launch plans kept, LRU;
 default 6), `dwt_on_device` (True: `inference` applies `wavelet_dec_2(images) / 2` on the device to the batches its loader yields, on the
@@ -139,10 +141,27 @@ class DiffusionClassifier(nn.Module):
         self.ema = EMA(self.model, beta=config.ema_beta, update_after_step=config.ema_warmup,
                        update_every=config.ema_update_freq)
         self.encoder_type = self.config.encoder_type
-        if self.encoder_type == 't5':
+        if self.encoder_type == 't5' and self.config.t5_path is None:
             raise NotImplementedError("encoder_type='t5' fetches t5-base over the network; not part of the scoring path. Text embeddings "
                                       "computed offline run through encoder_type='prompt' (config.prompt_tokens = S; copy them into "
                                       "encoder.weight [classes + 1, S, encoder_hid_dim])")
+        elif self.encoder_type == 't5':
+            # the reference's T5EncoderModel (:59-74), from a local directory; its output for one prompt per class (and the null prompt) fills
+            # the table 'prompt' uses — the reference's own 't5' loop hands integer class ids to the tokenizer (:695-698), which cannot classify
+            from ..nets.t5 import T5Encoder
+            S = self.config.prompt_tokens
+            assert isinstance(S, int) and S >= 1, "encoder_type='t5' needs config.prompt_tokens = S >= 1"
+            hid = getattr(backbone.config, "encoder_hid_dim", None)
+            if hid is None:
+                raise NotImplementedError("encoder_type='t5' needs a backbone with a projected context (config.encoder_hid_dim: UNetCondition2D)")
+            self.text_encoder = T5Encoder.from_directory(self.config.t5_path)
+            if self.text_encoder.config.d_model != hid:
+                raise ValueError(f"backbone.config.encoder_hid_dim = {hid} but the T5 encoder under {self.config.t5_path} has "
+                                 f"d_model = {self.text_encoder.config.d_model}")
+            self.encoder = PromptTable(self.config.classes + 1, S, hid)      # model_2.safetensors stays the table: no T5 weights in a checkpoint
+            self.tokenizer = None
+            self.null_token = self.config.classes
+            self._prompts_set = False
         elif self.encoder_type == 'prompt':
             S = self.config.prompt_tokens
             assert isinstance(S, int) and S >= 1, "encoder_type='prompt' needs config.prompt_tokens = S >= 1"
@@ -169,7 +188,8 @@ class DiffusionClassifier(nn.Module):
         if self.encoder_type == 'nn':
             embeddings = self.encoder(text)
             embeddings.unsqueeze_(1)
-        elif self.encoder_type == 'prompt':
+        elif self._table_mode():
+            self._require_prompts()
             embeddings = self.encoder(text)              # [B, S, hid], what the reference's text encoder returns (:93-98)
         elif self.encoder_type == 'DiT':
             embeddings = text
@@ -177,8 +197,40 @@ class DiffusionClassifier(nn.Module):
             raise NotImplementedError(self.encoder_type)
         return embeddings
 
+    def _table_mode(self):
+        """Is the conditioning a PromptTable row per class ('prompt', and 't5' whose encoder fills the same table)?"""
+        return self.encoder_type in ('prompt', 't5')
+
     def _ragged_table(self):
-        return self.encoder_type == 'prompt' and self.encoder.varlen
+        return self._table_mode() and self.encoder.varlen
+
+    def _require_prompts(self):
+        if self.encoder_type == 't5' and not self._prompts_set:
+            raise RuntimeError("encoder_type='t5': call set_class_prompts(input_ids, attention_mask) before classify / sample "
+                               "(the prompt table is still empty)")
+
+    @torch.no_grad()
+    def set_class_prompts(self, input_ids, attention_mask=None):
+        """encoder_type='t5': token ids [classes + 1, L <= S] of one prompt per class, the last row the null prompt (tokenising is the
+        caller's job), and their right-padded attention mask.  Runs the T5 encoder on the device (its compute dtype is
+        config.compute_dtype), writes weight[:, :L], zeroes the rest and records the token counts as the table's lengths."""
+        if self.encoder_type != 't5':
+            raise RuntimeError(f"set_class_prompts belongs to encoder_type='t5' (this classifier has {self.encoder_type!r})")
+        rows, S = self.encoder.weight.shape[0], self.encoder.weight.shape[1]
+        ids = torch.as_tensor(input_ids)
+        if ids.dim() != 2 or ids.shape[0] != rows or not 1 <= ids.shape[1] <= S:
+            raise ValueError(f"input_ids must be [{rows}, L <= {S}] (one prompt per class and the null prompt), got {tuple(ids.shape)}")
+        dev = self.encoder.weight.device
+        from ..engine_t5 import lengths_of_mask
+        lens = lengths_of_mask(attention_mask, ids.shape)
+        dt = self.config.compute_dtype or "bf16"
+        if self.text_encoder.compute_dtype != dt:
+            self.text_encoder.set_compute_dtype(dt)
+        emb = self.text_encoder(ids.to(dev), None if attention_mask is None else torch.as_tensor(attention_mask).to(dev))
+        self.encoder.weight.zero_()
+        self.encoder.weight[:, :ids.shape[1]] = emb.to(self.encoder.weight.dtype)
+        self.encoder.set_lengths(lens)
+        self._prompts_set = True
 
     def _refuse_ragged_on_foreign(self):
         if self._ragged_table():
@@ -206,6 +258,7 @@ class DiffusionClassifier(nn.Module):
                  rng="reference", seed=0, group=None):
         cfg = self.config
         assert self.encoder_type is not None, "Encoder must be provided for classification."
+        self._require_prompts()
         assert len(cfg.evaluation_per_stage) == cfg.n_stages, "Number of evaluations per stage must match the number of stages."
         assert len(cfg.n_keep_per_stage) == cfg.n_stages, "Number of classes to keep per stage must match the number of stages."
         assert cfg.n_keep_per_stage[-1] == 1, "Only one class should be selected at the end of the classification process."
@@ -523,6 +576,8 @@ class DiffusionClassifier(nn.Module):
             if enc_sd is None:
                 raise FileNotFoundError(f"no model_2.safetensors (class-token encoder) under {checkpoint_path}")
             self.encoder.load_state_dict(enc_sd)
+            if self.encoder_type == 't5':
+                self._prompts_set = True         # the checkpoint's table is the encoder's output for the prompts it was saved with
         st = os.path.join(checkpoint_path, "experiment_state.pth")
         if os.path.exists(st):
             state = torch.load(st, map_location="cpu", weights_only=False)
@@ -622,8 +677,8 @@ class _HipRunner:
         cfg = dc.config
         BS, Cc, H, W = self.x.shape
         wver = getattr(self.bb, "_wver", 0)
-        S = int(dc.encoder.weight.shape[1]) if dc.encoder_type == 'prompt' else 1      # tokens per context
-        varlen = dc.encoder_type == 'prompt' and dc.encoder.varlen                     # prompts of different lengths: a plan with ctx_len
+        S = int(dc.encoder.weight.shape[1]) if dc._table_mode() else 1                 # tokens per context
+        varlen = dc._ragged_table()                                                    # prompts of different lengths: a plan with ctx_len
         key = (BS, n_bj, k, self.dt, str(dev), (Cc, H, W), bool(getattr(self.bb, "share_trunk", True)), id(self.bb),
                self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ())
         sp = dc._score_plans.get(key)

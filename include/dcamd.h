@@ -17,6 +17,10 @@
  *                       (encode_text_prompt's [B, S, hid], diffusion_classifier.py:93-98; one token needs no kernel)
  *   dc_cross_attention_len  the same over prompts of different lengths padded to S tokens: a key count per context, which is
  *                       what diffusers' encoder_attention_mask expresses for a text encoder's padded output
+ *   dc_attention_bias / dc_rmsnorm / dc_embed_rows / dc_relu
+ *                       the T5 encoder behind encode_text_prompt (diffusion_classifier.py:59-74, :93-98: transformers' T5EncoderModel;
+ *                       its Linear layers are dc_igemm): self-attention with the relative-position bias and the padding mask, T5LayerNorm,
+ *                       the token embedding and the feed-forward's ReLU
  *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
@@ -43,7 +47,9 @@ extern "C" {
 /* 2: qstats records are (mean, M2) sets (version 1: sum, sum of squares) and qparts must divide HW
  * 3: dc_ddpm_step_params.one_plus_w; dc_attention requires scale > 0; dc_igemm_params.pn_* (producer-side GroupNorm)
  * (dc_cross_attention, dc_cross_attention_variant and DC_OP_CROSS_ATTENTION are additive within 4: no existing struct or symbol changed)
- * (dc_cross_attention_len, dc_cross_attention_len_variant, dc_cross_attention_len_params and DC_OP_CROSS_ATTENTION_LEN likewise) */
+ * (dc_cross_attention_len, dc_cross_attention_len_variant, dc_cross_attention_len_params and DC_OP_CROSS_ATTENTION_LEN likewise)
+ * (the T5 encoder's entries — dc_attention_bias, dc_attention_bias_variant, dc_rmsnorm, dc_embed_rows, dc_relu, their structs and
+ *  DC_OP_ATTENTION_BIAS / DC_OP_RMSNORM / DC_OP_EMBED_ROWS / DC_OP_RELU — likewise) */
 #define DC_ABI_VERSION 4
 
 typedef void* dc_stream; /* hipStream_t */
@@ -304,6 +310,56 @@ int dc_cross_attention_len(const dc_cross_attention_len_params* p, dc_stream s);
 /* As dc_cross_attention_variant: "mfma", "fp32" or "invalid" (the routing does not depend on kv_len). */
 const char* dc_cross_attention_len_variant(const dc_cross_attention_len_params* p);
 
+/* ---------------------------------------------------------------- T5 encoder ----- */
+/* Self-attention with an additive relative-position bias and a row count per sample (T5's attention under a right-padded mask):
+ *   out[i] = softmax(q_i k_i^T * scale + bias[h][k - q + L - 1]) v_i   over keys k < kv_len[i], for queries q < kv_len[i].
+ * q / k / v / out as for dc_attention: [n, L, heads, d] with row strides ld_qkv / ld_out (elements), one `dtype`.
+ * bias [heads][2L - 1] fp32 on the device, indexed by the relative distance k - q + L - 1 (built on the host: a bucket boundary must not
+ * depend on a device logarithm).  kv_len [n] int32 on the device, NULL meaning L everywhere; the kernels clamp it into [1, L].
+ * Rows >= kv_len[i] of q / k / v are never read (staged as zeros and masked: 0 x garbage cannot make a NaN) and output rows >= kv_len[i]
+ * are written as zeros.  scale must be > 0 (DC_ERR_ARG; T5 passes 1.0); 1 <= L <= DC_ATTENTION_BIAS_MAX_L and d in {16, 32, 64, 128}
+ * (DC_ERR_SHAPE otherwise).
+ * Routes: 16-bit with d = 64, 16-byte aligned q / k / v rows and 8-byte aligned output rows: the matrix-core kernel "mfma" (one wave per
+ * 32 queries of a (sample, head), online fp32 softmax over key blocks of 32, the wave's slice of the table in LDS); fp32, d = 16 / 32 /
+ * 128 and unaligned operands: the exact kernel "fp32".  (d = 32 / 128 would come from the matrix-core template too; they are not
+ * instantiated, no T5 v1.0 shape has them.)  Fixed summation order, no atomics: the bits of out[i] depend on sample i's own rows, its
+ * own length and the table only, not on n or on i. */
+#define DC_ATTENTION_BIAS_MAX_L 512
+typedef struct {
+  const void* q; const void* k; const void* v; void* out;
+  const float* bias;                                    /* [heads][2L - 1] */
+  const int32_t* kv_len;                                /* rows per sample; NULL = L everywhere */
+  int32_t dtype, n, L, heads, d, ld_qkv, ld_out; float scale;
+} dc_attention_bias_params;
+int dc_attention_bias(const dc_attention_bias_params* p, dc_stream s);
+/* Name of the kernel dc_attention_bias would launch for these parameters: "mfma" or "fp32"; "invalid" when it would refuse them
+ * (measurement / tests only; static string; touches no memory). */
+const char* dc_attention_bias_variant(const dc_attention_bias_params* p);
+
+/* RMS norm (T5LayerNorm: no mean subtraction, no bias): y[r, c] = x[r, c] * rsqrt(mean_c(x[r, :]^2) + eps) * weight[c].  fp32
+ * statistics; x [rows, C] is read in `dtype`, y written in `out_dtype` (the encoder's residual stream is fp32, the GEMM that follows
+ * reads the compute type).  row_len [rows / rows_per_sample] int32 on the device or NULL: rows whose index inside their sample is
+ * >= row_len[sample] are written as zeros and not read. */
+typedef struct {
+  const void* x; void* y; const float* weight; const int32_t* row_len;
+  int32_t dtype, out_dtype, rows, C, rows_per_sample; float eps;
+} dc_rmsnorm_params;
+int dc_rmsnorm(const dc_rmsnorm_params* p, dc_stream s);
+
+/* out[r, :] = table[ids[r], :] for r < rows: fp32 table [vocab, C], int64 ids on the device, out [rows, C] in out_dtype.  Ids are
+ * validated on the host where they enter; the kernel clamps them into [0, vocab) so that nothing outside the table is read. */
+typedef struct {
+  const float* table; const int64_t* ids; void* out;
+  int32_t out_dtype, rows, C, vocab;
+} dc_embed_rows_params;
+int dc_embed_rows(const dc_embed_rows_params* p, dc_stream s);
+
+/* x[i] = max(x[i], 0) in place for i < n (NaN stays NaN), 16-byte chunks; x 16-byte aligned.  One extra pass over the feed-forward's
+ * [rows, d_ff]: it exists so that dc_igemm and its shared epilogue stay untouched; ReLU as a dc_igemm activation is the follow-up to
+ * measure. */
+typedef struct { void* x; int64_t n; int32_t dtype, pad_; } dc_relu_params;
+int dc_relu(const dc_relu_params* p, dc_stream s);
+
 /* ---------------------------------------------------------------- transformer block, attention half --- */
 /* One launch for the self-attention half of a UNet transformer block (the backbone behind /root/reference/nets/unet.py:186-195:
  * Transformer2DModel.proj_in -> BasicTransformerBlock.norm1 -> attn1 (to_q/k/v, softmax, to_out) -> + attn2's class vector -> residual):
@@ -378,7 +434,8 @@ int dc_stage_maps(const int32_t* keep, int32_t BS, int32_t C, int32_t T, int32_t
 /* ---------------------------------------------------------------- plan ----------- */
 typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GROUPNORM = 4,
                DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8,
-               DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10 } dc_op_kind;
+               DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10, DC_OP_ATTENTION_BIAS = 11, DC_OP_RMSNORM = 12,
+               DC_OP_EMBED_ROWS = 13, DC_OP_RELU = 14 } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */
