@@ -14,6 +14,7 @@ from .nets.unet import UNetCondition2D, UNet2D  # noqa: F401
 from .nets.dit import DiT  # noqa: F401
 from .diffusion.diffusion_classifier import DiffusionClassifier  # noqa: F401
 from .utils.wavelet import wavelet_dec_2, wavelet_enc_2  # noqa: F401
+from .posterior import ClassPosterior  # noqa: F401
 
 
 class Config:

@@ -119,3 +119,160 @@ extern "C" int dc_stage_maps(const int32_t* keep, int32_t BS, int32_t C, int32_t
                      world, n_bj, n_mb, dump, maps);
   return dc_check_launch("dc_stage_maps");
 }
+
+// The class posterior, its entropy and the paired confidence of the decision, from the errors the last stage end reduced to a label
+// (include/dcamd.h has the definitions).  Same launch shape as stage_topk_kernel: one wave per image, lane l owns classes l, l+64, ...;
+// every per-class sum is sequential over j ascending, every wave reduction a fixed xor butterfly (commutative at each step, so all 64
+// lanes hold the same bits), no atomics.  The winner is picked with stage_order_key on (sum / t_end) + 0 — the value and the key
+// dc_reduce_argmin uses — among the classes with all t_end cells evaluated, so it cannot disagree with the label.  Cells j >= t_end
+// are never read.
+__device__ __forceinline__ int posterior_argmin(const uint32_t (&key)[16], uint32_t cand, int lane) {
+  uint32_t bv = 0xFFFFFFFFu;
+  int bc = 0x7fffffff;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = lane + 64 * i;
+    if (((cand >> i) & 1u) && (key[i] < bv || (key[i] == bv && c < bc))) { bv = key[i]; bc = c; }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const uint32_t ov = (uint32_t)__shfl_xor((int)bv, off, 64);
+    const int oc = __shfl_xor(bc, off, 64);
+    if (ov < bv || (ov == bv && oc < bc)) { bv = ov; bc = oc; }
+  }
+  return bc == 0x7fffffff ? -1 : bc;            // a candidate always beats the initial (all ones, int max) pair on c < bc
+}
+
+__device__ __forceinline__ float posterior_wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64) void class_posterior_kernel(const dc_class_posterior_params p) {
+  constexpr int MAXPL = 16;                     // classes per lane: C <= 1024
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int C = p.C, T = p.T, t_end = p.t_end;
+  const float inf = __builtin_inff(), nan = __builtin_nanf("");
+  const float* E = p.errors + (size_t)b * C * T;
+  float S[MAXPL];
+  int n[MAXPL];
+  uint32_t key[MAXPL];
+  uint32_t fin = 0;                             // bit i: class lane + 64 i is a finalist
+  int bad_cells = 0;
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i) {
+    const int c = lane + 64 * i;
+    S[i] = 0.f; n[i] = 0; key[i] = 0xFFFFFFFFu;
+    if (c < C) {
+      const float* e = E + (size_t)c * T;
+      float s = 0.f;
+      int cnt = 0;
+      for (int j = 0; j < t_end; ++j) {
+        const float v = e[j];
+        if (v != inf) { s += v; ++cnt; bad_cells += v != v; }
+      }
+      S[i] = s; n[i] = cnt;
+      float mean = cnt > 0 ? s / (float)cnt : inf;          // a finalist: the sum over all j < t_end divided by t_end, as stage_topk_kernel
+      if (p.means) p.means[(size_t)b * C + c] = mean;
+      if (p.n_eval) p.n_eval[(size_t)b * C + c] = cnt;
+      mean = mean + 0.f;                                    // -0 -> +0
+      key[i] = stage_order_key(mean);
+      if (cnt == t_end) fin |= 1u << i;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) bad_cells += __shfl_xor(bad_cells, off, 64);
+
+  const int win = posterior_argmin(key, fin, lane);
+  uint32_t fin2 = fin;
+  if (win >= 0 && (win & 63) == lane) fin2 &= ~(1u << (win >> 6));
+  const int run = win >= 0 ? posterior_argmin(key, fin2, lane) : -1;
+
+  // the winner's mean (every lane: the same loads in the same order as its owner's sum above) and the paired statistic
+  float mean_w = nan, margin = nan, margin_z = nan;
+  if (win >= 0) {
+    const float* ew = E + (size_t)win * T;
+    float sw = 0.f;
+    for (int j = 0; j < t_end; ++j) sw += ew[j];
+    mean_w = sw / (float)t_end;
+    if (run >= 0) {
+      const float* er = E + (size_t)run * T;
+      float sd = 0.f;
+      for (int j = 0; j < t_end; ++j) sd += er[j] - ew[j];
+      margin = sd / (float)t_end;
+      float ss = 0.f;
+      for (int j = 0; j < t_end; ++j) { const float d = (er[j] - ew[j]) - margin; ss += d * d; }
+      const float var = ss / (float)(t_end - 1);
+      margin_z = margin / sqrtf(var / (float)t_end);
+    } else {
+      margin = inf; margin_z = inf;
+    }
+  }
+  const bool bad = win < 0 || mean_w != mean_w;
+
+  // delta (kept in S) and the softmax over the classes that have one
+  uint32_t valid = 0;
+  float mx = -inf;
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i) {
+    const int c = lane + 64 * i;
+    if (c < C) {
+      float d = nan;
+      if (win >= 0) {
+        const float* e = E + (size_t)c * T;
+        const float* ew = E + (size_t)win * T;
+        float sw = 0.f;
+        for (int j = 0; j < t_end; ++j) if (e[j] != inf) sw += ew[j];
+        d = (S[i] - sw) / (float)n[i];
+      }
+      if (p.delta) p.delta[(size_t)b * C + c] = d;
+      if (n[i] > 0 && fabsf(d) < inf) {                     // finite: not NaN, not +-inf
+        valid |= 1u << i;
+        S[i] = -d / p.temperature;
+        mx = fmaxf(mx, S[i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float part = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i) {
+    S[i] = ((valid >> i) & 1u) ? expf(S[i] - mx) : 0.f;
+    part += S[i];
+  }
+  const float sum = posterior_wave_sum(part);
+  float h = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i) {
+    const int c = lane + 64 * i;
+    if (c < C) {
+      const float pr = ((valid >> i) & 1u) ? S[i] / sum : 0.f;
+      if (pr > 0.f) h += pr * logf(pr);
+      p.probs[(size_t)b * C + c] = bad ? nan : pr;
+    }
+  }
+  h = posterior_wave_sum(h);
+  if (lane == 0) {
+    p.entropy[b] = bad ? nan : 0.f - h;
+    p.margin[b] = bad ? nan : margin;
+    p.margin_z[b] = bad ? nan : margin_z;
+    p.winner[b] = win;
+    p.runner[b] = run;
+    p.invalid[b] = bad_cells;
+  }
+}
+
+extern "C" int dc_class_posterior(const dc_class_posterior_params* p, dc_stream s) {
+  DC_REQUIRE(p, DC_ERR_ARG, "dc_class_posterior: null params");
+  DC_REQUIRE(p->errors && p->probs, DC_ERR_ARG, "dc_class_posterior: null errors/probs");
+  DC_REQUIRE(p->entropy && p->margin && p->margin_z && p->winner && p->runner && p->invalid, DC_ERR_ARG,
+             "dc_class_posterior: null stats output (entropy, margin, margin_z, winner, runner and invalid are required)");
+  DC_REQUIRE(p->temperature > 0.f && p->temperature < __builtin_inff(), DC_ERR_ARG, "dc_class_posterior: temperature %g must be positive and finite",
+             (double)p->temperature);
+  DC_REQUIRE(p->BS > 0 && p->C > 0 && p->C <= 1024 && p->T > 0 && p->t_end > 0 && p->t_end <= p->T, DC_ERR_SHAPE,
+             "dc_class_posterior: BS=%d C=%d (<= 1024) T=%d t_end=%d", p->BS, p->C, p->T, p->t_end);
+  hipLaunchKernelGGL(class_posterior_kernel, dim3(p->BS), dim3(64), 0, reinterpret_cast<hipStream_t>(s), *p);
+  return dc_check_launch("dc_class_posterior");
+}

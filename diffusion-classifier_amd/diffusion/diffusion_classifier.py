@@ -33,6 +33,11 @@ Extra keyword-only arguments (defaults keep the reference behaviour):
   fast_select    inject the `randint` draw of fast mode
   return_errors  also return errors[BS, classes, T] (copied to the CPU; with the multi-GPU gather's host leg under gloo
                  the only device -> host copies of a classify call)
+  return_posterior  also return a `ClassPosterior` (posterior.py): class probabilities softmax(-delta / config.posterior_temperature) on the
+                 paired mean differences to the winner, their entropy, the runner-up with the paired margin and its z-score, trials per
+                 class and the NaN-cell count, computed after the last stage end from the gathered errors (`dc_class_posterior` for the
+                 HIP backbones, the same definitions in torch for a foreign one), left on the scoring device: no host synchronisation,
+                 identical on every rank.  argmax probs is the label.  Returns (labels, post), with return_errors (labels, errors, post)
   rng            "reference": draw rand(BS) / randn_like(x) per trial in the reference's order;
                  "philox":   t from the CPU generator, eps on device from Philox keyed by
                              (seed, image, trial) — no eps traffic, world-size independent
@@ -50,6 +55,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import dist as D
+from .. import posterior as P
 from .._ema import EMA
 
 
@@ -255,8 +261,9 @@ class DiffusionClassifier(nn.Module):
     # ---- the hot path ---------------------------------------------------------------------
     @torch.no_grad()
     def classify(self, x, text=None, fast=False, *, t=None, eps=None, fast_select=None, return_errors=False,
-                 rng="reference", seed=0, group=None):
+                 rng="reference", seed=0, group=None, return_posterior=False):
         cfg = self.config
+        tau = P.temperature_of(cfg) if return_posterior else None
         assert self.encoder_type is not None, "Encoder must be provided for classification."
         self._require_prompts()
         assert len(cfg.evaluation_per_stage) == cfg.n_stages, "Number of evaluations per stage must match the number of stages."
@@ -338,11 +345,13 @@ class DiffusionClassifier(nn.Module):
             classes = runner.stage_end(errors, ends[i + 1], cfg.n_keep_per_stage[i], last=i == cfg.n_stages - 1)
         assert classes.shape[1] == 1, "Only one class should be selected at the end of the classification process."
         out = classes[:, 0].to(device=x.device, dtype=torch.int64)
+        # the posterior reads the errors every rank holds after the last gather: the same bits everywhere
+        post = runner.posterior(errors, T, tau) if return_posterior else None
         if return_errors:
             err_host = errors.cpu()              # (synchronises: the cheap moment to look at the device-side failure counter)
             self.check_device_errors()
-            return out, err_host
-        return out
+            return (out, err_host, post) if return_posterior else (out, err_host)
+        return (out, post) if return_posterior else out
 
     def check_device_errors(self):
         """Raise if a producer-side-GroupNorm launch (csrc/epi_pn.h) gave up waiting for the other workgroups of a sample since the last
@@ -361,10 +370,19 @@ class DiffusionClassifier(nn.Module):
             batch = {k: v for k, v in batch.items()}
             x = batch["images"]
             p = batch["prompt"] if "prompt" in batch.keys() else None
-            sample = self.classify(x, p, fast=self.config.fast_classification) if classification else self.sample(x, p, from_t)
+            # a metric with `wants_posterior = True` (utils/metrics.py AUROC, SelectiveAccuracy) is fed (labels, batch, ClassPosterior)
+            want_post = classification and metrics is not None and any(getattr(m, "wants_posterior", False) for m in metrics)
+            post = None
+            if want_post:
+                sample, post = self.classify(x, p, fast=self.config.fast_classification, return_posterior=True)
+            else:
+                sample = self.classify(x, p, fast=self.config.fast_classification) if classification else self.sample(x, p, from_t)
             if metrics is not None:
                 for metric in metrics:
-                    metric.update((sample, batch))
+                    if post is not None and getattr(metric, "wants_posterior", False):
+                        metric.update((sample, batch, post))
+                    else:
+                        metric.update((sample, batch))
             val_samples.append(sample)
             batches.append(batch)
             if stop_idx is not None and idx == stop_idx:
@@ -623,6 +641,9 @@ class _ForeignRunner:
         _, keep_indices = torch.topk(end_of_stage_errors, num_keep, dim=1, largest=False)
         return keep_indices
 
+    def posterior(self, errors, t_end, temperature):
+        return P.class_posterior_torch(errors, t_end, temperature)
+
     def run_stage(self, pairs, classes, stage=None):
         dc, x, d = self.dc, self.x, self.d
         by_trial = {}
@@ -739,6 +760,9 @@ class _HipRunner:
             keep = torch.empty((BS, num_keep), dtype=torch.int32, device=errors.device)
             L.check(self.lib.dc_stage_topk(errors.data_ptr(), BS, ncls, T, t_end, num_keep, keep.data_ptr(), None, L.stream_ptr()), "dc_stage_topk")
         return keep
+
+    def posterior(self, errors, t_end, temperature):
+        return P.class_posterior_hip(errors, t_end, temperature)
 
     def run_stage(self, pairs, classes, stage=None):
         """pairs: this rank's (trial, image) pairs of the stage = D.local_pairs(t0, t1, BS, rank, world); stage = (t0, rank, world)."""

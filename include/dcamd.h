@@ -28,6 +28,8 @@
  *                       the stage end, diffusion_classifier.py:718-725 (mean over trials, k smallest classes) and the
  *                       per-image surviving-class lists of the next stage (:695-698, ragged after pruning / fast mode
  *                       :671-677) as device-side work-unit maps
+ *   dc_class_posterior  nothing in the reference: the class posterior (Li et al. 2023, eq. 5, on paired differences), its entropy and
+ *                       the paired confidence of the decision, from the errors tensor :718-725 reduces to one label
  *   dc_run_plan         the Python double loop body, diffusion_classifier.py:695-714, as
  *                       one native launch sequence (graph-capturable)
  *
@@ -49,7 +51,8 @@ extern "C" {
  * (dc_cross_attention, dc_cross_attention_variant and DC_OP_CROSS_ATTENTION are additive within 4: no existing struct or symbol changed)
  * (dc_cross_attention_len, dc_cross_attention_len_variant, dc_cross_attention_len_params and DC_OP_CROSS_ATTENTION_LEN likewise)
  * (the T5 encoder's entries — dc_attention_bias, dc_attention_bias_variant, dc_rmsnorm, dc_embed_rows, dc_relu, their structs and
- *  DC_OP_ATTENTION_BIAS / DC_OP_RMSNORM / DC_OP_EMBED_ROWS / DC_OP_RELU — likewise) */
+ *  DC_OP_ATTENTION_BIAS / DC_OP_RMSNORM / DC_OP_EMBED_ROWS / DC_OP_RELU — likewise)
+ * (dc_class_posterior and dc_class_posterior_params likewise; it is called directly, there is no DC_OP_* kind for it) */
 #define DC_ABI_VERSION 4
 
 typedef void* dc_stream; /* hipStream_t */
@@ -430,6 +433,34 @@ int dc_reduce_argmin(const float* errors, int32_t BS, int32_t C, int32_t T, int3
  * class id of each unit and the flat index of errors[b, class, j] it writes (dc_eps_mse out_index). */
 int dc_stage_maps(const int32_t* keep, int32_t BS, int32_t C, int32_t T, int32_t k, int32_t t0, int32_t n_pairs, int32_t rank,
                   int32_t world, int32_t n_bj, int32_t n_mb, int32_t dump, int32_t* maps, dc_stream s);
+
+/* ---------------------------------------------------------------- class posterior */
+/* What a finished classify call knows beyond the label, from the same errors [BS, C, T] (cells j < t_end; +inf = not evaluated, NaN
+ * counts as evaluated; cells j >= t_end are never read).  Per image, every sum fp32, sequential, j ascending (dc_stage_topk's order):
+ *   n[c]      evaluated cells of class c;  S[c] their sum;  mean[c] = S[c] / n[c] (+inf for n[c] = 0)
+ *   winner    arg-min of mean over the finalists (n[c] = t_end) by dc_reduce_argmin's key: NaN last, ties to the lower id; -1: none
+ *   delta[c]  (S[c] - Sw[c]) / n[c], Sw[c] = the winner's errors summed over the cells class c has: the paired mean difference
+ *             over the trials class c was scored on (all classes of a trial share (t, eps)); delta[winner] = 0
+ *   probs     softmax_c(-delta[c] / temperature) over classes with n[c] > 0 and finite delta (max subtracted); exactly 0 elsewhere
+ *   entropy   -sum p ln p in nats (p = 0 adds 0)
+ *   runner    arg-min of mean over the finalists without the winner, same key; -1: none
+ *   margin    mean_j d_j, d_j = errors[runner, j] - errors[winner, j];  margin_z = margin / sqrt(var / t_end), var = the two-pass sample
+ *             variance of d_j (t_end - 1 in the denominator), plain IEEE: t_end = 1 -> NaN, var = 0 -> +inf or NaN; no runner: both +inf
+ *   invalid   NaN cells among the evaluated ones
+ * winner = -1 or a NaN mean[winner]: probs, entropy, margin and margin_z of that image are NaN.
+ * For errors written by the scoring loop a pruned class lost to the winner on exactly its prefix, by these sums: every delta >= 0 and
+ * argmax probs = winner = the label.  One wave per image, wave reductions in a fixed order, no atomics: the same bits on every rank.
+ * probs / means / delta [BS, C] f32, n_eval [BS, C] int32, the rest [BS]; means, delta and n_eval optional (NULL).  C <= 1024;
+ * temperature > 0 (DC_ERR_ARG otherwise). */
+typedef struct {
+  const float* errors;
+  float* probs;
+  float* entropy; float* margin; float* margin_z;
+  int32_t* winner; int32_t* runner; int32_t* invalid;
+  float* means; float* delta; int32_t* n_eval;          /* optional */
+  int32_t BS, C, T, t_end; float temperature; int32_t pad_;
+} dc_class_posterior_params;
+int dc_class_posterior(const dc_class_posterior_params* p, dc_stream s);
 
 /* ---------------------------------------------------------------- plan ----------- */
 typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GROUPNORM = 4,
