@@ -17,6 +17,9 @@ OP_CROSS_ATTENTION = 9
 OP_CROSS_ATTENTION_LEN = 10
 OP_ATTENTION_BIAS, OP_RMSNORM, OP_EMBED_ROWS, OP_RELU = 11, 12, 13, 14
 ATTENTION_BIAS_MAX_L = 512      # include/dcamd.h DC_ATTENTION_BIAS_MAX_L
+OP_ATTENTION_CAUSAL, OP_LAYERNORM_ROWS, OP_EMBED_ROWS_POS, OP_ACT_PASS = 15, 16, 17, 18
+ATTENTION_CAUSAL_MAX_L = 512    # include/dcamd.h DC_ATTENTION_CAUSAL_MAX_L
+PASS_QUICK_GELU, PASS_GELU_ERF = 1, 2       # dc_pass_kind
 
 i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -100,6 +103,25 @@ class ReluParams(C.Structure):
     _fields_ = [("x", vp), ("n", i64), ("dtype", i32), ("pad_", i32)]
 
 
+class AttentionCausalParams(C.Structure):
+    _fields_ = [("q", vp), ("k", vp), ("v", vp), ("out", vp), ("row_len", vp),
+                ("dtype", i32), ("n", i32), ("L", i32), ("heads", i32), ("d", i32), ("ld_qkv", i32), ("ld_out", i32), ("scale", f32)]
+
+
+class LayernormRowsParams(C.Structure):
+    _fields_ = [("x", vp), ("y", vp), ("gamma", vp), ("beta", vp), ("row_len", vp),
+                ("dtype", i32), ("out_dtype", i32), ("rows", i32), ("C", i32), ("rows_per_sample", i32), ("eps", f32)]
+
+
+class EmbedRowsPosParams(C.Structure):
+    _fields_ = [("table", vp), ("pos", vp), ("ids", vp), ("out", vp),
+                ("out_dtype", i32), ("rows", i32), ("C", i32), ("vocab", i32), ("L", i32), ("pad_", i32)]
+
+
+class ActPassParams(C.Structure):
+    _fields_ = [("x", vp), ("n", i64), ("dtype", i32), ("kind", i32)]
+
+
 class TblockFrontParams(C.Structure):
     _fields_ = [("x", vp), ("Wp", vp), ("bp", vp), ("ln_g", vp), ("ln_b", vp), ("Wqkv", vp), ("Wo", vp), ("bo", vp),
                 ("rowvec", vp), ("rowvec_map", vp), ("out", vp),
@@ -132,7 +154,7 @@ class Op(C.Structure):
 # every symbol include/dcamd.h declares (tests check that the library exports all of them)
 EXPORTS = ["dc_abi_version", "dc_last_error", "dc_arch", "dc_qsample", "dc_philox_normal", "dc_sinusoid",
            "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
-           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_ddpm_step", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
+           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_ddpm_step", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
            "dc_packed_bytes", "dc_pack_weights_matrix", "dc_pack_weights_conv3x3", "dc_pack_weights_up4", "dc_pack_weights_geglu",
            "dc_fold_layernorm_bias", "dc_workspace_bytes_groupnorm", "dc_workspace_bytes_igemm", "dc_workspace_bytes_attention",
            "dc_workspace_bytes_layernorm"]
@@ -169,6 +191,10 @@ def lib():
                        ("dc_rmsnorm", [C.POINTER(RmsnormParams), vp]),
                        ("dc_embed_rows", [C.POINTER(EmbedRowsParams), vp]),
                        ("dc_relu", [C.POINTER(ReluParams), vp]),
+                       ("dc_attention_causal", [C.POINTER(AttentionCausalParams), vp]),
+                       ("dc_layernorm_rows", [C.POINTER(LayernormRowsParams), vp]),
+                       ("dc_embed_rows_pos", [C.POINTER(EmbedRowsPosParams), vp]),
+                       ("dc_act_pass", [C.POINTER(ActPassParams), vp]),
                        ("dc_tblock_front", [C.POINTER(TblockFrontParams), vp]),
                        ("dc_eps_mse", [C.POINTER(EpsMseParams), vp]),
                        ("dc_class_posterior", [C.POINTER(ClassPosteriorParams), vp]),
@@ -213,6 +239,8 @@ def lib():
     L.dc_cross_attention_len_variant.restype = C.c_char_p
     L.dc_attention_bias_variant.argtypes = [C.POINTER(AttentionBiasParams)]
     L.dc_attention_bias_variant.restype = C.c_char_p
+    L.dc_attention_causal_variant.argtypes = [C.POINTER(AttentionCausalParams)]
+    L.dc_attention_causal_variant.restype = C.c_char_p
     L.dc_groupnorm_variant.argtypes = [C.POINTER(GroupnormParams)]
     L.dc_groupnorm_variant.restype = C.c_char_p
     L.dc_layernorm_variant.argtypes = [C.POINTER(LayernormParams)]

@@ -76,6 +76,10 @@ static int run_one(const dc_op* ops, int i, dc_stream s) {
       case DC_OP_RMSNORM: rc = dc_rmsnorm(static_cast<const dc_rmsnorm_params*>(ops[i].params), s); break;
       case DC_OP_EMBED_ROWS: rc = dc_embed_rows(static_cast<const dc_embed_rows_params*>(ops[i].params), s); break;
       case DC_OP_RELU: rc = dc_relu(static_cast<const dc_relu_params*>(ops[i].params), s); break;
+      case DC_OP_ATTENTION_CAUSAL: rc = dc_attention_causal(static_cast<const dc_attention_causal_params*>(ops[i].params), s); break;
+      case DC_OP_LAYERNORM_ROWS: rc = dc_layernorm_rows(static_cast<const dc_layernorm_rows_params*>(ops[i].params), s); break;
+      case DC_OP_EMBED_ROWS_POS: rc = dc_embed_rows_pos(static_cast<const dc_embed_rows_pos_params*>(ops[i].params), s); break;
+      case DC_OP_ACT_PASS: rc = dc_act_pass(static_cast<const dc_act_pass_params*>(ops[i].params), s); break;
       case DC_OP_TBLOCK_FRONT: rc = dc_tblock_front(static_cast<const dc_tblock_front_params*>(ops[i].params), s); break;
       case DC_OP_EPS_MSE: rc = dc_eps_mse(static_cast<const dc_eps_mse_params*>(ops[i].params), s); break;
       default: dc_set_error("dc_run_plan: op %d has unknown kind %d", i, ops[i].kind); return DC_ERR_ARG;

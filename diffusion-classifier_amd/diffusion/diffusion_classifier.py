@@ -9,6 +9,7 @@ Kept surface (same names, argument meaning, assertions and return types):
 per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text encoder hands to the backbone (:93-98), without fetching one.
 't5' (with `config.t5_path`, a LOCAL Hugging Face directory, and `config.prompt_tokens = S`) runs the T5 encoder on the device
 (nets/t5.py) and fills the same table: `set_class_prompts(input_ids, attention_mask)`, then everything is the 'prompt' path.
+'clip' (additive, with `config.clip_path` and `config.prompt_tokens = S`) does the same with a CLIP text transformer (nets/clip.py).
 `config` is the reference's attribute bag (missing keys read as None).  Additive keys read
 here: `compute_dtype` ("bf16" default | "f16" | "f32"), `units_per_launch`, `score_plan_cache` (launch plans kept, LRU;
 default 6), `dwt_on_device` (True: `inference` applies `wavelet_dec_2(images) / 2` on the device to the batches its loader yields, on the
@@ -168,6 +169,28 @@ class DiffusionClassifier(nn.Module):
             self.tokenizer = None
             self.null_token = self.config.classes
             self._prompts_set = False
+        elif self.encoder_type == 'clip':
+            # a CLIP text transformer from a local directory (Stable Diffusion's text_encoder/, openai/clip-vit-*): its last_hidden_state
+            # for one prompt per class (and the null prompt) fills the table 'prompt' uses, exactly as 't5' does
+            if self.config.clip_path is None:
+                raise NotImplementedError("encoder_type='clip' needs config.clip_path: a LOCAL Hugging Face directory (config.json + "
+                                          "model.safetensors of a CLIP text model; nothing is fetched). Text embeddings computed offline "
+                                          "run through encoder_type='prompt' (config.prompt_tokens = S; copy them into encoder.weight "
+                                          "[classes + 1, S, encoder_hid_dim])")
+            from ..nets.clip import CLIPTextEncoder
+            S = self.config.prompt_tokens
+            assert isinstance(S, int) and S >= 1, "encoder_type='clip' needs config.prompt_tokens = S >= 1"
+            hid = getattr(backbone.config, "encoder_hid_dim", None)
+            if hid is None:
+                raise NotImplementedError("encoder_type='clip' needs a backbone with a projected context (config.encoder_hid_dim: UNetCondition2D)")
+            self.text_encoder = CLIPTextEncoder.from_directory(self.config.clip_path)
+            if self.text_encoder.config.hidden_size != hid:
+                raise ValueError(f"backbone.config.encoder_hid_dim = {hid} but the CLIP text encoder under {self.config.clip_path} has "
+                                 f"hidden_size = {self.text_encoder.config.hidden_size}")
+            self.encoder = PromptTable(self.config.classes + 1, S, hid)      # model_2.safetensors stays the table: no CLIP weights in a checkpoint
+            self.tokenizer = None
+            self.null_token = self.config.classes
+            self._prompts_set = False
         elif self.encoder_type == 'prompt':
             S = self.config.prompt_tokens
             assert isinstance(S, int) and S >= 1, "encoder_type='prompt' needs config.prompt_tokens = S >= 1"
@@ -204,24 +227,25 @@ class DiffusionClassifier(nn.Module):
         return embeddings
 
     def _table_mode(self):
-        """Is the conditioning a PromptTable row per class ('prompt', and 't5' whose encoder fills the same table)?"""
-        return self.encoder_type in ('prompt', 't5')
+        """Is the conditioning a PromptTable row per class ('prompt', and 't5' / 'clip' whose encoder fills the same table)?"""
+        return self.encoder_type in ('prompt', 't5', 'clip')
 
     def _ragged_table(self):
         return self._table_mode() and self.encoder.varlen
 
     def _require_prompts(self):
-        if self.encoder_type == 't5' and not self._prompts_set:
-            raise RuntimeError("encoder_type='t5': call set_class_prompts(input_ids, attention_mask) before classify / sample "
-                               "(the prompt table is still empty)")
+        if self.encoder_type in ('t5', 'clip') and not self._prompts_set:
+            raise RuntimeError(f"encoder_type={self.encoder_type!r}: call set_class_prompts(input_ids, attention_mask) before classify / "
+                               "sample (the prompt table is still empty)")
 
     @torch.no_grad()
     def set_class_prompts(self, input_ids, attention_mask=None):
-        """encoder_type='t5': token ids [classes + 1, L <= S] of one prompt per class, the last row the null prompt (tokenising is the
-        caller's job), and their right-padded attention mask.  Runs the T5 encoder on the device (its compute dtype is
-        config.compute_dtype), writes weight[:, :L], zeroes the rest and records the token counts as the table's lengths."""
-        if self.encoder_type != 't5':
-            raise RuntimeError(f"set_class_prompts belongs to encoder_type='t5' (this classifier has {self.encoder_type!r})")
+        """encoder_type='t5' / 'clip': token ids [classes + 1, L <= S] of one prompt per class, the last row the null prompt (tokenising
+        is the caller's job), and their right-padded attention mask.  Runs the text encoder on the device (its compute dtype is
+        config.compute_dtype), writes weight[:, :L], zeroes the rest and records the token counts as the table's lengths (without a
+        mask every row is a real state and the lengths are L: what Stable Diffusion feeds its UNet from CLIP)."""
+        if self.encoder_type not in ('t5', 'clip'):
+            raise RuntimeError(f"set_class_prompts belongs to encoder_type='t5' / 'clip' (this classifier has {self.encoder_type!r})")
         rows, S = self.encoder.weight.shape[0], self.encoder.weight.shape[1]
         ids = torch.as_tensor(input_ids)
         if ids.dim() != 2 or ids.shape[0] != rows or not 1 <= ids.shape[1] <= S:
@@ -594,7 +618,7 @@ class DiffusionClassifier(nn.Module):
             if enc_sd is None:
                 raise FileNotFoundError(f"no model_2.safetensors (class-token encoder) under {checkpoint_path}")
             self.encoder.load_state_dict(enc_sd)
-            if self.encoder_type == 't5':
+            if self.encoder_type in ('t5', 'clip'):
                 self._prompts_set = True         # the checkpoint's table is the encoder's output for the prompts it was saved with
         st = os.path.join(checkpoint_path, "experiment_state.pth")
         if os.path.exists(st):

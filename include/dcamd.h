@@ -21,6 +21,10 @@
  *                       the T5 encoder behind encode_text_prompt (diffusion_classifier.py:59-74, :93-98: transformers' T5EncoderModel;
  *                       its Linear layers are dc_igemm): self-attention with the relative-position bias and the padding mask, T5LayerNorm,
  *                       the token embedding and the feed-forward's ReLU
+ *   dc_attention_causal / dc_layernorm_rows / dc_embed_rows_pos / dc_act_pass
+ *                       a CLIP text transformer (transformers' CLIPTextModel) as the text encoder behind encode_text_prompt: causal
+ *                       self-attention with a row count per sample, LayerNorm from the fp32 stream into the compute type, token +
+ *                       position embedding, quick-GELU / erf-GELU
  *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
@@ -52,7 +56,10 @@ extern "C" {
  * (dc_cross_attention_len, dc_cross_attention_len_variant, dc_cross_attention_len_params and DC_OP_CROSS_ATTENTION_LEN likewise)
  * (the T5 encoder's entries — dc_attention_bias, dc_attention_bias_variant, dc_rmsnorm, dc_embed_rows, dc_relu, their structs and
  *  DC_OP_ATTENTION_BIAS / DC_OP_RMSNORM / DC_OP_EMBED_ROWS / DC_OP_RELU — likewise)
- * (dc_class_posterior and dc_class_posterior_params likewise; it is called directly, there is no DC_OP_* kind for it) */
+ * (dc_class_posterior and dc_class_posterior_params likewise; it is called directly, there is no DC_OP_* kind for it)
+ * (the CLIP text encoder's entries — dc_attention_causal, dc_attention_causal_variant, dc_layernorm_rows, dc_embed_rows_pos,
+ *  dc_act_pass, their structs, dc_pass_kind and DC_OP_ATTENTION_CAUSAL / DC_OP_LAYERNORM_ROWS / DC_OP_EMBED_ROWS_POS / DC_OP_ACT_PASS —
+ *  likewise) */
 #define DC_ABI_VERSION 4
 
 typedef void* dc_stream; /* hipStream_t */
@@ -363,6 +370,58 @@ int dc_embed_rows(const dc_embed_rows_params* p, dc_stream s);
 typedef struct { void* x; int64_t n; int32_t dtype, pad_; } dc_relu_params;
 int dc_relu(const dc_relu_params* p, dc_stream s);
 
+/* ---------------------------------------------------------------- CLIP text encoder ----- */
+/* Causal self-attention with a row count per sample (CLIP's text transformer under a right-padded mask):
+ *   out[i] = softmax(q_i k_i^T * scale over keys k <= q) v_i   for queries q < row_len[i].
+ * q / k / v / out as for dc_attention_bias: [n, L, heads, d] with row strides ld_qkv / ld_out (elements), one `dtype`.
+ * row_len [n] int32 on the device, NULL meaning L everywhere; the kernels clamp it into [1, L].  Causality already hides every key at
+ * or past the length from every query below it, so the length only decides which rows exist: rows >= row_len[i] of q / k / v are never
+ * read and output rows >= row_len[i] are written as zeros.  scale must be > 0 (DC_ERR_ARG); 1 <= L <= DC_ATTENTION_CAUSAL_MAX_L and
+ * d in {16, 32, 64, 128} (DC_ERR_SHAPE otherwise).
+ * Routes: 16-bit with d = 64, 16-byte aligned q / k / v rows and 8-byte aligned output rows: the matrix-core kernel "mfma" (one wave per
+ * 32 queries of a (sample, head); it walks the key blocks up to its own diagonal block only and masks inside that block alone); fp32,
+ * d = 16 / 32 / 128 and unaligned operands: the exact kernel "fp32" (an FMA chain over the keys 0 .. q in order).  Fixed summation
+ * order, no atomics: the bits of output row q of sample i depend on rows 0 .. q of sample i only.  (Masked positions carry P = 0
+ * exactly; on the matrix-core route a NON-FINITE v row above q, below row_len[i] and inside q's own block of 32 rows still reaches row
+ * q as 0 x NaN.  Rows at or past row_len[i] — what padding is — are never read on either route.) */
+#define DC_ATTENTION_CAUSAL_MAX_L 512
+typedef struct {
+  const void* q; const void* k; const void* v; void* out;
+  const int32_t* row_len;                               /* rows per sample; NULL = L everywhere */
+  int32_t dtype, n, L, heads, d, ld_qkv, ld_out; float scale;
+} dc_attention_causal_params;
+int dc_attention_causal(const dc_attention_causal_params* p, dc_stream s);
+/* Name of the kernel dc_attention_causal would launch for these parameters: "mfma" or "fp32"; "invalid" when it would refuse them
+ * (measurement / tests only; static string; touches no memory). */
+const char* dc_attention_causal_variant(const dc_attention_causal_params* p);
+
+/* LayerNorm with weight and bias whose input and output types differ: y[r, c] = (x[r, c] - mean_r) * rsqrt(var_r + eps) * gamma[c] +
+ * beta[c], fp32 statistics (the mean, then the centred second moment) in a fixed order.  x [rows, C] is read in `dtype` (the encoder's
+ * residual stream is fp32), y written in `out_dtype` (the compute type for the GEMM that follows, or fp32).  row_len
+ * [rows / rows_per_sample] int32 on the device or NULL: rows whose index inside their sample is >= row_len[sample] are written as
+ * zeros and not read.  (dc_layernorm requires one type for both sides and has no row_len; it stays as it is.) */
+typedef struct {
+  const void* x; void* y; const float* gamma; const float* beta; const int32_t* row_len;
+  int32_t dtype, out_dtype, rows, C, rows_per_sample; float eps;
+} dc_layernorm_rows_params;
+int dc_layernorm_rows(const dc_layernorm_rows_params* p, dc_stream s);
+
+/* out[r, :] = table[ids[r], :] + pos[r % L, :] for r < rows: fp32 tables [vocab, C] and [>= L, C], int64 ids on the device, one fp32
+ * add and one rounding to out_dtype.  Ids are validated on the host where they enter; the kernel clamps them into [0, vocab). */
+typedef struct {
+  const float* table; const float* pos; const int64_t* ids; void* out;
+  int32_t out_dtype, rows, C, vocab, L, pad_;
+} dc_embed_rows_pos_params;
+int dc_embed_rows_pos(const dc_embed_rows_pos_params* p, dc_stream s);
+
+/* x[i] = act(x[i]) in place for i < n, 16-byte chunks; x 16-byte aligned.  Evaluated in fp32 with one rounding to the storage type;
+ * NaN stays NaN.  DC_PASS_QUICK_GELU: x * sigmoid(1.702 x) (OpenAI CLIP's hidden_act); DC_PASS_GELU_ERF: x * Phi(x) (OpenCLIP's).
+ * A pass of its own over the feed-forward's [rows, intermediate] for the reason dc_relu is one: dc_igemm, its dispatcher and the
+ * shared epilogue stay untouched (dc_act is not extended); the activation inside the GEMM is the follow-up to measure. */
+typedef enum { DC_PASS_QUICK_GELU = 1, DC_PASS_GELU_ERF = 2 } dc_pass_kind;
+typedef struct { void* x; int64_t n; int32_t dtype, kind; } dc_act_pass_params;
+int dc_act_pass(const dc_act_pass_params* p, dc_stream s);
+
 /* ---------------------------------------------------------------- transformer block, attention half --- */
 /* One launch for the self-attention half of a UNet transformer block (the backbone behind /root/reference/nets/unet.py:186-195:
  * Transformer2DModel.proj_in -> BasicTransformerBlock.norm1 -> attn1 (to_q/k/v, softmax, to_out) -> + attn2's class vector -> residual):
@@ -466,7 +525,8 @@ int dc_class_posterior(const dc_class_posterior_params* p, dc_stream s);
 typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GROUPNORM = 4,
                DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8,
                DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10, DC_OP_ATTENTION_BIAS = 11, DC_OP_RMSNORM = 12,
-               DC_OP_EMBED_ROWS = 13, DC_OP_RELU = 14 } dc_op_kind;
+               DC_OP_EMBED_ROWS = 13, DC_OP_RELU = 14, DC_OP_ATTENTION_CAUSAL = 15, DC_OP_LAYERNORM_ROWS = 16, DC_OP_EMBED_ROWS_POS = 17,
+               DC_OP_ACT_PASS = 18 } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */
