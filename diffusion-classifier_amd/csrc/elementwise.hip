@@ -237,6 +237,7 @@ struct DdpmArgs {
   const float* z; const float* pred; const float* noise; float* out;
   int C, HW, W, ld, patch, v_param, n;
   float w, one_plus_w, alpha_t, sigma_t, alpha_s, c, sd;
+  int noise_div;          // trajectory b adds noise row b / noise_div (dc_ddpm_step: 1, a row per trajectory)
 };
 
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
@@ -260,21 +261,69 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
     float xp = a.v_param ? a.alpha_t * zt - a.sigma_t * pr : (zt - a.sigma_t * pr) / a.alpha_t;
     xp = fminf(fmaxf(xp, -1.f), 1.f);                                            // clip
     const float mu = a.alpha_s * (zt * (1.f - a.c) / a.alpha_t + a.c * xp);
-    a.out[i] = a.noise ? mu + a.noise[i] * a.sd : fminf(fmaxf(mu, -1.f), 1.f);   // last pass: the clipped mean
+    if (a.noise) {
+      const size_t ni = a.noise_div == 1 ? i : (size_t)(b / a.noise_div) * CHW + r;
+      a.out[i] = mu + a.noise[ni] * a.sd;
+    } else {
+      a.out[i] = fminf(fmaxf(mu, -1.f), 1.f);                                    // last pass: the clipped mean
+    }
   }
 }
 
-extern "C" int dc_ddpm_step(const dc_ddpm_step_params* p, dc_stream stream) {
-  DC_REQUIRE(p && p->z && p->pred && p->out, DC_ERR_ARG, "dc_ddpm_step: null pointer");
-  const int pp = p->patch > 1 ? p->patch : 1;
-  DC_REQUIRE(p->n > 0 && p->C > 0 && p->H > 0 && p->W > 0 && p->ld >= p->C * pp * pp, DC_ERR_SHAPE, "dc_ddpm_step: extents");
-  DC_REQUIRE(p->H % pp == 0 && p->W % pp == 0, DC_ERR_SHAPE, "dc_ddpm_step: patch=%d does not tile %dx%d", pp, p->H, p->W);
-  DdpmArgs a{p->z, p->pred, p->noise, p->out, p->C, p->H * p->W, p->W, p->ld, pp, p->v_param, p->n,
-             p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd};
-  const size_t total = (size_t)p->n * p->C * p->H * p->W;
+static int ddpm_step_launch(const char* who, const DdpmArgs& a, int H, dc_stream stream) {
+  DC_REQUIRE(a.z && a.pred && a.out, DC_ERR_ARG, "%s: null pointer", who);
+  DC_REQUIRE(a.noise_div >= 1 && a.n % a.noise_div == 0, DC_ERR_ARG, "%s: noise_div=%d must be >= 1 and divide n=%d", who, a.noise_div, a.n);
+  DC_REQUIRE(a.n > 0 && a.C > 0 && H > 0 && a.W > 0 && a.ld >= a.C * a.patch * a.patch, DC_ERR_SHAPE, "%s: extents", who);
+  DC_REQUIRE(H % a.patch == 0 && a.W % a.patch == 0, DC_ERR_SHAPE, "%s: patch=%d does not tile %dx%d", who, a.patch, H, a.W);
+  const size_t total = (size_t)a.n * a.C * a.HW;
   const unsigned grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
   hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  return dc_check_launch("dc_ddpm_step");
+  return dc_check_launch(who);
+}
+
+extern "C" int dc_ddpm_step(const dc_ddpm_step_params* p, dc_stream stream) {
+  DC_REQUIRE(p, DC_ERR_ARG, "dc_ddpm_step: null pointer");
+  DdpmArgs a{p->z, p->pred, p->noise, p->out, p->C, p->H * p->W, p->W, p->ld, p->patch > 1 ? p->patch : 1, p->v_param, p->n,
+             p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd, 1};
+  return ddpm_step_launch("dc_ddpm_step", a, p->H, stream);
+}
+
+extern "C" int dc_ddpm_step_shared(const dc_ddpm_step_shared_params* p, dc_stream stream) {
+  DC_REQUIRE(p, DC_ERR_ARG, "dc_ddpm_step_shared: null pointer");
+  DdpmArgs a{p->z, p->pred, p->noise, p->out, p->C, p->H * p->W, p->W, p->ld, p->patch > 1 ? p->patch : 1, p->v_param, p->n,
+             p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd, p->noise_div};
+  return ddpm_step_launch("dc_ddpm_step_shared", a, p->H, stream);
+}
+
+// ------------------------------------------------------------------ difference maps -
+// One lane per output pixel: the C planes of a and of its reference row are read coalesced across the wave, summed in channel order.
+__global__ __launch_bounds__(256) void abs_diff_map_kernel(const float* __restrict__ a, const float* __restrict__ r,
+                                                           const int32_t* __restrict__ r_of_a, float* __restrict__ out,
+                                                           long long total, int m, int C, int HW) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long u = i / HW;
+    const int p = (int)(i - u * HW);
+    const int ru = r_of_a[u];
+    float s = __builtin_nanf("");
+    if ((unsigned)ru < (unsigned)m) {
+      const float* pa = a + (size_t)u * C * HW + p;
+      const float* pr = r + (size_t)ru * C * HW + p;
+      s = 0.f;
+      for (int c = 0; c < C; ++c) s += fabsf(pa[(size_t)c * HW] - pr[(size_t)c * HW]);
+    }
+    out[i] = s;
+  }
+}
+
+extern "C" int dc_abs_diff_map(const dc_abs_diff_map_params* p, dc_stream stream) {
+  DC_REQUIRE(p && p->a && p->r && p->r_of_a && p->out, DC_ERR_ARG, "dc_abs_diff_map: null pointer");
+  DC_REQUIRE(p->n > 0 && p->m > 0 && p->C > 0 && p->H > 0 && p->W > 0, DC_ERR_SHAPE, "dc_abs_diff_map: extents n=%d m=%d C=%d H=%d W=%d",
+             p->n, p->m, p->C, p->H, p->W);
+  const long long total = (long long)p->n * p->H * p->W;
+  const unsigned grid = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
+  hipLaunchKernelGGL(abs_diff_map_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p->a, p->r, p->r_of_a,
+                     p->out, total, p->m, p->C, p->H * p->W);
+  return dc_check_launch("dc_abs_diff_map");
 }
 
 // ------------------------------------------------------------------ Haar -----------

@@ -46,6 +46,9 @@ Extra keyword-only arguments (defaults keep the reference behaviour):
                  ranks (every rank must pass the identical x; checked).  Default (None, `shard_grid`
                  unset): no grid sharding — under `accelerate launch` each rank scores its own images,
                  exactly like the reference (:615-617).
+
+Additive: `.counterfactual(x, classes, from_t, ...)` — every class from shared noise in one call, with difference maps (the
+reference's experiments/ipmsa/explain.py procedure; counterfactual.py).
 """
 import math
 import os
@@ -56,6 +59,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import dist as D
+from .. import counterfactual as CF
 from .. import posterior as P
 from .._ema import EMA
 
@@ -478,14 +482,21 @@ class DiffusionClassifier(nn.Module):
         mu = alpha_s * (z_t * (1 - c) / alpha_t + c * x_pred)
         return mu, (sigma_s ** 2) * c
 
-    def _fused_sampler_step(self, backbone, z_t, pair, lam_t, lam_s, noise):
-        """`ddpm_sampler_step` + the update `z = mu + noise * sqrt(var)` (noise None: the clipped mean of the last pass) on the
-        prediction pair of `forward_pair`, as one kernel.  The step's scalars are formed by the same fp32 torch ops as above."""
+    @staticmethod
+    def _sampler_step_scalars(lam_t, lam_s):
+        """(c, alpha_t, sigma_t, alpha_s, sd) of one sampler step as Python floats, from fp32 torch ops on the host: the expressions of
+        `ddpm_sampler_step` on 0-dim tensors, sd = sqrt(sigma_s^2 c)."""
         lt, ls = lam_t.detach().float().cpu().reshape(()), lam_s.detach().float().cpu().reshape(())
         c = -torch.special.expm1(lt - ls)
         alpha_t, alpha_s = torch.sqrt(torch.sigmoid(lt)), torch.sqrt(torch.sigmoid(ls))
         sigma_t, sigma_s = torch.sqrt(torch.sigmoid(-lt)), torch.sqrt(torch.sigmoid(-ls))
         sd = torch.sqrt((sigma_s ** 2) * c)
+        return float(c), float(alpha_t), float(sigma_t), float(alpha_s), float(sd)
+
+    def _fused_sampler_step(self, backbone, z_t, pair, lam_t, lam_s, noise):
+        """`ddpm_sampler_step` + the update `z = mu + noise * sqrt(var)` (noise None: the clipped mean of the last pass) on the
+        prediction pair of `forward_pair`, as one kernel.  The step's scalars are formed by the same fp32 torch ops as above."""
+        c, alpha_t, sigma_t, alpha_s, sd = self._sampler_step_scalars(lam_t, lam_s)
         N, Cc, H, W = z_t.shape
         z = z_t.detach().to(torch.float32).contiguous()
         out = torch.empty_like(z)
@@ -538,6 +549,32 @@ class DiffusionClassifier(nn.Module):
             if i == n:
                 return self.clip(mu)
             z_t = mu + torch.randn_like(mu) * torch.sqrt(var)
+
+    @torch.no_grad()
+    def counterfactual(self, x, classes=None, from_t=0.5, *, against="input", rng="reference", seed=0, pixel_space=False):
+        """Every class from shared noise in one call (reference experiments/ipmsa/explain.py: noise to `from_t`, denoise once per label
+        with the seed reset in front of each run, look at where the results differ) -> `Counterfactuals(samples, classes, maps)`.
+          classes      None: all config.classes; an int tensor [K] (the same for every image) or [BS, K]; K >= 1, duplicates allowed
+          samples      [BS, K, C, H, W] f32 on x.device; samples[b, k] is the image `sample(x, classes[:, k], from_t)` returns for image
+                       b: the K trajectories of an image start from one z_{from_t} (from_t in (0, 1]; 1: pure noise) and add the same
+                       noise at every step
+          rng          "reference": torch's generators in the order of ONE `sample` call (the initial draw, then one randn_like
+                       [BS, C, H, W] per step), each draw shared by the K classes — K calls of `sample` with `torch.manual_seed(s)`
+                       in front of each are the written statement of this function;
+                       "philox": all noise from Philox on the device keyed by (seed, row), row = b for the initial draw and
+                       (step + 1) * BS + b after it; no torch generator is touched, the result is the same bits from call to call.
+                       HIP backbones only
+          maps         [BS, K, H', W'] f32: sum over channels (ascending, fp32) of |samples[b, k] - base[b]|; against="input": base is
+                       x[b]; against = an int tensor [BS] of class ids (the label `classify` returned, say): base is that class's
+                       trajectory of the same image, which must be among classes[b]
+          pixel_space  models trained on `wavelet_dec_2(image) / 2`: samples and base go through `wavelet_enc_2(. * 2)` on the device
+                       before the maps are taken, and the returned samples are [BS, K, C / 4, 2H, 2W]
+        HIP backbones: the BS x K trajectories are the images of pair sessions (nets/unet.py PairSession: prompts projected once per
+        call), cut into chunks of whole images by classify's launch-size rule (config.units_per_launch), step-major and chunk-minor, one
+        `dc_ddpm_step_shared` per step and chunk, the maps by `dc_abs_diff_map`; nothing is copied to the host inside the loop.  A
+        foreign nn.Module takes the reference's eager form at batch BS and is bit-identical to the K reseeded `sample` calls."""
+        return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space,
+                      lambda H, W, k: _units_per_launch(self.config, H, W, k))
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----
     @torch.no_grad()
@@ -691,6 +728,17 @@ class _ForeignRunner:
                 self.err[bs.to(x.device), lab, j] = err
 
 
+def _units_per_launch(config, H, W, k):
+    """Work units one plan launch should hold (k: the units that must stay together); config.units_per_launch overrides the rule."""
+    u = config.units_per_launch
+    if u is None:
+        # ~8M output pixel rows per launch at full resolution (measured on cfg2: 1M -> 4M = +13 %, 4M -> 8M = +2.4 %), but never fewer than 192
+        # units: the deep levels of a 256x256 UNet see only units x 64 rows, and 64-unit launches left their GEMMs at
+        # 0.2-0.35 PF (IPMSA: 1.14 -> 1.27 img/s; ~200 MB of arena per unit, far inside 288 GB)
+        u = max(192, (1 << 23) // (H * W))
+    return max(k, int(u))
+
+
 class _HipRunner:
     """Micro-batched execution of the (image, trial, class) grid through libdcamd plans."""
 
@@ -709,13 +757,7 @@ class _HipRunner:
             assert (x.shape[1] * x.shape[2] * x.shape[3]) % 4 == 0
 
     def _units_per_launch(self, H, W, k):
-        u = self.dc.config.units_per_launch
-        if u is None:
-            # ~8M output pixel rows per launch at full resolution (measured on cfg2: 1M -> 4M = +13 %, 4M -> 8M = +2.4 %), but never fewer than 192
-            # units: the deep levels of a 256x256 UNet see only units x 64 rows, and 64-unit launches left their GEMMs at
-            # 0.2-0.35 PF (IPMSA: 1.14 -> 1.27 img/s; ~200 MB of arena per unit, far inside 288 GB)
-            u = max(192, (1 << 23) // (H * W))
-        return max(k, int(u))
+        return _units_per_launch(self.dc.config, H, W, k)
 
     def _plan(self, n_bj, k):
         dc, dev = self.dc, self.dev

@@ -17,7 +17,7 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import engine as E
 from .. import engine_dit as ED
-from .unet import _Bag, _HipBackbone
+from .unet import PairSession, _Bag, _HipBackbone
 
 
 def _sincos_1d(dim, pos):
@@ -140,6 +140,22 @@ class DiT(_HipBackbone):
         plan.ctx_of_unit.copy_(torch.stack([cond.reshape(-1), null.reshape(-1)], dim=1).reshape(-1).to(dev, torch.int32))
         plan.run()
         return plan.pred_view()
+
+    @torch.no_grad()
+    def pair_session(self, N, device, cond, null, slot=0):
+        """The once-per-call half of `forward_pair` for N images on `device`: the label pairs copied into the `ctx_of_unit` of a plan that
+        belongs to `slot`.  Returns a `PairSession` (nets/unet.py) whose `step(x, lam)` gives what `forward_pair(x, lam, cond, null)`
+        gives."""
+        L.require_gpu()
+        dev = torch.device(device)
+        if cond.numel() != N or null.numel() != N:
+            raise L.DcamdError(f"a pair session of {N} images needs {N} labels per side, got {cond.numel()} and {null.numel()}")
+        key = ("pair_session", slot, N, str(dev), self.compute_dtype)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self.make_plan(N, 2, None, dev)
+        plan.ctx_of_unit.copy_(torch.stack([cond.reshape(-1), null.reshape(-1)], dim=1).reshape(-1).to(dev, torch.int32))
+        return PairSession(self, plan, N)
 
     @torch.no_grad()
     def forward(self, x, noise_labels, encoder_hidden_states=None):

@@ -112,6 +112,24 @@ class _HipBackbone(nn.Module):
         return new
 
 
+class PairSession:
+    """`forward_pair` cut into "once per call" and "once per step", for a sampling loop whose contexts do not change from step to step.
+    The backbone's `pair_session(...)` does the first part (a plan of its own, the contexts and their lengths copied, the context plan
+    run); `step(x, noise_labels)` is the rest: feed x and lambda, run the plan, return `forward_pair`'s prediction view [2N, ...] (which
+    the next step overwrites).  A session owns its plan: sessions of different `slot`s hold different contexts at the same time."""
+
+    def __init__(self, backbone, plan, N):
+        self.backbone, self.plan, self.N = backbone, plan, N
+
+    @torch.no_grad()
+    def step(self, x, noise_labels):
+        if not x.is_cuda or x.shape[0] != self.N:
+            raise L.DcamdError(f"a pair session of {self.N} images needs a CUDA/HIP tensor of that batch, got {tuple(x.shape)} on {x.device}")
+        self.backbone._feed(self.plan, x, noise_labels)
+        self.plan.run()
+        return self.plan.pred_view()
+
+
 class UNetCondition2D(_HipBackbone):
     def __init__(
         self,
@@ -350,6 +368,31 @@ class UNetCondition2D(_HipBackbone):
         plan.run_ctx()
         plan.run()
         return plan.pred_view()
+
+    @torch.no_grad()
+    def pair_session(self, N, device, cond, null, cond_lengths=None, null_lengths=None, slot=0):
+        """The once-per-call half of `forward_pair` for N images on `device`: contexts (and lengths) copied into a plan that belongs to
+        `slot`, the context plan run once.  Returns a `PairSession`; its `step(x, lam)` gives what `forward_pair(x, lam, cond, null)`
+        gives, without projecting the prompts again."""
+        L.require_gpu()
+        dev = torch.device(device)
+        S = self._context_tokens(cond, null)
+        if cond.shape[0] != N or null.shape[0] != N:
+            raise L.DcamdError(f"a pair session of {N} images needs {N} contexts per side, got {cond.shape[0]} and {null.shape[0]}")
+        key = ("pair_session", slot, N, str(dev), self.compute_dtype, self.share_trunk, S)
+        varlen = cond_lengths is not None or null_lengths is not None
+        if varlen:
+            lens = torch.stack([self._context_lengths(cond_lengths, N, S), self._context_lengths(null_lengths, N, S)], dim=1)
+            key += ("varlen",)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self.make_plan(N, 2, 2 * N, dev, S=S, varlen=varlen)   # as forward_pair: one context per unit
+        ctx = torch.stack([cond, null], dim=1)                                # [N, 2, S, hid]: context 2b = cond[b], 2b + 1 = null[b]
+        plan.ctx.copy_(ctx.to(dev, torch.float32).reshape(plan.ctx.shape))
+        if varlen:
+            plan.ctx_len.copy_(lens.reshape(-1))
+        plan.run_ctx()
+        return PairSession(self, plan, N)
 
     def _feed(self, plan, x, noise_labels):
         """lambda and the conv_in GEMM operand (3x3 patches of x) of a plain forward."""

@@ -28,6 +28,8 @@
  *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
+ *   dc_ddpm_step_shared / dc_abs_diff_map
+ *                       experiments/ipmsa/explain.py: every class trajectory of an image from shared noise, and where they differ
  *   dc_stage_topk / dc_reduce_argmin / dc_stage_maps
  *                       the stage end, diffusion_classifier.py:718-725 (mean over trials, k smallest classes) and the
  *                       per-image surviving-class lists of the next stage (:695-698, ragged after pruning / fast mode
@@ -59,7 +61,8 @@ extern "C" {
  * (dc_class_posterior and dc_class_posterior_params likewise; it is called directly, there is no DC_OP_* kind for it)
  * (the CLIP text encoder's entries — dc_attention_causal, dc_attention_causal_variant, dc_layernorm_rows, dc_embed_rows_pos,
  *  dc_act_pass, their structs, dc_pass_kind and DC_OP_ATTENTION_CAUSAL / DC_OP_LAYERNORM_ROWS / DC_OP_EMBED_ROWS_POS / DC_OP_ACT_PASS —
- *  likewise) */
+ *  likewise)
+ * (dc_ddpm_step_shared, dc_abs_diff_map and their structs likewise; both are called directly) */
 #define DC_ABI_VERSION 4
 
 typedef void* dc_stream; /* hipStream_t */
@@ -472,6 +475,30 @@ typedef struct {
   float one_plus_w;        /* (float)(1.0 + (double)w): the reference forms 1 + w as a Python double and torch rounds it once */
 } dc_ddpm_step_params;
 int dc_ddpm_step(const dc_ddpm_step_params* p, dc_stream s);
+
+/* The same step on n = images x K trajectories that share their noise (counterfactual sampling: K class trajectories of one image see
+ * one z_{from_t} and one noise draw per step).  z / out [n, C, H, W], pred [2n, ...] as above; trajectory u adds row u / noise_div of
+ * noise [n / noise_div, C, H, W] (noise NULL: the clipped mean).  The arithmetic, its order and the kernel body are dc_ddpm_step's:
+ * with noise_div = 1, or on noise repeated noise_div times, the two agree bit for bit.  noise_div < 1 or n % noise_div != 0:
+ * DC_ERR_ARG. */
+typedef struct {
+  const float* z; const float* pred; const float* noise; float* out;
+  int32_t n, C, H, W, ld, patch, v_param;
+  int32_t noise_div;
+  float w, alpha_t, sigma_t, alpha_s, c, sd;
+  float one_plus_w;
+  int32_t pad_;
+} dc_ddpm_step_shared_params;
+int dc_ddpm_step_shared(const dc_ddpm_step_shared_params* p, dc_stream s);
+
+/* ---------------------------------------------------------------- difference maps - */
+/* out[i, y, x] = sum_c |a[i, c, y, x] - r[r_of_a[i], c, y, x]|, fp32, c ascending (a fixed order).  a [n, C, H, W], r [m, C, H, W],
+ * r_of_a [n] int32 (rows may repeat and be skipped), out [n, H, W].  An r_of_a[i] outside [0, m) reads nothing and writes NaN. */
+typedef struct {
+  const float* a; const float* r; const int32_t* r_of_a; float* out;
+  int32_t n, m, C, H, W, pad_;
+} dc_abs_diff_map_params;
+int dc_abs_diff_map(const dc_abs_diff_map_params* p, dc_stream s);
 
 /* ---------------------------------------------------------------- Haar ----------- */
 /* in [n, C, H, W] f32 -> out [n, 4C, H/2, W/2], channel 4i+{0,1,2,3} = cA,cH,cV,cD; out*=scale */
