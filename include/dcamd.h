@@ -153,7 +153,12 @@ typedef struct {
    * of HW / qparts pixels) and per quad q of 4 consecutive output channels the mean and the centred second moment
    * M2 = sum (v - mean)^2 of the quad's 4 * HW / qparts output values (fp32, before the rounding to out_dtype; shifted sums, no
    * cancellation for |mean| >> std): qstats[((n * qparts + part) * (Cout/4) + q) * 2 + (0 = mean | 1 = M2)],
-   * qparts = dc_igemm_qstats_parts().  The GroupNorm then streams the tensor once instead of reading it twice.  NULL otherwise. */
+   * qparts = dc_igemm_qstats_parts().  The GroupNorm then streams the tensor once instead of reading it twice.  NULL otherwise.
+   * Which pixels a part holds: images of at most 32 columns — part i is the row-major run [128 i, 128 i + 128) (one part: the whole
+   * image); wider images are cut into blocks of 8 rows x 32 columns, blocks in row-major order, and every block is two parts, its
+   * upper 4 rows before its lower 4.  up4: parts [phase * qparts/4, (phase + 1) * qparts/4), phase = 2a + b, are those of the
+   * low-resolution image by the same rule and hold the output pixels (2y+a, 2x+b).  (Every part has the same count, so a consumer
+   * that merges all parts of a sample need not know this.) */
   float* qstats;
   /* producer-side GroupNorm (only where dc_igemm_pn_ok() says so: 3x3 stride-1 conv on power-of-two images of 16x16 ... 64x64, one
    * source, Cout a multiple of 128): besides — or, with out == NULL, instead of — the raw output v the conv stores
