@@ -15,7 +15,8 @@ here: `compute_dtype` ("bf16" default | "f16" | "f32"), `units_per_launch`, `sco
 default 6), `dwt_on_device` (True: `inference` applies `wavelet_dec_2(images) / 2` on the device to the batches its loader yields, on the
 prefetch stream), `shard_grid` (opt-in: True
 shards the (trial, image) grid of ONE replicated batch over the default process group),
-`simulate_rank` ((r, N), bench.py only: time rank r's share of an N-rank sharded call on one GPU).
+`simulate_rank` ((r, N), bench.py only: time rank r's share of an N-rank sharded call on one GPU),
+`stop_margin_z` (opt-in per-image early stopping, see below; None: off, none of its code runs).
 
 What differs is HOW classify runs.  The reference walks a Python double loop — T trials x C
 classes sequential eager backbone calls at batch BS (:686-714).  Here the (image, trial, class)
@@ -26,8 +27,27 @@ trial), and errors scattered straight into `errors[b, class, j]`.  The stage end
 trials, top-k smallest, :718-721) runs ON THE DEVICE for the HIP backbones (`dc_stage_topk`,
 `dc_reduce_argmin`: fixed summation order, ties to the lower class id, NaN last — identical on
 every rank), and so do the next stage's work-unit maps (`dc_stage_maps`): nothing is copied to
-the host between stages.  A foreign `nn.Module` backbone takes the reference's own torch ops
+the host between stages as long as `stop_margin_z` is unset.  A foreign `nn.Module` backbone takes the reference's own torch ops
 (`_ForeignRunner.stage_end`).
+
+Per-image early stopping (`config.stop_margin_z` = a float > 0; +inf: never stop; anything else, or the key together with
+`simulate_rank`, raises ValueError): stage pruning drops classes, never images — with two classes every image pays all T trials.
+With the key set, the stages are checkpoints: after stage i < n_stages - 1 (and after its top-k pruning) every image still active
+gets winner, runner-up and margin_z over its cells j < t_end exactly as the posterior defines them (posterior.py); it stops iff
+margin_z >= stop_margin_z and its winner's mean is not NaN (a NaN z-score, e.g. at t_end = 1, never stops; no runner-up — margin_z =
++inf — does).  A stopped image keeps label = winner and t_done = t_end, its cells j >= t_done stay +inf for good, and it is in no
+later stage's pairs: the work of a batch is sum_b t_done[b] (trial, image) pairs instead of BS * T.  The last stage ends as always,
+the images that got there take its label and t_done = T; if no image is left after a checkpoint the remaining stages are skipped.
+HIP backbones decide on the device (`dc_stage_stop`: the posterior's own device code, so the z-score an image stopped on is the one
+the posterior reports; the undecided ids compacted in ascending order without atomics) and build the next stage's maps over the
+undecided images there (`dc_stage_maps_rows`); the PRICE is one pinned device-to-host copy of BS + 1 int32 (the ids and their
+count) and a wait for it at every stage end but the last — the host needs the count to size the launches.  A stage over a subset of
+the images takes its launch size from a short ladder (cap, cap/2, ... cap/32 pairs, padded with dump-cell slots), so that the
+changing number of undecided images does not build a plan per count.  A foreign backbone applies the same rule as torch statements
+(`posterior.stop_rule_torch`).  Under grid sharding every rank holds the same errors after each gather, takes the same decisions and
+builds the same image list: no extra collective.  With +inf labels, errors and posterior are bit-identical to the key unset.
+The rule looks at the data at every checkpoint: `stop_margin_z` is NOT a one-shot significance level (sequential testing) — a z
+reached at one of several looks is weaker evidence than the same z at a fixed T; calibrate the threshold on held-out data.
 
 Extra keyword-only arguments (defaults keep the reference behaviour):
   t, eps         inject the per-trial draws ([T,BS] and [T,BS,C,H,W]) — parity tests
@@ -38,7 +58,11 @@ Extra keyword-only arguments (defaults keep the reference behaviour):
                  paired mean differences to the winner, their entropy, the runner-up with the paired margin and its z-score, trials per
                  class and the NaN-cell count, computed after the last stage end from the gathered errors (`dc_class_posterior` for the
                  HIP backbones, the same definitions in torch for a foreign one), left on the scoring device: no host synchronisation,
-                 identical on every rank.  argmax probs is the label.  Returns (labels, post), with return_errors (labels, errors, post)
+                 identical on every rank.  argmax probs is the label.  Returns (labels, post), with return_errors (labels, errors, post).
+                 With stop_margin_z every image is evaluated over its own [0, t_done[b]) (one launch per stage end that was reached
+                 and a row select on the device); `n_trials` then reports the trials each image used
+  return_trials  also return t_done, int32 [BS] on the scoring device, as the LAST element of the tuple: the trials each image was
+                 scored on (T everywhere when stop_margin_z is unset)
   rng            "reference": draw rand(BS) / randn_like(x) per trial in the reference's order;
                  "philox":   t from the CPU generator, eps on device from Philox keyed by
                              (seed, image, trial) — no eps traffic, world-size independent
@@ -289,8 +313,11 @@ class DiffusionClassifier(nn.Module):
     # ---- the hot path ---------------------------------------------------------------------
     @torch.no_grad()
     def classify(self, x, text=None, fast=False, *, t=None, eps=None, fast_select=None, return_errors=False,
-                 rng="reference", seed=0, group=None, return_posterior=False):
+                 rng="reference", seed=0, group=None, return_posterior=False, return_trials=False):
         cfg = self.config
+        z_stop = P.stop_margin_of(cfg)           # None: no per-image early stopping, none of its code runs
+        if z_stop is not None and cfg.simulate_rank:
+            raise ValueError("stop_margin_z cannot be combined with simulate_rank: one rank's share of the errors decides nothing")
         tau = P.temperature_of(cfg) if return_posterior else None
         assert self.encoder_type is not None, "Encoder must be provided for classification."
         self._require_prompts()
@@ -361,25 +388,56 @@ class DiffusionClassifier(nn.Module):
             runner = _HipRunner(self, backbone, x, T, draws)           # libdcamd; raises without GPU / library
         else:
             runner = _ForeignRunner(self, backbone, x, T, draws)       # user-supplied nn.Module, eager torch
+        # per-image early stopping (config.stop_margin_z): t_done[b] = 0 while image b is undecided, else the trials it was decided on;
+        # `rows` = the undecided images (ascending ids; None: all of them, the plain path), the same list on every rank
+        t_done = frozen = rows = None
+        if z_stop is not None:
+            t_done, frozen = runner.stop_state()
         for i in range(cfg.n_stages):
-            pairs = D.local_pairs(ends[i], ends[i + 1], BS, rank, ws)
-            runner.run_stage(pairs, classes, stage=(ends[i], rank, ws))
+            last = i == cfg.n_stages - 1
+            if rows is None:
+                pairs = D.local_pairs(ends[i], ends[i + 1], BS, rank, ws)
+                runner.run_stage(pairs, classes, stage=(ends[i], rank, ws))
+            else:
+                pairs = D.local_pairs_rows(ends[i], ends[i + 1], rows, rank, ws)
+                runner.run_stage(pairs, classes, stage=(ends[i], rank, ws), rows=rows)
             errors = runner.errors()
             if not sim:
-                D.gather_stage_errors(errors, ends[i], ends[i + 1], rank, ws, group=group)
+                D.gather_stage_errors(errors, ends[i], ends[i + 1], rank, ws, group=group,
+                                      **({} if rows is None else {"rows": runner.rows_on_device(rows)}))
             # stage end (:718-721), identically on every rank: mean over the trials so far, the k smallest classes per image.
             # HIP backbones: on the device (dc_stage_topk / dc_reduce_argmin; the next stage's work-unit maps are built
-            # there too), so a multi-stage / fast classify never copies errors to the host between stages.
-            classes = runner.stage_end(errors, ends[i + 1], cfg.n_keep_per_stage[i], last=i == cfg.n_stages - 1)
-        assert classes.shape[1] == 1, "Only one class should be selected at the end of the classification process."
-        out = classes[:, 0].to(device=x.device, dtype=torch.int64)
+            # there too), so a multi-stage / fast classify never copies errors to the host between stages — unless stop_margin_z
+            # is set: the stop rule then hands the number and the ids of the undecided images to the host at every boundary.
+            # (A stopped image's cells past t_done stay +inf: its class list is meaningless from then on and never used.)
+            classes = runner.stage_end(errors, ends[i + 1], cfg.n_keep_per_stage[i], last=last)
+            if z_stop is not None and not last:
+                active = runner.stage_stop(errors, ends[i + 1], z_stop, t_done, frozen)
+                rows = None if len(active) == BS else active
+                if not active:
+                    break                        # every image is decided: the remaining stages have nothing to score
+        if z_stop is None or last:
+            assert classes.shape[1] == 1, "Only one class should be selected at the end of the classification process."
+        if z_stop is None:
+            out = classes[:, 0].to(device=x.device, dtype=torch.int64)
+        elif last:                               # the images that ran to T take the last stage's label, the others keep theirs
+            out = torch.where(t_done == 0, classes[:, 0].to(device=frozen.device, dtype=torch.int64), frozen).to(x.device)
+            t_done = torch.where(t_done == 0, torch.full_like(t_done, T), t_done)
+        else:
+            out = frozen.to(x.device)
         # the posterior reads the errors every rank holds after the last gather: the same bits everywhere
-        post = runner.posterior(errors, T, tau) if return_posterior else None
+        post = None
+        if return_posterior:
+            post = runner.posterior(errors, T, tau) if z_stop is None else runner.posterior(errors, t_done, tau, t_values=ends[1:i + 2])
+        res = (out,)
         if return_errors:
-            err_host = errors.cpu()              # (synchronises: the cheap moment to look at the device-side failure counter)
+            res += (errors.cpu(),)               # (synchronises: the cheap moment to look at the device-side failure counter)
             self.check_device_errors()
-            return (out, err_host, post) if return_posterior else (out, err_host)
-        return (out, post) if return_posterior else out
+        if return_posterior:
+            res += (post,)
+        if return_trials:
+            res += (t_done if t_done is not None else torch.full((BS,), T, dtype=torch.int32, device=errors.device),)
+        return res if len(res) > 1 else out
 
     def check_device_errors(self):
         """Raise if a producer-side-GroupNorm launch (csrc/epi_pn.h) gave up waiting for the other workgroups of a sample since the last
@@ -702,10 +760,22 @@ class _ForeignRunner:
         _, keep_indices = torch.topk(end_of_stage_errors, num_keep, dim=1, largest=False)
         return keep_indices
 
-    def posterior(self, errors, t_end, temperature):
-        return P.class_posterior_torch(errors, t_end, temperature)
+    def posterior(self, errors, t_end, temperature, t_values=None):
+        return P.class_posterior_torch(errors, t_end, temperature, t_values=t_values)
 
-    def run_stage(self, pairs, classes, stage=None):
+    def stop_state(self):
+        BS, dev = self.x.shape[0], self.x.device
+        return torch.zeros(BS, dtype=torch.int32, device=dev), torch.zeros(BS, dtype=torch.int64, device=dev)
+
+    def stage_stop(self, errors, t_end, z_stop, t_done, labels):
+        """The stop rule at a stage boundary as torch statements (posterior.stop_rule_torch), in place; the undecided image ids as a list."""
+        ids, n, _ = P.stop_rule_torch(errors, t_end, z_stop, t_done, labels)
+        return ids[:int(n)].tolist()
+
+    def rows_on_device(self, rows):
+        return rows
+
+    def run_stage(self, pairs, classes, stage=None, rows=None):
         dc, x, d = self.dc, self.x, self.d
         by_trial = {}
         for j, b in pairs:
@@ -827,21 +897,61 @@ class _HipRunner:
             L.check(self.lib.dc_stage_topk(errors.data_ptr(), BS, ncls, T, t_end, num_keep, keep.data_ptr(), None, L.stream_ptr()), "dc_stage_topk")
         return keep
 
-    def posterior(self, errors, t_end, temperature):
-        return P.class_posterior_hip(errors, t_end, temperature)
+    def posterior(self, errors, t_end, temperature, t_values=None):
+        return P.class_posterior_hip(errors, t_end, temperature, t_values=t_values)
 
-    def run_stage(self, pairs, classes, stage=None):
-        """pairs: this rank's (trial, image) pairs of the stage = D.local_pairs(t0, t1, BS, rank, world); stage = (t0, rank, world)."""
+    def stop_state(self):
+        BS = self.x.shape[0]
+        return torch.zeros(BS, dtype=torch.int32, device=self.dev), torch.zeros(BS, dtype=torch.int64, device=self.dev)
+
+    def stage_stop(self, errors, t_end, z_stop, t_done, labels):
+        """The stop rule at a stage boundary on the device (dc_stage_stop), in place on t_done / labels.  Returns the undecided image
+        ids (ascending) as a list: ONE pinned device-to-host copy of BS + 1 int32 (the ids and their count) and a wait for it — the
+        host needs the count to size the next stage's launches.  The ids stay on the device for dc_stage_maps_rows."""
+        BS = errors.shape[0]
+        block = torch.empty(BS + 1, dtype=torch.int32, device=self.dev)          # | active ids [BS] | their count |
+        ids, _, _ = P.stop_rule_hip(errors, t_end, z_stop, t_done, labels, out=block)
+        host = getattr(self.dc, "_stop_host", None)          # pinned staging kept across calls (pin_memory() is slow); free again after the wait
+        if host is None or host.numel() != BS + 1:
+            host = self.dc._stop_host = torch.zeros(BS + 1, dtype=torch.int32).pin_memory()
+        host.copy_(block, non_blocking=True)
+        torch.cuda.current_stream(self.dev).synchronize()
+        n = int(host[BS])
+        active = host[:n].tolist()
+        self._rows = (active, ids[:n])
+        return active
+
+    def rows_on_device(self, rows):
+        """The int32 device tensor of an image list: the one dc_stage_stop wrote when it is the list it returned."""
+        have = getattr(self, "_rows", None)
+        if have is not None and have[0] == list(rows):
+            return have[1]
+        return torch.tensor(list(rows), dtype=torch.int32).to(self.dev)
+
+    def run_stage(self, pairs, classes, stage=None, rows=None):
+        """pairs: this rank's (trial, image) pairs of the stage = D.local_pairs(t0, t1, BS, rank, world); stage = (t0, rank, world).
+        rows (per-image early stopping): the stage runs over these images only — pairs = D.local_pairs_rows(t0, t1, rows, rank, world)."""
         if not pairs:
             return
         dc, d, dev, T = self.dc, self.d, self.dev, self.T
         BS, Cc, H, W = self.x.shape
         ncls, k = dc.config.classes, classes.shape[1]
         on_dev = classes.is_cuda                         # stages >= 1: the surviving classes never left the device
-        n_bj = min(len(pairs), max(1, self._units_per_launch(H, W, k) // k))
-        # equal micro-batches: 800 pairs at a cap of 256 run as 4 x 200, not 3 x 256 + 32 padded to 256 (slots past the last pair
-        # repeat a pair into the dump cell: 28 % wasted work on the CheXpert workload at 8 images per step)
-        n_bj = -(-len(pairs) // -(-len(pairs) // n_bj))
+        cap = max(1, self._units_per_launch(H, W, k) // k)
+        if rows is None:
+            n_bj = min(len(pairs), cap)
+            # equal micro-batches: 800 pairs at a cap of 256 run as 4 x 200, not 3 x 256 + 32 padded to 256 (slots past the last pair
+            # repeat a pair into the dump cell: 28 % wasted work on the CheXpert workload at 8 images per step)
+            n_bj = -(-len(pairs) // -(-len(pairs) // n_bj))
+        else:
+            # a stage over the undecided images: their number changes from batch to batch, and every n_bj is a plan with an arena of
+            # its own — take the smallest rung of cap, cap/2, ... cap/32 that holds the pairs (cap when there are more) and pad the
+            # last micro-batch with dump-cell slots: at most 6 plan sizes per k, the default score_plan_cache
+            n_bj = cap
+            for _ in range(5):
+                if n_bj == 1 or -(-n_bj // 2) < len(pairs):
+                    break
+                n_bj = -(-n_bj // 2)
         sp = self._plan(n_bj, k)
         plan, score, U = sp["plan"], sp["score"], sp["U"]
         if self.err_dev is None:
@@ -866,7 +976,10 @@ class _HipRunner:
         # the index part of every control block (pair ids, image / class / output maps) depends on (pairs, classes) only:
         # built once and kept (stage 0 of every call sees the same pairs and the full class list); per call only the
         # three float rows (lambda, alpha, sigma of this call's t draws) are gathered.  Host time here is GPU idle time.
-        ck = (n_bj, len(pairs), pairs[0], pairs[-1], T, ncls, b"dev" if on_dev else classes.numpy().tobytes())
+        # (pairs over a subset of the images: two subsets can agree in length, first and last pair — the ids are part of the key; a
+        # caller that hands over pairs without naming their stage is keyed by the pairs themselves)
+        ck = (n_bj, len(pairs), pairs[0], pairs[-1], T, ncls, b"dev" if on_dev else classes.numpy().tobytes(),
+              tuple(rows) if rows is not None else (None if stage is not None else tuple(pairs)))
         cache = sp.setdefault("idx_cache", {})
         ent = cache.get(ck)
         if ent is None:
@@ -907,8 +1020,13 @@ class _HipRunner:
             # class-dependent maps of every micro-batch of the stage, built on the device from the surviving classes
             t0, rank, ws = stage
             maps = torch.empty((n_mb, 2 * U), dtype=torch.int32, device=dev)
-            L.check(self.lib.dc_stage_maps(classes.data_ptr(), BS, ncls, T, k, t0, len(pairs), rank, ws, n_bj, n_mb, dump,
-                                           maps.data_ptr(), L.stream_ptr()), "dc_stage_maps")
+            if rows is None:
+                L.check(self.lib.dc_stage_maps(classes.data_ptr(), BS, ncls, T, k, t0, len(pairs), rank, ws, n_bj, n_mb, dump,
+                                               maps.data_ptr(), L.stream_ptr()), "dc_stage_maps")
+            else:
+                rd = self.rows_on_device(rows)
+                L.check(self.lib.dc_stage_maps_rows(classes.data_ptr(), rd.data_ptr(), len(rows), BS, ncls, T, k, t0, len(pairs), rank, ws,
+                                                    n_bj, n_mb, dump, maps.data_ptr(), L.stream_ptr()), "dc_stage_maps_rows")
         for m in range(n_mb):
             chunk = pairs[m * n_bj:(m + 1) * n_bj]
             if on_dev:

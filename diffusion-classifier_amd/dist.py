@@ -70,31 +70,49 @@ def local_pairs(stage_start, stage_end, BS, rank, world_size):
     return [(stage_start + g // BS, g % BS) for g in range(rank, P, world_size)]     # == stage_pairs(...)[rank::world_size]
 
 
+def local_pairs_rows(stage_start, stage_end, rows, rank, world_size):
+    """Pairs of the stage owned by `rank` when only the images `rows` (ascending ids: the images per-image early stopping has not
+    decided yet) are scored: pair g = (j - stage_start) * len(rows) + i is (j, rows[i]) and belongs to rank g % world.
+    rows = range(BS) is `local_pairs`."""
+    A = len(rows)
+    P = (stage_end - stage_start) * A
+    return [(stage_start + g // A, rows[g % A]) for g in range(rank, P, world_size)]
+
+
 def slab_len(stage_start, stage_end, BS, world_size):
     return -(-((stage_end - stage_start) * BS) // world_size)
 
 
-def gather_stage_errors(errors, stage_start, stage_end, rank, world_size, group=None):
+def gather_stage_errors(errors, stage_start, stage_end, rank, world_size, group=None, rows=None):
     """In place: complete errors[:, :, stage_start:stage_end] on every rank from the owners.
 
     `errors` is [BS, classes, T]; on entry each rank has filled only the cells of its own pairs.
+    rows (a sequence or an int tensor of A ascending image ids): the stage ran over these images only (`local_pairs_rows`) — the slab
+    holds (stage_end - stage_start) * A pairs and pair g goes back to errors[rows[g % A], :, stage_start + g // A]; the cells of the
+    other images are left alone.  Every rank holds the same errors after each gather, so every rank takes the same stop decisions
+    and builds the same rows: no extra collective.
     """
     if world_size == 1:
         return errors
     BS, ncls = errors.shape[0], errors.shape[1]
+    dev = errors.device
+    if rows is not None:                 # the stage's images: BS below is their number, img() their ids
+        rows = torch.as_tensor(rows, device=dev).to(torch.int64)
+        BS = int(rows.numel())
+    img = (lambda i: i) if rows is None else (lambda i: rows[i])
     n = slab_len(stage_start, stage_end, BS, world_size)
     P = (stage_end - stage_start) * BS
-    dev = errors.device
     # pair g = (j - stage_start) * BS + b lives on rank g % world, row g // world of that rank's slab: index arithmetic on
     # the device instead of Python lists of pairs (6400 pairs x 8 ranks per call at N = 8 sat on the critical path)
     g_mine = torch.arange(rank, P, world_size, device=dev)
     slab = torch.full((n, ncls), float("inf"), dtype=errors.dtype, device=dev)
     if g_mine.numel():
-        slab[: g_mine.numel()] = errors[g_mine % BS, :, stage_start + g_mine // BS]
+        slab[: g_mine.numel()] = errors[img(g_mine % BS), :, stage_start + g_mine // BS]
     host = errors.is_cuda and dist.get_backend(group) == "gloo"     # gloo (single-GPU rehearsals, CPU tests) gathers on the host
     flat = torch.empty((world_size * n, ncls), dtype=errors.dtype, device="cpu" if host else dev)   # dim-0 concatenation (gloo needs this form)
     dist.all_gather_into_tensor(flat, slab.cpu() if host else slab.contiguous(), group=group)
     flat = flat.to(dev)
     g = torch.arange(P, device=dev)
-    errors[g % BS, :, stage_start + g // BS] = flat[(g % world_size) * n + g // world_size]
+    errors[img(g % BS), :, stage_start + g // BS] = flat[(g % world_size) * n + g // world_size]
     return errors
+

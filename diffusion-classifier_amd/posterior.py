@@ -14,6 +14,14 @@ sequential, j ascending (include/dcamd.h `dc_class_posterior` has the full state
   invalid               NaN cells among the evaluated ones
 `class_posterior_hip` is the kernel (csrc/stage.hip), `class_posterior_torch` the same definitions as plain fp32 torch statements on
 whatever device the errors live on: the path of foreign backbones, and the written form of the kernel.
+
+Per-image early stopping (config key `stop_margin_z`, include/dcamd.h `dc_stage_stop`): at a stage boundary an image that is still
+active stops iff its margin_z over the cells j < t_end is >= the threshold and its winner's mean is not NaN (a NaN margin_z never
+stops, no runner-up — margin_z = +inf — does); it keeps label = winner and t_done = t_end.  `stop_rule_torch` is that rule on the
+statements above: the path of foreign backbones and the written form of the kernel.  After such a call every image has its own
+number of trials: both posterior functions take t_end as an int tensor [BS] and evaluate each image over its own [0, t_end[b]).
+The rule looks at the data at every stage boundary, so the threshold is NOT a one-shot significance level: a z of 2 reached at one of
+several looks is weaker evidence than a z of 2 at a single, fixed T (sequential testing).
 """
 import ctypes as C
 from collections import namedtuple
@@ -35,6 +43,37 @@ def temperature_of(config):
     if not (tau > 0.0 and tau < float("inf")):
         raise ValueError(f"posterior_temperature must be a positive finite number, got {tau}")
     return tau
+
+
+def stop_margin_of(config):
+    """config.stop_margin_z: None (per-image early stopping off) or a float > 0, +inf allowed ("never stop").  Anything else: ValueError."""
+    z = getattr(config, "stop_margin_z", None)
+    if z is None:
+        return None
+    if isinstance(z, bool) or not isinstance(z, (int, float)) or not float(z) > 0.0:
+        raise ValueError(f"stop_margin_z must be a number > 0 (+inf: never stop) or None, got {z!r}")
+    return float(z)
+
+
+def _per_image(fn, errors, t_done, temperature, return_parts, t_values):
+    """fn at every distinct value of t_done (t_values: the values that can occur, known to the caller — else read from t_done, which
+    synchronises), each image's rows taken from the evaluation at its own value: exact, a row select on the device."""
+    if t_done.dim() != 1 or t_done.numel() != errors.shape[0] or t_done.dtype.is_floating_point:
+        raise ValueError(f"a per-image t_end must be an int tensor [BS = {errors.shape[0]}], got {t_done.dtype} {tuple(t_done.shape)}")
+    t_done = t_done.to(errors.device)
+    values = sorted(set(int(v) for v in (t_values if t_values is not None else t_done.tolist())))
+    out = None
+    for v in values:
+        res = fn(errors, v, temperature, return_parts=True)
+        flat = tuple(res[0]) + tuple(res[1:])
+        if out is None:
+            out = flat
+            continue
+        pick = t_done == v
+        out = tuple(torch.where(pick.view(-1, *([1] * (a.dim() - 1))), b, a) for a, b in zip(out, flat))
+    nf = len(ClassPosterior._fields)
+    post = ClassPosterior(*out[:nf])
+    return (post,) + out[nf:] if return_parts else post
 
 
 def _check(errors, t_end, temperature):
@@ -60,8 +99,11 @@ def _argmin_nan_last(mean, cand):
     return torch.where(best_tier[:, 0] == 2, torch.full_like(first, -1), first)
 
 
-def class_posterior_torch(errors, t_end, temperature=1.0, return_parts=False):
-    """The definitions in fp32 torch on errors.device.  return_parts: also (winner, means, delta)."""
+def class_posterior_torch(errors, t_end, temperature=1.0, return_parts=False, t_values=None):
+    """The definitions in fp32 torch on errors.device.  return_parts: also (winner, means, delta).
+    t_end an int tensor [BS]: each image over its own [0, t_end[b]) (`_per_image`)."""
+    if torch.is_tensor(t_end) and t_end.dim() > 0:
+        return _per_image(class_posterior_torch, errors, t_end, temperature, return_parts, t_values)
     _check(errors, t_end, temperature)
     E = errors[:, :, :int(t_end)]
     BS, C_, n_t = E.shape
@@ -110,7 +152,9 @@ def class_posterior_torch(errors, t_end, temperature=1.0, return_parts=False):
         d = (Er[:, j] - Ew[:, j]) - margin
         ss = ss + d * d
     var = ss / torch.tensor(float(n_t - 1), **f32)           # t_end = 1: 0 / 0 = NaN
-    margin_z = margin / torch.sqrt(var / float(n_t))
+    # the square root through float64: torch's vectorised fp32 sqrt on the CPU is not always the correctly rounded one, the square root
+    # of an fp32 number taken in fp64 and rounded once more is (53 >= 2 * 24 + 2 bits) — the kernel's, bit for bit
+    margin_z = margin / torch.sqrt((var / float(n_t)).double()).float()
     margin = torch.where(has_r, margin, torch.full_like(margin, inf))
     margin_z = torch.where(has_r, margin_z, torch.full_like(margin_z, inf))
 
@@ -123,9 +167,45 @@ def class_posterior_torch(errors, t_end, temperature=1.0, return_parts=False):
     return (post, winner.to(torch.int64), mean, delta) if return_parts else post
 
 
-def class_posterior_hip(errors, t_end, temperature=1.0, return_parts=False):
+def stop_rule_torch(errors, t_end, z_stop, t_done, labels):
+    """The stop rule at the boundary t_end, in place on t_done [BS] int32 (0 = active) and labels [BS] int64; rows already stopped are
+    left alone.  Returns (active_ids [BS] int32: the ids still active, ascending, then -1; n_active [1] int32; margin_z [BS] f32 of
+    the rows that were active, NaN elsewhere) on errors.device — what `dc_stage_stop` writes."""
+    if not float(z_stop) > 0.0:
+        raise ValueError(f"z_stop must be > 0 (+inf: never stop), got {z_stop}")
+    post, winner, _, _ = class_posterior_torch(errors, t_end, 1.0, return_parts=True)
+    active = t_done == 0
+    z = torch.where(active, post.margin_z, torch.full_like(post.margin_z, float("nan")))      # NaN: no winner, a NaN winner mean, t_end = 1
+    stop = active & (z >= float(z_stop))                                                       # NaN >= z is false
+    labels.copy_(torch.where(stop, winner.to(labels.dtype), labels))
+    t_done.copy_(torch.where(stop, torch.full_like(t_done, int(t_end)), t_done))
+    ids = torch.nonzero(t_done == 0).view(-1).to(torch.int32)
+    active_ids = torch.full((t_done.numel(),), -1, dtype=torch.int32, device=errors.device)
+    active_ids[: ids.numel()] = ids
+    return active_ids, torch.tensor([ids.numel()], dtype=torch.int32, device=errors.device), z
+
+
+def stop_rule_hip(errors, t_end, z_stop, t_done, labels, out=None):
+    """dc_stage_stop on the current stream, in place on t_done / labels (on the device).  Returns (active_ids, n_active, margin_z) like
+    `stop_rule_torch`; active_ids and n_active are views of one int32 [BS + 1] block (`out`, made here when None).  No synchronisation."""
+    lib = L.require_gpu()
+    BS, C_, T = errors.shape
+    assert errors.is_cuda and errors.is_contiguous() and errors.dtype == torch.float32
+    assert t_done.dtype == torch.int32 and labels.dtype == torch.int64 and t_done.is_contiguous() and labels.is_contiguous()
+    if out is None:
+        out = torch.empty(BS + 1, dtype=torch.int32, device=errors.device)
+    z = torch.full((BS,), float("nan"), dtype=torch.float32, device=errors.device)
+    L.check(lib.dc_stage_stop(errors.data_ptr(), BS, C_, T, int(t_end), float(z_stop), t_done.data_ptr(), labels.data_ptr(), out.data_ptr(),
+                              out[BS:].data_ptr(), z.data_ptr(), L.stream_ptr()), "dc_stage_stop")
+    return out[:BS], out[BS:], z
+
+
+def class_posterior_hip(errors, t_end, temperature=1.0, return_parts=False, t_values=None):
     """dc_class_posterior on the current stream: errors [BS, classes, T] f32 contiguous on the device.  No synchronisation.
-    return_parts: also (winner int32 [BS], means, delta [BS, classes]) — the kernel's optional outputs, for the tests."""
+    return_parts: also (winner int32 [BS], means, delta [BS, classes]) — the kernel's optional outputs, for the tests.
+    t_end an int tensor [BS]: one launch per value of t_values and a row select on the device (`_per_image`)."""
+    if torch.is_tensor(t_end) and t_end.dim() > 0:
+        return _per_image(class_posterior_hip, errors, t_end, temperature, return_parts, t_values)
     _check(errors, t_end, temperature)
     lib = L.require_gpu()
     assert errors.is_cuda and errors.is_contiguous()

@@ -34,6 +34,10 @@
  *                       the stage end, diffusion_classifier.py:718-725 (mean over trials, k smallest classes) and the
  *                       per-image surviving-class lists of the next stage (:695-698, ragged after pruning / fast mode
  *                       :671-677) as device-side work-unit maps
+ *   dc_stage_stop / dc_stage_maps_rows
+ *                       nothing in the reference: per-image early stopping at a stage boundary (config key stop_margin_z) — the images
+ *                       whose paired z-score reached the threshold keep their label and leave the grid; the next stage's maps over
+ *                       the images still undecided
  *   dc_class_posterior  nothing in the reference: the class posterior (Li et al. 2023, eq. 5, on paired differences), its entropy and
  *                       the paired confidence of the decision, from the errors tensor :718-725 reduces to one label
  *   dc_run_plan         the Python double loop body, diffusion_classifier.py:695-714, as
@@ -62,7 +66,8 @@ extern "C" {
  * (the CLIP text encoder's entries — dc_attention_causal, dc_attention_causal_variant, dc_layernorm_rows, dc_embed_rows_pos,
  *  dc_act_pass, their structs, dc_pass_kind and DC_OP_ATTENTION_CAUSAL / DC_OP_LAYERNORM_ROWS / DC_OP_EMBED_ROWS_POS / DC_OP_ACT_PASS —
  *  likewise)
- * (dc_ddpm_step_shared, dc_abs_diff_map and their structs likewise; both are called directly) */
+ * (dc_ddpm_step_shared, dc_abs_diff_map and their structs likewise; both are called directly)
+ * (dc_stage_stop and dc_stage_maps_rows likewise; both are called directly) */
 #define DC_ABI_VERSION 4
 
 typedef void* dc_stream; /* hipStream_t */
@@ -524,6 +529,23 @@ int dc_reduce_argmin(const float* errors, int32_t BS, int32_t C, int32_t T, int3
  * class id of each unit and the flat index of errors[b, class, j] it writes (dc_eps_mse out_index). */
 int dc_stage_maps(const int32_t* keep, int32_t BS, int32_t C, int32_t T, int32_t k, int32_t t0, int32_t n_pairs, int32_t rank,
                   int32_t world, int32_t n_bj, int32_t n_mb, int32_t dump, int32_t* maps, dc_stream s);
+
+/* dc_stage_maps over a subset of the images: rows [n_rows] int32 on the device (ascending image ids, dc_stage_stop's active_ids).
+ * Global pair g = rank + r*world has trial j = t0 + g / n_rows and image b = rows[g % n_rows]; padding, the dump cell and the clamping
+ * of foreign class ids are dc_stage_maps' (an id in rows outside [0, BS) is clamped the same way).  1 <= n_rows <= BS. */
+int dc_stage_maps_rows(const int32_t* keep, const int32_t* rows, int32_t n_rows, int32_t BS, int32_t C, int32_t T, int32_t k, int32_t t0,
+                       int32_t n_pairs, int32_t rank, int32_t world, int32_t n_bj, int32_t n_mb, int32_t dump, int32_t* maps, dc_stream s);
+/* Per-image early stopping at a stage boundary.  t_done [BS] int32 in/out: 0 = the image is still active, otherwise the number of
+ * trials it was decided on (such a row is not touched: neither t_done, labels nor margin_z).  For every active image winner, runner
+ * and margin_z over the cells j < t_end are dc_class_posterior's, computed by the same device code (the same bits); the image stops
+ * iff margin_z >= z_stop and it has a winner whose mean is not NaN — a NaN margin_z (t_end = 1) never stops, no runner-up (margin_z =
+ * +inf) does.  A stopped image gets labels[b] = winner (int64) and t_done[b] = t_end.  Then active_ids [BS] int32 = the ids of the
+ * images still active, ascending (entries from n_active on: -1), and n_active [1] int32 = their count: ballots and popcount prefix
+ * sums in one workgroup, no atomics — the list is the same on every rank and from launch to launch.  margin_z [BS] f32 optional
+ * (NULL): the z-score of each active image (NaN where dc_class_posterior reports NaN).  z_stop > 0, +inf allowed (DC_ERR_ARG
+ * otherwise); C <= 1024.  Two launches on the stream. */
+int dc_stage_stop(const float* errors, int32_t BS, int32_t C, int32_t T, int32_t t_end, float z_stop, int32_t* t_done, int64_t* labels,
+                  int32_t* active_ids, int32_t* n_active, float* margin_z, dc_stream s);
 
 /* ---------------------------------------------------------------- class posterior */
 /* What a finished classify call knows beyond the label, from the same errors [BS, C, T] (cells j < t_end; +inf = not evaluated, NaN
