@@ -44,7 +44,7 @@ extern "C" void dc_debug_set_halo_abl(int v) { (void)hipMemcpyToSymbol(HIP_SYMBO
 
 static __device__ unsigned g_pn_timeouts;     // producer-side GroupNorm: waves whose wait for their sample's statistics ran out (epi_pn.h)
 static __device__ chunk16 g_zero_page[16];   // per translation unit (no device-side linking)
-#include "conv3_halo.h"
+#include "conv3_halo_plan.h"
 DC_CLOCK_DECL(conv3_halo)
 
 // NTAP: 9 = the 3x3 conv.  4 = one PHASE of "nearest-2x upsample, then 3x3 conv" (dc_igemm_params.up4): output pixel
@@ -420,9 +420,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
         constexpr int ky = UP4 ? (tap >> 1) : tap / 3, kx = UP4 ? (tap & 1) : tap - ky * 3;
         const uint32_t rowo = xbo + (uint32_t)(((ky + pa) * g.hw + pb) * 64);      // wave-uniform; kx * 64 is the instruction's immediate
         const uint32_t wso = (uint32_t)((s0 + tap) % WR) * HALO_WST;
-        // ---- half a: reads, then 16 MFMAs with this step's W LDS-DMA after the fourth (an LDS-DMA issued among MFMAs costs the
-        // wave ~60 cycles; issued in front of the fragment reads it held the whole read phase up: 1880 -> 1266 cycles per step
-        // without the instruction, tools/stamp_halo.py ablations) ----
+        // ---- half a: reads, this step's W LDS-DMA behind them, then 16 MFMAs.  (The LDS-DMA issued in front of the fragment reads held
+        // the whole read phase up: 1880 -> 1266 cycles per step without the instruction, tools/stamp_halo.py ablations; issued among
+        // the MFMAs, after the fourth, it costs the wave ~60 cycles: 13.6 vs 13.2 ms.) ----
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         if (!(abl & 2)) {
@@ -434,34 +434,20 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
         for (int j = 0; j < TM / 2; ++j) xf[j] = ds_read16_async_off<kx * 64>(xaddr[j] + rowo);
         }
         constexpr int t2 = tap + PD;
-#ifndef DC_STG_W_IN_M     // the W tile's LDS-DMA goes out in the read phase, behind the fragment reads (inside the MFMA block: 13.6 vs 13.2 ms)
         if (!(abl & 4)) {
         if (t2 < NTAP) issue_w(cc, t2, (s0 + t2) % WR);
         else if (side_next) { if (t2 - NTAP < nx) issue_w2(t2 - NTAP, (s0 + t2) % WR); }
         else if (has_next) issue_w(cc + 1, t2 - NTAP, (s0 + t2) % WR);
         }
-#endif
-#ifdef DC_STG_WAIT_FIRST  // experiment: retire the fragment reads in front of the barrier instead of behind it
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]), "+v"(xf[0]), "+v"(xf[1]), "+v"(xf[2]), "+v"(xf[3]));
-        __builtin_amdgcn_s_barrier();
-#else
         __builtin_amdgcn_s_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]), "+v"(xf[0]), "+v"(xf[1]), "+v"(xf[2]), "+v"(xf[3]));
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if (!(abl & 1)) {
 #pragma unroll
         for (int i = 0; i < TN; ++i) acc[i][0] = Mma<T>::run(wf[i], xf[0], acc[i][0]);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifdef DC_STG_W_IN_M
-        if (!(abl & 4)) {
-        if (t2 < NTAP) issue_w(cc, t2, (s0 + t2) % WR);
-        else if (side_next) { if (t2 - NTAP < nx) issue_w2(t2 - NTAP, (s0 + t2) % WR); }
-        else if (has_next) issue_w(cc + 1, t2 - NTAP, (s0 + t2) % WR);
-        }
-#endif
-        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);       // (the slot of the LDS-DMA in the order that lost)
         if (!(abl & 1)) {
 #pragma unroll
         for (int j = 1; j < TM / 2; ++j)
@@ -469,8 +455,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
           for (int i = 0; i < TN; ++i) acc[i][j] = Mma<T>::run(wf[i], xf[j], acc[i][j]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        // ---- half b: reads of pixel fragments 4-7; the NEXT chunk's halo pieces ride inside the MFMA block (3x3: two at tap 0, one at
-        // taps 1-5; four-tap form: all at tap 0) ----
+        // ---- half b: reads of pixel fragments 4-7, with the NEXT chunk's halo pieces behind them (3x3: two at tap 0, one at taps 1-5;
+        // four-tap form: all at tap 0) ----
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         if (!(abl & 2)) {
@@ -482,8 +468,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
         // s-1 | W(s+3) | this wait: the younger groups that may stay in flight are the W groups that exist and the X pieces of the two
         // previous taps.  At the chunk's last tap no X piece is younger: the whole next halo is in.
         constexpr int XP_A = UP4 ? (tap == 1 ? NXL : 0) : (tap == 1 ? 2 : (tap >= 2 && tap <= 6 ? 1 : 0));     // pieces issued at tap - 1
-#ifndef DC_STG_X_IN_M     // the halo pieces go out in the read phase, in front of this wait (inside the MFMA block — DC_STG_X_IN_M — they idle the
-                          // matrix pipe for the ~470 cycles an HBM-bound piece takes to issue: conv3_halo<8w> 15.3 vs 13.9 ms per cfg2 step)
+        // the halo pieces go out in the read phase, in front of this wait (inside the MFMA block they idle the matrix pipe for the
+        // ~470 cycles an HBM-bound piece takes to issue: conv3_halo<8w> 15.3 vs 13.9 ms per cfg2 step)
         constexpr int XP_C = UP4 ? (tap == 0 ? NXL : 0) : (tap == 0 ? 2 : (tap <= 5 ? 1 : 0));               // pieces issued at this tap
         if (has_next && !(abl & 12)) {
           if constexpr (UP4) { if (tap == 0) issue_x(cc + 1); }
@@ -491,9 +477,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
           else if constexpr (tap <= 5) issue_x(cc + 1, tap + 1, tap + 2);
         }
         constexpr int XP_B = XP_C + (UP4 ? (tap == 2 ? NXL : 0) : (tap == 2 ? 2 : (tap >= 3 && tap <= 7 ? 1 : 0)));
-#else
-        constexpr int XP_B = UP4 ? (tap == 2 ? NXL : 0) : (tap == 2 ? 2 : (tap >= 3 && tap <= 7 ? 1 : 0));     // pieces issued at tap - 2
-#endif
         if (has_next) {
           if (tap == NTAP - 1 && side_next && nx < PD) hwait_vmcnt<0>();      // fewer side-source W tiles than the prefetch distance
           else hwait_vmcnt<(PD - 1) * WLD + XP_A + XP_B>();
@@ -501,27 +484,15 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
           constexpr int left = NTAP - 1 - tap;          // W groups behind this step's
           if constexpr (left > 0) hwait_vmcnt<((left - 1) < (PD - 1) ? (left - 1) : (PD - 1)) * WLD>();
         }
-#ifdef DC_STG_WAIT_FIRST
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xf[0]), "+v"(xf[1]), "+v"(xf[2]), "+v"(xf[3]));
-        __builtin_amdgcn_s_barrier();
-#else
         __builtin_amdgcn_s_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xf[0]), "+v"(xf[1]), "+v"(xf[2]), "+v"(xf[3]));
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if (!(abl & 1)) {
 #pragma unroll
         for (int i = 0; i < TN; ++i) acc[i][TM / 2] = Mma<T>::run(wf[i], xf[0], acc[i][TM / 2]);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifdef DC_STG_X_IN_M
-        if (has_next && !(abl & 12)) {
-          if constexpr (UP4) { if (tap == 0) issue_x(cc + 1); }
-          else if constexpr (tap == 0) issue_x(cc + 1, 0, 2);
-          else if constexpr (tap <= 5) issue_x(cc + 1, tap + 1, tap + 2);
-        }
-#endif
-        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);       // (the slot of the LDS-DMA in the order that lost)
         if (!(abl & 1)) {
 #pragma unroll
         for (int j = 1; j < TM / 2; ++j)
@@ -834,8 +805,6 @@ bool dc_conv3_thin_applicable(const IgemmArgs& a, int dtype) {
   return a.C0 % bke == 0 && a.C1 % bke == 0;
 }
 
-static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
 // true when the halo kernel can take this problem (3x3 stride 1, pow-2 extents >= 8, no activation / gate)
 bool dc_conv3_halo_applicable(const IgemmArgs& a, int dtype) {
   // plain convolutions only (bias / per-sample row vector / residual): the 128-accumulator wave tile leaves room for ONE
@@ -851,142 +820,6 @@ bool dc_conv3_halo_applicable(const IgemmArgs& a, int dtype) {
   return true;
 }
 
-template <typename T, int NW>
-static int launch_halo(const IgemmArgs& a0, int n_img, hipStream_t s, bool up4 = false) {
-  using Cfg = HaloCfg<NW>;
-  static bool attr_done_v[2] = {false, false};
-  bool& attr_done = attr_done_v[up4 ? 1 : 0];
-  void (*kern)(const IgemmArgs, const HaloGeom) = up4 ? conv3_halo_kernel<T, NW, 4> : conv3_halo_kernel<T, NW>;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_halo_kernel<T, NW, 9, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_halo_kernel<T, NW, 4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    if constexpr (NW == 8) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_halo_kernel<T, NW, 9, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_halo_kernel<T, NW, 4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    }
-    attr_done = true;
-  }
-  IgemmArgs a = a0;
-  HaloGeom g;
-  g.H = a.Hin; g.W = a.Win; g.n_img = n_img;
-  const int tw = g.W < 32 ? g.W : 32;
-  int th = Cfg::PIX / tw; if (th > g.H) th = g.H;
-  const int ni = Cfg::PIX / (tw * th);
-  g.ltw = ilog2(tw); g.lth = ilog2(th); g.lni = ilog2(ni);
-  g.tiles_x = g.W / tw; g.tiles_y = g.H / th;
-  g.hw = tw + 2; g.hp = (th + 2) * g.hw; g.HR = ni * g.hp;
-  g.mos = 0; g.lmc = 0; g.inv_ch = g.inv_cw = 0.f;
-  if (g.H < 8 || g.W < 8) {            // whole small images: mosaic with shared zero borders (only the 512-pixel patch takes them)
-    if (NW != 8 || tw != g.W || th != g.H || ni < 2) { dc_set_error("conv3_halo: %dx%d images need the 8-wave patch", g.H, g.W); return DC_ERR_SHAPE; }
-    g.mos = 1;
-    g.lmc = (g.lni + 1) / 2;           // columns >= rows: 32 images -> 8 x 4
-    const int cols = 1 << g.lmc, rows = ni >> g.lmc;
-    g.hw = cols * (tw + 1) + 1;
-    g.hp = 0;
-    g.HR = (rows * (th + 1) + 1) * g.hw;
-    g.inv_ch = 1.0f / (float)(th + 1); g.inv_cw = 1.0f / (float)(tw + 1);
-  }
-  g.inv_hp = g.hp ? 1.0f / (float)g.hp : 0.f; g.inv_hw = 1.0f / (float)g.hw;
-  g.sws = (g.ltw < 4 ? g.ltw : 4) - 2;     // tw >= 16: 2, 8: 1, 4 (mosaic): 0
-  g.lpt = ilog2(g.tiles_x * g.tiles_y);
-  {
-    const long long hws = (long long)(a.upsample ? (g.H >> 1) * (g.W >> 1) : g.H * g.W);
-    const long long ldmax = a.ld0 > a.ld1 ? (a.ld0 > a.ld2 ? a.ld0 : a.ld2) : (a.ld1 > a.ld2 ? a.ld1 : a.ld2);
-    g.xbuf = (ni == 1 && !g.mos && hws * ldmax * (long long)sizeof(T) < (1LL << 31) &&
-              (long long)a.tiles_n * 128 * a.Ktot * (long long)sizeof(T) < (1LL << 31)) ? 1 : 0;
-  }
-  if ((long long)a.tiles_n * 128 * a.Ktot >= (1LL << 31)) { dc_set_error("conv3_halo: weight matrix of %d x %d too large", a.tiles_n * 128, a.Ktot); return DC_ERR_SHAPE; }
-  g.nxl = (g.HR * 4 + Cfg::NT - 1) / Cfg::NT;
-  if (g.HR > Cfg::XROWS || g.nxl > Cfg::NXL || g.nxl < 3) { dc_set_error("conv3_halo: halo of %d rows does not fit", g.HR); return DC_ERR_SHAPE; }
-  a.tiles_m = ((n_img + ni - 1) / ni) * g.tiles_x * g.tiles_y;
-  const long long nblk = (long long)a.tiles_m * a.tiles_n;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) { dc_set_error("conv3_halo: bad grid %lld", nblk); return DC_ERR_SHAPE; }
-  if (g.xbuf) kern = up4 ? conv3_halo_kernel<T, NW, 4, 1> : conv3_halo_kernel<T, NW, 9, 1>;
-  bool pn_local = false;
-  if (a.pn_out) {
-    // producer-side GroupNorm: images that span workgroups -> the one-image-per-patch form with the exchange of epi_pn.h; 8x8 images ->
-    // the staggered 8-wave kernel, every image inside one wave; dc_conv3_halo_pn_ok said so, this is the launch-time proof
-    if constexpr (NW == 4) {
-      if (!g.xbuf || ni != 1) { dc_set_error("conv3_halo: producer-side GroupNorm needs the one-image-per-patch form"); return DC_ERR_SHAPE; }
-      static bool pn_attr[2] = {false, false};
-      kern = up4 ? conv3_halo_kernel<T, 4, 4, 1, false, true> : conv3_halo_kernel<T, 4, 9, 1, false, true>;
-      if (!pn_attr[up4 ? 1 : 0]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS); pn_attr[up4 ? 1 : 0] = true; }
-    } else {
-      const bool i8 = !g.mos && !g.xbuf && g.H == 8 && g.W == 8 && ni == 8, i4 = g.mos && g.H == 4 && g.W == 4 && ni == 32;
-      if (up4 || !(i8 || i4)) { dc_set_error("conv3_halo: producer-side GroupNorm on the 8-wave patch needs 8x8 or 4x4 images"); return DC_ERR_SHAPE; }
-      pn_local = true;
-    }
-  }
-  if constexpr (NW == 8) {
-    if (g.mos) kern = up4 ? conv3_halo_kernel<T, NW, 4, 2> : conv3_halo_kernel<T, NW, 9, 2>;
-    // staggered wave groups (STG) unless DCAMD_HALO_NO_STAG (read per call: A/B runs in one process)
-    // (the four-tap upsample form stays on the lock-step loop: its whole next halo would ride in one MFMA block — measured slower)
-    if (!up4 && !getenv("DCAMD_HALO_NO_STAG") && (long long)a.tiles_n * 128 * a.Ktot * (long long)sizeof(T) < (1LL << 31)) {
-      const int mode = pn_local ? (g.mos ? 4 : 3) : (g.mos ? 2 : (g.xbuf ? 1 : 0));
-      static bool stg_attr[5] = {false, false, false, false, false};
-      switch (mode) {
-        case 4: kern = conv3_halo_kernel<T, NW, 9, 2, true, true>; break;
-        case 3: kern = conv3_halo_kernel<T, NW, 9, 0, true, true>; break;
-        case 0: kern = conv3_halo_kernel<T, NW, 9, 0, true>; break;
-        case 1: kern = conv3_halo_kernel<T, NW, 9, 1, true>; break;
-        default: kern = conv3_halo_kernel<T, NW, 9, 2, true>; break;
-      }
-      if (!stg_attr[mode]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-        stg_attr[mode] = true;
-      }
-    }
-  }
-  if constexpr (NW == 8) {
-    if (pn_local && kern != conv3_halo_kernel<T, 8, 9, 0, true, true> && kern != conv3_halo_kernel<T, 8, 9, 2, true, true>) { dc_set_error("conv3_halo: producer-side GroupNorm on 8x8 images needs the staggered loop"); return DC_ERR_SHAPE; }
-  }
-  long long grid = nblk;
-  if (a.pn_out && !pn_local) {          // whole groups of 2^lpt workgroups, a multiple of 8 of them (PN block order, see the kernel)
-    const long long groups = (long long)n_img * (up4 ? a.tiles_n >> 2 : a.tiles_n);
-    grid = ((groups + 7) / 8 * 8) << (g.lpt + (up4 ? 2 : 0));
-    if (grid > 0x7fffffffLL) { dc_set_error("conv3_halo: bad grid %lld", grid); return DC_ERR_SHAPE; }
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(Cfg::NT), Cfg::LDS, s, a, g);
-  return dc_check_launch("dc_igemm(conv3_halo)");
-}
-
-// producer-side GroupNorm (epi_pn.h): the conv must be the 4-wave one-image-per-patch form (power-of-two images of 16x16 ... 64x64: at
-// most 16 workgroups and 32 quad-record parts per sample), Cout a multiple of 128 whose GroupNorm groups are 4 ... 32 channels wide
-// (a group never leaves a wave's 64 channels); output (raw and normalised) in the compute type
-constexpr int PN_MAX_TILES = 16;
-bool dc_conv3_halo_pn_ok(const IgemmArgs& a, int dtype, bool up4) {
-  static const bool off = getenv("DCAMD_NO_PN") != nullptr;
-  if (off || a.src1) return false;
-  if (!up4 && ((a.Hin == 8 && a.Win == 8) || (a.Hin == 4 && a.Win == 4 && !getenv("DCAMD_NO_MOSAIC")))) {
-    // 8x8 / 4x4 images: the staggered 8-wave kernel, every image inside one wave, the statistics never leave it (EpiPnLocal8x8 / 4x4)
-    if (a.upsample || !dc_conv3_halo_applicable(a, dtype) || getenv("DCAMD_HALO_NO_STAG")) return false;
-    if (a.Cout % 128 || a.pn_groups <= 0 || a.Cout % a.pn_groups) return false;
-    const int cpg8 = a.Cout / a.pn_groups;
-    if (cpg8 != 4 && cpg8 != 8 && cpg8 != 16 && cpg8 != 32) return false;
-    return (long long)a.tiles_n * 128 * a.Ktot * dc_dtype_size(dtype) < (1LL << 31);
-  }
-  // four-phase upsample conv: the kernel walks the low-resolution image, and the four phases of every tile share the output sample
-  if (up4 ? !(a.upsample && dc_conv3_up4_applicable(a, dtype)) : (a.upsample || !dc_conv3_halo_applicable(a, dtype))) return false;
-  const int H = up4 ? a.Hin >> 1 : a.Hin, W = up4 ? a.Win >> 1 : a.Win;
-  if (H < 16 || W < 16 || H * W < 256 || ((H * W) / 256) * (up4 ? 4 : 1) > PN_MAX_TILES) return false;
-  if (a.Cout % 128 || a.pn_groups <= 0 || a.Cout % a.pn_groups) return false;
-  const int cpg = a.Cout / a.pn_groups;
-  if (cpg != 4 && cpg != 8 && cpg != 16 && cpg != 32) return false;
-  const long long es = dc_dtype_size(dtype);
-  const long long ldmax = a.ld0 > a.ld2 ? a.ld0 : a.ld2;
-  if ((long long)H * W * ldmax * es >= (1LL << 31)) return false;                       // buffer-descriptor loaders (HaloGeom::xbuf)
-  if ((long long)a.tiles_n * 128 * a.Ktot * es >= (1LL << 31)) return false;
-  return true;
-}
-
-unsigned dc_conv3_halo_pn_timeouts() {
-  unsigned v = 0, z = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_pn_timeouts), sizeof(v)) != hipSuccess) return ~0u;
-  if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pn_timeouts), &z, sizeof(z));
-  return v;
-}
-
 // "nearest-2x upsample, then 3x3 conv" as four 2x2-tap phases on the low-resolution image (a.W: the phase-summed weights
 // [4][Cout_pad][4 * C], see dc_igemm_params.up4): 4/9 of the MACs
 bool dc_conv3_up4_applicable(const IgemmArgs& a, int dtype) {
@@ -996,29 +829,154 @@ bool dc_conv3_up4_applicable(const IgemmArgs& a, int dtype) {
   return dc_conv3_halo_applicable(lo, dtype);
 }
 
-// a: the extents the kernel walks (8 or 4 waves by them)
-static int launch_halo_by_dtype(const IgemmArgs& a, int dtype, int n_img, hipStream_t s, bool up4) {
-  const bool w8 = dc_conv3_halo_waves(a.Hin, a.Win) == 8;
-  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) {
-    return w8 ? launch_halo<decltype(t), 8>(a, n_img, s, up4) : launch_halo<decltype(t), 4>(a, n_img, s, up4);
-  });
-}
-
-int dc_conv3_up4_launch(const IgemmArgs& a0, int dtype, int n_img, hipStream_t s) {
+IgemmArgs dc_conv3_up4_walked(const IgemmArgs& a0) {
   IgemmArgs a = a0;
   a.upsample = 0; a.Hin = a0.Hin >> 1; a.Win = a0.Win >> 1;      // the kernel walks the LOW-resolution image
   a.Ktot = 4 * (a.C0 + a.C1);
   a.tiles_n = 4 * a0.tiles_n;                                    // phase-major N tiles
   a.n_fast = 0;
-  return launch_halo_by_dtype(a, dtype, n_img, s, true);
+  return a;
 }
 
-int dc_conv3_halo_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) { return launch_halo_by_dtype(a, dtype, n_img, s, false); }
+// The one place that decides the patch, xbuf, the mosaic, the staggered loop and the producer-side GroupNorm form of a conv3_halo /
+// conv3_up4 launch.  a: the extents the kernel walks (8 or 4 waves by them)
+HaloPlan dc_conv3_halo_plan(const IgemmArgs& a, int dtype, int n_img, bool up4) {
+  HaloPlan pl;
+  HaloGeom& g = pl.g;
+  const int NW = dc_conv3_halo_waves(a.Hin, a.Win);
+  HaloKey& k = pl.key;
+  k = HaloKey{NW, up4 ? 4 : 9, 0, false, false};
+  const bool fits = halo_geom(g, a.Hin, a.Win, n_img, NW * 64, NW * 64, NW == 4 ? HaloCfg<4>::NXL : HaloCfg<8>::NXL, NW == 8);
+  const int ni = 1 << g.lni;
+  // whole small images: only the 512-pixel patch takes them, as a mosaic
+  if ((g.H < 8 || g.W < 8) && !g.mos) return halo_plan_fail(pl, "conv3_halo: %dx%d images need the 8-wave patch", g.H, g.W);
+  g.sws = (g.ltw < 4 ? g.ltw : 4) - 2;     // tw >= 16: 2, 8: 1, 4 (mosaic): 0
+  const long long es = dc_dtype_size(dtype);
+  g.xbuf = (ni == 1 && !g.mos && halo_xbuf_reach(a, dtype)) ? 1 : 0;
+  k.MODE = g.mos ? 2 : (g.xbuf ? 1 : 0);
+  if ((long long)a.tiles_n * 128 * a.Ktot >= (1LL << 31)) return halo_plan_fail(pl, "conv3_halo: weight matrix of %d x %d too large", a.tiles_n * 128, a.Ktot);
+  if (!fits || g.nxl < 3) return halo_plan_fail(pl, "conv3_halo: halo of %d rows does not fit", g.HR);
+  pl.tiles_m = ((n_img + ni - 1) / ni) * g.tiles_x * g.tiles_y;
+  long long grid = (long long)pl.tiles_m * a.tiles_n;
+  if (grid <= 0 || grid > 0x7fffffffLL) return halo_plan_fail(pl, "conv3_halo: bad grid %lld", grid);
+  // staggered wave groups (STG) on the 8-wave patch unless DCAMD_HALO_NO_STAG (read per call: A/B runs in one process)
+  // (the four-tap upsample form stays on the lock-step loop: its whole next halo would ride in one MFMA block — measured slower)
+  k.STG = NW == 8 && !up4 && !getenv("DCAMD_HALO_NO_STAG") && (long long)a.tiles_n * 128 * a.Ktot * es < (1LL << 31);
+  if (a.pn_out) {
+    // producer-side GroupNorm: images that span workgroups -> the one-image-per-patch form with the exchange of epi_pn.h; 8x8 / 4x4
+    // images -> the staggered 8-wave kernel, every image inside one wave
+    if (NW == 4) {
+      if (!g.xbuf || ni != 1) return halo_plan_fail(pl, "conv3_halo: producer-side GroupNorm needs the one-image-per-patch form");
+      // whole groups of 2^lpt workgroups, a multiple of 8 of them (PN block order, see the kernel)
+      const long long groups = (long long)n_img * (up4 ? a.tiles_n >> 2 : a.tiles_n);
+      grid = ((groups + 7) / 8 * 8) << (g.lpt + (up4 ? 2 : 0));
+      if (grid > 0x7fffffffLL) return halo_plan_fail(pl, "conv3_halo: bad grid %lld", grid);
+    } else {
+      const bool i8 = !g.mos && !g.xbuf && g.H == 8 && g.W == 8 && ni == 8, i4 = g.mos && g.H == 4 && g.W == 4 && ni == 32;
+      if (up4 || !(i8 || i4)) return halo_plan_fail(pl, "conv3_halo: producer-side GroupNorm on the 8-wave patch needs 8x8 or 4x4 images");
+      if (!k.STG) return halo_plan_fail(pl, "conv3_halo: producer-side GroupNorm on 8x8 images needs the staggered loop");
+    }
+    k.PN = true;
+  }
+  pl.grid = (unsigned)grid;
+  return pl;
+}
+
+using HaloKern = void (*)(const IgemmArgs, const HaloGeom);
+
+// one instance; its first use raises its dynamic-LDS limit
+template <typename T, int NW, int NTAP, int MODE, bool STG = false, bool PN = false>
+static HaloKern halo_instance() {
+  static bool attr_done = false;
+  const HaloKern kern = conv3_halo_kernel<T, NW, NTAP, MODE, STG, PN>;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, HaloCfg<NW>::LDS);
+    attr_done = true;
+  }
+  return kern;
+}
+
+// key -> kernel: the 17 instances per dtype that exist (nullptr: none)
+template <typename T>
+static HaloKern halo_kernel(const HaloKey& k) {
+  auto is = [&](int nw, int ntap, int mode, bool stg = false, bool pn = false) {
+    return k.NW == nw && k.NTAP == ntap && k.MODE == mode && k.STG == stg && k.PN == pn;
+  };
+  if (is(8, 4, 0)) return halo_instance<T, 8, 4, 0>();
+  if (is(8, 9, 0)) return halo_instance<T, 8, 9, 0>();
+  if (is(8, 9, 1)) return halo_instance<T, 8, 9, 1>();
+  if (is(8, 4, 1)) return halo_instance<T, 8, 4, 1>();
+  if (is(8, 9, 2)) return halo_instance<T, 8, 9, 2>();
+  if (is(8, 4, 2)) return halo_instance<T, 8, 4, 2>();
+  if (is(8, 9, 2, true, true)) return halo_instance<T, 8, 9, 2, true, true>();
+  if (is(8, 9, 0, true, true)) return halo_instance<T, 8, 9, 0, true, true>();
+  if (is(8, 9, 0, true)) return halo_instance<T, 8, 9, 0, true>();
+  if (is(8, 9, 1, true)) return halo_instance<T, 8, 9, 1, true>();
+  if (is(8, 9, 2, true)) return halo_instance<T, 8, 9, 2, true>();
+  if (is(4, 4, 0)) return halo_instance<T, 4, 4, 0>();
+  if (is(4, 9, 0)) return halo_instance<T, 4, 9, 0>();
+  if (is(4, 9, 1)) return halo_instance<T, 4, 9, 1>();
+  if (is(4, 4, 1)) return halo_instance<T, 4, 4, 1>();
+  if (is(4, 4, 1, false, true)) return halo_instance<T, 4, 4, 1, false, true>();
+  if (is(4, 9, 1, false, true)) return halo_instance<T, 4, 9, 1, false, true>();
+  return nullptr;
+}
+
+// a0: as dc_igemm filled it; pl: dc_conv3_halo_plan of the extents the kernel walks
+int dc_conv3_halo_launch(const HaloPlan& pl, const IgemmArgs& a0, int dtype, bool up4, hipStream_t s) {
+  if (pl.status != DC_OK) { dc_set_error("%s", pl.message); return pl.status; }
+  IgemmArgs a = up4 ? dc_conv3_up4_walked(a0) : a0;
+  a.tiles_m = pl.tiles_m;
+  const HaloKey& k = pl.key;
+  HaloKern kern = nullptr;
+  const int rc = dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { kern = halo_kernel<decltype(t)>(k); return (int)DC_OK; });
+  if (rc != DC_OK) return rc;
+  if (!kern) { dc_set_error("conv3_halo: no instance <%d,%d,%d,%d,%d>", k.NW, k.NTAP, k.MODE, (int)k.STG, (int)k.PN); return DC_ERR_UNSUPPORTED; }
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(k.NW * 64), k.NW == 4 ? HaloCfg<4>::LDS : HaloCfg<8>::LDS, s, a, pl.g);
+  return dc_check_launch("dc_igemm(conv3_halo)");
+}
+
+// producer-side GroupNorm (epi_pn.h): the plan has a PN form for the problem (the 4-wave one-image-per-patch form, power-of-two images
+// of 16x16 ... 64x64; or 8x8 / 4x4 images on the staggered 8-wave kernel), and on the producer's side: at most 16 workgroups (and 32
+// quad-record parts) per sample, no second source, Cout a multiple of 128 whose GroupNorm groups are 4 ... 32 channels wide (a group never
+// leaves a wave's 64 channels); output (raw and normalised) in the compute type.  a: an applicable problem with pn_out, as dc_igemm
+// filled it; pl: its plan
+constexpr int PN_MAX_TILES = 16;
+bool dc_conv3_halo_pn_ok(const IgemmArgs& a, const HaloPlan& pl, bool up4) {
+  static const bool off = getenv("DCAMD_NO_PN") != nullptr;
+  if (off || a.src1 || (!up4 && a.upsample)) return false;
+  if (pl.status != DC_OK || !pl.key.PN) return false;
+  // (four-phase upsample conv: the four phases of every tile share the output sample)
+  if (((1 << pl.g.lpt) << (up4 ? 2 : 0)) > PN_MAX_TILES) return false;
+  if (a.Cout % 128 || a.pn_groups <= 0 || a.Cout % a.pn_groups) return false;
+  const int cpg = a.Cout / a.pn_groups;
+  return cpg == 4 || cpg == 8 || cpg == 16 || cpg == 32;
+}
+
+unsigned dc_conv3_halo_pn_timeouts() {
+  unsigned v = 0, z = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_pn_timeouts), sizeof(v)) != hipSuccess) return ~0u;
+  if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pn_timeouts), &z, sizeof(z));
+  return v;
+}
+
+HaloPlan dc_conv3_thin_plan(const IgemmArgs& a, int n_img) {
+  HaloPlan pl;
+  pl.key = HaloKey{4, 9, 0, false, false};
+  HaloGeom& g = pl.g;        // xbuf = sws = 0: the thin kernel keeps its own un-swizzled image
+  if (!halo_geom(g, a.Hin, a.Win, n_img, 256, ThinCfg::NT, ThinCfg::NXL, false)) return halo_plan_fail(pl, "conv3_thin: halo of %d rows does not fit", g.HR);
+  const int ni = 1 << g.lni;
+  const long long nblk = (long long)((n_img + ni - 1) / ni) * g.tiles_x * g.tiles_y;
+  if (nblk <= 0 || nblk > 0x7fffffffLL) return halo_plan_fail(pl, "conv3_thin: bad grid %lld", nblk);
+  if (a.gn_scale && ni != 1) return halo_plan_fail(pl, "conv3_thin: the fused GroupNorm needs one sample per patch");
+  pl.tiles_m = (int)nblk; pl.grid = (unsigned)nblk;
+  return pl;
+}
 
 template <typename T>
-static int launch_thin(const IgemmArgs& a0, int n_img, hipStream_t s) {
+static int launch_thin(const HaloPlan& pl, const IgemmArgs& a, hipStream_t s) {
   static bool attr_done = false;
-  const bool gn = a0.gn_scale != nullptr;
+  const bool gn = a.gn_scale != nullptr;
   void (*kern)(const IgemmArgs, const HaloGeom) = gn ? conv3_thin_kernel<T, true> : conv3_thin_kernel<T, false>;
   const int lds = gn ? ThinCfg::LDS_GN : ThinCfg::LDS;
   if (!attr_done) {
@@ -1026,26 +984,12 @@ static int launch_thin(const IgemmArgs& a0, int n_img, hipStream_t s) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_thin_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ThinCfg::LDS_GN);
     attr_done = true;
   }
-  IgemmArgs a = a0;
-  HaloGeom g;
-  g.H = a.Hin; g.W = a.Win; g.n_img = n_img;
-  const int tw = g.W < 32 ? g.W : 32;
-  int th = 256 / tw; if (th > g.H) th = g.H;
-  const int ni = 256 / (tw * th);
-  g.ltw = ilog2(tw); g.lth = ilog2(th); g.lni = ilog2(ni);
-  g.tiles_x = g.W / tw; g.tiles_y = g.H / th;
-  g.hw = tw + 2; g.hp = (th + 2) * g.hw; g.HR = ni * g.hp;
-  g.mos = 0; g.lmc = 0; g.inv_ch = g.inv_cw = 0.f; g.xbuf = 0; g.sws = 0;     // (the thin kernel keeps its own un-swizzled image)
-  g.inv_hp = 1.0f / (float)g.hp; g.inv_hw = 1.0f / (float)g.hw;
-  g.nxl = (g.HR * 4 + ThinCfg::NT - 1) / ThinCfg::NT;
-  if (g.nxl > ThinCfg::NXL) { dc_set_error("conv3_thin: halo of %d rows does not fit", g.HR); return DC_ERR_SHAPE; }
-  const long long nblk = (long long)((n_img + ni - 1) / ni) * g.tiles_x * g.tiles_y;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) { dc_set_error("conv3_thin: bad grid %lld", nblk); return DC_ERR_SHAPE; }
-  if (gn && ni != 1) { dc_set_error("conv3_thin: the fused GroupNorm needs one sample per patch"); return DC_ERR_SHAPE; }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(ThinCfg::NT), lds, s, a, g);
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(ThinCfg::NT), lds, s, a, pl.g);
   return dc_check_launch("dc_igemm(conv3_thin)");
 }
 
 int dc_conv3_thin_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) {
-  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_thin<decltype(t)>(a, n_img, s); });
+  const HaloPlan pl = dc_conv3_thin_plan(a, n_img);
+  if (pl.status != DC_OK) { dc_set_error("%s", pl.message); return pl.status; }
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_thin<decltype(t)>(pl, a, s); });
 }

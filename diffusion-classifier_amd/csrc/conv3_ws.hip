@@ -44,7 +44,7 @@ extern "C" void dc_debug_set_ws_abl(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(
 #define DC_WAIT_ADD(sum) do {} while (0)
 #define DC_STAMP_VAL(k, v) do {} while (0)
 #endif
-#include "conv3_halo.h"
+#include "conv3_halo_plan.h"
 DC_CLOCK_DECL(conv3_ws)
 
 struct WsCfg {
@@ -368,30 +368,35 @@ __global__ __launch_bounds__(512, 2) void conv3_ws_kernel(const IgemmArgs a, con
 #endif
 }
 
-static int ws_ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
 // true when the wave-specialised kernel can take this problem: what conv3_halo's one-image-per-patch / buffer-descriptor form takes
 // (3x3 stride 1, power-of-two images of at least 256 pixels and 16 columns, every source sample below 2 GiB), affine table within its slot
 bool dc_conv3_ws_ok(const IgemmArgs& a, int dtype) {
   static const bool off = getenv("DCAMD_NO_WS") != nullptr;
   if (off || !dc_conv3_halo_applicable(a, dtype) || a.upsample) return false;
-  const int H = a.Hin, W = a.Win;
-  if (H < 8 || W < 16 || H * W < 256) return false;
-  const int tw = W < 32 ? W : 32;
-  const int th = 256 / tw;
-  if (th > H) return false;
-  const int hr = (th + 2) * (tw + 2);
-  if ((hr * 4 + WsCfg::NTL - 1) / WsCfg::NTL > WsCfg::NXL) return false;
+  HaloGeom g;
+  if (!halo_geom(g, a.Hin, a.Win, 1, 256, WsCfg::NTL, WsCfg::NXL, false)) return false;
+  if (a.Win < 16 || g.lni != 0) return false;           // fragments of 16 pixels in a row, one image per (full) patch
   if (a.gn_scale && a.C0 + a.C1 > WsCfg::GNMAXC) return false;
-  const long long es = dc_dtype_size(dtype);
-  const long long ldmax = a.ld0 > a.ld1 ? (a.ld0 > a.ld2 ? a.ld0 : a.ld2) : (a.ld1 > a.ld2 ? a.ld1 : a.ld2);
-  if ((long long)H * W * ldmax * es >= (1LL << 31)) return false;
-  if ((long long)a.tiles_n * 128 * a.Ktot * es >= (1LL << 31)) return false;
-  return true;
+  return halo_xbuf_reach(a, dtype);
+}
+
+HaloPlan dc_conv3_ws_plan(const IgemmArgs& a, int n_img) {
+  HaloPlan pl;
+  pl.key = HaloKey{8, 9, 1, false, false};
+  HaloGeom& g = pl.g;
+  const bool fits = halo_geom(g, a.Hin, a.Win, n_img, 256, WsCfg::NTL, WsCfg::NXL, false);
+  g.xbuf = 1;
+  g.sws = 2;          // fragments of 16 pixels in a row (tw >= 16)
+  if (!fits || g.nxl < 3) return halo_plan_fail(pl, "conv3_ws: halo of %d rows does not fit", g.HR);
+  pl.tiles_m = n_img * g.tiles_x * g.tiles_y;
+  const long long nblk = (long long)pl.tiles_m * a.tiles_n;
+  if (nblk <= 0 || nblk > 0x7fffffffLL) return halo_plan_fail(pl, "conv3_ws: bad grid %lld", nblk);
+  pl.grid = (unsigned)nblk;
+  return pl;
 }
 
 template <typename T>
-static int launch_ws(const IgemmArgs& a0, int n_img, hipStream_t s) {
+static int launch_ws(const HaloPlan& pl, const IgemmArgs& a0, hipStream_t s) {
   using Cfg = WsCfg;
   static bool attr_done = false;
   if (!attr_done) {
@@ -400,25 +405,14 @@ static int launch_ws(const IgemmArgs& a0, int n_img, hipStream_t s) {
     attr_done = true;
   }
   IgemmArgs a = a0;
-  HaloGeom g;
-  g.H = a.Hin; g.W = a.Win; g.n_img = n_img;
-  const int tw = g.W < 32 ? g.W : 32, th = 256 / tw;
-  g.ltw = ws_ilog2(tw); g.lth = ws_ilog2(th); g.lni = 0;
-  g.tiles_x = g.W / tw; g.tiles_y = g.H / th;
-  g.hw = tw + 2; g.hp = (th + 2) * g.hw; g.HR = g.hp;
-  g.mos = 0; g.lmc = 0; g.inv_ch = g.inv_cw = 0.f; g.xbuf = 1;
-  g.sws = 2;          // fragments of 16 pixels in a row (tw >= 16)
-  g.inv_hp = 1.0f / (float)g.hp; g.inv_hw = 1.0f / (float)g.hw;
-  g.nxl = (g.HR * 4 + Cfg::NTL - 1) / Cfg::NTL;
-  if (g.nxl > Cfg::NXL || g.nxl < 3) { dc_set_error("conv3_ws: halo of %d rows does not fit", g.HR); return DC_ERR_SHAPE; }
-  a.tiles_m = n_img * g.tiles_x * g.tiles_y;
-  const long long nblk = (long long)a.tiles_m * a.tiles_n;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) { dc_set_error("conv3_ws: bad grid %lld", nblk); return DC_ERR_SHAPE; }
+  a.tiles_m = pl.tiles_m;
   void (*kern)(const IgemmArgs, const HaloGeom) = a.gn_scale ? conv3_ws_kernel<T, true> : conv3_ws_kernel<T, false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(Cfg::NT), Cfg::LDS, s, a, g);
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(Cfg::NT), Cfg::LDS, s, a, pl.g);
   return dc_check_launch("dc_igemm(conv3_ws)");
 }
 
 int dc_conv3_ws_launch(const IgemmArgs& a, int dtype, int n_img, hipStream_t s) {
-  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_ws<decltype(t)>(a, n_img, s); });
+  const HaloPlan pl = dc_conv3_ws_plan(a, n_img);
+  if (pl.status != DC_OK) { dc_set_error("%s", pl.message); return pl.status; }
+  return dc_by_dtype(dtype, "dc_igemm: dtype", [&](auto t) { return launch_ws<decltype(t)>(pl, a, s); });
 }

@@ -22,7 +22,7 @@
 // same weight panel.
 #include <stdio.h>
 #include <stdlib.h>
-#include "conv3_halo.h"
+#include "conv3_halo_plan.h"
 
 template <typename T, int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
@@ -161,8 +161,8 @@ extern "C" int32_t dc_igemm_cout_pad(int32_t cout, int32_t tile_n) {
 }
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------------------------
-// dc_igemm, dc_igemm_variant and the dc_igemm_*_ok probes all go the same way: igemm_validate_and_fill, then igemm_choose — the one
-// place that picks a kernel or refuses — and then igemm_launch, igemm_name or a look at the choice.
+// dc_igemm, dc_igemm_variant, dc_igemm_instance and the dc_igemm_*_ok probes all go the same way: igemm_validate_and_fill, then
+// igemm_choose — the one place that picks a kernel or refuses — and then igemm_launch, igemm_name or a look at the choice.
 
 static int igemm_validate_and_fill(const dc_igemm_params* p, IgemmArgs& a) {
   DC_REQUIRE(p, DC_ERR_ARG, "dc_igemm: null params");
@@ -239,18 +239,19 @@ enum IgemmKernel { IG_THIN, IG_WS, IG_HALO, IG_UP4_HALO, IG_UP4_PIPE, IG_XREG, I
 // What dc_igemm does with a valid problem: the kernel, or (status != DC_OK) the opted-in feature it cannot serve
 struct IgemmChoice {
   IgemmKernel kernel = IG_REG32;
-  int waves = 0;                   // IG_HALO / IG_UP4_HALO: dc_conv3_halo_waves of the extents the kernel walks
   int shape = 0;                   // IG_PIPE: dc_igemm_pipe_shape
   bool gn = false, pn = false;     // IG_WS: GroupNorm prologue; IG_HALO / IG_UP4_HALO: producer-side GroupNorm
   int status = DC_OK;
   const char* tag = nullptr;       // refusal: what dc_igemm_variant reports ...
   const char* message = nullptr;   // ... and what dc_last_error reports after dc_igemm
+  HaloPlan halo;                   // IG_HALO / IG_UP4_HALO: the launch (a plan that failed is the launch's error, not a refusal)
 };
 
 // the caller opted in to a feature (src2, gn_scale, qstats, pn_out, up4, ln_eps), so a problem that cannot take it is an error
-static IgemmChoice refuse(const char* tag, const char* message) { return IgemmChoice{IG_REG32, 0, 0, false, false, DC_ERR_UNSUPPORTED, tag, message}; }
+static IgemmChoice refuse(const char* tag, const char* message) { return IgemmChoice{IG_REG32, 0, false, false, DC_ERR_UNSUPPORTED, tag, message}; }
 
-// p, a: after igemm_validate_and_fill.  No launch, no formatting, no dc_set_error: dc_run_plan comes through here for every op of every step
+// p, a: after igemm_validate_and_fill.  No launch, no formatting (but the message of a halo plan that failed), no dc_set_error: dc_run_plan
+// comes through here for every op of every step
 static IgemmChoice igemm_choose(const dc_igemm_params* p, const IgemmArgs& a) {
   const int dt = p->dtype, bn = p->tile_n, epc = 16 / dc_dtype_size(dt);
   const int cout_out = p->act == DC_ACT_GEGLU ? p->Cout / 2 : p->Cout;
@@ -280,12 +281,13 @@ static IgemmChoice igemm_choose(const dc_igemm_params* p, const IgemmArgs& a) {
     const bool up4_pipe = !up4_halo && lds_dma && !a.src1 && !a.qstats && p->taps == 9 && p->stride == 1 &&
                           p->upsample && p->act == DC_ACT_NONE && !p->gate && !p->residual && !a.gn_scale && !a.src2 &&
                           p->Hin >= 4 && p->Win >= 4 && p->Hin % 2 == 0 && p->Win % 2 == 0 && (p->Hin < 16 || p->Win < 16);
+    const HaloPlan plan = up4_halo ? dc_conv3_halo_plan(dc_conv3_up4_walked(a), dt, p->n_img, true) : HaloPlan{};
     // producer-side GroupNorm on the four-phase form: the 4-wave one-image-per-patch kernel only (sources of 16x16 and more)
-    if (use_pn && !(up4_halo && a.Hin > 16 && a.Win > 16 && dc_conv3_halo_pn_ok(a, dt, true) && a.qstats && pn_args_ok))
+    if (use_pn && !(up4_halo && a.Hin > 16 && a.Win > 16 && dc_conv3_halo_pn_ok(a, plan, true) && a.qstats && pn_args_ok))
       return refuse("producer-groupnorm-unsupported", "dc_igemm: pn_out given but this upsample conv cannot normalise its own output (see dc_igemm_pn_ok)");
     if (!up4_halo && !up4_pipe)
       return refuse("up4-unsupported", "dc_igemm: up4 given but this problem cannot take the four-phase upsample conv (see dc_igemm_up4_ok)");
-    if (up4_halo) return IgemmChoice{IG_UP4_HALO, dc_conv3_halo_waves(a.Hin >> 1, a.Win >> 1), 0, false, use_pn};
+    if (up4_halo) return IgemmChoice{IG_UP4_HALO, 0, false, use_pn, DC_OK, nullptr, nullptr, plan};
     return IgemmChoice{IG_UP4_PIPE};
   }
 
@@ -296,6 +298,8 @@ static IgemmChoice igemm_choose(const dc_igemm_params* p, const IgemmArgs& a) {
   static const bool ws_plain = getenv("DCAMD_WS_PLAIN") != nullptr;
   const bool ws_ok = halo_ok && dc_conv3_ws_ok(a, dt) && !thin_app;
   const bool use_ws = ws_ok && (a.gn_scale || ws_plain);
+  // the route of the plain halo conv, unless a refusal below
+  const HaloPlan plan = halo_ok && !thin && !use_ws ? dc_conv3_halo_plan(a, dt, p->n_img, false) : HaloPlan{};
   const int bke64 = 64 / dc_dtype_size(dt);
   if (a.src2 && !(halo_ok && (!a.gn_scale || ws_ok) && !a.upsample && a.W2 && a.C2 >= 2 * bke64 && a.C2 % bke64 == 0 && a.ld2 % epc == 0 &&
                   (((uintptr_t)a.src2 | (uintptr_t)a.W2) & 15) == 0))
@@ -304,7 +308,7 @@ static IgemmChoice igemm_choose(const dc_igemm_params* p, const IgemmArgs& a) {
     return refuse("gn-not-fusable", "dc_igemm: gn_scale/gn_shift given but this problem cannot take the fused GroupNorm prologue (see dc_igemm_gn_fusable)");
   if (a.qstats && !(halo_ok && !thin_app && qs_args_ok && a.Hin >= 8 && a.Win >= 8))      // mosaic patches (images below 8x8) emit none: a wave's half holds four images
     return refuse("qstats-unsupported", "dc_igemm: qstats given but this problem cannot emit quad statistics (see dc_igemm_qstats_parts)");
-  if (use_pn && !(halo_ok && !use_ws && !a.gn_scale && !thin_app && dc_conv3_halo_pn_ok(a, dt, false) &&
+  if (use_pn && !(halo_ok && !use_ws && !a.gn_scale && !thin_app && dc_conv3_halo_pn_ok(a, plan, false) &&
                   (a.qstats || (a.Hin == 4 && a.Win == 4)) && pn_args_ok))
     return refuse("producer-groupnorm-unsupported", "dc_igemm: pn_out given but this problem cannot normalise its own output (see dc_igemm_pn_ok)");
   const bool xreg_app = dc_igemm_xreg_applicable(a, dt);
@@ -312,14 +316,14 @@ static IgemmChoice igemm_choose(const dc_igemm_params* p, const IgemmArgs& a) {
     return refuse("row-layernorm-unsupported", "dc_igemm: ln_eps given but this problem cannot take the fused row LayerNorm (see dc_igemm_ln_ok)");
 
   if (thin) return IgemmChoice{IG_THIN};
-  if (use_ws) return IgemmChoice{IG_WS, 0, 0, a.gn_scale != nullptr};
-  if (halo_ok) return IgemmChoice{IG_HALO, dc_conv3_halo_waves(a.Hin, a.Win), 0, false, use_pn};
+  if (use_ws) return IgemmChoice{IG_WS, 0, a.gn_scale != nullptr};
+  if (halo_ok) return IgemmChoice{IG_HALO, 0, false, use_pn, DC_OK, nullptr, nullptr, plan};
   if (!lds_dma) return IgemmChoice{bn == 128 ? IG_REG128 : IG_REG32};
   // short-K GEMMs: the activation-stationary kernel wins for GEGLU (448 vs 376 TFLOP/s at K = 256, 584 vs 544 at K = 512);
   // for plain epilogues the 256x256 tile is faster where it applies (q/k/v 505-709 vs 478-556), xreg elsewhere
   const int shape = dc_igemm_pipe_shape(a);
   if (xreg_app && (p->act == DC_ACT_GEGLU || a.ln_eps > 0.f || shape != 2)) return IgemmChoice{IG_XREG};
-  return IgemmChoice{IG_PIPE, 0, shape};
+  return IgemmChoice{IG_PIPE, shape};
 }
 
 static const char* igemm_name(const IgemmChoice& c, int dtype) {
@@ -330,8 +334,8 @@ static const char* igemm_name(const IgemmChoice& c, int dtype) {
   switch (c.kernel) {
     case IG_THIN: snprintf(name, sizeof(name), "conv3_thin<%s>", dn); break;
     case IG_WS: snprintf(name, sizeof(name), c.gn ? "conv3_ws<%s,gn>" : "conv3_ws<%s>", dn); break;
-    case IG_HALO: snprintf(name, sizeof(name), c.pn ? "conv3_halo<%s,%dw,pn>" : "conv3_halo<%s,%dw>", dn, c.waves); break;
-    case IG_UP4_HALO: snprintf(name, sizeof(name), c.pn ? "conv3_up4<%s,%dw,pn>" : "conv3_up4<%s,%dw>", dn, c.waves); break;
+    case IG_HALO: snprintf(name, sizeof(name), c.pn ? "conv3_halo<%s,%dw,pn>" : "conv3_halo<%s,%dw>", dn, c.halo.key.NW); break;
+    case IG_UP4_HALO: snprintf(name, sizeof(name), c.pn ? "conv3_up4<%s,%dw,pn>" : "conv3_up4<%s,%dw>", dn, c.halo.key.NW); break;
     case IG_UP4_PIPE: snprintf(name, sizeof(name), "igemm_pipe_up4<%s,256x128,3st>", dn); break;
     case IG_XREG: snprintf(name, sizeof(name), "igemm_xreg<%s,96xN>", dn); break;
     case IG_PIPE: snprintf(name, sizeof(name), pipe_fmt[c.shape], dn); break;
@@ -346,8 +350,8 @@ static int igemm_launch(const IgemmChoice& c, const IgemmArgs& a, const dc_igemm
   switch (c.kernel) {
     case IG_THIN: return dc_conv3_thin_launch(a, p->dtype, p->n_img, s);
     case IG_WS: return dc_conv3_ws_launch(a, p->dtype, p->n_img, s);
-    case IG_HALO: return dc_conv3_halo_launch(a, p->dtype, p->n_img, s);
-    case IG_UP4_HALO: return dc_conv3_up4_launch(a, p->dtype, p->n_img, s);
+    case IG_HALO: return dc_conv3_halo_launch(c.halo, a, p->dtype, false, s);
+    case IG_UP4_HALO: return dc_conv3_halo_launch(c.halo, a, p->dtype, true, s);
     case IG_UP4_PIPE: return dc_igemm_launch_pipe_up4(a, p->dtype, s);
     case IG_XREG: return dc_igemm_xreg_launch(a, p->dtype, s);
     case IG_PIPE: return dc_igemm_launch_pipe(a, p->dtype, c.shape, s);
@@ -371,6 +375,29 @@ extern "C" const char* dc_igemm_variant(const dc_igemm_params* p) {
   if (igemm_validate_and_fill(p, a) != DC_OK) return "invalid";
   const IgemmChoice c = igemm_choose(p, a);
   return c.status == DC_OK ? igemm_name(c, p->dtype) : c.tag;
+}
+
+extern "C" const char* dc_igemm_instance(const dc_igemm_params* p, int32_t* geom) {
+  IgemmArgs a;
+  if (igemm_validate_and_fill(p, a) != DC_OK) return "invalid";
+  const IgemmChoice c = igemm_choose(p, a);
+  if (c.status != DC_OK) return c.tag;
+  static thread_local char name[64];
+  const char* dn = p->dtype == DC_BF16 ? "bf16" : (p->dtype == DC_F16 ? "f16" : "f32");
+  HaloPlan pl;
+  switch (c.kernel) {
+    case IG_HALO: case IG_UP4_HALO: {
+      pl = c.halo;
+      const HaloKey& k = pl.key;
+      snprintf(name, sizeof(name), "conv3_halo_kernel<%s,%d,%d,%d%s%s>", dn, k.NW, k.NTAP, k.MODE, k.STG ? ",stag" : "", k.PN ? ",pn" : "");
+      break;
+    }
+    case IG_THIN: pl = dc_conv3_thin_plan(a, p->n_img); snprintf(name, sizeof(name), "conv3_thin_kernel<%s,%s>", dn, a.gn_scale ? "gn" : "plain"); break;
+    case IG_WS: pl = dc_conv3_ws_plan(a, p->n_img); snprintf(name, sizeof(name), "conv3_ws_kernel<%s,%s>", dn, a.gn_scale ? "gn" : "plain"); break;
+    default: return igemm_name(c, p->dtype);
+  }
+  if (geom) halo_plan_ints(pl, geom);
+  return name;
 }
 
 // ---- probes: plant what the feature needs where the caller left it out, choose, test ---------------------------------------------

@@ -68,7 +68,7 @@ extern "C" {
  *  likewise)
  * (dc_ddpm_step_shared, dc_abs_diff_map and their structs likewise; both are called directly)
  * (dc_stage_stop and dc_stage_maps_rows likewise; both are called directly) */
-#define DC_ABI_VERSION 4
+#define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
 
@@ -183,6 +183,15 @@ int32_t dc_igemm_cout_pad(int32_t cout, int32_t tile_n);
 /* Name of the kernel dc_igemm would launch for these parameters, e.g. "conv3_halo<bf16,4w>",
  * "igemm_pipe<bf16,256x128,3st>" (measurement / profiling only; static string). */
 const char* dc_igemm_variant(const dc_igemm_params* p);
+/* The template instance behind that name (measurement / tests only; static string).  The three halo-tile 3x3 kernels:
+ * "conv3_halo_kernel<T,NW,NTAP,MODE[,stag][,pn]>" (NW waves; NTAP 9, or 4 for up4; MODE 0 per-lane addresses, 1 buffer-descriptor loaders,
+ * 2 mosaic of images below 8x8; stag: the staggered tap loop; pn: producer-side GroupNorm), "conv3_thin_kernel<T,gn|plain>",
+ * "conv3_ws_kernel<T,gn|plain>"; every other kernel, a refusal and invalid parameters: what dc_igemm_variant returns.  geom, where not
+ * NULL and the kernel is one of those three, receives 14 ints, the patch geometry of the launch:
+ *   tw, th, ni (tile width / height, images per patch), tiles_x, tiles_y (tiles per image), hw (halo width), HR (halo rows per patch),
+ *   nxl (halo loads per lane), mos (mosaic), xbuf (buffer-descriptor loaders), sws (chunk swizzle shift), lpt (log2 of the tiles per
+ *   image), tiles_m (patches x tiles per image), grid (workgroups). */
+const char* dc_igemm_instance(const dc_igemm_params* p, int32_t* geom);
 /* 1 when dc_igemm can take gn_scale/gn_shift for this problem (the other fields as for dc_igemm). */
 int32_t dc_igemm_gn_fusable(const dc_igemm_params* p);
 /* 1 when dc_igemm can take the 1x1 side source src2 / W2 for this problem. */

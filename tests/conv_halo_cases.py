@@ -1,4 +1,4 @@
-"""The cases of the 3x3 halo-convolution parity tests (conv3_halo<T,4w|8w> in every instance launch_halo picks, conv3_ws<T,gn>, conv3_thin<T>,
+"""The cases of the 3x3 halo-convolution parity tests (conv3_halo<T,4w|8w> in every instance dc_conv3_halo_plan picks, conv3_ws<T,gn>, conv3_thin<T>,
 conv3_up4<T,4w|8w>, igemm_pipe_up4<T,256x128,3st>), their operands, their fp64 reference, the per-element error bound and the checker —
 one table, two consumers: tests/test_conv_halo_cases.py (host only: routing, coverage, geometry, the checker held against planted faults)
 and tests/test_gpu_conv_halo.py (the kernels themselves).
@@ -11,8 +11,8 @@ A case is a dict of dc_igemm's plain fields (the dc_igemm_params names) plus
     n_src / n_src2 / n_vec / n_res   samples in a source read through map0 / map1, in the side source (map2), rows of the row-vector
               table, samples of the residual (each only where its map is set: a table without a map has n_img rows)
     expect    the exact dc_igemm_variant string
-    env       {} or {"DCAMD_HALO_NO_STAG": "1"} — the one switch launch_halo reads per call
-    instance  the template instance launch_halo / launch_ws / launch_thin picks, from geometry(case)
+    env       {} or {"DCAMD_HALO_NO_STAG": "1"} — the one switch dc_conv3_halo_plan reads per call
+    instance  the template instance the launch takes, from geometry(case) (tests/test_conv_halo_cases.py holds it against dc_igemm_instance)
     H, W      the image the kernel walks (four-phase upsample: the LOW-resolution source; Hin = 2 H)
 Not in scope: producer-side GroupNorm (pn_out: tests/test_gpu_ops.py has its tests, and its cross-workgroup waits are no place for a
 shape sweep on shared machines), the switches read once per process (DCAMD_WS_PLAIN, DCAMD_NO_MOSAIC, ...), and every kernel that is not
@@ -43,7 +43,7 @@ NO_STAG = {"DCAMD_HALO_NO_STAG": "1"}
 RECORDED = {"halo4": 0.912, "halo8": 0.919, "halo8_lockstep": 0.902, "ws_gn": 0.923, "thin": 0.808, "up4": 0.889}
 
 
-# ---- geometry: launch_halo / launch_ws / launch_thin on the host ------------------------------------------------------------------
+# ---- geometry: halo_geom and the plans of conv3_halo_plan.h, on the host ------------------------------------------------------------------
 def _ilog2(v):
     return max(0, (v - 1).bit_length())
 

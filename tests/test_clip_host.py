@@ -203,7 +203,7 @@ def test_structs_match_header_field_order_and_every_symbol_is_exported():
     lib = L.lib()
     for name in NEW_SYMBOLS:
         assert getattr(lib, name) is not None and re.search(r"\b" + name + r"\(", hdr), name
-    assert lib.dc_abi_version() == 4
+    assert lib.dc_abi_version() == 5
 
 
 PTR = 1 << 20

@@ -1,8 +1,11 @@
 """The 3x3 halo-convolution parity cases (tests/conv_halo_cases.py) held to account without a GPU: every case is routed to the kernel it
 names, the table covers every instance it claims to, its geometry has the properties it promises, and the checker the GPU test relies on
-passes a plain emulation of the kernels and fails each of a list of planted faults.  dc_igemm_variant and the probes run on the host alone,
-as in tests/test_igemm_dispatch.py."""
+passes a plain emulation of the kernels and fails each of a list of planted faults.  dc_igemm_variant, dc_igemm_instance (the template
+instance and the patch geometry the library itself works out for the launch) and the probes run on the host alone, as in
+tests/test_igemm_dispatch.py."""
+import ctypes
 import itertools
+import re
 
 import pytest
 import torch
@@ -21,6 +24,21 @@ def _lib():
 
 def _params(c, mod):
     return mod.IgemmParams(**G.igemm_fields(c, {f: FAKE for f in G.PTR_FIELDS}))
+
+
+GEOM = ("tw", "th", "ni", "tiles_x", "tiles_y", "hw", "HR", "nxl", "mos", "xbuf", "sws", "lpt", "tiles_m", "grid")      # include/dcamd.h
+
+
+def _instance(lib, p):
+    """(instance string, {geometry field: value}) from the library; the geometry is all -1 where the library wrote none."""
+    geom = (ctypes.c_int32 * len(GEOM))(*([-1] * len(GEOM)))
+    return lib.dc_igemm_instance(p, geom).decode(), dict(zip(GEOM, geom))
+
+
+def _halo_key(name):
+    """(NW, TAPS, MODE, staggered) of a conv3_halo_kernel instance string without pn, None for every other string."""
+    m = re.fullmatch(r"conv3_halo_kernel<\w+,(\d+),(\d+),(\d+)(,stag)?>", name)
+    return m and (int(m[1]), int(m[2]), int(m[3]), bool(m[4]))
 
 
 def _set_env(c, monkeypatch):
@@ -56,7 +74,17 @@ def test_every_case_is_routed_to_the_kernel_it_names(c, monkeypatch):
     _set_env(c, monkeypatch)
     p = _params(c, mod)
     assert lib.dc_igemm_variant(p).decode() == c["expect"], c["name"]
-    assert c["instance"] == G.instance(c)
+    # the instance and the geometry the table claims are the library's own (the ws cases' "+silu" is this table's label, no template argument)
+    name, lg = _instance(lib, p)
+    assert c["instance"] == G.instance(c) and name == G.instance(c).replace("+silu", ""), (c["name"], name)
+    g = G.geometry(c)
+    if g["kind"] == "pipe_up4":
+        assert set(lg.values()) == {-1}
+    else:
+        mine = dict({k: g[k] for k in ("tw", "th", "ni", "tiles_x", "tiles_y", "HR", "nxl")}, mos=int(g["mosaic"]), xbuf=int(g["xbuf"]))
+        assert {k: lg[k] for k in mine} == mine, (c["name"], lg, mine)
+        assert 1 << lg["lpt"] == g["tiles_x"] * g["tiles_y"]
+        assert lg["sws"] == {"thin": 0, "ws": 2}.get(g["kind"], min(g["tw"].bit_length() - 1, 4) - 2), (c["name"], lg)
     # the quad-record part count the reference uses is the library's; the mosaic and the tap-gather kernel form none
     kw = G.igemm_fields(c, {f: FAKE for f in G.PTR_FIELDS})
     kw.pop("qstats", None)
@@ -70,15 +98,20 @@ def test_every_case_is_routed_to_the_kernel_it_names(c, monkeypatch):
 
 
 # ---- b. coverage ------------------------------------------------------------------------------------------------------------------
-# every instance of conv3_halo_kernel<T, NW, TAPS, MODE, STG> launch_halo can name without pn_out
+# every instance of conv3_halo_kernel<T, NW, TAPS, MODE, STG> dc_conv3_halo_plan can name without pn_out
 ALL_HALO = {(8, 9, m, s) for m in (0, 1, 2) for s in (False, True)} | {(8, 4, m, False) for m in (0, 1, 2)} | \
            {(4, 9, m, False) for m in (0, 1)} | {(4, 4, m, False) for m in (0, 1)}
 
 
 def test_the_table_reaches_every_instance_or_proves_it_unreachable(monkeypatch):
+    mod, lib = _lib()
     for dt in G.DTS:
         mine = [c for c in G.CASES if c["dtype"] == dt]
-        reached = {G.halo_instance_key(c) for c in mine} - {None}
+        reached = set()
+        for c in mine:         # what the library says it launches, not what this table derives
+            _set_env(c, monkeypatch)
+            reached.add(_halo_key(_instance(lib, _params(c, mod))[0]))
+        reached -= {None}
         assert reached | set(G.UNREACHABLE) == ALL_HALO and not reached & set(G.UNREACHABLE), (dt, ALL_HALO - reached)
         assert {(c["gn_silu"]) for c in mine if G.kind(c) == "ws"} == {0, 1}
         assert {("gn" in c["use"]) for c in mine if G.kind(c) == "thin"} == {False, True}
@@ -87,7 +120,6 @@ def test_the_table_reaches_every_instance_or_proves_it_unreachable(monkeypatch):
                                                                        "conv3_up4<%s,4w>", "conv3_up4<%s,8w>", "igemm_pipe_up4<%s,256x128,3st>")}
     # what the table does not reach is out of the launcher's reach: on a probe grid every 4-wave problem gets the buffer-descriptor loaders,
     # and only a source sample of 2 GiB flips it
-    mod, lib = _lib()
     monkeypatch.delenv("DCAMD_HALO_NO_STAG", raising=False)
     n = 0
     for dt, (H, W), c0, pad, up4 in itertools.product(G.DTS, [(16, 16), (16, 32), (32, 16), (64, 64), (128, 128), (512, 256), (16, 1024)], (1, 4, 20), (0, 64),
@@ -95,7 +127,7 @@ def test_the_table_reaches_every_instance_or_proves_it_unreachable(monkeypatch):
         c = G._case("probe", dt, "up4" if up4 else "halo4", H, W, 1, C0=c0 * G.BKE[dt], ld0_pad=pad, up4=up4, use={"bias"},
                     expect="conv3_up4<%s,4w>" if up4 else "conv3_halo<%s,4w>")
         assert lib.dc_igemm_variant(_params(c, mod)).decode() == c["expect"]
-        assert G.halo_instance_key(c) == (4, 4 if up4 else 9, 1, False), c
+        assert G.halo_instance_key(c) == _halo_key(_instance(lib, _params(c, mod))[0]) == (4, 4 if up4 else 9, 1, False), c
         n += 1
     assert n == 252
     for key, why in G.UNREACHABLE.items():
@@ -103,7 +135,7 @@ def test_the_table_reaches_every_instance_or_proves_it_unreachable(monkeypatch):
         up4 = key[1] == 4
         c = G._case("probe", BF16, "up4" if up4 else "halo4", 4096, 4096, 1, C0=64, up4=up4, use={"bias"},
                     expect="conv3_up4<%s,4w>" if up4 else "conv3_halo<%s,4w>")
-        assert 4096 * 4096 * 64 * 2 == 2 ** 31 and G.halo_instance_key(c) == key
+        assert 4096 * 4096 * 64 * 2 == 2 ** 31 and G.halo_instance_key(c) == _halo_key(_instance(lib, _params(c, mod))[0]) == key
 
 
 def test_the_cases_have_the_geometry_they_are_there_for():

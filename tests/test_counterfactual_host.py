@@ -175,8 +175,8 @@ def test_struct_fields_match_the_header_and_the_abi_version_stays():
     for name in ("dc_ddpm_step_shared", "dc_abs_diff_map"):
         assert name in L.EXPORTS and getattr(lib, name) is not None
         assert re.search(r"\bint " + name + r"\(", src)
-    assert lib.dc_abi_version() == 4 and L.ABI_VERSION == 4
-    assert re.search(r"#define DC_ABI_VERSION 4\b", src)
+    assert lib.dc_abi_version() == 5 and L.ABI_VERSION == 5
+    assert re.search(r"#define DC_ABI_VERSION 5\b", src)
 
 
 def _step_params(**over):

@@ -291,8 +291,8 @@ def test_both_symbols_are_exported_and_declared_and_the_abi_version_stays():
     for name in ("dc_stage_stop", "dc_stage_maps_rows"):
         assert name in L.EXPORTS and getattr(lib, name) is not None
         assert re.search(r"\bint %s\(" % name, src)
-    assert lib.dc_abi_version() == 4 and L.ABI_VERSION == 4
-    assert re.search(r"#define DC_ABI_VERSION 4\b", src)
+    assert lib.dc_abi_version() == 5 and L.ABI_VERSION == 5
+    assert re.search(r"#define DC_ABI_VERSION 5\b", src)
 
 
 def _stop_args(**over):

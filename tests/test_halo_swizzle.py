@@ -37,7 +37,7 @@ def fragment_address(lane, frag_xy, pitch, x0, y0, kx, sws):
     return row * 64 + slot * 16
 
 
-# (name, lane -> (row, column) inside the fragment, halo pitch, column origins of a fragment, halo rows to try, sws of launch_halo)
+# (name, lane -> (row, column) inside the fragment, halo pitch, column origins of a fragment, halo rows to try, sws of dc_conv3_halo_plan)
 GEOMETRIES = [
     ("32-wide tile", lambda lr: (0, lr), 34, [0, 16], range(10), 2),
     ("16-wide tile", lambda lr: (0, lr), 18, [0], range(18), 2),
@@ -56,7 +56,7 @@ def test_swizzled_halo_reads_are_conflict_free(name, frag_xy, pitch, x0s, y0s, s
 
 
 def test_sws_follows_the_tile_width():
-    # launch_halo: sws = min(log2(tile width), 4) - 2
+    # dc_conv3_halo_plan: sws = min(log2(tile width), 4) - 2
     for ltw, want in ((5, 2), (4, 2), (3, 1), (2, 0)):
         assert min(ltw, 4) - 2 == want
 

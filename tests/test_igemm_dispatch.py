@@ -258,6 +258,34 @@ def test_each_switch_matches_recorded_dispatch():
             (tables[name]["probes"] != _reduced_default_probes(tables)).any(), f"{name} changes nothing on the reduced grid"
 
 
+def test_instance_agrees_with_variant_on_every_halo_conv(monkeypatch):
+    """dc_igemm_instance against dc_igemm_variant over the whole sweep, default environment: a conv3_halo<...> / conv3_up4<...> problem runs
+    conv3_halo_kernel in the variant's dtype and wave count, with 4 taps exactly for the four-phase form and pn exactly where the variant
+    says so, and a producer-side-GroupNorm launch is one of the four instances that exist for it."""
+    monkeypatch.delenv("DCAMD_HALO_NO_STAG", raising=False)
+    L = _load_lib()
+    lib = L.lib()
+    n, pn_seen = 0, set()
+    for c in all_cases():
+        p = L.IgemmParams(**{k: v for k, v in c.items() if v is not None})
+        v = re.fullmatch(r"conv3_(halo|up4)<(\w+),([48])w(,pn)?>", lib.dc_igemm_variant(p).decode())
+        if not v:
+            continue
+        inst = lib.dc_igemm_instance(p, None).decode()
+        k = re.fullmatch(r"conv3_halo_kernel<(\w+),(\d+),(\d+),(\d+)(,stag)?(,pn)?>", inst)
+        assert k, (c, v[0], inst)
+        up4 = v[1] == "up4"
+        key = (int(k[2]), int(k[3]), int(k[4]), bool(k[5]), bool(k[6]))
+        assert k[1] == v[2] and key[0] == int(v[3]) and key[1] == (4 if up4 else 9) and key[4] == bool(v[4]) and up4 == bool(c.get("up4")), (c, v[0], inst)
+        if key[4]:
+            want = ((4, 4, 1, False, True) if up4 else (4, 9, 1, False, True)) if key[0] == 4 else \
+                {(8, 8): (8, 9, 0, True, True), (4, 4): (8, 9, 2, True, True)}.get((c["Hin"], c["Win"]))
+            assert key == want, (c, v[0], inst)
+            pn_seen.add(key)
+        n += 1
+    assert n > 10000 and len(pn_seen) == 4, (n, pn_seen)
+
+
 def _reduced_index():
     """Positions of the reduced cases inside the full list (the reduced grid is a subset of the full one; the feature cases are shared)."""
     pos = {repr(sorted(c.items())): i for i, c in enumerate(all_cases())}

@@ -39,8 +39,8 @@ def test_struct_fields_match_the_header_and_the_abi_version_stays():
     assert "dc_class_posterior" in L.EXPORTS
     lib = L.lib()
     assert lib.dc_class_posterior is not None
-    assert lib.dc_abi_version() == 4 and L.ABI_VERSION == 4
-    assert re.search(r"#define DC_ABI_VERSION 4\b", src)
+    assert lib.dc_abi_version() == 5 and L.ABI_VERSION == 5
+    assert re.search(r"#define DC_ABI_VERSION 5\b", src)
 
 
 def _params(**over):

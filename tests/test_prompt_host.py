@@ -74,7 +74,7 @@ def test_cross_attention_struct_matches_header_field_order():
     assert names == [n for n, _ in L.CrossAttentionParams._fields_]
     assert "DC_OP_CROSS_ATTENTION = 9" in hdr and L.OP_CROSS_ATTENTION == 9
     assert {"dc_cross_attention", "dc_cross_attention_variant"} <= set(L.EXPORTS)
-    assert L.lib().dc_abi_version() == 4
+    assert L.lib().dc_abi_version() == 5
 
 
 def _params(**kw):

@@ -41,7 +41,7 @@ def test_cross_attention_len_struct_matches_header_field_order():
     assert {"dc_cross_attention_len", "dc_cross_attention_len_variant"} <= set(L.EXPORTS)
     lib = L.lib()
     assert lib.dc_cross_attention_len and lib.dc_cross_attention_len_variant
-    assert lib.dc_abi_version() == 4 and "#define DC_ABI_VERSION 4" in hdr
+    assert lib.dc_abi_version() == 5 and "#define DC_ABI_VERSION 5" in hdr
 
 
 def _params(**kw):

@@ -207,7 +207,7 @@ def test_structs_match_header_field_order_and_ops_are_declared():
     assert (L.OP_ATTENTION_BIAS, L.OP_RMSNORM, L.OP_EMBED_ROWS, L.OP_RELU) == (11, 12, 13, 14)
     assert f"#define DC_ATTENTION_BIAS_MAX_L {L.ATTENTION_BIAS_MAX_L}" in hdr
     assert {"dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu"} <= set(L.EXPORTS)
-    assert L.lib().dc_abi_version() == 4
+    assert L.lib().dc_abi_version() == 5
 
 
 PTR = 1 << 20
