@@ -95,3 +95,9 @@ template <int N> __device__ __forceinline__ void hwait_vmcnt() { asm volatile("s
 
 template <int V> struct IC { static constexpr int value = V; };
 
+// register quads of the pixel-fragment ring of the lock-step tap loop (conv3_halo.hip, mma_tap): quads - 1 reads stay in flight under a
+// group of 4 MFMAs.  A stamp build may override it (-DHALO_XDEPTH=2) to compare depths.
+#ifndef HALO_XDEPTH
+#define HALO_XDEPTH 3
+#endif
+

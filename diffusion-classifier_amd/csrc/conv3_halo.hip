@@ -119,9 +119,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
   int phase = 0;
   if (UP4) { const int tn = a.tiles_n >> 2; phase = tile_n / tn; tile_n -= phase * tn; }
   const int pa = phase >> 1, pb = phase & 1;
-  const int tx = tile_m % g.tiles_x;
-  const int ty = (tile_m / g.tiles_x) % g.tiles_y;
-  const int ng = tile_m / (g.tiles_x * g.tiles_y);
+  int tx = tile_m % g.tiles_x;
+  int ty = (tile_m / g.tiles_x) % g.tiles_y;
+  int ng = tile_m / (g.tiles_x * g.tiles_y);
   const int tw = 1 << g.ltw, th = 1 << g.lth;
   const int HW = g.H * g.W;                             // g.H x g.W: the conv's (= output) extent; the source is half of it when upsampling
   const int HWs = a.upsample ? (g.H >> 1) * (g.W >> 1) : HW;
@@ -364,25 +364,46 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
 #pragma unroll
     for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // one tap of one channel chunk: W fragments, then the X fragments in two halves that share registers (all eight at once
-  // need 16 more VGPRs than this kernel has: a spill inside the tap loop is reloaded behind vmcnt(0), which drains the
-  // LDS-DMA ring); MFMAs in j-major order.  The sched_barrier keeps hipcc from hoisting the second half's reads.
-  auto mma_tap = [&](const char* Wst, const char* Xb, int tapoff, auto kxc) {
+  // one tap of one channel chunk in the lock-step loops: 4 W fragments, then the 8 pixel fragments through a ring of XD register quads,
+  // 4 MFMAs (one per W fragment) per pixel fragment, j-major.  The reads are opaque instructions with counted waits tied to the quad
+  // they release (common.h) and every MFMA group is fenced with sched_barrier: left to hipcc, at ~250 VGPRs the plain C++ loads were
+  // folded onto ONE quad and each read sat directly in front of the 4 MFMAs that use it behind a full lgkmcnt(0) — eight exposed LDS
+  // round trips per tap in every wave (tools/halo_loop_isa.py shows the form at a glance).  Here fragment j + XD is issued as soon as
+  // the MFMAs of fragment j have read its quad, so XD - 1 reads are in flight under every group but the last XD - 1 of a tap.
+  // Addresses are 32-bit LDS addresses: per-lane part (waddr, xlv) + a wave-uniform part formed on the scalar unit; the W fragments
+  // use the instruction's immediate offset.  One accumulator still gets one MFMA per tap, taps in order: the bits do not change.
+  // (All eight fragments at once need 16 more VGPRs than this kernel has: a spill inside the tap loop is reloaded behind vmcnt(0),
+  // which drains the LDS-DMA ring.)
+  constexpr int XD = HALO_XDEPTH;
+  static_assert(XD >= 2 && XD <= TM, "pixel-fragment ring: 2 ... TM quads");
+  const uint32_t lds0 = lds_addr_of(smem);
+  const uint32_t waddr = lds_addr_of(Wring) + (uint32_t)woff0;
+  auto mma_tap = [&](uint32_t wso, uint32_t xbo, int tapoff, auto kxc) {      // byte offsets of the W tile in the ring / of the halo buffer
     constexpr int kx = decltype(kxc)::value;      // swizzle variant of the tap's column offset
-    chunk16 wf[TN];
+    chunk16 wf[TN], xq[XD];
+    const uint32_t xu = lds0 + xbo + (uint32_t)tapoff;      // wave-uniform
+    auto xread = [&](int j) { return ds_read16_async(xu + (uint32_t)joff[j] + (uint32_t)xlv[MOS ? ((kx + j) & 1) : kx]); };
+    __builtin_amdgcn_sched_barrier(0);
+    const uint32_t wa = waddr + wso;
+    wf[0] = ds_read16_async_off<0>(wa);
+    wf[1] = ds_read16_async_off<1024>(wa);
+    wf[2] = ds_read16_async_off<2048>(wa);
+    wf[3] = ds_read16_async_off<3072>(wa);
 #pragma unroll
-    for (int i = 0; i < TN; ++i) wf[i] = *reinterpret_cast<const chunk16*>(Wst + woff0 + i * 1024);
+    for (int j = 0; j < XD; ++j) xq[j] = xread(j);
+    auto group = [&](auto jc) {
+      constexpr int j = decltype(jc)::value, q = j % XD;
+      constexpr int fly = (TM - 1 - j) < (XD - 1) ? (TM - 1 - j) : (XD - 1);      // reads issued behind fragment j
+      if constexpr (j == 0) lgkm_wait<fly>(wf[0], wf[1], wf[2], wf[3], xq[0]);
+      else lgkm_wait<fly>(xq[q]);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      chunk16 xf[TM / 2];
-#pragma unroll
-      for (int j = 0; j < TM / 2; ++j) xf[j] = *reinterpret_cast<const chunk16*>(Xb + (tapoff + joff[h * (TM / 2) + j]) + xlv[MOS ? ((kx + j) & 1) : kx]);
-#pragma unroll
-      for (int j = 0; j < TM / 2; ++j)
-#pragma unroll
-        for (int i = 0; i < TN; ++i) acc[i][h * (TM / 2) + j] = Mma<T>::run(wf[i], xf[j], acc[i][h * (TM / 2) + j]);
-      if (h == 0) __builtin_amdgcn_sched_barrier(0);
-    }
+      for (int i = 0; i < TN; ++i) acc[i][j] = Mma<T>::run(wf[i], xq[q], acc[i][j]);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (j + XD < TM) xq[q] = xread(j + XD);
+    };
+    group(IC<0>{}); group(IC<1>{}); group(IC<2>{}); group(IC<3>{}); group(IC<4>{}); group(IC<5>{}); group(IC<6>{}); group(IC<7>{});
+    __builtin_amdgcn_sched_barrier(0);
   };
 
   DC_STAMP(1);
@@ -401,11 +422,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
     // fragment reads as opaque instructions with explicit waits tied to their registers (common.h), MFMA blocks fenced with
     // sched_barrier: hipcc otherwise moves the MFMAs across the barriers (two s_barrier back to back in the ISA) and re-serialises
     // the reads.  Addresses: per-lane LDS address of pixel fragment j (8 registers) + a wave-uniform (buffer, tap row) part.
-    const uint32_t lds0 = lds_addr_of(smem);
     uint32_t xaddr[TM];                   // per-lane LDS address of pixel fragment j (no swizzle here: xlv[0] = xlv[1] = xlv[2])
 #pragma unroll
     for (int j = 0; j < TM; ++j) xaddr[j] = lds0 + (uint32_t)(joff[j] + xlv[0]);
-    const uint32_t waddr = lds_addr_of(Wring) + (uint32_t)woff0;
     for (int cc = 0; cc < nchunks; ++cc) {
       const bool side_next = cc + 1 == nchunks && nx > 0;
       const bool has_next = cc + 1 < nchunks || side_next;
@@ -521,7 +540,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
     const bool side_next = cc + 1 == nchunks && nx > 0;
     const bool has_next = cc + 1 < nchunks || side_next;
     const int s0 = cc * NTAP;
-    const char* Xb = smem + (cc & 1) * Cfg::XBUF;
+    const uint32_t xbo = (uint32_t)(cc & 1) * Cfg::XBUF;
     auto step = [&](auto tapc) {
       constexpr int tap = decltype(tapc)::value;
       // W(s) (and X(cc) when tap == 0) must have landed.  Younger LDS-DMA groups that may stay in flight: W(s+1) ..
@@ -540,10 +559,10 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
       else if (has_next) issue_w(cc + 1, t2 - NTAP, (s0 + t2) % WR);
       if (tap == 0 && has_next) issue_x(cc + 1);
 
-      const char* Wst = Wring + ((s0 + tap) % WR) * HALO_WST;
+      const uint32_t wso = (uint32_t)((s0 + tap) % WR) * HALO_WST;
       constexpr int ky = UP4 ? (tap >> 1) : tap / 3, kx = UP4 ? (tap & 1) : tap - ky * 3;
       const int tapoff = ((ky + pa) * g.hw + kx + pb) * 64;       // pa = pb = 0 for the 3x3 conv
-      mma_tap(Wst, Xb, tapoff, IC<kx>{});
+      mma_tap(wso, xbo, tapoff, IC<kx>{});
     };
     step(IC<0>{}); step(IC<1>{}); step(IC<2>{}); step(IC<3>{});
     if constexpr (NTAP == 9) { step(IC<4>{}); step(IC<5>{}); step(IC<6>{}); step(IC<7>{}); step(IC<8>{}); }
@@ -564,14 +583,19 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
       __builtin_amdgcn_s_barrier();
       if (e + PD < nx) issue_w2(e + PD, (NSm + e + PD) % WR);
       if (e + 1 < nx) issue_x(nchunks + e + 1);
-      const char* Xb = smem + ((nchunks + e) & 1) * Cfg::XBUF;
-      const char* Wst = Wring + ((NSm + e) % WR) * HALO_WST;
+      const uint32_t xbo = (uint32_t)((nchunks + e) & 1) * Cfg::XBUF;
+      const uint32_t wso = (uint32_t)((NSm + e) % WR) * HALO_WST;
       const int tapoff = (g.hw + 1) * 64;              // centre tap
-      mma_tap(Wst, Xb, tapoff, IC<1>{});
+      mma_tap(wso, xbo, tapoff, IC<1>{});
     }
   }
 
   DC_STAMP(2);
+  // The tile coordinates are made opaque in front of the epilogue, so that everything the epilogue derives from them is formed HERE.
+  // While tile_of_block kept tile_m / tile_n in stack slots their reloads had that effect by accident; with them in registers and
+  // without this line the 16-bit per-lane-address and mosaic instances spill ~100 accumulator registers in the epilogue (ScratchSize
+  // 408-440 B per lane against 0 with it; tools/halo_loop_isa.py).
+  if constexpr (!XB) asm volatile("" : "+v"(tx), "+v"(ty), "+v"(ng), "+v"(tile_n));
   // ---- epilogue: straight from the accumulators (igemm_epilogue.h: the weight rows were loaded permuted) ----
   const int nw0 = min((ng << g.lni) + ((wm * 128) >> (g.ltw + g.lth)), g.n_img - 1);
   const int nw1 = min((ng << g.lni) + ((wm * 128 + 127) >> (g.ltw + g.lth)), g.n_img - 1);

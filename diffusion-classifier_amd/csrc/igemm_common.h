@@ -60,13 +60,17 @@ __device__ __forceinline__ void tile_of_block(const IgemmArgs& a, int& tile_m, i
   const int nblk = gridDim.x, bid = blockIdx.x;
   const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
   const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  if (a.n_fast) {
-    tile_m = lid / a.tiles_n;
-    tile_n = lid - tile_m * a.tiles_n;
-  } else {
-    tile_n = lid / a.tiles_m;
-    tile_m = lid - tile_n * a.tiles_m;
-  }
+  // One quotient / remainder by the fast extent, then a select of VALUES.  Written as two branches that assign through the references,
+  // hipcc selects between the two ADDRESSES: tile_m / tile_n then live in stack slots, and the callers reload them inside their main
+  // loops behind a vmcnt(0) that drains every LDS-DMA in flight.  The extents are opaque local copies for the same reason: a select
+  // between two fields of the by-value argument struct is again a select of addresses.
+  const bool nf = a.n_fast != 0;
+  int tn = a.tiles_n, tm = a.tiles_m;
+  asm volatile("" : "+s"(tn), "+s"(tm));
+  const int d = nf ? tn : tm;
+  const int qt = lid / d, rm = lid - qt * d;
+  tile_m = nf ? qt : rm;
+  tile_n = nf ? rm : qt;
 }
 
 // Epilogue of one wave: acc[i][j] is the 16x16 tile (cout block i, pixel block j); the lane holds 4
