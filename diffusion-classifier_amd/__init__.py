@@ -15,6 +15,7 @@ from .nets.dit import DiT  # noqa: F401
 from .diffusion.diffusion_classifier import DiffusionClassifier  # noqa: F401
 from .utils.wavelet import wavelet_dec_2, wavelet_enc_2  # noqa: F401
 from .posterior import ClassPosterior  # noqa: F401
+from .evidence import ClassEvidence  # noqa: F401
 from .counterfactual import Counterfactuals  # noqa: F401
 
 

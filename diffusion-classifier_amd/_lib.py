@@ -20,6 +20,8 @@ ATTENTION_BIAS_MAX_L = 512      # include/dcamd.h DC_ATTENTION_BIAS_MAX_L
 OP_ATTENTION_CAUSAL, OP_LAYERNORM_ROWS, OP_EMBED_ROWS_POS, OP_ACT_PASS = 15, 16, 17, 18
 ATTENTION_CAUSAL_MAX_L = 512    # include/dcamd.h DC_ATTENTION_CAUSAL_MAX_L
 PASS_QUICK_GELU, PASS_GELU_ERF = 1, 2       # dc_pass_kind
+OP_ERR_MAP = 19
+EVIDENCE_FRAC_BITS, EVIDENCE_VMAX = 30, 16384.0      # include/dcamd.h DC_EVIDENCE_FRAC_BITS / DC_EVIDENCE_VMAX
 
 i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -135,6 +137,20 @@ class EpsMseParams(C.Structure):
                 ("out", vp), ("n_units", i32), ("C", i32), ("H", i32), ("W", i32), ("ld", i32), ("v_param", i32), ("patch", i32)]
 
 
+class ErrMapParams(C.Structure):
+    _fields_ = [("pred", vp), ("eps", vp), ("x", vp), ("alpha", vp), ("sigma", vp),
+                ("bj_of_unit", vp), ("img_of_bj", vp), ("out_index", vp),
+                ("acc", vp), ("bad", vp),
+                ("n_units", i32), ("C", i32), ("H", i32), ("W", i32), ("ld", i32), ("v_param", i32), ("patch", i32),
+                ("T", i32), ("cells", i32), ("pad_", i32)]
+
+
+class EvidenceMapsParams(C.Structure):
+    _fields_ = [("acc", vp), ("bad", vp), ("stage_ends", vp), ("n_eval", vp), ("winner", vp),
+                ("mean_map", vp), ("delta_map", vp), ("invalid", vp),
+                ("n_stages", i32), ("BS", i32), ("C", i32), ("HW", i32)]
+
+
 class DdpmStepParams(C.Structure):
     _fields_ = [("z", vp), ("pred", vp), ("noise", vp), ("out", vp),
                 ("n", i32), ("C", i32), ("H", i32), ("W", i32), ("ld", i32), ("patch", i32), ("v_param", i32),
@@ -165,7 +181,7 @@ class Op(C.Structure):
 # every symbol include/dcamd.h declares (tests check that the library exports all of them)
 EXPORTS = ["dc_abi_version", "dc_last_error", "dc_arch", "dc_qsample", "dc_philox_normal", "dc_sinusoid",
            "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_instance", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
-           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_ddpm_step", "dc_ddpm_step_shared", "dc_abs_diff_map", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_stage_maps_rows", "dc_stage_stop", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
+           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_err_map", "dc_evidence_maps", "dc_ddpm_step", "dc_ddpm_step_shared", "dc_abs_diff_map", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_stage_maps_rows", "dc_stage_stop", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
            "dc_packed_bytes", "dc_pack_weights_matrix", "dc_pack_weights_conv3x3", "dc_pack_weights_up4", "dc_pack_weights_geglu",
            "dc_fold_layernorm_bias", "dc_workspace_bytes_groupnorm", "dc_workspace_bytes_igemm", "dc_workspace_bytes_attention",
            "dc_workspace_bytes_layernorm"]
@@ -208,6 +224,8 @@ def lib():
                        ("dc_act_pass", [C.POINTER(ActPassParams), vp]),
                        ("dc_tblock_front", [C.POINTER(TblockFrontParams), vp]),
                        ("dc_eps_mse", [C.POINTER(EpsMseParams), vp]),
+                       ("dc_err_map", [C.POINTER(ErrMapParams), vp]),
+                       ("dc_evidence_maps", [C.POINTER(EvidenceMapsParams), vp]),
                        ("dc_class_posterior", [C.POINTER(ClassPosteriorParams), vp]),
                        ("dc_ddpm_step", [C.POINTER(DdpmStepParams), vp]),
                        ("dc_ddpm_step_shared", [C.POINTER(DdpmStepSharedParams), vp]),

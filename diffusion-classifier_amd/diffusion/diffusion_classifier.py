@@ -61,6 +61,13 @@ Extra keyword-only arguments (defaults keep the reference behaviour):
                  identical on every rank.  argmax probs is the label.  Returns (labels, post), with return_errors (labels, errors, post).
                  With stop_margin_z every image is evaluated over its own [0, t_done[b]) (one launch per stage end that was reached
                  and a row select on the device); `n_trials` then reports the trials each image used
+  return_evidence  also return a `ClassEvidence` (evidence.py): per-pixel maps [BS, classes, H, W] of the mean squared eps-error of every
+                 class and of its paired difference to the posterior's winner (the spatial form of the posterior's delta; exactly 0 for
+                 the winner), from the predictions the scoring loop already holds — one more elementwise op per launch (`dc_err_map`:
+                 fixed-point int64 sums, the same bits for every micro-batch split and world size), one `dc_evidence_maps` at the end
+                 and, under grid sharding, one int64 all-reduce per call; no backbone forward is added.  Placed after the posterior and
+                 before t_done in the returned tuple.  T <= 2^18; with `simulate_rank` ValueError.  Models trained on
+                 `wavelet_dec_2(image) / 2`: the maps live on the wavelet grid
   return_trials  also return t_done, int32 [BS] on the scoring device, as the LAST element of the tuple: the trials each image was
                  scored on (T everywhere when stop_margin_z is unset)
   rng            "reference": draw rand(BS) / randn_like(x) per trial in the reference's order;
@@ -85,6 +92,7 @@ from .. import _lib as L
 from .. import dist as D
 from .. import counterfactual as CF
 from .. import posterior as P
+from .. import evidence as EV
 from .._ema import EMA
 
 
@@ -313,12 +321,14 @@ class DiffusionClassifier(nn.Module):
     # ---- the hot path ---------------------------------------------------------------------
     @torch.no_grad()
     def classify(self, x, text=None, fast=False, *, t=None, eps=None, fast_select=None, return_errors=False,
-                 rng="reference", seed=0, group=None, return_posterior=False, return_trials=False):
+                 rng="reference", seed=0, group=None, return_posterior=False, return_trials=False, return_evidence=False):
         cfg = self.config
         z_stop = P.stop_margin_of(cfg)           # None: no per-image early stopping, none of its code runs
         if z_stop is not None and cfg.simulate_rank:
             raise ValueError("stop_margin_z cannot be combined with simulate_rank: one rank's share of the errors decides nothing")
         tau = P.temperature_of(cfg) if return_posterior else None
+        if return_evidence and cfg.simulate_rank:
+            raise ValueError("return_evidence cannot be combined with simulate_rank: one rank's share of the grid explains nothing")
         assert self.encoder_type is not None, "Encoder must be provided for classification."
         self._require_prompts()
         assert len(cfg.evaluation_per_stage) == cfg.n_stages, "Number of evaluations per stage must match the number of stages."
@@ -330,6 +340,8 @@ class DiffusionClassifier(nn.Module):
         ends = [0] + list(cfg.evaluation_per_stage)
         T, ncls = ends[-1], cfg.classes
         BS = x.shape[0]
+        if return_evidence:
+            EV.check_trials(T)
         # grid sharding is opt-in: the reference shards the DATALOADER over ranks, so an initialised process group alone
         # must not make ranks mix the errors of different images
         shard = group is not None or cfg.shard_grid is True
@@ -393,8 +405,12 @@ class DiffusionClassifier(nn.Module):
         t_done = frozen = rows = None
         if z_stop is not None:
             t_done, frozen = runner.stop_state()
+        if return_evidence:
+            runner.evidence_begin(cfg.n_stages)      # per-stage int64 accumulators; the plans of this call carry the map op
         for i in range(cfg.n_stages):
             last = i == cfg.n_stages - 1
+            if return_evidence:
+                runner.ev_stage = i
             if rows is None:
                 pairs = D.local_pairs(ends[i], ends[i + 1], BS, rank, ws)
                 runner.run_stage(pairs, classes, stage=(ends[i], rank, ws))
@@ -426,8 +442,16 @@ class DiffusionClassifier(nn.Module):
         else:
             out = frozen.to(x.device)
         # the posterior reads the errors every rank holds after the last gather: the same bits everywhere
-        post = None
-        if return_posterior:
+        post = evid = None
+        if return_evidence:
+            # the maps are paired to the posterior's winner over the posterior's trial counts: its parts are computed either way
+            pk = dict(return_parts=True) if z_stop is None else dict(return_parts=True, t_values=ends[1:i + 2])
+            post, winner, means, _ = runner.posterior(errors, T if z_stop is None else t_done, 1.0 if tau is None else tau, **pk)
+            acc, bad = runner.ev
+            if ws > 1:
+                D.reduce_evidence(acc, bad, ws, group=group)     # exact integer sums: the same bits on every rank and for every world size
+            evid = runner.evidence(ends[1:], post.n_trials, EV.winner_or_none(winner, means))
+        elif return_posterior:
             post = runner.posterior(errors, T, tau) if z_stop is None else runner.posterior(errors, t_done, tau, t_values=ends[1:i + 2])
         res = (out,)
         if return_errors:
@@ -435,6 +459,8 @@ class DiffusionClassifier(nn.Module):
             self.check_device_errors()
         if return_posterior:
             res += (post,)
+        if return_evidence:
+            res += (evid,)
         if return_trials:
             res += (t_done if t_done is not None else torch.full((BS,), T, dtype=torch.int32, device=errors.device),)
         return res if len(res) > 1 else out
@@ -760,8 +786,17 @@ class _ForeignRunner:
         _, keep_indices = torch.topk(end_of_stage_errors, num_keep, dim=1, largest=False)
         return keep_indices
 
-    def posterior(self, errors, t_end, temperature, t_values=None):
-        return P.class_posterior_torch(errors, t_end, temperature, t_values=t_values)
+    def posterior(self, errors, t_end, temperature, t_values=None, return_parts=False):
+        return P.class_posterior_torch(errors, t_end, temperature, t_values=t_values, return_parts=return_parts)
+
+    ev = None            # (acc, bad) per-stage evidence accumulators of a return_evidence call (evidence.py), `ev_stage` the running stage
+
+    def evidence_begin(self, n_stages):
+        BS, _, H, W = self.x.shape
+        self.ev, self.ev_stage = EV.new_slabs(n_stages, BS * self.dc.config.classes, H * W, self.x.device), 0
+
+    def evidence(self, stage_ends, n_eval, winner):
+        return EV.evidence_maps_torch(self.ev[0], self.ev[1], stage_ends, n_eval, winner, self.x.shape[2], self.x.shape[3])
 
     def stop_state(self):
         BS, dev = self.x.shape[0], self.x.device
@@ -796,6 +831,8 @@ class _ForeignRunner:
                 eps_pred = sg * z + al * pred if dc.pred_param == 'v' else pred
                 err = torch.norm((eps_pred - e).view(len(bl), -1), dim=1, p=2) ** 2
                 self.err[bs.to(x.device), lab, j] = err
+                if self.ev is not None:
+                    EV.err_map_torch(eps_pred, e, bs.to(x.device) * dc.config.classes + lab, self.ev[0][self.ev_stage], self.ev[1][self.ev_stage])
 
 
 def _units_per_launch(config, H, W, k):
@@ -837,7 +874,7 @@ class _HipRunner:
         S = int(dc.encoder.weight.shape[1]) if dc._table_mode() else 1                 # tokens per context
         varlen = dc._ragged_table()                                                    # prompts of different lengths: a plan with ctx_len
         key = (BS, n_bj, k, self.dt, str(dev), (Cc, H, W), bool(getattr(self.bb, "share_trunk", True)), id(self.bb),
-               self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ())
+               self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ()) + (("evidence",) if self.ev is not None else ())
         sp = dc._score_plans.get(key)
         if sp is not None:
             dc._score_plans[key] = dc._score_plans.pop(key)      # most recently used last
@@ -865,6 +902,9 @@ class _HipRunner:
             errors=torch.full((BS * cfg.classes * T + 1,), float("inf"), dtype=torch.float32, device=dev),
             lam=lam, alpha=alpha, sigma=sigma, img_of_bj=img_of_bj, ctx_of_unit=ctx_of_unit, out_index=out_index,
             v_param=dc.pred_param == 'v')
+        if self.ev is not None:          # such plans own the accumulators their map op adds into (one stage at a time: run_stage)
+            score["emap_acc"], score["emap_bad"] = (v[0] for v in EV.new_slabs(1, BS * cfg.classes, H * W, dev))
+            score["emap_T"] = T
         plan = self.bb.make_plan(n_bj, k, cfg.classes, dev, score=score, **({"S": S} if S > 1 else {}), **({"varlen": True} if varlen else {}))
         sp = dict(plan=plan, score=score, ctl=ctl, pair_id=pair_id, words=words, n_bj=n_bj, k=k, U=U)
         dc._score_plans[key] = sp
@@ -897,8 +937,17 @@ class _HipRunner:
             L.check(self.lib.dc_stage_topk(errors.data_ptr(), BS, ncls, T, t_end, num_keep, keep.data_ptr(), None, L.stream_ptr()), "dc_stage_topk")
         return keep
 
-    def posterior(self, errors, t_end, temperature, t_values=None):
-        return P.class_posterior_hip(errors, t_end, temperature, t_values=t_values)
+    def posterior(self, errors, t_end, temperature, t_values=None, return_parts=False):
+        return P.class_posterior_hip(errors, t_end, temperature, t_values=t_values, return_parts=return_parts)
+
+    ev = None            # (acc, bad) per-stage evidence accumulators of a return_evidence call (evidence.py), `ev_stage` the running stage
+
+    def evidence_begin(self, n_stages):
+        BS, _, H, W = self.x.shape
+        self.ev, self.ev_stage = EV.new_slabs(n_stages, BS * self.dc.config.classes, H * W, self.dev), 0
+
+    def evidence(self, stage_ends, n_eval, winner):
+        return EV.evidence_maps_hip(self.ev[0], self.ev[1], stage_ends, n_eval, winner, self.x.shape[2], self.x.shape[3])
 
     def stop_state(self):
         BS = self.x.shape[0]
@@ -959,6 +1008,9 @@ class _HipRunner:
         elif score["errors"] is not self.err_dev:
             score["errors"].copy_(self.err_dev)
         self.err_dev = score["errors"]
+        if self.ev is not None:
+            score["emap_acc"].zero_()
+            score["emap_bad"].zero_()
         score["x"].copy_(self.x_dev)
         if dc.encoder is not None:
             plan.ctx.copy_(dc.encoder.weight[:ncls].detach().to(dev, torch.float32).reshape(plan.ctx.shape))
@@ -1058,3 +1110,6 @@ class _HipRunner:
         if ev is None:
             ev = sp["host_ev"] = torch.cuda.Event()
         ev.record()
+        if self.ev is not None:          # the stage's sums into the call's slab (int64 adds on the stream: exact)
+            self.ev[0][self.ev_stage] += score["emap_acc"]
+            self.ev[1][self.ev_stage] += score["emap_bad"]

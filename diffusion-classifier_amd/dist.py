@@ -116,3 +116,20 @@ def gather_stage_errors(errors, stage_start, stage_end, rank, world_size, group=
     errors[img(g % BS), :, stage_start + g // BS] = flat[(g % world_size) * n + g // world_size]
     return errors
 
+
+
+def reduce_evidence(acc, bad, world_size, group=None):
+    """In place: the per-stage evidence accumulators (evidence.py: acc int64 [n_stages, cells + 1, HW], bad int32 [n_stages, cells + 1])
+    summed over the ranks — every (image, class, trial) unit was scored by exactly one rank.  ONE collective per classify call, made
+    only when the maps were asked for: the two tensors travel as one int64 block.  Integer sums are exact, so — unlike the errors,
+    which are gathered for that reason — an all-reduce gives every rank and every world size the same bits."""
+    if world_size == 1:
+        return acc, bad
+    block = torch.cat([acc.reshape(-1), bad.reshape(-1).to(torch.int64)])
+    host = block.is_cuda and dist.get_backend(group) == "gloo"      # gloo (single-GPU rehearsals, CPU tests) reduces on the host
+    buf = block.cpu() if host else block
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    buf = buf.to(acc.device)
+    acc.copy_(buf[:acc.numel()].view_as(acc))
+    bad.copy_(buf[acc.numel():].view_as(bad).to(torch.int32))
+    return acc, bad

@@ -389,6 +389,15 @@ class PlanBuilder:
         self._emit(L.OP_EPS_MSE, L.EpsMseParams, f, [pred, eps, alpha, sigma], [],
                    dict(name="eps_mse", family="eps_mse", flops=0.0, bytes=8.0 * self.n["unit"] * Cin * pred.H * g * pred.W * g))
 
+    def err_map(self, pred, eps, x_ptr, alpha, sigma, bj_of_unit, img_of_bj, out_index, acc_ptr, bad_ptr, Cin, v_param, T, cells, patch=0):
+        """Per-pixel form of eps_mse into the plan's evidence accumulators (evidence.py); emitted right after it, only when asked."""
+        g = patch if patch > 1 else 1
+        f = dict(pred=pred, eps=eps, x=x_ptr, alpha=alpha, sigma=sigma, bj_of_unit=bj_of_unit, img_of_bj=img_of_bj,
+                 out_index=out_index, acc=acc_ptr, bad=bad_ptr, n_units=self.n["unit"], C=Cin, H=pred.H * g, W=pred.W * g, ld=pred.ld,
+                 v_param=int(v_param), patch=int(patch), T=int(T), cells=int(cells))
+        self._emit(L.OP_ERR_MAP, L.ErrMapParams, f, [pred, eps, alpha, sigma], [],
+                   dict(name="err_map", family="err_map", flops=0.0, bytes=(8.0 * Cin + 8.0) * self.n["unit"] * pred.H * g * pred.W * g))
+
     # ---- finalize: liveness-based arena + ctypes records ----------------------------
     def finalize(self, keep_alive=()):
         """keep_alive: tensors that must survive to the end of the plan (outputs)."""
@@ -1119,6 +1128,10 @@ class UNetPlan:
         if score is not None:
             pb.eps_mse(pred, eps_t, pb.const(score["x"]), al, sg, pb.const(self.bj_of_unit), pb.const(score["img_of_bj"]),
                        pb.const(score["out_index"]), pb.const(score["errors"]), cfg.in_channels, score["v_param"])
+            if score.get("emap_acc") is not None:
+                pb.err_map(pred, eps_t, pb.const(score["x"]), al, sg, pb.const(self.bj_of_unit), pb.const(score["img_of_bj"]),
+                           pb.const(score["out_index"]), pb.const(score["emap_acc"]), pb.const(score["emap_bad"]), cfg.in_channels,
+                           score["v_param"], score["emap_T"], score["emap_acc"].shape[0] - 1)
         pb.finalize(keep_alive=[pred])
 
     def run(self):

@@ -127,6 +127,10 @@ class DiTPlan:
         if score is not None:
             pb.eps_mse(pred, eps_t, pb.const(score["x"]), al, sg, pb.const(self.bj_of_unit), pb.const(score["img_of_bj"]),
                        pb.const(score["out_index"]), pb.const(score["errors"]), cfg.in_channels, score["v_param"], patch=p)
+            if score.get("emap_acc") is not None:
+                pb.err_map(pred, eps_t, pb.const(score["x"]), al, sg, pb.const(self.bj_of_unit), pb.const(score["img_of_bj"]),
+                           pb.const(score["out_index"]), pb.const(score["emap_acc"]), pb.const(score["emap_bad"]), cfg.in_channels,
+                           score["v_param"], score["emap_T"], score["emap_acc"].shape[0] - 1, patch=p)
         pb.finalize(keep_alive=[pred])
 
     def run(self):

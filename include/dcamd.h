@@ -40,6 +40,9 @@
  *                       the images still undecided
  *   dc_class_posterior  nothing in the reference: the class posterior (Li et al. 2023, eq. 5, on paired differences), its entropy and
  *                       the paired confidence of the decision, from the errors tensor :718-725 reduces to one label
+ *   dc_err_map / dc_evidence_maps
+ *                       nothing in the reference: per-pixel class evidence from the scoring loop — where in the image a class explains
+ *                       the noise worse than the winner (the spatial form of dc_class_posterior's delta), from the same predictions
  *   dc_run_plan         the Python double loop body, diffusion_classifier.py:695-714, as
  *                       one native launch sequence (graph-capturable)
  *
@@ -67,7 +70,9 @@ extern "C" {
  *  dc_act_pass, their structs, dc_pass_kind and DC_OP_ATTENTION_CAUSAL / DC_OP_LAYERNORM_ROWS / DC_OP_EMBED_ROWS_POS / DC_OP_ACT_PASS —
  *  likewise)
  * (dc_ddpm_step_shared, dc_abs_diff_map and their structs likewise; both are called directly)
- * (dc_stage_stop and dc_stage_maps_rows likewise; both are called directly) */
+ * (dc_stage_stop and dc_stage_maps_rows likewise; both are called directly)
+ * (dc_err_map, dc_err_map_params and DC_OP_ERR_MAP, and dc_evidence_maps with dc_evidence_maps_params — called directly — are additive
+ *  within 5: no existing struct or symbol changed) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -584,12 +589,55 @@ typedef struct {
 } dc_class_posterior_params;
 int dc_class_posterior(const dc_class_posterior_params* p, dc_stream s);
 
+/* ---------------------------------------------------------------- class evidence maps */
+/* Where, not only which: the per-pixel form of the eps-error and of dc_class_posterior's paired delta.
+ * For unit u = (image b, class c, trial j) and pixel (y, x) of the model's [H, W] grid
+ *   v[u, y, x] = sum_ch (eps_hat_u[ch, y, x] - eps_bj[ch, y, x])^2          fp32, ch ascending,
+ * eps_hat formed exactly as dc_eps_mse forms it (the v-param conversion, the patch > 1 un-patchified read).  Accumulation over trials is
+ * FIXED-POINT, hence associative — the same bits for every micro-batch split, launch shape, arrival order and world size:
+ *   q = (int64) rint((double) v * 2^DC_EVIDENCE_FRAC_BITS)    for a finite v with 0 <= v <= DC_EVIDENCE_VMAX;
+ * any other v (NaN, inf, larger) adds 0 and increments the int32 counter bad[cell].  With at most 2^18 trials (the caller's limit)
+ * 2^(14 + 30 + 18) < 2^63: the int64 sum cannot overflow.
+ * dc_err_map takes dc_eps_mse's inputs and adds q to acc[cell, y, x], cell = out_index[u] / T (out_index NULL: u / T); an index outside
+ * [0, cells * T) — the errors dump cell of padded slots — goes to the extra plane `cells`.  acc int64 [cells + 1, H * W], bad int32
+ * [cells + 1]; both are accumulated into (the caller zeroes them).  A lane owns a pixel and loops over the channels; the adds are
+ * 64-bit integer global atomics, one wave adding 512 contiguous bytes.  It runs right after DC_OP_EPS_MSE, which it leaves alone. */
+#define DC_EVIDENCE_FRAC_BITS 30
+#define DC_EVIDENCE_VMAX 16384.0f
+typedef struct {
+  const float* pred; const float* eps; const float* x; const float* alpha; const float* sigma;
+  const int32_t* bj_of_unit; const int32_t* img_of_bj; const int32_t* out_index;
+  int64_t* acc; int32_t* bad;
+  int32_t n_units, C, H, W, ld, v_param, patch;
+  int32_t T, cells, pad_;
+} dc_err_map_params;
+int dc_err_map(const dc_err_map_params* p, dc_stream s);
+
+/* The maps of a finished call from per-stage accumulators: acc int64 [n_stages, BS * C + 1, HW] (slab s = the trials of stage s: the
+ * cells of [stage_ends[s - 1], stage_ends[s])), bad int32 [n_stages, BS * C + 1], stage_ends int32 [n_stages] ascending (on the
+ * device), n_eval int32 [BS, C] and winner int32 [BS] as dc_class_posterior reports them (the caller passes -1 for an image whose
+ * winner's mean is NaN).  Pruning and early stopping act at stage ends only, so n = n_eval[b, c] is 0 or a stage end; s_c = the
+ * number of stages class c was scored on (stage_ends[s_c - 1] = n), w = winner[b]:
+ *   mean_map[b, c]  = (sum_{s < s_c} acc[s, b, c]) * 2^-F / n
+ *   delta_map[b, c] = (sum_{s < s_c} (acc[s, b, c] - acc[s, b, w])) * 2^-F / n      the int64 difference is exact; it is converted
+ *                     once (to double, times 2^-F, divided by n, rounded to f32): delta_map[b, w] is exactly 0 everywhere
+ *   invalid[b]      = sum of bad[s, b, c] over the scored cells (n > 0, s < s_c) of the image
+ * Both maps of a cell are NaN for n = 0, for an n that is no stage end, for a cell with bad > 0 on its stages, and for an image
+ * with winner outside [0, C).  mean_map / delta_map [BS, C, HW] f32, invalid [BS] int32.  One pass over acc, no atomics.
+ * 1 <= n_stages <= 64. */
+typedef struct {
+  const int64_t* acc; const int32_t* bad; const int32_t* stage_ends; const int32_t* n_eval; const int32_t* winner;
+  float* mean_map; float* delta_map; int32_t* invalid;
+  int32_t n_stages, BS, C, HW;
+} dc_evidence_maps_params;
+int dc_evidence_maps(const dc_evidence_maps_params* p, dc_stream s);
+
 /* ---------------------------------------------------------------- plan ----------- */
 typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GROUPNORM = 4,
                DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8,
                DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10, DC_OP_ATTENTION_BIAS = 11, DC_OP_RMSNORM = 12,
                DC_OP_EMBED_ROWS = 13, DC_OP_RELU = 14, DC_OP_ATTENTION_CAUSAL = 15, DC_OP_LAYERNORM_ROWS = 16, DC_OP_EMBED_ROWS_POS = 17,
-               DC_OP_ACT_PASS = 18 } dc_op_kind;
+               DC_OP_ACT_PASS = 18, DC_OP_ERR_MAP = 19 } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */
