@@ -98,6 +98,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
       if (geglu) {
         if (i & 1) continue;
         oc = ((n0 + i * 16) >> 1) + lq * 4;
+        if (oc >= cout_out) continue;       // a part-empty N tile: no bias entry exists past channel Cout
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float val = acc[i][j][r], g = acc[(i + 1) % TN][j][r];

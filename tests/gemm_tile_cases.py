@@ -175,16 +175,19 @@ def igemm_fields(c, ptrs):
 
 # ---- operands -------------------------------------------------------------------------------------------------------------------
 def make_operands(c, seed=0):
-    """CPU fp32 tensors, the MFMA operands and the residual already rounded to the compute type (the kernel's operands are exactly these):
-    x0 / x1 [n_src, Hin, Win, C], w [Cout, K] with k = tap * (C0 + C1) + c (GEGLU: value rows, then gate rows), bias [Cout], tables and maps."""
+    """CPU fp32 tensors, the MFMA operands already rounded to the compute type and the residual to ITS type (the kernel's operands are
+    exactly these): x0 / x1 [n_src, Hs, Ws, C] (Hs x Ws = Hin x Win, with `upsample` the source of half those extents), w [Cout, K] with
+    k = tap * (C0 + C1) + c (GEGLU: value rows, then gate rows), bias [Cout], tables and maps."""
     gen = torch.Generator().manual_seed(1000 + seed)
     rn = lambda *s: torch.randn(*s, generator=gen)
     ri = lambda hi, n: torch.randint(0, hi, (n,), generator=gen, dtype=torch.int32)
     q = lambda t: t.to(TD[c["dtype"]]).float()
+    qr = lambda t: t.to(TD[c["res_dtype"]]).float()
     use, K, co = c["use"], k_total(c), cout_out(c)
-    o = dict(x0=q(rn(c["n_src"], c["Hin"], c["Win"], c["C0"])), w=q(rn(c["Cout"], K) / K ** 0.5))
+    Hs, Ws = (c["Hin"] // 2, c["Win"] // 2) if c["upsample"] else (c["Hin"], c["Win"])
+    o = dict(x0=q(rn(c["n_src"], Hs, Ws, c["C0"])), w=q(rn(c["Cout"], K) / K ** 0.5))
     if c["C1"]:
-        o["x1"] = q(rn(c["n_src"], c["Hin"], c["Win"], c["C1"]))
+        o["x1"] = q(rn(c["n_src"], Hs, Ws, c["C1"]))
     for m in ("map0", "map1"):
         if m in use:
             o[m] = ri(c["n_src"], c["n_img"])
@@ -199,18 +202,21 @@ def make_operands(c, seed=0):
         if "gate_map" in use:
             o["gate_map"] = ri(c["n_vec"], c["n_img"])
     if "residual" in use:
-        o["residual"] = q(rn(c["n_res"] if "res_map" in use else c["n_img"], c["Hout"] * c["Wout"], co))
+        o["residual"] = qr(rn(c["n_res"] if "res_map" in use else c["n_img"], c["Hout"] * c["Wout"], co))
         if "res_map" in use:
             o["res_map"] = ri(c["n_res"], c["n_img"])
     return o
 
 
 def a_matrix(c, o, dtype=torch.float64):
-    """The GEMM's A operand [M, K] (the gather through the sample maps and, for 9 taps, the zero-padded 3x3 stride-2 patches, k = tap * C + ch)."""
+    """The GEMM's A operand [M, K] (the gather through the sample maps, with `upsample` the nearest 2x of the gathered source, and, for
+    9 taps, the zero-padded 3x3 patches at the case's stride, k = tap * C + ch)."""
     x = o["x0"][o["map0"].long()] if "map0" in o else o["x0"]
     if c["C1"]:
         x = torch.cat([x, o["x1"][o["map1"].long()] if "map1" in o else o["x1"]], -1)
     x = x.to(dtype)
+    if c["upsample"]:
+        x = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
     C = x.shape[-1]
     if c["taps"] == 1:
         return x.reshape(-1, C)
@@ -298,19 +304,25 @@ def e_act(tag, x, fast):
 # not run on a device; fill in from its first run.
 
 
-def reference(c, o):
+def reference(c, o, A=None, amb=None, detail=False):
     """(ref, bound): the fp64 result of the documented epilogue  (+bias)(+rowvec) -> act -> (*gate)(+residual)  over every output element
     [M, cout_out], and the per-element bound on |got - ref|:
 
         1.02 u_out |ref| + floor + 2 e,   e = the forward error of the fp32 evaluation:
         act NONE:    e = (K + 8) 2^-24 ((|A| |W|^T + |bias| + |rowvec|) |gate| + |residual|)
-        SiLU / GELU: e = LIP e_pre + e_act(x) (+ (K + 8) 2^-24 |residual|),  e_pre = (K + 8) 2^-24 (|A| |W|^T + |bias| + |rowvec|)
+        SiLU / GELU: e = (LIP e_pre + e_act(x)) |gate| (+ (K + 8) 2^-24 |residual|),  e_pre = (K + 8) 2^-24 (|A| |W|^T + |bias| + |rowvec|)
         GEGLU:       e = |gelu(g)| e_pre(u) + |u| (LIP e_pre(g) + e_act(g)) (+ the residual term)
 
-    (K + 8) 2^-24 is the forward bound of an fp32 dot product of length K in any summation order plus the handful of epilogue operations;
+    (K + 8) 2^-24 is the forward bound of an fp32 dot product of length K in any summation order plus the handful of epilogue operations
+    (a gate behind an activation is one of them: |act(x)| <= |x|, so its rounding is within 2^-24 of what e_pre already weighs);
     the factor 2 because the matrix core's internal accumulation is not documented to round every addition to nearest.  u_out / floor: the
-    rounding of the stored value (U_OUT, FLOOR).  Nothing here comes from what a kernel returned."""
-    A, W = a_matrix(c, o), o["w"].double()
+    rounding of the stored value (U_OUT, FLOOR).  Nothing here comes from what a kernel returned.
+
+    A, amb: a prologue's A operand [M, K] in place of a_matrix(c, o), and how far the device's copy of each of its elements may lie from
+    it (tests/gemm_small_cases.py: the fused row LayerNorm).  amb |W|^T then takes the way of e_pre through the epilogue — without the
+    factor 2: it is a statement about the operand, not about the accumulation — and joins the bound.  detail: a third value, the dict of
+    that term per output element (`amb`) and the forward error (`e`)."""
+    A, W = a_matrix(c, o) if A is None else A, o["w"].double()
     K, tag = k_total(c), c["tag"]
     pre, S = A @ W.t(), A.abs() @ W.abs().t()
     del A
@@ -323,24 +335,27 @@ def reference(c, o):
         S += rv.abs()
     gam = (K + 8) * EPS32
     e_pre = gam * S
-    fast = c["dtype"] != F32
+    a_pre = torch.zeros_like(S) if amb is None else amb @ W.abs().t()
+    fast = c.get("fast_act", c["dtype"] != F32)      # the tile kernels: v_exp_f32 / v_rcp_f32 forms for 16-bit types; the cases of igemm.hip say otherwise
     if c["act"] == ACT_NONE:
-        val, e = pre, e_pre
-        if "gate" in o:
-            gt = per_row(c, o, "gate", "gate_map").double()
-            val, e = val * gt, e * gt.abs()
+        val, e, a_out = pre, e_pre, a_pre
     elif c["act"] == ACT_SILU:
-        val, e = F.silu(pre), LIP * e_pre + e_act("silu", pre, fast)
+        val, e, a_out = F.silu(pre), LIP * e_pre + e_act("silu", pre, fast), LIP * a_pre
     elif c["act"] == ACT_GELU_TANH:
-        val, e = F.gelu(pre, approximate="tanh"), LIP * e_pre + e_act("gelu_tanh", pre, fast)
+        val, e, a_out = F.gelu(pre, approximate="tanh"), LIP * e_pre + e_act("gelu_tanh", pre, fast), LIP * a_pre
     else:
-        (u, g), (eu, eg) = pre.chunk(2, dim=-1), e_pre.chunk(2, dim=-1)
+        (u, g), (eu, eg), (au, ag) = pre.chunk(2, dim=-1), e_pre.chunk(2, dim=-1), a_pre.chunk(2, dim=-1)
         gg = F.gelu(g)
-        val, e = u * gg, gg.abs() * eu + u.abs() * (LIP * eg + e_act("geglu", g, fast))
+        val, e, a_out = u * gg, gg.abs() * eu + u.abs() * (LIP * eg + e_act("geglu", g, fast)), gg.abs() * au + u.abs() * LIP * ag + LIP * au * ag
+    if "gate" in o and c["act"] != ACT_GEGLU:
+        gt = per_row(c, o, "gate", "gate_map").double()
+        val, e, a_out = val * gt, e * gt.abs(), a_out * gt.abs()
     if "residual" in o:
         r = residual_rows(c, o).double()
         val, e = val + r, e + gam * r.abs()
-    bound = 1.02 * U_OUT[c["out_dtype"]] * val.abs() + FLOOR[c["out_dtype"]] + 2.0 * e
+    bound = 1.02 * U_OUT[c["out_dtype"]] * val.abs() + FLOOR[c["out_dtype"]] + 2.0 * e + a_out
+    if detail:
+        return val, bound, dict(amb=a_out, e=e)
     return val, bound
 
 
