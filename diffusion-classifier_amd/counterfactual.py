@@ -9,6 +9,8 @@ reset in front of each run, and compares the generated images.  `DiffusionClassi
 HIP backbones run all BS x K trajectories as the units of one pair session per chunk of images (`run_hip`: the prompts are projected
 once per call, the step scalars are formed before the loop, nothing is copied to the host inside it; `dc_ddpm_step_shared`,
 `dc_abs_diff_map`).  A foreign nn.Module takes the reference's own form in eager torch (`run_foreign`): it is the written statement.
+With config.sampler = "ddim" | "dpmpp_2m" (solver.py) the trajectories are deterministic after their start (`dc_solver_step`), and
+start="invert" takes that start from DDIM inversion of the image instead of from noise.
 """
 import ctypes as C
 from collections import namedtuple
@@ -16,6 +18,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from . import solver as S
 
 Counterfactuals = namedtuple("Counterfactuals", ["samples", "classes", "maps"])
 Counterfactuals.__doc__ = """Result of `DiffusionClassifier.counterfactual` (tensors on the input's device).
@@ -85,12 +88,16 @@ def image_chunks(BS, K, units):
     return [(b0, min(BS, b0 + per)) for b0 in range(0, BS, per)]
 
 
-def run_foreign(dc, backbone, x, cl, from_t):
+def run_foreign(dc, backbone, x, cl, from_t, sampler=None, z0=None):
     """The reference's form: per step and class one conditional and one null call at batch BS and `ddpm_sampler_step`, every class
-    adding the step's one `randn_like` — op for op what K calls of `sample` with the seed reset in front of each compute."""
+    adding the step's one `randn_like` — op for op what K calls of `sample` with the seed reset in front of each compute.
+    sampler "ddim" / "dpmpp_2m": the K classes by `solver.run_eager` from the one start instead, no draw after it; z0 [BS, C, H, W]:
+    that start (an inverted latent) in place of the noised image, no draw at all."""
     dev = x.device
     BS, K = cl.shape
-    if from_t == 1:
+    if z0 is not None:
+        pass
+    elif from_t == 1:
         z0 = torch.randn(x.shape).to(dev)
     else:
         lam = dc.schedule(torch.ones(BS) * from_t).to(dev)
@@ -99,6 +106,10 @@ def run_foreign(dc, backbone, x, cl, from_t):
     labs = [cl[:, k].to(lab_dev) for k in range(K)]
     conds = [dc.encode_text_prompt(lab).to(dev) for lab in labs]
     null = dc.encode_text_prompt(torch.full_like(labs[0], dc.null_token)).to(dev)
+    if sampler is not None:
+        lams = S.grid_lams(dc, from_t, 0.0)
+        scal = S.step_scalars(lams, sampler, "denoise")
+        return torch.stack([S.run_eager(dc, z0, lams, scal, dc.cfg_w, cond, null) for cond in conds], dim=1).to(torch.float32)
     steps = torch.linspace(from_t, 0.0, dc.config.sampling_steps + 1)
     n = len(steps) - 1
     zs = [z0] * K
@@ -117,10 +128,14 @@ def run_foreign(dc, backbone, x, cl, from_t):
         zs = [mu + noise * torch.sqrt(var) for mu in mus]
 
 
-def run_hip(dc, backbone, x, cl, from_t, rng, seed, units):
+def run_hip(dc, backbone, x, cl, from_t, rng, seed, units, sampler=None, z0=None, invert=False, w=None):
     """All BS x K trajectories on a HIP backbone: trajectory b * K + k is one image of a pair session (unit pair: class token || null
     token), the loop is step-major and chunk-minor, the noise of a step is drawn for the whole batch and read by the K trajectories
-    of an image through `dc_ddpm_step_shared`."""
+    of an image through `dc_ddpm_step_shared`.
+    sampler "ddim" / "dpmpp_2m" (solver.py): sampling_steps deterministic passes, one `dc_solver_step` per step and chunk, no draw
+    after the start, one history buffer of data predictions for the second-order passes.  z0 [BS, C, H, W]: the start, in place of the
+    noised image (no draw at all).  invert: the grid is walked upwards from z = alpha(lam(0)) x to `from_t` (DDIM inversion; K = 1,
+    the labels are cl[:, 0]).  w: the guidance weight, config.cfg_w when None."""
     lib = L.require_gpu()
     if not x.is_cuda:
         raise L.DcamdError("counterfactual on a HIP backbone needs a CUDA/HIP tensor (as sample does; no CPU fallback)")
@@ -135,15 +150,20 @@ def run_hip(dc, backbone, x, cl, from_t, rng, seed, units):
     philox = rng == "philox"
     if philox and CHW % 4:
         raise L.DcamdError(f"rng='philox' needs C * H * W to be a multiple of 4, got {CHW}")
-    steps = torch.linspace(from_t, 0.0, dc.config.sampling_steps + 1)
+    steps = torch.linspace(0.0, from_t, dc.config.sampling_steps + 1) if invert else torch.linspace(from_t, 0.0, dc.config.sampling_steps + 1)
     n = len(steps) - 1
 
     # ---- before the loop: lambda of every grid point (0-dim evaluations, as `sample` forms them), the scalars of every pass ----
     lams = [dc.schedule(steps[j]) for j in range(n + 1)]
     lam_dev = torch.stack([v.detach().float().reshape(()) for v in lams]).to(dev)
-    passes = [(i, i + 1) if i < n else (n - 1, n) for i in range(n + 1)]
-    scal = [dc._sampler_step_scalars(lams[t], lams[s]) for t, s in passes]
-    w, one_plus_w, v_param = float(dc.cfg_w), float(1.0 + float(dc.cfg_w)), int(dc.pred_param == 'v')
+    if sampler is None:
+        passes = [(i, i + 1) if i < n else (n - 1, n) for i in range(n + 1)]
+        scal = [dc._sampler_step_scalars(lams[t], lams[s]) for t, s in passes]
+    else:
+        passes = [(i, i + 1) for i in range(n)]
+        scal = S.step_scalars(lams, sampler, "invert" if invert else "denoise")
+    w = float(dc.cfg_w) if w is None else float(w)
+    one_plus_w, v_param = float(1.0 + w), int(dc.pred_param == 'v')
 
     # ---- noise: torch's generators in `sample`'s order, or Philox rows b (initial) and (step + 1) * BS + b ----
     if philox:
@@ -153,7 +173,11 @@ def run_hip(dc, backbone, x, cl, from_t, rng, seed, units):
         def draw(row0):
             L.check(lib.dc_philox_normal(nbuf.data_ptr(), BS, CHW, row_ids[row0:row0 + BS].data_ptr(), int(seed), L.stream_ptr()), "dc_philox_normal")
             return nbuf
-    if from_t == 1:
+    if z0 is not None:
+        pass
+    elif invert:
+        z0 = torch.sqrt(torch.sigmoid(lams[0])).to(dev) * x
+    elif from_t == 1:
         z0 = draw(0).clone() if philox else torch.randn(x.shape).to(dev)
     else:
         lam = dc.schedule(torch.ones(BS) * from_t).to(dev)
@@ -161,6 +185,7 @@ def run_hip(dc, backbone, x, cl, from_t, rng, seed, units):
         z0 = al * x + sg * draw(0) if philox else dc.diffuse(x, al, sg)[0]
     za = z0.detach().to(torch.float32).repeat_interleave(K, dim=0).contiguous()          # trajectory b * K + k starts from z0[b]
     zb = torch.empty_like(za)
+    hist = torch.empty_like(za) if sampler is not None and any(sc[4] is not None for sc in scal) else None   # x of the pass before
 
     # ---- once per call and chunk: contexts, lengths, the context plan ----
     chunks = image_chunks(BS, K, units)
@@ -177,13 +202,25 @@ def run_hip(dc, backbone, x, cl, from_t, rng, seed, units):
 
     # ---- the loop: step-major, chunk-minor; no device -> host copy ----
     for i, (t, _s) in enumerate(passes):
-        c, alpha_t, sigma_t, alpha_s, sd = scal[i]
         noise = None
-        if i < n:
-            noise = draw((i + 1) * BS) if philox else torch.randn_like(z0).to(torch.float32).contiguous()
+        if sampler is None:
+            c, alpha_t, sigma_t, alpha_s, sd = scal[i]
+            if i < n:
+                noise = draw((i + 1) * BS) if philox else torch.randn_like(z0).to(torch.float32).contiguous()
+        else:
+            alpha_t, sigma_t, k1, k2, k3, final = scal[i]
         for (b0, b1), ses in zip(chunks, sessions):
             zc = za[b0 * K:b1 * K]
             pair = ses.step(zc, lam_dev[t:t + 1])
+            if sampler is not None:
+                # 2M: pass 0 writes the history, a second-order pass reads its element and writes it again; the final pass needs none
+                hc = None if hist is None or final else hist[b0 * K:b1 * K].data_ptr()
+                p = L.SolverStepParams(z=zc.data_ptr(), pred=pair.data_ptr(), xprev=hc if k3 is not None else None, xhat=hc,
+                                       out=zb[b0 * K:b1 * K].data_ptr(), n=(b1 - b0) * K, C=Cc, H=H, W=W, ld=pair.shape[-1], patch=patch,
+                                       v_param=v_param, clamp=1, final_pass=int(final), w=w, one_plus_w=one_plus_w, alpha_t=alpha_t,
+                                       sigma_t=sigma_t, k1=k1, k2=k2, k3=0.0 if k3 is None else k3)
+                L.check(lib.dc_solver_step(C.byref(p), L.stream_ptr()), "dc_solver_step")
+                continue
             p = L.DdpmStepSharedParams(z=zc.data_ptr(), pred=pair.data_ptr(), noise=None if noise is None else noise[b0:b1].data_ptr(),
                                        out=zb[b0 * K:b1 * K].data_ptr(), n=(b1 - b0) * K, C=Cc, H=H, W=W, ld=pair.shape[-1], patch=patch,
                                        v_param=v_param, noise_div=K, w=w, alpha_t=alpha_t, sigma_t=sigma_t, alpha_s=alpha_s, c=c, sd=sd,
@@ -194,8 +231,16 @@ def run_hip(dc, backbone, x, cl, from_t, rng, seed, units):
 
 
 @torch.no_grad()
-def run(dc, x, classes, from_t, against, rng, seed, pixel_space, units_per_launch):
+def run(dc, x, classes, from_t, against, rng, seed, pixel_space, units_per_launch, start="noise", invert_class=None):
     """`DiffusionClassifier.counterfactual` (its docstring is the interface); units_per_launch(H, W, k) is classify's launch-size rule."""
+    sampler = S.sampler_of(dc.config)
+    if start not in ("noise", "invert"):
+        raise ValueError(f"start must be 'noise' or 'invert', got {start!r}")
+    if start == "invert" and sampler is None:
+        raise ValueError("start='invert' needs a deterministic config.sampler ('ddim' or 'dpmpp_2m'): ancestral DDPM adds fresh noise to "
+                         "the inverted latent at every step, which defeats the inversion")
+    if start == "noise" and invert_class is not None:
+        raise ValueError("invert_class belongs to start='invert'")
     if rng not in ("reference", "philox"):
         raise ValueError(f"rng must be 'reference' or 'philox', got {rng!r}")
     from_t = float(from_t)
@@ -216,13 +261,18 @@ def run(dc, x, classes, from_t, against, rng, seed, pixel_space, units_per_launc
         base = base_rows(against, cl)
     backbone = dc.ema.ema_model
     hip = hasattr(backbone, "pair_session")
-    if hip:
-        samples = run_hip(dc, backbone, x, cl, from_t, rng, seed, units_per_launch(x.shape[2], x.shape[3], 2 * K))
-    else:
+    if not hip:
         if rng == "philox":
             raise L.DcamdError("rng='philox' needs a HIP backbone (UNetCondition2D / DiT)")
         dc._refuse_ragged_on_foreign()
-        samples = run_foreign(dc, backbone, x, cl, from_t)
+    z0 = None
+    if start == "invert":
+        inv = S.label_rows(invert_class, BS, dc.config.classes, "invert_class")
+        z0 = S.invert(dc, x, inv, from_t, 0.0, units_per_launch)         # z_{from_t} of the image itself: no noise is drawn
+    if hip:
+        samples = run_hip(dc, backbone, x, cl, from_t, rng, seed, units_per_launch(x.shape[2], x.shape[3], 2 * K), sampler=sampler, z0=z0)
+    else:
+        samples = run_foreign(dc, backbone, x, cl, from_t, sampler=sampler, z0=z0)
     flat = samples.reshape((BS * K,) + tuple(samples.shape[2:])).contiguous()
     xb = x.detach().to(torch.float32).contiguous()
     if pixel_space:

@@ -295,6 +295,59 @@ extern "C" int dc_ddpm_step_shared(const dc_ddpm_step_shared_params* p, dc_strea
   return ddpm_step_launch("dc_ddpm_step_shared", a, p->H, stream);
 }
 
+// ------------------------------------------------------------------ solver step ----
+// One pass of a deterministic data-prediction solver on the same prediction pair (include/dcamd.h dc_solver_step): the guidance mix and
+// the x-prediction are ddpm_step_kernel's, then the update z_s = k1 z + k2 D with D = x (DDIM) or x + k3 (x - xprev) (DPM-Solver++ 2M).
+// Same indexing as ddpm_step_kernel, the operation order of the header's expressions, no contraction.  xhat may be xprev's buffer: a
+// thread reads its element of xprev before it writes the same element of xhat, and no other thread touches that element.
+struct SolverArgs {
+  const float* z; const float* pred; const float* xprev; float* xhat; float* out;
+  int C, HW, W, ld, patch, v_param, clamp, final_pass, n;
+  float w, one_plus_w, alpha_t, sigma_t, k1, k2, k3;
+};
+
+__global__ __launch_bounds__(256) void solver_step_kernel(const SolverArgs a) {
+#pragma clang fp contract(off)
+  const size_t CHW = (size_t)a.C * a.HW, total = CHW * a.n;
+  const size_t rows = a.patch > 1 ? (size_t)a.HW / (a.patch * a.patch) : (size_t)a.HW;
+  for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int b = (int)(i / CHW);
+    const size_t r = i - (size_t)b * CHW;
+    const int c = (int)(r / a.HW), p = (int)(r - (size_t)c * a.HW);
+    size_t pi;
+    if (a.patch > 1) {
+      const int y = p / a.W, xw = p - y * a.W, pp = a.patch;
+      pi = ((size_t)(y / pp) * (a.W / pp) + xw / pp) * a.ld + (size_t)((y % pp) * pp + xw % pp) * a.C + c;
+    } else {
+      pi = (size_t)p * a.ld + c;
+    }
+    const float pc = a.pred[(size_t)(2 * b) * rows * a.ld + pi], pu = a.pred[(size_t)(2 * b + 1) * rows * a.ld + pi];
+    const float zt = a.z[i];
+    const float pr = a.one_plus_w * pc - a.w * pu;
+    float x = a.v_param ? a.alpha_t * zt - a.sigma_t * pr : (zt - a.sigma_t * pr) / a.alpha_t;
+    if (a.clamp) x = fminf(fmaxf(x, -1.f), 1.f);
+    float D = x;
+    if (a.xprev) D = x + a.k3 * (x - a.xprev[i]);                                // read before the write below: xhat may be xprev
+    if (a.xhat) a.xhat[i] = x;
+    a.out[i] = a.final_pass ? fminf(fmaxf(D, -1.f), 1.f) : a.k1 * zt + a.k2 * D;
+  }
+}
+
+extern "C" int dc_solver_step(const dc_solver_step_params* p, dc_stream stream) {
+  DC_REQUIRE(p, DC_ERR_ARG, "dc_solver_step: null pointer");
+  DC_REQUIRE(p->z && p->pred && p->out, DC_ERR_ARG, "dc_solver_step: null pointer");
+  DC_REQUIRE(p->out != p->z, DC_ERR_ARG, "dc_solver_step: out must not alias z");
+  const int pp = p->patch > 1 ? p->patch : 1;
+  DC_REQUIRE(p->n > 0 && p->C > 0 && p->H > 0 && p->W > 0 && p->ld >= p->C * pp * pp, DC_ERR_SHAPE, "dc_solver_step: extents");
+  DC_REQUIRE(p->H % pp == 0 && p->W % pp == 0, DC_ERR_SHAPE, "dc_solver_step: patch=%d does not tile %dx%d", pp, p->H, p->W);
+  SolverArgs a{p->z, p->pred, p->xprev, p->xhat, p->out, p->C, p->H * p->W, p->W, p->ld, pp, p->v_param, p->clamp, p->final_pass, p->n,
+               p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->k1, p->k2, p->k3};
+  const size_t total = (size_t)p->n * p->C * a.HW;
+  const unsigned grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+  hipLaunchKernelGGL(solver_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return dc_check_launch("dc_solver_step");
+}
+
 // ------------------------------------------------------------------ difference maps -
 // One lane per output pixel: the C planes of a and of its reference row are read coalesced across the wave, summed in channel order.
 __global__ __launch_bounds__(256) void abs_diff_map_kernel(const float* __restrict__ a, const float* __restrict__ r,

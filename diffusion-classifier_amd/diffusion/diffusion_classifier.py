@@ -79,7 +79,9 @@ Extra keyword-only arguments (defaults keep the reference behaviour):
                  exactly like the reference (:615-617).
 
 Additive: `.counterfactual(x, classes, from_t, ...)` — every class from shared noise in one call, with difference maps (the
-reference's experiments/ipmsa/explain.py procedure; counterfactual.py).
+reference's experiments/ipmsa/explain.py procedure; counterfactual.py).  `config.sampler` ("ddim" | "dpmpp_2m"; unset or "ddpm": the
+ancestral sampler) makes `sample` and `counterfactual` deterministic after their start, `.invert(x, text, to_t)` is DDIM inversion and
+`counterfactual(..., start="invert")` decodes every class from the image's own inverted latent (solver.py).
 """
 import math
 import os
@@ -93,6 +95,7 @@ from .. import dist as D
 from .. import counterfactual as CF
 from .. import posterior as P
 from .. import evidence as EV
+from .. import solver as S
 from .._ema import EMA
 
 
@@ -596,7 +599,13 @@ class DiffusionClassifier(nn.Module):
 
     @torch.no_grad()
     def sample(self, x, text=None, from_t=1):
-        """Ancestral DDPM sampling with classifier-free guidance (reference :210-293), same RNG consumption order as the reference."""
+        """Ancestral DDPM sampling with classifier-free guidance (reference :210-293), same RNG consumption order as the reference.
+        config.sampler = "ddim" | "dpmpp_2m" (additive; unset or "ddpm": everything below, untouched): the start is drawn as ever, then
+        sampling_steps deterministic passes on linspace(from_t, 0, sampling_steps + 1) (solver.py) — only the initial draw is taken
+        from torch's generator."""
+        sampler = S.sampler_of(self.config)
+        if sampler is not None:
+            return S.sample(self, x, text, from_t, sampler, lambda H, W, k: _units_per_launch(self.config, H, W, k))
         dev = x.device
         if from_t == 1:
             z_t = torch.randn(x.shape).to(dev)
@@ -635,7 +644,8 @@ class DiffusionClassifier(nn.Module):
             z_t = mu + torch.randn_like(mu) * torch.sqrt(var)
 
     @torch.no_grad()
-    def counterfactual(self, x, classes=None, from_t=0.5, *, against="input", rng="reference", seed=0, pixel_space=False):
+    def counterfactual(self, x, classes=None, from_t=0.5, *, against="input", rng="reference", seed=0, pixel_space=False,
+                       start="noise", invert_class=None):
         """Every class from shared noise in one call (reference experiments/ipmsa/explain.py: noise to `from_t`, denoise once per label
         with the seed reset in front of each run, look at where the results differ) -> `Counterfactuals(samples, classes, maps)`.
           classes      None: all config.classes; an int tensor [K] (the same for every image) or [BS, K]; K >= 1, duplicates allowed
@@ -656,9 +666,28 @@ class DiffusionClassifier(nn.Module):
         HIP backbones: the BS x K trajectories are the images of pair sessions (nets/unet.py PairSession: prompts projected once per
         call), cut into chunks of whole images by classify's launch-size rule (config.units_per_launch), step-major and chunk-minor, one
         `dc_ddpm_step_shared` per step and chunk, the maps by `dc_abs_diff_map`; nothing is copied to the host inside the loop.  A
-        foreign nn.Module takes the reference's eager form at batch BS and is bit-identical to the K reseeded `sample` calls."""
+        foreign nn.Module takes the reference's eager form at batch BS and is bit-identical to the K reseeded `sample` calls.
+        config.sampler = "ddim" | "dpmpp_2m" (additive; unset or "ddpm": all of the above, untouched): the K trajectories are
+        deterministic after their start — sampling_steps passes, one `dc_solver_step` per step and chunk, no draw per step.
+          start        "noise": the start is drawn as above (torch, or Philox row b);
+                       "invert": the start is `invert(x, invert_class, from_t)`, the image's own z_{from_t} — no noise at all, the call
+                       touches no generator and returns the same bits every time; needs a deterministic config.sampler (ValueError
+                       otherwise: noise added to an inverted latent defeats it)
+          invert_class an int tensor [BS] of class ids to invert under (the label `classify` returned, say); None: the null token"""
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space,
-                      lambda H, W, k: _units_per_launch(self.config, H, W, k))
+                      lambda H, W, k: _units_per_launch(self.config, H, W, k), start=start, invert_class=invert_class)
+
+    @torch.no_grad()
+    def invert(self, x, text=None, to_t=0.5, *, guidance=0.0):
+        """DDIM inversion: the latent z_{to_t} [BS, C, H, W] f32 that the deterministic sampler decodes back to x (up to the solver's
+        error, which shrinks as 1 / sampling_steps and is not small at few steps).  The grid is linspace(0, to_t, sampling_steps + 1),
+        the start z = alpha(lam(0)) x, then sampling_steps first-order passes upwards with the data prediction clipped.
+          text      an int tensor [BS] of class ids to condition on; None: the null token
+          guidance  the w of the inversion only (config.cfg_w is not read).  0, the default, is the conditional prediction alone: guided
+                    inversion is known to be unstable
+        Works whatever config.sampler says (always DDIM).  HIP backbones run a pair session per chunk of images and one `dc_solver_step`
+        per step and chunk; a foreign nn.Module takes the eager form (solver.py)."""
+        return S.invert(self, x, text, to_t, guidance, lambda H, W, k: _units_per_launch(self.config, H, W, k))
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----
     @torch.no_grad()

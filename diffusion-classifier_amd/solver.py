@@ -1,0 +1,179 @@
+"""Deterministic samplers and DDIM inversion for `sample`, `counterfactual` and `invert` (config.sampler = "ddim" | "dpmpp_2m").
+
+The schedule is a log-SNR schedule, so the half-log-SNR step of the data-prediction solvers is exact: h = (lam_s - lam_t) / 2.  One pass
+from grid point t to grid point s, on the guided prediction pr = (1 + w) pred_c - w pred_u:
+  x   = alpha_t z - sigma_t pr  (v)   |   (z - sigma_t pr) / alpha_t  (eps);   x = clip(x, -1, 1)
+  D   = x                            first order: DDIM, z_s = alpha_s x + sigma_s (z - alpha_t x) / sigma_t, in either direction
+      = x + k3 (x - x_prev)          second order: DPM-Solver++(2M), k3 = h / (2 h_prev)
+  z_s = k1 z + k2 D                  k1 = sigma_s / sigma_t, k2 = -alpha_s expm1(-h) (= alpha_s - alpha_t sigma_s / sigma_t)
+The last denoising pass returns clip(x) at the last grid point, so n steps are n backbone passes (ancestral DDPM makes n + 1).
+Inversion walks the grid upwards (h < 0), first order throughout, and starts from z = alpha(lam(0)) x.
+
+`eager_pass` / `run_eager` are the written statement — two backbone calls per pass and the expressions above in fp32 torch — and the
+path of a foreign nn.Module.  HIP backbones run the same passes as `counterfactual.run_hip`'s loop with one `dc_solver_step` per step
+and chunk.
+"""
+import torch
+
+SAMPLERS = ("ddim", "dpmpp_2m")
+
+
+def sampler_of(config):
+    """config.sampler -> None (unset or "ddpm": the ancestral path, untouched) | "ddim" | "dpmpp_2m"; anything else: ValueError."""
+    s = config.sampler
+    if s is None or s == "ddpm":
+        return None
+    if isinstance(s, str) and s in SAMPLERS:
+        return s
+    raise ValueError(f"config.sampler must be one of 'ddpm', 'ddim', 'dpmpp_2m' (unset: 'ddpm'), got {s!r}")
+
+
+def grid_lams(dc, u_from, u_to):
+    """lambda at the points of linspace(u_from, u_to, sampling_steps + 1): 0-dim evaluations of the schedule, as `sample` forms them."""
+    steps = torch.linspace(u_from, u_to, dc.config.sampling_steps + 1)
+    return [dc.schedule(steps[j]) for j in range(len(steps))]
+
+
+def step_scalars(lams, sampler, direction):
+    """The per-pass scalars of a walk over the grid `lams` (n + 1 lambdas in the order they are visited) as Python floats, from fp32
+    torch ops on 0-dim tensors on the host: [(alpha_t, sigma_t, k1, k2, k3 | None, final)] of n passes.
+      direction "denoise": pass 0 is first order (k3 None); with "dpmpp_2m" passes 1 .. n-2 are second order; pass n-1 is `final` (first
+                           order, it returns the clipped data prediction)
+      direction "invert":  first order throughout, no final pass"""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if direction not in ("denoise", "invert"):
+        raise ValueError(f"direction must be 'denoise' or 'invert', got {direction!r}")
+    lam = [v.detach().float().cpu().reshape(()) for v in lams]
+    n = len(lam) - 1
+    out, h_prev = [], None
+    for i in range(n):
+        lt, ls = lam[i], lam[i + 1]
+        alpha_t, alpha_s = torch.sqrt(torch.sigmoid(lt)), torch.sqrt(torch.sigmoid(ls))
+        sigma_t, sigma_s = torch.sqrt(torch.sigmoid(-lt)), torch.sqrt(torch.sigmoid(-ls))
+        h = (ls - lt) / 2
+        k1 = sigma_s / sigma_t
+        k2 = -alpha_s * torch.special.expm1(-h)
+        final = direction == "denoise" and i == n - 1
+        second = sampler == "dpmpp_2m" and direction == "denoise" and 1 <= i <= n - 2
+        k3 = float(0.5 * h / h_prev) if second else None
+        out.append((float(alpha_t), float(sigma_t), float(k1), float(k2), k3, final))
+        h_prev = h
+    return out
+
+
+def eager_pass(dc, z, pred, u_pred, w, sc, x_prev, clamp=True):
+    """One pass in torch, the statement of `dc_solver_step`: -> (z_s or the final image, x for the next pass's history)."""
+    alpha_t, sigma_t, k1, k2, k3, final = sc
+    pr = (1 + w) * pred - w * u_pred
+    x = alpha_t * z - sigma_t * pr if dc.pred_param == 'v' else (z - sigma_t * pr) / alpha_t
+    if clamp:
+        x = dc.clip(x)
+    D = x + k3 * (x - x_prev) if k3 is not None else x
+    return (dc.clip(D) if final else k1 * z + k2 * D), x
+
+
+def run_eager(dc, z, lams, scal, w, cond, null, lens=None):
+    """The passes `scal` from z on the grid `lams`: per pass one conditional and one null backbone call at z's batch."""
+    dev = z.device
+    kc = {"encoder_lengths": lens["cond"]} if lens else {}
+    kn = {"encoder_lengths": lens["null"]} if lens else {}
+    x_prev = None
+    for i, sc in enumerate(scal):
+        lam_t = lams[i].to(dev).unsqueeze(0)
+        pred = dc.ema(z, lam_t, encoder_hidden_states=cond, **kc)
+        u_pred = dc.ema(z, lam_t, encoder_hidden_states=null, **kn)
+        z, x_prev = eager_pass(dc, z, pred, u_pred, w, sc, x_prev)
+    return z
+
+
+def initial_latent(dc, x, from_t):
+    """`sample`'s start: randn for from_t == 1, else diffuse(x) to from_t — one draw from torch's generator."""
+    dev = x.device
+    if from_t == 1:
+        return torch.randn(x.shape).to(dev)
+    lam = dc.schedule(torch.ones(x.shape[0]) * from_t).to(dev)
+    return dc.diffuse(x, torch.sqrt(torch.sigmoid(lam)).view(-1, 1, 1, 1), torch.sqrt(torch.sigmoid(-lam)).view(-1, 1, 1, 1))[0]
+
+
+def contexts(dc, text, dev, backbone):
+    """(cond, null, lens) of `sample`: the encoded labels, the encoded null token and, for a ragged prompt table, the rows' token counts."""
+    cond = null = None
+    lens = None
+    if text is not None and dc.encoder_type is not None:
+        cond = dc.encode_text_prompt(text).to(dev)
+        null = dc.encode_text_prompt(torch.full_like(text, dc.null_token)).to(dev)
+        if dc._ragged_table():
+            if not hasattr(backbone, "make_plan"):
+                dc._refuse_ragged_on_foreign()
+            ln = dc.encoder.lengths.cpu()
+            lens = dict(cond=ln[text.detach().cpu()], null=ln[torch.full_like(text, dc.null_token).cpu()])
+    return cond, null, lens
+
+
+def decode_eager(dc, z, text, from_t, sampler):
+    """The latent z at from_t decoded under the labels `text` in eager torch on any backbone: n passes on
+    linspace(from_t, 0, sampling_steps + 1) with config.cfg_w."""
+    cond, null, lens = contexts(dc, text, z.device, dc.ema.ema_model)
+    lams = grid_lams(dc, from_t, 0.0)
+    return run_eager(dc, z, lams, step_scalars(lams, sampler, "denoise"), dc.cfg_w, cond, null, lens)
+
+
+def sample_eager(dc, x, text, from_t, sampler):
+    """`sample` under a deterministic sampler in eager torch: the start as ever, then `decode_eager`."""
+    return decode_eager(dc, initial_latent(dc, x, from_t), text, from_t, sampler)
+
+
+def sample(dc, x, text, from_t, sampler, units_per_launch):
+    """`DiffusionClassifier.sample` with config.sampler set.  A HIP backbone with labels runs the trajectories as a pair session
+    (`counterfactual.run_hip` with one class per image); everything else takes the eager form."""
+    backbone = dc.ema.ema_model
+    if hasattr(backbone, "pair_session") and text is not None and dc.encoder_type is not None and x.is_cuda:
+        from . import counterfactual as CF
+        cl = text.detach().cpu().reshape(-1, 1).to(torch.int64)
+        out = CF.run_hip(dc, backbone, x, cl, from_t, "reference", 0, units_per_launch(x.shape[2], x.shape[3], 2), sampler=sampler)
+        return out[:, 0]
+    return sample_eager(dc, x, text, from_t, sampler)
+
+
+def label_rows(text, BS, n_classes, name):
+    """An int tensor [BS] of class ids (None: the null token, id n_classes) -> int64 [BS] on the CPU, validated."""
+    if text is None:
+        return torch.full((BS,), n_classes, dtype=torch.int64)
+    lab = torch.as_tensor(text).detach().cpu()
+    if lab.dtype.is_floating_point or lab.dtype == torch.bool or lab.dim() != 1 or lab.numel() != BS:
+        raise ValueError(f"{name} must be None or an int tensor [{BS}] of class ids, got {lab.dtype} {tuple(lab.shape)}")
+    lab = lab.to(torch.int64).contiguous()
+    if int(lab.min()) < 0 or int(lab.max()) > n_classes:
+        raise ValueError(f"{name}: class ids must lie in [0, {n_classes}] ({n_classes}: the null token), got {lab.tolist()}")
+    return lab
+
+
+def invert_eager(dc, x, lab, to_t, guidance):
+    """DDIM inversion in eager torch: z = alpha(lam(0)) x, then n first-order passes up linspace(0, to_t, sampling_steps + 1)."""
+    dev = x.device
+    lams = grid_lams(dc, 0.0, to_t)
+    z = torch.sqrt(torch.sigmoid(lams[0])).to(dev) * x
+    lab_dev = dc.encoder.weight.device if dc.encoder is not None else dev
+    cond, null, lens = contexts(dc, lab.to(lab_dev), dev, dc.ema.ema_model)
+    return run_eager(dc, z, lams, step_scalars(lams, "ddim", "invert"), float(guidance), cond, null, lens)
+
+
+@torch.no_grad()
+def invert(dc, x, text, to_t, guidance, units_per_launch):
+    """`DiffusionClassifier.invert` (its docstring is the interface)."""
+    to_t = float(to_t)
+    if not 0.0 < to_t <= 1.0:
+        raise ValueError(f"to_t must lie in (0, 1], got {to_t}")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [BS, C, H, W], got {tuple(x.shape)}")
+    assert dc.encoder_type is not None, "Encoder must be provided for inversion."
+    dc._require_prompts()
+    lab = label_rows(text, x.shape[0], dc.config.classes, "text")
+    backbone = dc.ema.ema_model
+    if hasattr(backbone, "pair_session"):
+        from . import counterfactual as CF
+        units = units_per_launch(x.shape[2], x.shape[3], 2)
+        return CF.run_hip(dc, backbone, x, lab.view(-1, 1), to_t, "reference", 0, units, sampler="ddim", invert=True, w=float(guidance))[:, 0]
+    dc._refuse_ragged_on_foreign()
+    return invert_eager(dc, x, lab, to_t, guidance).to(torch.float32)

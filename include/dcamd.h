@@ -30,6 +30,8 @@
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
  *   dc_ddpm_step_shared / dc_abs_diff_map
  *                       experiments/ipmsa/explain.py: every class trajectory of an image from shared noise, and where they differ
+ *   dc_solver_step      nothing in the reference: one pass of a deterministic sampler (DDIM, DPM-Solver++ 2M) or of DDIM inversion on
+ *                       the prediction pair dc_ddpm_step reads, for sample / counterfactual with config.sampler set and for invert
  *   dc_stage_topk / dc_reduce_argmin / dc_stage_maps
  *                       the stage end, diffusion_classifier.py:718-725 (mean over trials, k smallest classes) and the
  *                       per-image surviving-class lists of the next stage (:695-698, ragged after pruning / fast mode
@@ -72,7 +74,8 @@ extern "C" {
  * (dc_ddpm_step_shared, dc_abs_diff_map and their structs likewise; both are called directly)
  * (dc_stage_stop and dc_stage_maps_rows likewise; both are called directly)
  * (dc_err_map, dc_err_map_params and DC_OP_ERR_MAP, and dc_evidence_maps with dc_evidence_maps_params — called directly — are additive
- *  within 5: no existing struct or symbol changed) */
+ *  within 5: no existing struct or symbol changed)
+ * (dc_solver_step and dc_solver_step_params — called directly — are additive within 5 likewise) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -514,6 +517,27 @@ typedef struct {
   int32_t pad_;
 } dc_ddpm_step_shared_params;
 int dc_ddpm_step_shared(const dc_ddpm_step_shared_params* p, dc_stream s);
+
+/* One pass of a deterministic data-prediction solver on the same prediction pair, in the layouts dc_ddpm_step reads (z / out / xprev /
+ * xhat [n, C, H, W] f32 NCHW; pred [2n, H, W, ld] f32 NHWC, rows 2b and 2b+1; patch > 1: DiT's un-patchified projection, feature
+ * stride C).  Per element, in this order, no contraction:
+ *   pr  = one_plus_w * pc - w * pu
+ *   x   = v_param ? alpha_t * z - sigma_t * pr : (z - sigma_t * pr) / alpha_t
+ *   x   = clamp ? min(max(x, -1), 1) : x
+ *   if (xhat) xhat[i] = x                                  (the history of the next pass)
+ *   D   = xprev ? x + k3 * (x - xprev[i]) : x
+ *   out = final_pass ? min(max(D, -1), 1) : k1 * z + k2 * D
+ * With h = (lam_s - lam_t) / 2, k1 = sigma_s / sigma_t and k2 = -alpha_s * expm1(-h) the first-order pass (xprev NULL, k3 unused) is
+ * DDIM, z_s = alpha_s x + sigma_s (z - alpha_t x) / sigma_t, in either direction (inversion: h < 0); with xprev and
+ * k3 = 0.5 * h / h_prev it is DPM-Solver++(2M).  The caller forms the scalars.  The kernel equals the torch evaluation of the same
+ * expressions bit for bit for the same fp32 scalars.  xhat may be the buffer of xprev (every thread reads its element before it writes
+ * it); out must not alias z (DC_ERR_ARG). */
+typedef struct {
+  const float* z; const float* pred; const float* xprev; float* xhat; float* out;
+  int32_t n, C, H, W, ld, patch, v_param, clamp, final_pass;
+  float w, one_plus_w, alpha_t, sigma_t, k1, k2, k3;
+} dc_solver_step_params;
+int dc_solver_step(const dc_solver_step_params* p, dc_stream s);
 
 /* ---------------------------------------------------------------- difference maps - */
 /* out[i, y, x] = sum_c |a[i, c, y, x] - r[r_of_a[i], c, y, x]|, fp32, c ascending (a fixed order).  a [n, C, H, W], r [m, C, H, W],
