@@ -459,7 +459,15 @@ int dc_act_pass(const dc_act_pass_params* p, dc_stream s);
  *   [i d, (i+1) d), d = C / heads);  o = softmax(q k^T * scale) v per (sample, head);  out = ((o Wo^T + bo) + rowvec[rowvec_map[n]]) + h.
  * x [n, L, ldx], out [n, L, ld_out] in `dtype` (16-bit); Wp / Wo [C][C], Wqkv [3C][C] packed as dc_igemm takes them (dc_pack_weights_matrix,
  * tile_n 128); biases, LayerNorm affine and rowvec fp32.  h, hn, q, k, v, p, o are rounded to `dtype` where the separate launches
- * (dc_igemm, dc_layernorm, dc_attention) store them, so results agree with that chain to accumulation order.
+ * (dc_igemm, dc_layernorm, dc_attention) store them, so results agree with that chain to accumulation order.  The softmax row sum is
+ * taken over the UNROUNDED fp32 p (p is rounded only as the operand of p v), and o = round((p v) * (1 / sum)); the epilogue adds in fp32 in
+ * the order written above and rounds once.
+ * Optional pointers: bo null: no to_out bias (+ 0).  rowvec null: no row vector (+ 0); rowvec_ld and rowvec_map are then ignored
+ * (rowvec_ld = 0 is fine).  rowvec set, rowvec_map null: sample n takes row n of a table of n rows; rowvec_map set: row rowvec_map[n]
+ * (int32 on the device, any order, rows may repeat; not range-checked).  rowvec rows are rowvec_ld >= C floats apart, rowvec_ld % 4 == 0.
+ * ldx, ld_out >= C and multiples of 8 (rows are moved in 16-byte pieces); only columns [0, C) of a row are read or written.
+ * Status: DC_ERR_SHAPE for L / C / heads / n / ldx / ld_out / rowvec_ld < C, DC_ERR_ALIGN for a pointer off 16 bytes or rowvec_ld % 4,
+ * DC_ERR_ARG for a null required pointer or scale / ln_eps <= 0 — all before any launch, the output untouched.
  * Shapes: dc_tblock_front_ok() (L = 64, C = 256, heads = 4 or 8 today); anything else returns DC_ERR_SHAPE. */
 typedef struct {
   const void* x; const void* Wp; const float* bp;
