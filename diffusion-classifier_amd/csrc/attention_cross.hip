@@ -25,9 +25,6 @@ struct CrossArgs {
   const int32_t* kv_len;   // LEN instantiations only: keys per context, clamped into [1, S] by the kernel
 };
 
-// every stored query is real; the keys stop at the context's length (S without LEN), which only the ragged last block can cross
-struct CrossMode : KeyBound { static constexpr bool kZeroPad = false, kBiased = false; };
-
 // keys per block: 8 staging chunks per lane and operand at most, and an LDS strip small enough for 2 - 4 workgroups per CU
 static constexpr int cross_kb(int D) { return D <= 32 ? 64 : 32; }
 
@@ -49,7 +46,7 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(const CrossArgs a) {
   int wave, i, h, q0;
   if (!strip_item(a.n, a.heads, a.Lq, wave, i, h, q0)) return;
   const StripView<T> w = cross_view<T, LEN>(a, i, h, D, q0, KB);
-  CrossMode mode{{w.nk}};
+  PlainMode mode{{w.nk}};                                    // the keys stop at the context's length (S without LEN)
   T *Kl, *Vl;
   strip_lds<T, D, KB>(smem, wave, Kl, Vl);
   attn_strip_run<T, D, KB>(w, mode, a.scale, Kl, Vl);
@@ -72,7 +69,7 @@ __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) 
   int i, h, q0;
   exact_item(a.heads, a.Lq, 256 / (a.d / SW), i, h, q0);
   const StripView<T> w = cross_view<T, LEN>(a, i, h, a.d, q0, a.KB);
-  attn_exact_run<T, SW>(w, CrossMode{{w.nk}}, a.scale, a.d, a.KB, kv);
+  attn_exact_run<T, SW>(w, PlainMode{{w.nk}}, a.scale, a.d, a.KB, kv);
 }
 
 // `fn`: the entry point's name in front of every message (dc_cross_attention / dc_cross_attention_len validate alike)

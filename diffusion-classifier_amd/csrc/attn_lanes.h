@@ -1,5 +1,5 @@
 // attn_lanes.h — reductions over the four lanes that share a query column in the transposed-score attention kernels
-// (attention_mfma.hip: self-attention; attn_strip.h: the body of cross-, bias and causal attention).
+// (attention.hip: self-attention's flash and wave kernels; attn_strip.h: the body of cross-, bias and causal attention).
 #pragma once
 #include "common.h"
 

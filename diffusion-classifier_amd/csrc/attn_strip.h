@@ -1,6 +1,8 @@
 // attn_strip.h — the two attention bodies that attention_cross.hip (cross-attention), t5.hip (relative-position bias, a length per
-// sample) and clip.hip (causal, a length per sample) share.  Each of those files keeps thin __global__ kernels that decode their
-// item, fill a StripView and a Mode, and call a body; what differs between them lives in the Mode alone:
+// sample) and clip.hip (causal, a length per sample) share; attention.hip (self-attention) runs the exact body and builds its two
+// transposed-score kernels from the same three pieces as attn_strip_run (attn_score_tile, attn_exp_pack, attn_pv_step).  Each of
+// those files keeps thin __global__ kernels that decode their item, fill a StripView and a Mode, and call a body; what differs between
+// them lives in the Mode alone:
 //   kZeroPad              queries at or past the length exist as rows: written as zeros, and a whole tile of them reads nothing
 //   kBiased               the score is fma(q k^T, scale, bias(key, query)) and the max runs over it; otherwise the max runs over the raw
 //                         q k^T and the scale is folded into the exponent's FMA (valid for scale > 0 only)
@@ -29,6 +31,63 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
 
+// ------------------------------------------------------------------------------------------------
+// The three pieces of every transposed-score kernel (attn_strip_run below; attn_flash_t_kernel and attn_wave_kernel of attention.hip).
+// lr = lane & 15, lq = lane >> 4; K / V images are row-major with a pitch of PITCH = D + 8 elements.
+
+// one S^T tile: keys 16 kt .. +15 (rows) x the 16 queries of qf (column lr); qf: query lr, d = 32 kb + 8 lq .. +7
+template <typename T, int NKB, int PITCH>
+__device__ __forceinline__ f32x4 attn_score_tile(const T* Kb, int kt, const chunk16 (&qf)[NKB], int lr, int lq) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kb = 0; kb < NKB; ++kb) {
+    const chunk16 kf = *reinterpret_cast<const chunk16*>(Kb + (kt * 16 + lr) * PITCH + kb * 32 + lq * 8);
+    acc = Mma<T>::run(kf, qf[kb], acc);                       // rows = keys, column = query
+  }
+  return acc;
+}
+
+// p2 (the caller's score -> probability) of each score, four packed to the compute type per tile; returns the lane's partial row sum
+// (of the unrounded p)
+template <typename T, int NKT, typename F>
+__device__ __forceinline__ float attn_exp_pack(const f32x4 (&S)[NKT], s16x4 (&P)[NKT], F&& p2) {
+  float ps = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+    float pv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { pv[r] = p2(S[kt][r]); ps += pv[r]; }
+    typename Elem<T>::vec4 pk;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pk[r] = Elem<T>::from_f(pv[r]);
+    P[kt] = __builtin_bit_cast(s16x4, pk);
+  }
+  return ps;
+}
+
+// acc += V^T P^T for d rows 16 dt .. +15 over all NKT key tiles of the V image
+template <typename T, int NKT, int PITCH>
+__device__ __forceinline__ f32x4 attn_pv_step(f32x4 acc, const T* Vb, int dt, const s16x4 (&P)[NKT], int lr, int lq) {
+#pragma unroll
+  for (int kp = 0; kp < NKT / 2; ++kp) {
+    // one 16x16x32 MFMA per PAIR of key tiles: the sum over k is order-free as long as both operands agree, so lane group lq takes
+    // as its 8 k-slots the keys 4 lq .. +3 of tile 2 kp and of tile 2 kp + 1 — exactly the two packed P^T D-fragments it already
+    // holds (B operand), and two transposed reads of the row-major V image (A operand): for each, the 16-lane group takes keys
+    // 16 kt + 4 lq .. +3 x d columns 16 dt .. +15; lane 4q+p supplies the address of key row q, columns 4p .. 4p+3 and receives
+    // column lr of the four rows
+    s16x4 vf[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const T* vp = Vb + ((2 * kp + u) * 16 + lq * 4 + (lr >> 2)) * PITCH + dt * 16 + (lr & 3) * 4;
+      vf[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(const_cast<T*>(vp)));
+    }
+    const s16x8 av = __builtin_shufflevector(vf[0], vf[1], 0, 1, 2, 3, 4, 5, 6, 7);
+    const s16x8 bv = __builtin_shufflevector(P[2 * kp], P[2 * kp + 1], 0, 1, 2, 3, 4, 5, 6, 7);
+    acc = Mma<T>::run(__builtin_bit_cast(chunk16, av), __builtin_bit_cast(chunk16, bv), acc);   // rows = d, column = query
+  }
+  return acc;
+}
+
 // what a body sees of one (sample, head): row 0 of its q / k / v / out, and the bounds of its walk
 template <typename T> struct StripView {
   const T* q; const T* k; const T* v; T* out;
@@ -46,6 +105,10 @@ struct KeyBound {
   int len;
   template <bool LAST> __device__ __forceinline__ bool masked(int key, int) const { return LAST && key >= len; }
 };
+
+// every stored query is real and the scores are raw; the keys stop at a bound (cross-attention: the context's length, which only the
+// ragged last block can cross; self-attention's exact kernel: L)
+struct PlainMode : KeyBound { static constexpr bool kZeroPad = false, kBiased = false; };
 
 // an entry of a device array of lengths: clamped rather than trusted; uniform -> the scalar path
 __device__ __forceinline__ int clamped_len(const int32_t* len, int i, int rows) {
@@ -153,12 +216,7 @@ __device__ __forceinline__ void attn_strip_run(const StripView<T>& w, Mode& mode
       float mx = m[qt];                                       // running max: of the biased scores, or of the raw ones (scale > 0: same arg max)
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-          const chunk16 kf = *reinterpret_cast<const chunk16*>(Kl + (kt * 16 + lr) * PITCH + kb * 32 + lq * 8);
-          acc = Mma<T>::run(kf, qf[qt][kb], acc);             // rows = keys, column = query
-        }
+        f32x4 acc = attn_score_tile<T, NKB, PITCH>(Kl, kt, qf[qt], lr, lq);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + kt * 16 + lq * 4 + r, query = w.q0 + qt * 16 + lr;
@@ -178,39 +236,15 @@ __device__ __forceinline__ void attn_strip_run(const StripView<T>& w, Mode& mode
       };
       const float corr = p2(m[qt]);                           // 0 on the first block
       m[qt] = mx;
-      float ps = 0.f;
       s16x4 P[NKT];
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        float pv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { pv[r] = p2(Sc[kt][r]); ps += pv[r]; }
-        typename Elem<T>::vec4 pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pk[r] = Elem<T>::from_f(pv[r]);
-        P[kt] = __builtin_bit_cast(s16x4, pk);
-      }
+      const float ps = attn_exp_pack<T>(Sc, P, p2);
       l[qt] = l[qt] * corr + ps;                              // per-lane partial row sum: reduced once, behind the loop
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
         f32x4 acc = O[qt][dt];
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] *= corr;
-#pragma unroll
-        for (int kp = 0; kp < NKT / 2; ++kp) {
-          // one 16x16x32 MFMA per PAIR of key tiles: lane group lq takes as its 8 k-slots the keys 4 lq .. +3 of tile 2 kp and of tile
-          // 2 kp + 1 — the two packed P^T fragments it holds (B) against two transposed reads of the row-major V strip (A)
-          s16x4 vf[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const T* vp = Vl + ((2 * kp + u) * 16 + lq * 4 + (lr >> 2)) * PITCH + dt * 16 + (lr & 3) * 4;
-            vf[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(const_cast<T*>(vp)));
-          }
-          const s16x8 av = __builtin_shufflevector(vf[0], vf[1], 0, 1, 2, 3, 4, 5, 6, 7);
-          const s16x8 bv = __builtin_shufflevector(P[2 * kp], P[2 * kp + 1], 0, 1, 2, 3, 4, 5, 6, 7);
-          acc = Mma<T>::run(__builtin_bit_cast(chunk16, av), __builtin_bit_cast(chunk16, bv), acc);   // rows = d, column = query
-        }
-        O[qt][dt] = acc;
+        O[qt][dt] = attn_pv_step<T, NKT, PITCH>(acc, Vl, dt, P, lr, lq);
       }
     }
     if (more) {

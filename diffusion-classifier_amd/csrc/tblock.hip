@@ -47,7 +47,7 @@ struct TbArgs {
 
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
-// xor-16 / xor-32 butterflies over the four lanes that share a query column (attention_mfma.hip has the story of the builtin)
+// xor-16 / xor-32 butterflies over the four lanes that share a query column (attn_lanes.h has the story of the builtin)
 template <bool WIDE> __device__ __forceinline__ void tb_lane_swap(float x, float& lo, float& hi) {
   unsigned u = __builtin_bit_cast(unsigned, x), v = u;
   if constexpr (WIDE) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(u), "+v"(v));

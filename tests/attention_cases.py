@@ -1,5 +1,5 @@
-"""The cases of the self-attention parity tests (dc_attention: attn_wave_kernel, attn_mfma_kernel, attn_flash_t_kernel, attn_small_kernel
-behind attn_route of csrc/attention.hip), their operands, their fp64 reference, the per-element error bound and the checker — one table,
+"""The cases of the self-attention parity tests (dc_attention: attn_wave_kernel, attn_mfma_kernel, attn_flash_t_kernel, attn_self_f32_kernel
+behind attn_plan of csrc/attention.hip), their operands, their fp64 reference, the per-element error bound and the checker — one table,
 two consumers: tests/test_attention_cases.py (host only: routing, coverage, the checker held against an emulation of each route and against
 planted faults) and tests/test_gpu_attention.py (the kernels themselves).
 
@@ -8,7 +8,7 @@ A case is a dict of dc_attention_params' plain fields (dtype, n, L, heads, d, ld
     expect    the exact dc_attention_variant string: "wave", "mfma", "flash" or "fp32"
     instance  the kernel instance: ("wave", "bf16", 64, 4) = attn_wave_kernel<bf16, 64, NKT = 4>; ("mfma", "f16", "G2") = attn_mfma_kernel<f16>
               with two pairs per workgroup ("G4": L = 16, "G2": L = 32, "G1", "G4w": L = 64 with d <= 64); ("flash", "bf16", 96) =
-              attn_flash_t_kernel<bf16, 96>; ("fp32", "f32", 24, "streamed") = attn_small_kernel<f32, SW = 24> with K / V in blocks ("whole": one block)
+              attn_flash_t_kernel<bf16, 96>; ("fp32", "f32", 24, "streamed") = attn_self_f32_kernel<f32, SW = 24> with K / V in blocks ("whole": one block)
     layout    "fused"      one [n, L, 3 heads d] tensor, three offset pointers
               "wide"       fused with ld_qkv = 3 heads d + 8 and ld_out = heads d + 8 (the pad columns of q/k/v hold NaN)
               "split"      three separate tensors, ld_qkv = heads d
@@ -37,14 +37,14 @@ GUARD = 4096                                               # elements behind the
 MATRIX_ROUTES = ("wave", "mfma", "flash")                  # they round P to the compute type in front of P.V
 
 
-# ---- what the dispatcher and the kernels derive from a shape (csrc/attention.hip, csrc/attention_mfma.hip) --------------------------
+# ---- what the dispatcher and the kernels derive from a shape (attn_plan of csrc/attention.hip) ------------------------------------------
 def flash_kb(d):
     """Keys per block of attn_flash_t_kernel<T, d>."""
     return 128 if d <= 32 else (64 if d <= 96 else 32)
 
 
 def fp32_kb(L, d):
-    """Keys per LDS block of attn_small_kernel: the whole sequence while 2 L d floats fit 160 KiB, else 8192 / d."""
+    """Keys per LDS block of attn_self_f32_kernel: the whole sequence while 2 L d floats fit 160 KiB, else 8192 / d."""
     return L if 2 * L * d * 4 <= 160 * 1024 else 8192 // d
 
 
@@ -53,7 +53,7 @@ def fp32_sw(d):
 
 
 def fp32_qt(d):
-    """Queries per workgroup of attn_small_kernel."""
+    """Queries per workgroup of attn_self_f32_kernel."""
     return 256 // (d // fp32_sw(d))
 
 
@@ -241,10 +241,10 @@ NO_FUSED = {
     **{("mfma", t, "G4w"): "L = 64 with d <= 64 goes to the wave kernel unless ld_out % 4 != 0" for t in ("bf16", "f16")},
     **{("fp32", t, 24, "streamed"): "d = 96 beyond 213 tokens goes to the flash kernel unless ld_out % 4 != 0 or q/k/v are unaligned" for t in ("bf16", "f16")},
 }
-# Forms of a kernel that its own applicability test admits and dc_attention never produces; tests/test_attention_cases.py proves each on a probe grid
+# Forms a kernel could run and dc_attention never produces — attn_plan has no such form; tests/test_attention_cases.py proves each on a probe grid
 UNREACHABLE = {
-    **{("mfma", t, "L>128"): "dc_attn_mfma_applicable admits L <= 256, attn_route sends everything beyond 128 tokens elsewhere" for t in ("bf16", "f16")},
-    **{("flash", t, "L<=128"): "dc_attn_flash_applicable admits any L >= 1, attn_route asks it beyond 128 tokens only" for t in ("bf16", "f16")},
+    **{("mfma", t, "L>128"): "attn_plan has no whole-sequence form beyond 128 tokens: everything longer goes elsewhere" for t in ("bf16", "f16")},
+    **{("flash", t, "L<=128"): "attn_plan has no flash form at or below 128 tokens: the fp32 image of such a sequence always fits 160 KiB" for t in ("bf16", "f16")},
 }
 
 # bit-identity whatever the sample's place in the batch: one case per route and dtype (run at n = 1 and at n = 3)

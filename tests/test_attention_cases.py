@@ -51,7 +51,7 @@ def test_every_case_is_routed_to_the_kernel_it_names(c):
 
 
 def test_unaligned_sixteen_bit_operands_take_the_exact_kernel():
-    """dc_attn_mfma_applicable used not to look at the pointers: at L % 16 == 0, L <= 128, d % 32 == 0 the dispatcher named "mfma" and
+    """The whole-sequence route used not to look at the pointers: at L % 16 == 0, L <= 128, d % 32 == 0 the dispatcher named "mfma" and
     dc_attention returned DC_ERR_ALIGN, while the same pointers ran on the fp32 kernel at L = 40 or 144.  Aligned problems keep their route."""
     for dt in (A.BF16, A.F16):
         for (L, d), aligned_route in (((64, 64), "wave"), ((96, 32), "mfma"), ((128, 96), "mfma"), ((300, 64), "flash"), ((16, 96), "mfma"), ((40, 64), "wave"), ((144, 64), "flash")):
@@ -96,7 +96,7 @@ def test_the_table_reaches_every_instance_or_proves_it_unreachable():
         assert any(c["mode"] == "peaked" for c in mine) and any(c["mode"] == "random" for c in mine), inst
         if any(A.padded_keys(c) for c in mine):
             assert any(c["mode"] == "negative" and A.padded_keys(c) for c in mine), inst
-    # what the applicability tests admit and the table does not reach must be out of the dispatcher's reach too, on a probe grid
+    # forms the kernels could run and the table does not reach must be out of the dispatcher's reach too (the plan has none), on a probe grid
     for (route, t, form), why in A.UNREACHABLE.items():
         dt = A.BF16 if t == "bf16" else A.F16
         Ls = (144, 160, 176, 192, 208, 224, 240, 256) if form == "L>128" else (1, 15, 16, 17, 40, 63, 64, 65, 100, 127, 128)

@@ -1,4 +1,4 @@
-"""GPU: the four kernels behind dc_attention — attn_wave_kernel, attn_mfma_kernel, attn_flash_t_kernel, attn_small_kernel — every instance
+"""GPU: the four kernels behind dc_attention — attn_wave_kernel, attn_mfma_kernel, attn_flash_t_kernel, attn_self_f32_kernel — every instance
 and every route, against an fp64 reference over EVERY output element with a derived per-element bound (tests/attention_cases.py: the cases,
 the operands, the reference, the bound and the checker; tests/test_attention_cases.py pins their routing and holds the checker against an
 emulation of each route and against planted faults on the host).

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of dc_attention on the DiT-B/4 shape (1024 tokens, 12 heads x 64, f16 / bf16), a 4096-token one, and head dim 96:
-the CheXpert experiment UNet's 768-channel level (1024 / 4096 tokens x 8 heads) and DiT-XL/2 (256 tokens x 16 heads of 72, padded to 96)
+the CheXpert experiment UNet's 768-channel level (1024 / 4096 tokens x 8 heads) and DiT-XL/2 (256 tokens x 16 heads of 72, padded to 96);
+the one-wave-per-pair kernel (64 and 16 tokens x 8 heads x 64) and the whole-sequence kernel (64 tokens x 8 heads x 96) at batches of
+about 3 GB of q / k / v + output per call, so that ten calls take tens of milliseconds
 (developer tool; DCAMD_LIB selects the library, so A/B builds can be timed in one session).
 
   python tools/bench_attention.py [n_samples]
@@ -13,7 +15,8 @@ from diffusion_classifier_amd import _lib as L
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 for dt, td in ((L.DC_F16, torch.float16), (L.DC_BF16, torch.bfloat16)):
     for Lq, heads, d, nn in ((1024, 12, 64, n), (4096, 12, 64, max(1, n // 16)),
-                             (1024, 8, 96, n), (4096, 8, 96, max(1, n // 16)), (256, 16, 96, 4 * n)):
+                             (1024, 8, 96, n), (4096, 8, 96, max(1, n // 16)), (256, 16, 96, 4 * n),
+                             (64, 8, 64, 128 * n), (16, 8, 64, 512 * n), (64, 8, 96, 96 * n)):
         Cc = heads * d
         torch.manual_seed(1)
         qkv = (torch.randn(nn, Lq, 3 * Cc, device="cuda") * 1.2).to(td)
