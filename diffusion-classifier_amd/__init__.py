@@ -17,6 +17,7 @@ from .utils.wavelet import wavelet_dec_2, wavelet_enc_2  # noqa: F401
 from .posterior import ClassPosterior  # noqa: F401
 from .evidence import ClassEvidence  # noqa: F401
 from .counterfactual import Counterfactuals  # noqa: F401
+from .ddpm_invert import DdpmInversion  # noqa: F401
 
 
 class Config:

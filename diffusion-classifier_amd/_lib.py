@@ -169,6 +169,12 @@ class SolverStepParams(C.Structure):
                 ("w", f32), ("one_plus_w", f32), ("alpha_t", f32), ("sigma_t", f32), ("k1", f32), ("k2", f32), ("k3", f32)]
 
 
+class DdpmNoiseMapParams(C.Structure):
+    _fields_ = [("z", vp), ("pred", vp), ("x_next", vp), ("out", vp),
+                ("n", i32), ("C", i32), ("H", i32), ("W", i32), ("ld", i32), ("patch", i32), ("v_param", i32),
+                ("w", f32), ("one_plus_w", f32), ("alpha_t", f32), ("sigma_t", f32), ("alpha_s", f32), ("c", f32), ("sd", f32)]
+
+
 class AbsDiffMapParams(C.Structure):
     _fields_ = [("a", vp), ("r", vp), ("r_of_a", vp), ("out", vp),
                 ("n", i32), ("m", i32), ("C", i32), ("H", i32), ("W", i32), ("pad_", i32)]
@@ -187,7 +193,7 @@ class Op(C.Structure):
 # every symbol include/dcamd.h declares (tests check that the library exports all of them)
 EXPORTS = ["dc_abi_version", "dc_last_error", "dc_arch", "dc_qsample", "dc_philox_normal", "dc_sinusoid",
            "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_instance", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
-           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_err_map", "dc_evidence_maps", "dc_ddpm_step", "dc_ddpm_step_shared", "dc_solver_step", "dc_abs_diff_map", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_stage_maps_rows", "dc_stage_stop", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
+           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_err_map", "dc_evidence_maps", "dc_ddpm_step", "dc_ddpm_step_shared", "dc_solver_step", "dc_ddpm_noise_map", "dc_abs_diff_map", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_stage_maps_rows", "dc_stage_stop", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
            "dc_packed_bytes", "dc_pack_weights_matrix", "dc_pack_weights_conv3x3", "dc_pack_weights_up4", "dc_pack_weights_geglu",
            "dc_fold_layernorm_bias", "dc_workspace_bytes_groupnorm", "dc_workspace_bytes_igemm", "dc_workspace_bytes_attention",
            "dc_workspace_bytes_layernorm"]
@@ -236,6 +242,7 @@ def lib():
                        ("dc_ddpm_step", [C.POINTER(DdpmStepParams), vp]),
                        ("dc_ddpm_step_shared", [C.POINTER(DdpmStepSharedParams), vp]),
                        ("dc_solver_step", [C.POINTER(SolverStepParams), vp]),
+                       ("dc_ddpm_noise_map", [C.POINTER(DdpmNoiseMapParams), vp]),
                        ("dc_abs_diff_map", [C.POINTER(AbsDiffMapParams), vp]),
                        ("dc_run_plan", [C.POINTER(Op), i32, vp]),
                        ("dc_run_plan_timed", [C.POINTER(Op), i32, vp, vp]),

@@ -10,7 +10,9 @@ HIP backbones run all BS x K trajectories as the units of one pair session per c
 once per call, the step scalars are formed before the loop, nothing is copied to the host inside it; `dc_ddpm_step_shared`,
 `dc_abs_diff_map`).  A foreign nn.Module takes the reference's own form in eager torch (`run_foreign`): it is the written statement.
 With config.sampler = "ddim" | "dpmpp_2m" (solver.py) the trajectories are deterministic after their start (`dc_solver_step`), and
-start="invert" takes that start from DDIM inversion of the image instead of from noise.
+start="invert" takes that start from DDIM inversion of the image instead of from noise.  Under the ancestral sampler
+start="ddpm_invert" takes the start AND the noise of every step from the image's edit-friendly DDPM inversion (ddpm_invert.py): the
+decode under the inversion's class is the image again, and the loop draws nothing.
 """
 import ctypes as C
 from collections import namedtuple
@@ -18,6 +20,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from . import ddpm_invert as DI
 from . import solver as S
 
 Counterfactuals = namedtuple("Counterfactuals", ["samples", "classes", "maps"])
@@ -88,11 +91,28 @@ def image_chunks(BS, K, units):
     return [(b0, min(BS, b0 + per)) for b0 in range(0, BS, per)]
 
 
-def run_foreign(dc, backbone, x, cl, from_t, sampler=None, z0=None):
+def pair_sessions(dc, backbone, cl, chunks, dev):
+    """One pair session per chunk (b0, b1) of images for the labels cl [BS, K]: unit pair b * K + k is class token cl[b, k] || null
+    token; contexts, lengths and the context plan once per call and chunk, session ci in slot ci."""
+    table = dc.encoder is not None
+    lab_dev = dc.encoder.weight.device if table else dev
+    ln = dc.encoder.lengths.cpu() if dc._ragged_table() else None
+    sessions = []
+    for ci, (b0, b1) in enumerate(chunks):
+        lab = cl[b0:b1].reshape(-1)
+        nul = torch.full_like(lab, dc.null_token)
+        cond, null = dc.encode_text_prompt(lab.to(lab_dev)).to(dev), dc.encode_text_prompt(nul.to(lab_dev)).to(dev)
+        kw = dict(cond_lengths=ln[lab], null_lengths=ln[nul]) if ln is not None else {}
+        sessions.append(backbone.pair_session(lab.numel(), dev, cond, null, slot=ci, **kw))
+    return sessions
+
+
+def run_foreign(dc, backbone, x, cl, from_t, sampler=None, z0=None, noise_maps=None):
     """The reference's form: per step and class one conditional and one null call at batch BS and `ddpm_sampler_step`, every class
     adding the step's one `randn_like` — op for op what K calls of `sample` with the seed reset in front of each compute.
     sampler "ddim" / "dpmpp_2m": the K classes by `solver.run_eager` from the one start instead, no draw after it; z0 [BS, C, H, W]:
-    that start (an inverted latent) in place of the noised image, no draw at all."""
+    that start (an inverted latent) in place of the noised image, no draw at all.  noise_maps [n, BS, C, H, W] (ancestral sampler, with
+    z0; ddpm_invert.py): step i adds noise_maps[i] in place of its draw."""
     dev = x.device
     BS, K = cl.shape
     if z0 is not None:
@@ -124,18 +144,19 @@ def run_foreign(dc, backbone, x, cl, from_t, sampler=None, z0=None):
             mus.append(mu)
         if i == n:
             return torch.stack([dc.clip(mu) for mu in mus], dim=1).to(torch.float32)
-        noise = torch.randn_like(mus[0])
+        noise = torch.randn_like(mus[0]) if noise_maps is None else noise_maps[i]
         zs = [mu + noise * torch.sqrt(var) for mu in mus]
 
 
-def run_hip(dc, backbone, x, cl, from_t, rng, seed, units, sampler=None, z0=None, invert=False, w=None):
+def run_hip(dc, backbone, x, cl, from_t, rng, seed, units, sampler=None, z0=None, invert=False, w=None, noise_maps=None):
     """All BS x K trajectories on a HIP backbone: trajectory b * K + k is one image of a pair session (unit pair: class token || null
     token), the loop is step-major and chunk-minor, the noise of a step is drawn for the whole batch and read by the K trajectories
     of an image through `dc_ddpm_step_shared`.
     sampler "ddim" / "dpmpp_2m" (solver.py): sampling_steps deterministic passes, one `dc_solver_step` per step and chunk, no draw
     after the start, one history buffer of data predictions for the second-order passes.  z0 [BS, C, H, W]: the start, in place of the
     noised image (no draw at all).  invert: the grid is walked upwards from z = alpha(lam(0)) x to `from_t` (DDIM inversion; K = 1,
-    the labels are cl[:, 0]).  w: the guidance weight, config.cfg_w when None."""
+    the labels are cl[:, 0]).  w: the guidance weight, config.cfg_w when None.  noise_maps [n, BS, C, H, W] f32 on the device (ancestral
+    sampler, with z0; ddpm_invert.py): step i reads noise_maps[i] in place of a draw, so the loop draws nothing."""
     lib = L.require_gpu()
     if not x.is_cuda:
         raise L.DcamdError("counterfactual on a HIP backbone needs a CUDA/HIP tensor (as sample does; no CPU fallback)")
@@ -189,23 +210,16 @@ def run_hip(dc, backbone, x, cl, from_t, rng, seed, units, sampler=None, z0=None
 
     # ---- once per call and chunk: contexts, lengths, the context plan ----
     chunks = image_chunks(BS, K, units)
-    table = dc.encoder is not None
-    lab_dev = dc.encoder.weight.device if table else dev
-    ln = dc.encoder.lengths.cpu() if dc._ragged_table() else None
-    sessions = []
-    for ci, (b0, b1) in enumerate(chunks):
-        lab = cl[b0:b1].reshape(-1)
-        nul = torch.full_like(lab, dc.null_token)
-        cond, null = dc.encode_text_prompt(lab.to(lab_dev)).to(dev), dc.encode_text_prompt(nul.to(lab_dev)).to(dev)
-        kw = dict(cond_lengths=ln[lab], null_lengths=ln[nul]) if ln is not None else {}
-        sessions.append(backbone.pair_session(lab.numel(), dev, cond, null, slot=ci, **kw))
+    sessions = pair_sessions(dc, backbone, cl, chunks, dev)
 
     # ---- the loop: step-major, chunk-minor; no device -> host copy ----
     for i, (t, _s) in enumerate(passes):
         noise = None
         if sampler is None:
             c, alpha_t, sigma_t, alpha_s, sd = scal[i]
-            if i < n:
+            if i < n and noise_maps is not None:
+                noise = noise_maps[i]
+            elif i < n:
                 noise = draw((i + 1) * BS) if philox else torch.randn_like(z0).to(torch.float32).contiguous()
         else:
             alpha_t, sigma_t, k1, k2, k3, final = scal[i]
@@ -234,13 +248,16 @@ def run_hip(dc, backbone, x, cl, from_t, rng, seed, units, sampler=None, z0=None
 def run(dc, x, classes, from_t, against, rng, seed, pixel_space, units_per_launch, start="noise", invert_class=None):
     """`DiffusionClassifier.counterfactual` (its docstring is the interface); units_per_launch(H, W, k) is classify's launch-size rule."""
     sampler = S.sampler_of(dc.config)
-    if start not in ("noise", "invert"):
-        raise ValueError(f"start must be 'noise' or 'invert', got {start!r}")
+    if start not in ("noise", "invert", "ddpm_invert"):
+        raise ValueError(f"start must be 'noise', 'invert' or 'ddpm_invert', got {start!r}")
     if start == "invert" and sampler is None:
         raise ValueError("start='invert' needs a deterministic config.sampler ('ddim' or 'dpmpp_2m'): ancestral DDPM adds fresh noise to "
                          "the inverted latent at every step, which defeats the inversion")
+    if start == "ddpm_invert" and sampler is not None:
+        raise ValueError(f"start='ddpm_invert' needs the ancestral sampler (config.sampler unset or 'ddpm'), got config.sampler = "
+                         f"{sampler!r}: its noise maps stand in for the ancestral sampler's draws, a deterministic sampler takes none")
     if start == "noise" and invert_class is not None:
-        raise ValueError("invert_class belongs to start='invert'")
+        raise ValueError("invert_class belongs to start='invert' / 'ddpm_invert'")
     if rng not in ("reference", "philox"):
         raise ValueError(f"rng must be 'reference' or 'philox', got {rng!r}")
     from_t = float(from_t)
@@ -265,14 +282,19 @@ def run(dc, x, classes, from_t, against, rng, seed, pixel_space, units_per_launc
         if rng == "philox":
             raise L.DcamdError("rng='philox' needs a HIP backbone (UNetCondition2D / DiT)")
         dc._refuse_ragged_on_foreign()
-    z0 = None
+    z0 = nmaps = None
     if start == "invert":
         inv = S.label_rows(invert_class, BS, dc.config.classes, "invert_class")
         z0 = S.invert(dc, x, inv, from_t, 0.0, units_per_launch)         # z_{from_t} of the image itself: no noise is drawn
+    elif start == "ddpm_invert":
+        # rng and seed govern the inversion's draws; the decode reads its noise from the maps and draws nothing
+        inv = DI.invert(dc, x, invert_class, from_t, None, rng, seed, units_per_launch, name="invert_class")
+        z0, nmaps, rng = inv.start, inv.noise, "reference"
     if hip:
-        samples = run_hip(dc, backbone, x, cl, from_t, rng, seed, units_per_launch(x.shape[2], x.shape[3], 2 * K), sampler=sampler, z0=z0)
+        samples = run_hip(dc, backbone, x, cl, from_t, rng, seed, units_per_launch(x.shape[2], x.shape[3], 2 * K), sampler=sampler, z0=z0,
+                          noise_maps=nmaps)
     else:
-        samples = run_foreign(dc, backbone, x, cl, from_t, sampler=sampler, z0=z0)
+        samples = run_foreign(dc, backbone, x, cl, from_t, sampler=sampler, z0=z0, noise_maps=nmaps)
     flat = samples.reshape((BS * K,) + tuple(samples.shape[2:])).contiguous()
     xb = x.detach().to(torch.float32).contiguous()
     if pixel_space:

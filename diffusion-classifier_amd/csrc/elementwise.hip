@@ -1,6 +1,6 @@
 // elementwise.hip — the HBM-bound ends of the scoring step, gfx950:
 //   q_sample (+ im2col of conv_in), Philox normal noise, sinusoidal log-SNR embedding,
-//   eps-MSE reduction, Haar DWT / inverse.
+//   eps-MSE reduction, the sampler steps and the noise map of the ancestral one, Haar DWT / inverse.
 // Reference lines: diffusion/diffusion_classifier.py:100-117, :690-692 (q_sample),
 // :706-711 (v->eps, squared L2 error); utils/wavelet.py:4-68 (Haar); diffusers Timesteps.
 #include "common.h"
@@ -240,27 +240,36 @@ struct DdpmArgs {
   int noise_div;          // trajectory b adds noise row b / noise_div (dc_ddpm_step: 1, a row per trajectory)
 };
 
+// The posterior mean of element i = (b, r) of z: the indexing of the prediction pair and the arithmetic up to mu.  One body for
+// ddpm_step_kernel and ddpm_noise_map_kernel, so the mean a noise map is solved against is the mean the step adds it to.
+__device__ __forceinline__ float ddpm_mean(const DdpmArgs& a, size_t i, size_t CHW, size_t rows, int& b, size_t& r) {
+#pragma clang fp contract(off)
+  b = (int)(i / CHW);
+  r = i - (size_t)b * CHW;
+  const int c = (int)(r / a.HW), p = (int)(r - (size_t)c * a.HW);
+  size_t pi;
+  if (a.patch > 1) {
+    const int y = p / a.W, xw = p - y * a.W, pp = a.patch;
+    pi = ((size_t)(y / pp) * (a.W / pp) + xw / pp) * a.ld + (size_t)((y % pp) * pp + xw % pp) * a.C + c;
+  } else {
+    pi = (size_t)p * a.ld + c;
+  }
+  const float pc = a.pred[(size_t)(2 * b) * rows * a.ld + pi], pu = a.pred[(size_t)(2 * b + 1) * rows * a.ld + pi];
+  const float zt = a.z[i];
+  const float pr = a.one_plus_w * pc - a.w * pu;                                // pred = (1 + w) * pred - w * u_pred
+  float xp = a.v_param ? a.alpha_t * zt - a.sigma_t * pr : (zt - a.sigma_t * pr) / a.alpha_t;
+  xp = fminf(fmaxf(xp, -1.f), 1.f);                                              // clip
+  return a.alpha_s * (zt * (1.f - a.c) / a.alpha_t + a.c * xp);
+}
+
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
 #pragma clang fp contract(off)
   const size_t CHW = (size_t)a.C * a.HW, total = CHW * a.n;
   const size_t rows = a.patch > 1 ? (size_t)a.HW / (a.patch * a.patch) : (size_t)a.HW;
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int b = (int)(i / CHW);
-    const size_t r = i - (size_t)b * CHW;
-    const int c = (int)(r / a.HW), p = (int)(r - (size_t)c * a.HW);
-    size_t pi;
-    if (a.patch > 1) {
-      const int y = p / a.W, xw = p - y * a.W, pp = a.patch;
-      pi = ((size_t)(y / pp) * (a.W / pp) + xw / pp) * a.ld + (size_t)((y % pp) * pp + xw % pp) * a.C + c;
-    } else {
-      pi = (size_t)p * a.ld + c;
-    }
-    const float pc = a.pred[(size_t)(2 * b) * rows * a.ld + pi], pu = a.pred[(size_t)(2 * b + 1) * rows * a.ld + pi];
-    const float zt = a.z[i];
-    const float pr = a.one_plus_w * pc - a.w * pu;                              // pred = (1 + w) * pred - w * u_pred
-    float xp = a.v_param ? a.alpha_t * zt - a.sigma_t * pr : (zt - a.sigma_t * pr) / a.alpha_t;
-    xp = fminf(fmaxf(xp, -1.f), 1.f);                                            // clip
-    const float mu = a.alpha_s * (zt * (1.f - a.c) / a.alpha_t + a.c * xp);
+    int b;
+    size_t r;
+    const float mu = ddpm_mean(a, i, CHW, rows, b, r);
     if (a.noise) {
       const size_t ni = a.noise_div == 1 ? i : (size_t)(b / a.noise_div) * CHW + r;
       a.out[i] = mu + a.noise[ni] * a.sd;
@@ -270,14 +279,32 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
   }
 }
 
-static int ddpm_step_launch(const char* who, const DdpmArgs& a, int H, dc_stream stream) {
+// The noise map of the same step (include/dcamd.h dc_ddpm_noise_map): out = (x_next - mu) / sd on ddpm_step_kernel's mean.  out may be
+// x_next's buffer: a thread reads its element before it writes it, and no other thread touches that element.
+__global__ __launch_bounds__(256) void ddpm_noise_map_kernel(const DdpmArgs a, const float* x_next) {
+#pragma clang fp contract(off)
+  const size_t CHW = (size_t)a.C * a.HW, total = CHW * a.n;
+  const size_t rows = a.patch > 1 ? (size_t)a.HW / (a.patch * a.patch) : (size_t)a.HW;
+  for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    int b;
+    size_t r;
+    const float mu = ddpm_mean(a, i, CHW, rows, b, r);
+    a.out[i] = (x_next[i] - mu) / a.sd;
+  }
+}
+
+// Argument checks and launch shape shared by the step and its noise map (x_next NULL: the step).
+static int ddpm_step_launch(const char* who, const DdpmArgs& a, int H, dc_stream stream, const float* x_next = nullptr) {
   DC_REQUIRE(a.z && a.pred && a.out, DC_ERR_ARG, "%s: null pointer", who);
   DC_REQUIRE(a.noise_div >= 1 && a.n % a.noise_div == 0, DC_ERR_ARG, "%s: noise_div=%d must be >= 1 and divide n=%d", who, a.noise_div, a.n);
   DC_REQUIRE(a.n > 0 && a.C > 0 && H > 0 && a.W > 0 && a.ld >= a.C * a.patch * a.patch, DC_ERR_SHAPE, "%s: extents", who);
   DC_REQUIRE(H % a.patch == 0 && a.W % a.patch == 0, DC_ERR_SHAPE, "%s: patch=%d does not tile %dx%d", who, a.patch, H, a.W);
   const size_t total = (size_t)a.n * a.C * a.HW;
   const unsigned grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  if (x_next)
+    hipLaunchKernelGGL(ddpm_noise_map_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, x_next);
+  else
+    hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   return dc_check_launch(who);
 }
 
@@ -293,6 +320,15 @@ extern "C" int dc_ddpm_step_shared(const dc_ddpm_step_shared_params* p, dc_strea
   DdpmArgs a{p->z, p->pred, p->noise, p->out, p->C, p->H * p->W, p->W, p->ld, p->patch > 1 ? p->patch : 1, p->v_param, p->n,
              p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd, p->noise_div};
   return ddpm_step_launch("dc_ddpm_step_shared", a, p->H, stream);
+}
+
+extern "C" int dc_ddpm_noise_map(const dc_ddpm_noise_map_params* p, dc_stream stream) {
+  DC_REQUIRE(p && p->x_next, DC_ERR_ARG, "dc_ddpm_noise_map: null pointer");
+  DC_REQUIRE(p->sd > 0.f && p->sd < __builtin_huge_valf(), DC_ERR_ARG,      // NaN fails both comparisons
+             "dc_ddpm_noise_map: sd=%g must be finite and > 0", (double)p->sd);
+  DdpmArgs a{p->z, p->pred, nullptr, p->out, p->C, p->H * p->W, p->W, p->ld, p->patch > 1 ? p->patch : 1, p->v_param, p->n,
+             p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd, 1};
+  return ddpm_step_launch("dc_ddpm_noise_map", a, p->H, stream, p->x_next);
 }
 
 // ------------------------------------------------------------------ solver step ----

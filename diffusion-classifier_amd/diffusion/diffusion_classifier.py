@@ -82,6 +82,9 @@ Additive: `.counterfactual(x, classes, from_t, ...)` — every class from shared
 reference's experiments/ipmsa/explain.py procedure; counterfactual.py).  `config.sampler` ("ddim" | "dpmpp_2m"; unset or "ddpm": the
 ancestral sampler) makes `sample` and `counterfactual` deterministic after their start, `.invert(x, text, to_t)` is DDIM inversion and
 `counterfactual(..., start="invert")` decodes every class from the image's own inverted latent (solver.py).
+`.invert_ddpm(x, text, from_t)` is the edit-friendly DDPM inversion — a start and one noise map per step under which the ancestral sampler
+decodes the image back exactly — and `counterfactual(..., start="ddpm_invert")` decodes every class from it (ddpm_invert.py;
+`ddpm_invert_max_bytes` caps the maps' buffer, default 2 GiB).
 """
 import math
 import os
@@ -93,6 +96,7 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import dist as D
 from .. import counterfactual as CF
+from .. import ddpm_invert as DI
 from .. import posterior as P
 from .. import evidence as EV
 from .. import solver as S
@@ -558,11 +562,12 @@ class DiffusionClassifier(nn.Module):
         return torch.clamp(x, -1, 1)
 
     @torch.no_grad()
-    def ddpm_sampler_step(self, z_t, pred, u_pred, logsnr_t, logsnr_s):
+    def ddpm_sampler_step(self, z_t, pred, u_pred, logsnr_t, logsnr_s, w=None):
+        """(mu, var) of one ancestral step; w: the guidance weight, config.cfg_w when None (`invert_ddpm` passes its own)."""
         c = -torch.special.expm1(logsnr_t - logsnr_s)
         alpha_t, alpha_s = torch.sqrt(torch.sigmoid(logsnr_t)), torch.sqrt(torch.sigmoid(logsnr_s))
         sigma_t, sigma_s = torch.sqrt(torch.sigmoid(-logsnr_t)), torch.sqrt(torch.sigmoid(-logsnr_s))
-        w = self.cfg_w
+        w = self.cfg_w if w is None else w
         pred = (1 + w) * pred - w * u_pred                                   # classifier-free guidance mix
         x_pred = alpha_t * z_t - sigma_t * pred if self.pred_param == 'v' else (z_t - sigma_t * pred) / alpha_t
         x_pred = self.clip(x_pred)
@@ -672,8 +677,16 @@ class DiffusionClassifier(nn.Module):
           start        "noise": the start is drawn as above (torch, or Philox row b);
                        "invert": the start is `invert(x, invert_class, from_t)`, the image's own z_{from_t} — no noise at all, the call
                        touches no generator and returns the same bits every time; needs a deterministic config.sampler (ValueError
-                       otherwise: noise added to an inverted latent defeats it)
-          invert_class an int tensor [BS] of class ids to invert under (the label `classify` returned, say); None: the null token"""
+                       otherwise: noise added to an inverted latent defeats it);
+                       "ddpm_invert": see below
+          invert_class an int tensor [BS] of class ids to invert under (the label `classify` returned, say); None: the null token
+        start="ddpm_invert" (the ancestral sampler only: config.sampler unset or "ddpm"; ValueError under a deterministic one): the
+        start and the noise of every step come from `invert_ddpm(x, invert_class, from_t, rng=rng, seed=seed)` — the K trajectories of
+        image b start from its x_0 and step i adds its noise map i through `dc_ddpm_step_shared`, then `sample`'s last pass, the clipped
+        mean, as ever.  Under invert_class itself every step lands on the inversion's next latent again (fp32 rounding is the only
+        error, at any sampling_steps and cfg_w), so that class's sample is the last pass applied to the image's own x_n and its map
+        holds no solver error; another class's map is the label's effect.  rng / seed govern the inversion's n + 1 draws; the decode
+        draws nothing.  Costs one more backbone pass per step and the maps' memory (config.ddpm_invert_max_bytes)"""
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space,
                       lambda H, W, k: _units_per_launch(self.config, H, W, k), start=start, invert_class=invert_class)
 
@@ -688,6 +701,27 @@ class DiffusionClassifier(nn.Module):
         Works whatever config.sampler says (always DDIM).  HIP backbones run a pair session per chunk of images and one `dc_solver_step`
         per step and chunk; a foreign nn.Module takes the eager form (solver.py)."""
         return S.invert(self, x, text, to_t, guidance, lambda H, W, k: _units_per_launch(self.config, H, W, k))
+
+    @torch.no_grad()
+    def invert_ddpm(self, x, text=None, from_t=0.5, *, guidance=None, rng="reference", seed=0):
+        """Edit-friendly DDPM inversion (Huberman-Spiegelglas et al., CVPR 2024) -> `DdpmInversion(start, noise, from_t, guidance)`: the
+        noise maps under which the ANCESTRAL sampler decodes x back.  On `sample`'s grid linspace(from_t, 0, sampling_steps + 1), points
+        i = 0 .. n: the latents x_i = alpha_i x + sigma_i e_i are drawn independently, and noise[i] = (x_{i+1} - mu_i) / sd_i with mu_i,
+        sd_i the posterior mean and deviation of `ddpm_sampler_step` at (x_i, lam_i -> lam_{i+1}).  The sampler started at `start` = x_0
+        and fed noise[i] in place of its draws lands on x_{i+1} after every step — exactly up to fp32 rounding, at any sampling_steps
+        and any guidance, the clip of the data prediction included — and ends with its usual last pass from x_n.
+          start     [BS, C, H, W] f32;  noise [sampling_steps, BS, C, H, W] f32 on x.device: 4 * sampling_steps * x.numel() bytes, refused
+                    with a ValueError above config.ddpm_invert_max_bytes (additive key; unset: 2 GiB)
+          text      an int tensor [BS] of class ids to condition on; None: the null token
+          guidance  the w the maps are solved under; None: config.cfg_w, so that the sampler under the same class reproduces the
+                    latents.  Any float works: the maps absorb whatever the prediction is (unlike `invert`, nothing is unstable here)
+          rng       "reference": n + 1 `torch.randn_like(x)` draws in the order i = 0 .. n; "philox": `dc_philox_normal` row i * BS + b
+                    keyed by `seed` (counterfactual's convention), no torch generator touched, the same bits from call to call; HIP
+                    backbones only, C * H * W a multiple of 4
+        Every refusal comes before the first draw.  HIP backbones run a pair session per chunk of images (classify's launch-size rule)
+        and one `dc_ddpm_noise_map` per pass and chunk, nothing is copied to the host inside the loop; a foreign nn.Module takes the
+        eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`."""
+        return DI.invert(self, x, text, from_t, guidance, rng, seed, lambda H, W, k: _units_per_launch(self.config, H, W, k))
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----
     @torch.no_grad()

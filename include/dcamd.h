@@ -32,6 +32,8 @@
  *                       experiments/ipmsa/explain.py: every class trajectory of an image from shared noise, and where they differ
  *   dc_solver_step      nothing in the reference: one pass of a deterministic sampler (DDIM, DPM-Solver++ 2M) or of DDIM inversion on
  *                       the prediction pair dc_ddpm_step reads, for sample / counterfactual with config.sampler set and for invert
+ *   dc_ddpm_noise_map   nothing in the reference: the noise under which one ancestral step lands on a given next latent (edit-friendly
+ *                       DDPM inversion), for invert_ddpm and counterfactual(start="ddpm_invert")
  *   dc_stage_topk / dc_reduce_argmin / dc_stage_maps
  *                       the stage end, diffusion_classifier.py:718-725 (mean over trials, k smallest classes) and the
  *                       per-image surviving-class lists of the next stage (:695-698, ragged after pruning / fast mode
@@ -75,7 +77,8 @@ extern "C" {
  * (dc_stage_stop and dc_stage_maps_rows likewise; both are called directly)
  * (dc_err_map, dc_err_map_params and DC_OP_ERR_MAP, and dc_evidence_maps with dc_evidence_maps_params — called directly — are additive
  *  within 5: no existing struct or symbol changed)
- * (dc_solver_step and dc_solver_step_params — called directly — are additive within 5 likewise) */
+ * (dc_solver_step and dc_solver_step_params — called directly — are additive within 5 likewise)
+ * (dc_ddpm_noise_map and dc_ddpm_noise_map_params — called directly — likewise) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -546,6 +549,23 @@ typedef struct {
   float w, one_plus_w, alpha_t, sigma_t, k1, k2, k3;
 } dc_solver_step_params;
 int dc_solver_step(const dc_solver_step_params* p, dc_stream s);
+
+/* The noise map of one ancestral step (edit-friendly DDPM inversion, Huberman-Spiegelglas et al. 2024): the noise under which
+ * dc_ddpm_step takes z to x_next.  Layouts and indexing are dc_ddpm_step's (z / x_next / out [n, C, H, W] f32 NCHW; pred [2n, H, W, ld]
+ * f32 NHWC, rows 2b and 2b+1; patch > 1: DiT's un-patchified projection, feature stride C).  Per element, in this order, no contraction:
+ *   pr  = one_plus_w * pc - w * pu
+ *   x   = v_param ? alpha_t * z - sigma_t * pr : (z - sigma_t * pr) / alpha_t;   x = min(max(x, -1), 1)
+ *   mu  = alpha_s * (z * (1 - c) / alpha_t + c * x)                              (dc_ddpm_step's mean: the same device code)
+ *   out = (x_next - mu) / sd
+ * so that dc_ddpm_step on (z, pred) with noise = out gives mu + out * sd = x_next up to the rounding of the last two operations.  The
+ * kernel equals the torch evaluation of the same expressions bit for bit for the same fp32 scalars.  out may be the buffer of x_next
+ * (every thread reads its element before it writes it).  NULL pointers, or an sd that is not finite and > 0: DC_ERR_ARG. */
+typedef struct {
+  const float* z; const float* pred; const float* x_next; float* out;
+  int32_t n, C, H, W, ld, patch, v_param;
+  float w, one_plus_w, alpha_t, sigma_t, alpha_s, c, sd;
+} dc_ddpm_noise_map_params;
+int dc_ddpm_noise_map(const dc_ddpm_noise_map_params* p, dc_stream s);
 
 /* ---------------------------------------------------------------- difference maps - */
 /* out[i, y, x] = sum_c |a[i, c, y, x] - r[r_of_a[i], c, y, x]|, fp32, c ascending (a fixed order).  a [n, C, H, W], r [m, C, H, W],
