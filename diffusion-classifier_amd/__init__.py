@@ -12,6 +12,7 @@ All arithmetic of the scoring path runs in `libdcamd.so` (HIP kernels + C-ABI, c
 from . import _lib  # noqa: F401
 from .nets.unet import UNetCondition2D, UNet2D  # noqa: F401
 from .nets.dit import DiT  # noqa: F401
+from .nets.vae import VAEEncoder  # noqa: F401
 from .diffusion.diffusion_classifier import DiffusionClassifier  # noqa: F401
 from .utils.wavelet import wavelet_dec_2, wavelet_enc_2  # noqa: F401
 from .posterior import ClassPosterior  # noqa: F401
@@ -126,6 +127,12 @@ def ipmsa_experiment_unet_kwargs(image_channels=10, image_size=256, wavelet_tran
                 up_block_types=("CrossAttnUpBlock2D",) * 2 + ("UpBlock2D",) * 3,
                 mid_block_type="UNetMidBlock2DCrossAttn", encoder_hid_dim=256, encoder_hid_dim_type="text_proj",
                 cross_attention_dim=256)
+
+
+def sd_vae_kwargs():
+    # the published Stable Diffusion AutoencoderKL (sd-vae-ft-mse / -ema, the `vae/` of SD 1.x): encoder side, 8x downsampling
+    return dict(in_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2, norm_num_groups=32,
+                scaling_factor=0.18215)
 
 
 def chexpert_dit_b4_kwargs(wavelet_transform=True):

@@ -83,6 +83,8 @@ static int run_one(const dc_op* ops, int i, dc_stream s) {
       case DC_OP_TBLOCK_FRONT: rc = dc_tblock_front(static_cast<const dc_tblock_front_params*>(ops[i].params), s); break;
       case DC_OP_EPS_MSE: rc = dc_eps_mse(static_cast<const dc_eps_mse_params*>(ops[i].params), s); break;
       case DC_OP_ERR_MAP: rc = dc_err_map(static_cast<const dc_err_map_params*>(ops[i].params), s); break;
+      case DC_OP_ATTENTION_WIDE: rc = dc_attention_wide(static_cast<const dc_attention_wide_params*>(ops[i].params), s); break;
+      case DC_OP_IM2COL_S2: rc = dc_im2col_s2(static_cast<const dc_im2col_s2_params*>(ops[i].params), s); break;
       default: dc_set_error("dc_run_plan: op %d has unknown kind %d", i, ops[i].kind); return DC_ERR_ARG;
     }
     if (rc != DC_OK) {

@@ -1,6 +1,7 @@
 // attn_strip.h — the two attention bodies that attention_cross.hip (cross-attention), t5.hip (relative-position bias, a length per
 // sample) and clip.hip (causal, a length per sample) share; attention.hip (self-attention) runs the exact body and builds its two
-// transposed-score kernels from the same three pieces as attn_strip_run (attn_score_tile, attn_exp_pack, attn_pv_step).  Each of
+// transposed-score kernels from the same three pieces as attn_strip_run (attn_score_tile, attn_exp_pack, attn_pv_step);
+// attention_wide.hip (heads of 256 / 512 channels) does the same with a query tile spread over four waves.  Each of
 // those files keeps thin __global__ kernels that decode their item, fill a StripView and a Mode, and call a body; what differs between
 // them lives in the Mode alone:
 //   kZeroPad              queries at or past the length exist as rows: written as zeros, and a whole tile of them reads nothing

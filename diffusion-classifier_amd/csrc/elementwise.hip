@@ -547,3 +547,48 @@ extern "C" int dc_haar_idwt2(const float* in, float* out, int32_t n, int32_t C, 
   hipLaunchKernelGGL(haar_idwt2_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), in, out, total, C, h, w, scale);
   return dc_check_launch("dc_haar_idwt2");
 }
+
+// ------------------------------------------------------------------ im2col, stride 2 -
+// out[i, oy, ox, (ky 3 + kx) C + c] = x[i, 2 oy + ky, 2 ox + kx, c], zero where 2 oy + ky >= H or 2 ox + kx >= W: the A operand of a
+// stride-2 3x3 conv padded at the bottom and right only (AutoencoderKL's downsampler, F.pad(x, (0, 1, 0, 1)) in front of a stride-2 conv
+// without padding) as a 1x1 GEMM over K = 9 C.  A pure move: one lane per unit U of the output (16 bytes where x, out, C and ld allow
+// it, else one element), consecutive lanes on consecutive output units.  Cu / ldu: C and the row stride of x in units.
+template <typename U>
+__global__ __launch_bounds__(256) void im2col_s2_kernel(const U* __restrict__ x, U* __restrict__ out, long long total, int H, int W, int Cu, int ldu) {
+  const int Ho = H / 2, Wo = W / 2;
+  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const int c = (int)(idx % Cu); long long r = idx / Cu;
+    const int tap = (int)(r % 9); r /= 9;
+    const int ox = (int)(r % Wo); r /= Wo;
+    const int oy = (int)(r % Ho);
+    const long long i = r / Ho;
+    const int iy = 2 * oy + tap / 3, ix = 2 * ox + tap % 3;
+    U v = {};
+    if (iy < H && ix < W) v = x[((i * H + iy) * W + ix) * ldu + c];
+    out[idx] = v;
+  }
+}
+
+extern "C" int dc_im2col_s2(const dc_im2col_s2_params* p, dc_stream stream) {
+  DC_REQUIRE(p && p->x && p->out, DC_ERR_ARG, "dc_im2col_s2: null pointer");
+  DC_REQUIRE(p->dtype == DC_F32 || p->dtype == DC_BF16 || p->dtype == DC_F16, DC_ERR_DTYPE, "dc_im2col_s2: dtype %d", p->dtype);
+  DC_REQUIRE(p->n > 0 && p->C > 0 && p->H > 0 && p->W > 0, DC_ERR_SHAPE, "dc_im2col_s2: extents n=%d C=%d H=%d W=%d", p->n, p->C, p->H, p->W);
+  DC_REQUIRE(p->H % 2 == 0 && p->W % 2 == 0, DC_ERR_SHAPE, "dc_im2col_s2: H=%d W=%d must be even", p->H, p->W);
+  DC_REQUIRE(p->ld >= p->C, DC_ERR_SHAPE, "dc_im2col_s2: ld=%d < C=%d", p->ld, p->C);
+  const int es = dc_dtype_size(p->dtype), epc = 16 / es;
+  DC_REQUIRE((((uintptr_t)p->x | (uintptr_t)p->out) & (uintptr_t)(es - 1)) == 0, DC_ERR_ALIGN, "dc_im2col_s2: x/out must be element aligned");
+  const long long elems = (long long)p->n * (p->H / 2) * (p->W / 2) * 9 * p->C;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  auto grid = [](long long items) { const long long b = (items + 255) / 256; return (unsigned)(b > 65536 ? 65536 : b); };
+  if (p->C % epc == 0 && p->ld % epc == 0 && (((uintptr_t)p->x | (uintptr_t)p->out) & 15) == 0) {
+    hipLaunchKernelGGL(im2col_s2_kernel<chunk16>, dim3(grid(elems / epc)), dim3(256), 0, s, reinterpret_cast<const chunk16*>(p->x),
+                       reinterpret_cast<chunk16*>(p->out), elems / epc, p->H, p->W, p->C / epc, p->ld / epc);
+  } else if (es == 4) {
+    hipLaunchKernelGGL(im2col_s2_kernel<uint32_t>, dim3(grid(elems)), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(p->x),
+                       reinterpret_cast<uint32_t*>(p->out), elems, p->H, p->W, p->C, p->ld);
+  } else {
+    hipLaunchKernelGGL(im2col_s2_kernel<uint16_t>, dim3(grid(elems)), dim3(256), 0, s, reinterpret_cast<const uint16_t*>(p->x),
+                       reinterpret_cast<uint16_t*>(p->out), elems, p->H, p->W, p->C, p->ld);
+  }
+  return dc_check_launch("dc_im2col_s2");
+}

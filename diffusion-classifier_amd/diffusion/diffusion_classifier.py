@@ -16,7 +16,9 @@ default 6), `dwt_on_device` (True: `inference` applies `wavelet_dec_2(images) / 
 prefetch stream), `shard_grid` (opt-in: True
 shards the (trial, image) grid of ONE replicated batch over the default process group),
 `simulate_rank` ((r, N), bench.py only: time rank r's share of an N-rank sharded call on one GPU),
-`stop_margin_z` (opt-in per-image early stopping, see below; None: off, none of its code runs).
+`stop_margin_z` (opt-in per-image early stopping, see below; None: off, none of its code runs),
+`vae_path` (a LOCAL diffusers AutoencoderKL directory: `classify` encodes images to latents on the device first, nets/vae.py;
+`vae_dtype` its compute dtype, default the backbone's; `encode_latents(x)`; `classify(..., latents=True)` takes latents as they are).
 
 What differs is HOW classify runs.  The reference walks a Python double loop — T trials x C
 classes sequential eager backbone calls at batch BS (:686-714).  Here the (image, trial, class)
@@ -252,6 +254,16 @@ class DiffusionClassifier(nn.Module):
             self.encoder = None
             self.null_token = self.config.classes
         print(f"Parameter count: {sum(p.numel() for p in self.model.parameters())}")
+        # latent-space backbones (additive key vae_path): the encoder half of an AutoencoderKL from a local diffusers directory, in front
+        # of classify; a submodule, so it moves with the classifier.  Without the key nothing below exists
+        self.vae = None
+        if self.config.vae_path is not None:
+            from ..nets.vae import VAEEncoder
+            self.vae = VAEEncoder.from_directory(self.config.vae_path)
+            self.vae.set_compute_dtype(self.config.vae_dtype or self.config.compute_dtype or "bf16")
+            zc, ic = self.vae.config.latent_channels, getattr(backbone.config, "in_channels", None)
+            if ic != zc:
+                raise ValueError(f"backbone.config.in_channels = {ic} but the VAE under {self.config.vae_path} has latent_channels = {zc}")
         self._score_plans = {}
         self._timed_sink = None      # bench.py: list collecting (plan, per-op event ms) instead of plain runs
 
@@ -325,10 +337,23 @@ class DiffusionClassifier(nn.Module):
     def logsnr_schedule_cosine_shifted(self, t):
         return self.logsnr_schedule_cosine(t) + 2 * math.log(self.noise_d / self.image_d)
 
+    @torch.no_grad()
+    def encode_latents(self, x):
+        """config.vae_path set: images [B, C, H, W] in [-1, 1] -> the latents [B, latent_channels, H / f, W / f] fp32 the backbone is
+        trained on, (posterior mean - shift_factor) * scaling_factor, on the VAE's device (nets/vae.py: all of it in libdcamd; x is moved
+        there if it is elsewhere).  The mean, not a posterior sample: the same image always gives the same latents."""
+        if self.vae is None:
+            raise RuntimeError("encode_latents needs config.vae_path: a LOCAL diffusers AutoencoderKL directory")
+        return self.vae(x.to(device=self.vae.encoder.conv_in.weight.device, dtype=torch.float32))
+
     # ---- the hot path ---------------------------------------------------------------------
     @torch.no_grad()
     def classify(self, x, text=None, fast=False, *, t=None, eps=None, fast_select=None, return_errors=False,
-                 rng="reference", seed=0, group=None, return_posterior=False, return_trials=False, return_evidence=False):
+                 rng="reference", seed=0, group=None, return_posterior=False, return_trials=False, return_evidence=False, latents=False):
+        """latents (additive; config.vae_path only): True says x already holds latents (`encode_latents`); otherwise x is an image
+        batch and is encoded first — t / eps, the evidence maps and everything else then live on the latent grid."""
+        if self.vae is not None and not latents:
+            x = self.encode_latents(x)
         cfg = self.config
         z_stop = P.stop_margin_of(cfg)           # None: no per-image early stopping, none of its code runs
         if z_stop is not None and cfg.simulate_rank:
@@ -607,7 +632,8 @@ class DiffusionClassifier(nn.Module):
         """Ancestral DDPM sampling with classifier-free guidance (reference :210-293), same RNG consumption order as the reference.
         config.sampler = "ddim" | "dpmpp_2m" (additive; unset or "ddpm": everything below, untouched): the start is drawn as ever, then
         sampling_steps deterministic passes on linspace(from_t, 0, sampling_steps + 1) (solver.py) — only the initial draw is taken
-        from torch's generator."""
+        from torch's generator.
+        With config.vae_path, x and the result are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
         sampler = S.sampler_of(self.config)
         if sampler is not None:
             return S.sample(self, x, text, from_t, sampler, lambda H, W, k: _units_per_launch(self.config, H, W, k))
@@ -686,7 +712,8 @@ class DiffusionClassifier(nn.Module):
         mean, as ever.  Under invert_class itself every step lands on the inversion's next latent again (fp32 rounding is the only
         error, at any sampling_steps and cfg_w), so that class's sample is the last pass applied to the image's own x_n and its map
         holds no solver error; another class's map is the label's effect.  rng / seed govern the inversion's n + 1 draws; the decode
-        draws nothing.  Costs one more backbone pass per step and the maps' memory (config.ddpm_invert_max_bytes)"""
+        draws nothing.  Costs one more backbone pass per step and the maps' memory (config.ddpm_invert_max_bytes)
+        With config.vae_path, x, the samples and the maps are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space,
                       lambda H, W, k: _units_per_launch(self.config, H, W, k), start=start, invert_class=invert_class)
 
@@ -699,7 +726,8 @@ class DiffusionClassifier(nn.Module):
           guidance  the w of the inversion only (config.cfg_w is not read).  0, the default, is the conditional prediction alone: guided
                     inversion is known to be unstable
         Works whatever config.sampler says (always DDIM).  HIP backbones run a pair session per chunk of images and one `dc_solver_step`
-        per step and chunk; a foreign nn.Module takes the eager form (solver.py)."""
+        per step and chunk; a foreign nn.Module takes the eager form (solver.py).
+        With config.vae_path, x and the result are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
         return S.invert(self, x, text, to_t, guidance, lambda H, W, k: _units_per_launch(self.config, H, W, k))
 
     @torch.no_grad()
@@ -720,7 +748,8 @@ class DiffusionClassifier(nn.Module):
                     backbones only, C * H * W a multiple of 4
         Every refusal comes before the first draw.  HIP backbones run a pair session per chunk of images (classify's launch-size rule)
         and one `dc_ddpm_noise_map` per pass and chunk, nothing is copied to the host inside the loop; a foreign nn.Module takes the
-        eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`."""
+        eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`.
+        With config.vae_path, x, start and noise are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
         return DI.invert(self, x, text, from_t, guidance, rng, seed, lambda H, W, k: _units_per_launch(self.config, H, W, k))
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----

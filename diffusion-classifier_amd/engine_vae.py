@@ -1,0 +1,186 @@
+"""AutoencoderKL encoder as ONE launch plan for libdcamd — see engine.py for the plan model.
+
+Restated: the encoder half of diffusers' `AutoencoderKL` (0.31 layout) and the mean of its posterior, scaled:
+    conv_in -> per level [layers_per_block x ResNet, then (all but the last level) pad (0, 1, 0, 1) + 3x3 stride-2 conv]
+            -> mid block [ResNet, single-head attention over the H x W tokens, ResNet] -> GroupNorm + SiLU -> conv_out -> quant_conv
+    latent = (mean - shift_factor) * scaling_factor,    mean = the first latent_channels of the 2 x latent_channels moments
+A ResNet is GroupNorm(eps 1e-6) + SiLU -> conv3x3 -> GroupNorm + SiLU -> conv3x3, plus the input (through a 1x1 conv_shortcut when the
+channel count changes); there is no time embedding.  The attention is GroupNorm -> to_q | to_k | to_v (with bias) -> softmax(q k^T C^-1/2) v
+over ONE head as wide as the level -> to_out.0 + bias + the block input.
+
+What runs where:
+  conv_in          the im2col GEMM, its operand written by dc_qsample (alpha = 1, sigma = 0, im2col = 1) as in UNetCondition2D.forward
+  3x3 convs        dc_igemm taps = 9 behind a dc_groupnorm pass: the plain route.  The producer-side GroupNorm hand-off (pn_claim) is the
+                   UNet plan's business and is never claimed here; the convs do write the quad statistics (qstats) the GroupNorm pass
+                   behind them reads, where dc_igemm offers them
+  downsampler      dc_im2col_s2 + a 1x1 dc_igemm over K = 9 C: dc_igemm's stride-2 conv pads every side and reads other pixels
+  mid attention    dc_attention_wide (C = 256 / 512), dc_attention where C <= 128
+  tail             quant_conv's mean rows, scaling_factor and shift_factor are folded into conv_out on the host in fp64 (fold_tail): the
+                   plan's last conv writes latent_channels fp32 channels and nothing of the log-variance half is computed
+The residual stream is in the compute dtype, as in the UNet plan.
+"""
+import os
+
+import torch
+
+from . import _lib as L
+from .engine import DT_SIZE, PlanBuilder, bke, f32c, pack_conv3x3, pack_matrix, round_up
+
+GN_EPS = 1e-6
+MID_WIDTHS = (64, 128) + L.ATTENTION_WIDE_DIMS      # dc_attention / dc_attention_wide, and a multiple of the GEMMs' K granule
+CHANNEL_GRANULE = 64                                # K granule of the 16-bit GEMMs (128-byte LDS rows)
+
+
+def fold_tail(conv_out_w, conv_out_b, quant_w, quant_b, latent_channels, scaling_factor, shift_factor):
+    """conv_out [2z, C, 3, 3] followed by the mean rows of quant_conv [2z, 2z, 1, 1] (None: no quant_conv) and by
+    (mean - shift) * scaling, as ONE 3x3 conv [z, C, 3, 3] with bias [z]: a 1x1 conv after a 3x3 conv is a 3x3 conv.  fp64 on the host."""
+    z = latent_channels
+    w, b = conv_out_w.detach().double().cpu(), conv_out_b.detach().double().cpu()
+    if quant_w is not None:
+        q = quant_w.detach().double().cpu().reshape(quant_w.shape[0], -1)[:z]          # [z, 2z]: the rows that give the mean
+        w = torch.einsum("om,mckl->ockl", q, w)
+        b = q @ b + quant_b.detach().double().cpu()[:z]
+    else:
+        w, b = w[:z], b[:z]
+    s = float(scaling_factor)
+    return (w * s).contiguous(), ((b - float(shift_factor or 0.0)) * s).contiguous()
+
+
+def pack_down(w, dt, device):
+    """Conv2d weight [Cout, Cin, 3, 3] of a downsampler -> packed [Cout_pad, 9 Cin] in the (ky, kx, c) order dc_im2col_s2 writes."""
+    return pack_matrix(w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1), dt, device)
+
+
+class VaeWeights:
+    """Device-resident packed weights of a VAEEncoder for one compute dtype."""
+
+    def __init__(self, model, dt, device):
+        self.dt, self.dev = dt, device
+        cfg = model.config
+        sd = model.state_dict()
+        self.kin = round_up(9 * cfg.in_channels, bke(dt))
+        P = {}
+
+        def conv3(key, **kw):
+            P[key + ".w"] = pack_conv3x3(sd[key + ".weight"], dt, device, **kw)
+            P[key + ".b"] = f32c(sd[key + ".bias"], device)
+
+        def norm(key):
+            P[key + ".g"], P[key + ".b"] = f32c(sd[key + ".weight"], device), f32c(sd[key + ".bias"], device)
+
+        def resnet(key):
+            norm(key + ".norm1"); conv3(key + ".conv1"); norm(key + ".norm2"); conv3(key + ".conv2")
+            if key + ".conv_shortcut.weight" in sd:
+                P[key + ".conv_shortcut.w"] = pack_matrix(sd[key + ".conv_shortcut.weight"], dt, device)
+                P[key + ".conv_shortcut.b"] = f32c(sd[key + ".conv_shortcut.bias"], device)
+
+        conv3("encoder.conv_in", kpad=self.kin)
+        nb = len(cfg.block_out_channels)
+        for i in range(nb):
+            for j in range(cfg.layers_per_block):
+                resnet(f"encoder.down_blocks.{i}.resnets.{j}")
+            if i != nb - 1:
+                key = f"encoder.down_blocks.{i}.downsamplers.0.conv"
+                P[key + ".w"] = pack_down(sd[key + ".weight"], dt, device)
+                P[key + ".b"] = f32c(sd[key + ".bias"], device)
+        resnet("encoder.mid_block.resnets.0")
+        resnet("encoder.mid_block.resnets.1")
+        a = "encoder.mid_block.attentions.0."
+        norm(a + "group_norm")
+        # q | k | v as one [3 C, C] GEMM with the stacked bias
+        P[a + "qkv.w"] = pack_matrix(torch.cat([sd[a + f"to_{n}.weight"] for n in "qkv"], 0), dt, device)
+        P[a + "qkv.b"] = f32c(torch.cat([sd[a + f"to_{n}.bias"] for n in "qkv"], 0), device)
+        P[a + "to_out.0.w"] = pack_matrix(sd[a + "to_out.0.weight"], dt, device)
+        P[a + "to_out.0.b"] = f32c(sd[a + "to_out.0.bias"], device)
+        norm("encoder.conv_norm_out")
+        qc = cfg.use_quant_conv
+        w, b = fold_tail(sd["encoder.conv_out.weight"], sd["encoder.conv_out.bias"], sd["quant_conv.weight"] if qc else None,
+                         sd["quant_conv.bias"] if qc else None, cfg.latent_channels, cfg.scaling_factor, cfg.shift_factor)
+        self.tail_tile_n = 32 if cfg.latent_channels <= 32 else 128
+        P["tail.w"] = pack_conv3x3(w.float(), dt, device, tile_n=self.tail_tile_n)
+        P["tail.b"] = f32c(b.float(), device)
+        self.P = P
+
+
+class VaePlan:
+    """input: x [B, in_channels, H, W] fp32 (a device buffer of the plan: copy into it, then run()).
+    output: latents [B, H / f, W / f, latent_channels] fp32 NHWC (out_view), f = 2^(levels - 1)."""
+
+    def __init__(self, model, weights, B, H, W):
+        cfg = model.config
+        dev, dt, P = weights.dev, weights.dt, weights.P
+        boc, G = cfg.block_out_channels, cfg.norm_num_groups
+        use_qs = os.environ.get("DCAMD_NO_QSTATS") is None
+        self.B, self.H, self.W, self.dt = B, H, W, dt
+        pb = self.pb = PlanBuilder(dev, B, 1, 1)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.x = torch.zeros(B, cfg.in_channels, H, W, **f32)
+        xt = pb.external("x", self.x, "bj", 1, 1, 1, L.DC_F32)
+        one = pb.external("alpha", torch.ones(B, **f32), "bj", 1, 1, 1, L.DC_F32)
+        zero = pb.external("sigma", torch.zeros(B, **f32), "bj", 1, 1, 1, L.DC_F32)
+        # z = 1 * x + 0 * x as 3x3 patches: the A operand of conv_in as a GEMM
+        a0 = pb.qsample("a0", pb.const(self.x), xt, one, zero, None, cfg.in_channels, H, W, weights.kin, dt, im2col=True)
+        es = DT_SIZE[dt]
+
+        def gn(name, x, key, silu):
+            return pb.groupnorm(name, x, pb.const(P[key + ".g"]), pb.const(P[key + ".b"]), G, GN_EPS, silu)
+
+        def resnet(key, x):
+            Cout = P[key + ".conv1.b"].shape[0]
+            h = gn(key + ".gn1", x, key + ".norm1", True)
+            h = pb.igemm(key + ".conv1", h, pb.const(P[key + ".conv1.w"]), Cout, taps=9, bias=pb.const(P[key + ".conv1.b"]), qstats=use_qs)
+            h = gn(key + ".gn2", h, key + ".norm2", True)
+            sc = x
+            if key + ".conv_shortcut.w" in P:
+                sc = pb.igemm(key + ".short", x, pb.const(P[key + ".conv_shortcut.w"]), Cout, bias=pb.const(P[key + ".conv_shortcut.b"]))
+            return pb.igemm(key + ".conv2", h, pb.const(P[key + ".conv2.w"]), Cout, taps=9, bias=pb.const(P[key + ".conv2.b"]),
+                            residual=sc, qstats=use_qs)
+
+        def downsample(key, x):
+            col = pb.tensor(key + ".col", "bj", x.H // 2, x.W // 2, 9 * x.C, dt)
+            pb._emit(L.OP_IM2COL_S2, L.Im2colS2Params, dict(x=x, out=col, dtype=dt, n=B, H=x.H, W=x.W, C=x.C, ld=x.ld), [x], [col],
+                     dict(name=key + ".col", family="im2col_s2", flops=0.0, bytes=float(B * x.H * x.W * x.C * es + B * col.H * col.W * col.C * es)))
+            return pb.igemm(key, col, pb.const(P[key + ".w"]), x.C, bias=pb.const(P[key + ".b"]))
+
+        def attention(key, x):
+            Cc, Lq = x.C, x.H * x.W
+            hn = gn(key + "gn", x, key + "group_norm", False)
+            qkv = pb.igemm(key + "qkv", hn, pb.const(P[key + "qkv.w"]), 3 * Cc, bias=pb.const(P[key + "qkv.b"]))
+            q, k, v = qkv.view(0, Cc), qkv.view(Cc, Cc), qkv.view(2 * Cc, Cc)
+            if Cc <= 128:
+                o = pb.attention(key + "attn", q, k, v, 1, Cc)
+            else:
+                o = pb.tensor(key + "attn", "bj", x.H, x.W, Cc, dt)
+                pb._emit(L.OP_ATTENTION_WIDE, L.AttentionWideParams,
+                         dict(q=q, k=k, v=v, out=o, dtype=dt, n=B, L=Lq, heads=1, d=Cc, ld_qkv=qkv.ld, ld_out=o.ld, scale=float(Cc) ** -0.5),
+                         [q, k, v], [o], dict(name=key + "attn", family="attention_wide", flops=4.0 * B * Lq * Lq * Cc, bytes=4.0 * B * Lq * Cc * es))
+            return pb.igemm(key + "to_out", o, pb.const(P[key + "to_out.0.w"]), Cc, bias=pb.const(P[key + "to_out.0.b"]), residual=x)
+
+        h = pb.igemm("encoder.conv_in", a0, pb.const(P["encoder.conv_in.w"]), boc[0], bias=pb.const(P["encoder.conv_in.b"]),
+                     k_real=9 * cfg.in_channels)
+        for i in range(len(boc)):
+            for j in range(cfg.layers_per_block):
+                h = resnet(f"encoder.down_blocks.{i}.resnets.{j}", h)
+            if i != len(boc) - 1:
+                h = downsample(f"encoder.down_blocks.{i}.downsamplers.0.conv", h)
+        h = resnet("encoder.mid_block.resnets.0", h)
+        h = attention("encoder.mid_block.attentions.0.", h)
+        h = resnet("encoder.mid_block.resnets.1", h)
+        h = gn("encoder.conv_norm_out", h, "encoder.conv_norm_out", True)
+        self.out = pb.igemm("encoder.conv_out", h, pb.const(P["tail.w"]), cfg.latent_channels, taps=9, bias=pb.const(P["tail.b"]),
+                            out_dt=L.DC_F32, tile_n=weights.tail_tile_n)
+        pb.finalize(keep_alive=[self.out])
+        for i, (kd, _, _) in enumerate(pb.ops):
+            if kd == L.OP_ATTENTION_WIDE:
+                pb.meta[i]["variant"] = L.lib().dc_attention_wide_variant(pb.structs[i]).decode()
+            if pb.meta[i].get("variant") == "invalid" or pb.meta[i]["family"] == "invalid":
+                raise L.DcamdError(f"VaePlan: libdcamd refuses {pb.meta[i]['name']} at {B} x {H} x {W} in {model.compute_dtype}")
+
+    def run(self):
+        self.pb.run()
+
+    def run_timed(self):
+        return self.pb.run_timed()
+
+    def out_view(self):
+        return self.pb.tensor_view(self.out)

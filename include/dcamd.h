@@ -25,6 +25,10 @@
  *                       a CLIP text transformer (transformers' CLIPTextModel) as the text encoder behind encode_text_prompt: causal
  *                       self-attention with a row count per sample, LayerNorm from the fp32 stream into the compute type, token +
  *                       position embedding, quick-GELU / erf-GELU
+ *   dc_attention_wide / dc_im2col_s2
+ *                       nothing in the reference: the encoder half of diffusers' AutoencoderKL in front of a latent-space backbone
+ *                       (config key vae_path) — its mid-block attention over one head of 256 / 512 channels, and the A operand of its
+ *                       bottom/right-padded stride-2 downsampling conv; every other layer of the encoder is dc_igemm / dc_groupnorm
  *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
@@ -78,7 +82,9 @@ extern "C" {
  * (dc_err_map, dc_err_map_params and DC_OP_ERR_MAP, and dc_evidence_maps with dc_evidence_maps_params — called directly — are additive
  *  within 5: no existing struct or symbol changed)
  * (dc_solver_step and dc_solver_step_params — called directly — are additive within 5 likewise)
- * (dc_ddpm_noise_map and dc_ddpm_noise_map_params — called directly — likewise) */
+ * (dc_ddpm_noise_map and dc_ddpm_noise_map_params — called directly — likewise)
+ * (the AutoencoderKL encoder's entries — dc_attention_wide, dc_attention_wide_variant, dc_im2col_s2, their structs and
+ *  DC_OP_ATTENTION_WIDE / DC_OP_IM2COL_S2 — likewise) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -310,6 +316,29 @@ int dc_attention(const dc_attention_params* p, dc_stream s);
  * "invalid" when dc_attention would refuse them (measurement / tests only; static string). */
 const char* dc_attention_variant(const dc_attention_params* p);
 int64_t dc_workspace_bytes_attention(const dc_attention_params* p);
+
+/* The same arithmetic for heads of d = 256 or 512 channels (DC_ERR_SHAPE otherwise): the mid-block attention of an AutoencoderKL
+ * encoder, one head as wide as the level.  Fields, layout, scale > 0 and the error codes as for dc_attention; L >= 1 of any size.
+ * Routes: "wide", 16-bit with q / k / v 16-byte aligned, ld_qkv % 8 == 0, out 8-byte aligned and ld_out % 4 == 0 — one workgroup
+ * of four waves per (sample, head, 32 queries), wave w on channels [w d/4, (w+1) d/4) of the score product and of the output, the four
+ * partial score tiles summed through LDS in a fixed order, P rounded to the compute type for P.V only; "fp32", everything else — the
+ * exact fp32 kernel.  No atomics: out[i] depends on sample i's rows only. */
+typedef struct {
+  const void* q; const void* k; const void* v; void* out;
+  int32_t dtype, n, L, heads, d, ld_qkv, ld_out; float scale;
+} dc_attention_wide_params;
+int dc_attention_wide(const dc_attention_wide_params* p, dc_stream s);
+/* "wide" or "fp32"; "invalid" when dc_attention_wide would refuse the parameters (measurement / tests only; static string). */
+const char* dc_attention_wide_variant(const dc_attention_wide_params* p);
+
+/* ---------------------------------------------------------------- im2col, stride 2  */
+/* out[i, oy, ox, (ky*3 + kx)*C + c] = x[i, 2*oy + ky, 2*ox + kx, c], zero where 2*oy + ky >= H or 2*ox + kx >= W: the A operand of a
+ * stride-2 3x3 conv padded at the bottom and right only (AutoencoderKL's downsampler), which then runs as a 1x1 dc_igemm over
+ * K = 9 C with weights [Cout, (ky, kx, c)].  x [n, H, W, C] with row stride ld (elements); out [n, H/2, W/2, 9 C] dense; one dtype
+ * (DC_F32 / DC_BF16 / DC_F16).  H and W must be even (DC_ERR_SHAPE).  16-byte moves where x and out are 16-byte aligned and C and ld
+ * are multiples of 16 bytes, element moves otherwise. */
+typedef struct { const void* x; void* out; int32_t dtype, n, H, W, C, ld; } dc_im2col_s2_params;
+int dc_im2col_s2(const dc_im2col_s2_params* p, dc_stream s);
 
 /* ---------------------------------------------------------------- cross-attention */
 /* out[i] = softmax(q[q_map[i]] k[kv_map[i]]^T * scale) v[kv_map[i]] per head, for i < n: attention whose keys and values come from
@@ -689,7 +718,7 @@ typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GRO
                DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8,
                DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10, DC_OP_ATTENTION_BIAS = 11, DC_OP_RMSNORM = 12,
                DC_OP_EMBED_ROWS = 13, DC_OP_RELU = 14, DC_OP_ATTENTION_CAUSAL = 15, DC_OP_LAYERNORM_ROWS = 16, DC_OP_EMBED_ROWS_POS = 17,
-               DC_OP_ACT_PASS = 18, DC_OP_ERR_MAP = 19 } dc_op_kind;
+               DC_OP_ACT_PASS = 18, DC_OP_ERR_MAP = 19, DC_OP_ATTENTION_WIDE = 20, DC_OP_IM2COL_S2 = 21 } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */
