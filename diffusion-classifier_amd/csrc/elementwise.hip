@@ -233,16 +233,17 @@ extern "C" int dc_eps_mse(const dc_eps_mse_params* p, dc_stream stream) {
 // the image instead of ~14 elementwise torch launches.  Same operation ORDER as the reference's torch expressions and no
 // contraction, so every element equals the torch evaluation of the same fp32 scalars bit for bit — (1 + w) included: the caller
 // passes one_plus_w = float(1.0 + w), the Python double rounded ONCE as torch does (1.f + (float)w can differ by an ulp).
-struct DdpmArgs {
-  const float* z; const float* pred; const float* noise; float* out;
+// What the step kernels share: the latent, the prediction pair and its geometry, the guidance weights, the pass's alpha_t and sigma_t.
+struct StepArgs {
+  const float* z; const float* pred; float* out;
   int C, HW, W, ld, patch, v_param, n;
-  float w, one_plus_w, alpha_t, sigma_t, alpha_s, c, sd;
-  int noise_div;          // trajectory b adds noise row b / noise_div (dc_ddpm_step: 1, a row per trajectory)
+  float w, one_plus_w, alpha_t, sigma_t;
 };
 
-// The posterior mean of element i = (b, r) of z: the indexing of the prediction pair and the arithmetic up to mu.  One body for
-// ddpm_step_kernel and ddpm_noise_map_kernel, so the mean a noise map is solved against is the mean the step adds it to.
-__device__ __forceinline__ float ddpm_mean(const DdpmArgs& a, size_t i, size_t CHW, size_t rows, int& b, size_t& r) {
+// Element i = (b, r) of z: the indexing of the prediction pair, the guidance mix and the data prediction (clipped when `clip`) -> x;
+// zt = z[i].  One body for every step kernel, so the mean a noise map is solved against is the mean the step adds it to and the
+// solvers' x is the ancestral sampler's.
+__device__ __forceinline__ float step_xpred(const StepArgs& a, size_t i, size_t CHW, size_t rows, bool clip, int& b, size_t& r, float& zt) {
 #pragma clang fp contract(off)
   b = (int)(i / CHW);
   r = i - (size_t)b * CHW;
@@ -254,27 +255,56 @@ __device__ __forceinline__ float ddpm_mean(const DdpmArgs& a, size_t i, size_t C
   } else {
     pi = (size_t)p * a.ld + c;
   }
-  const float pc = a.pred[(size_t)(2 * b) * rows * a.ld + pi], pu = a.pred[(size_t)(2 * b + 1) * rows * a.ld + pi];
-  const float zt = a.z[i];
-  const float pr = a.one_plus_w * pc - a.w * pu;                                // pred = (1 + w) * pred - w * u_pred
-  float xp = a.v_param ? a.alpha_t * zt - a.sigma_t * pr : (zt - a.sigma_t * pr) / a.alpha_t;
-  xp = fminf(fmaxf(xp, -1.f), 1.f);                                              // clip
-  return a.alpha_s * (zt * (1.f - a.c) / a.alpha_t + a.c * xp);
+  const float* pair = a.pred + (size_t)(2 * b) * rows * a.ld + pi;               // image b's conditional rows, then its null rows
+  const float pc = pair[0], pu = pair[rows * a.ld];
+  zt = a.z[i];
+  const float pr = a.one_plus_w * pc - a.w * pu;                                 // pred = (1 + w) * pred - w * u_pred
+  float x = a.v_param ? a.alpha_t * zt - a.sigma_t * pr : (zt - a.sigma_t * pr) / a.alpha_t;
+  if (clip) x = fminf(fmaxf(x, -1.f), 1.f);
+  return x;
+}
+
+// Pointer, extent and patch checks, the kernels' common arguments and the grid size, for any of the four param structs.
+template <typename P>
+static int step_args(const char* who, const P* p, StepArgs& a, unsigned& grid) {
+  DC_REQUIRE(p && p->z && p->pred && p->out, DC_ERR_ARG, "%s: null pointer", who);
+  const int pp = p->patch > 1 ? p->patch : 1;
+  DC_REQUIRE(p->n > 0 && p->C > 0 && p->H > 0 && p->W > 0 && p->ld >= p->C * pp * pp, DC_ERR_SHAPE, "%s: extents", who);
+  DC_REQUIRE(p->H % pp == 0 && p->W % pp == 0, DC_ERR_SHAPE, "%s: patch=%d does not tile %dx%d", who, pp, p->H, p->W);
+  a = StepArgs{p->z, p->pred, p->out, p->C, p->H * p->W, p->W, p->ld, pp, p->v_param, p->n, p->w, p->one_plus_w, p->alpha_t, p->sigma_t};
+  const size_t total = (size_t)p->n * p->C * a.HW;
+  grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+  return DC_OK;
+}
+
+struct DdpmArgs {
+  StepArgs s;
+  const float* noise;
+  float alpha_s, c, sd;
+  int noise_div;          // trajectory b adds noise row b / noise_div (dc_ddpm_step: 1, a row per trajectory)
+};
+
+// The posterior mean of element i on the clipped data prediction.
+__device__ __forceinline__ float ddpm_mean(const DdpmArgs& a, size_t i, size_t CHW, size_t rows, int& b, size_t& r) {
+#pragma clang fp contract(off)
+  float zt;
+  const float xp = step_xpred(a.s, i, CHW, rows, true, b, r, zt);
+  return a.alpha_s * (zt * (1.f - a.c) / a.s.alpha_t + a.c * xp);
 }
 
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
 #pragma clang fp contract(off)
-  const size_t CHW = (size_t)a.C * a.HW, total = CHW * a.n;
-  const size_t rows = a.patch > 1 ? (size_t)a.HW / (a.patch * a.patch) : (size_t)a.HW;
+  const size_t CHW = (size_t)a.s.C * a.s.HW, total = CHW * a.s.n;
+  const size_t rows = (size_t)a.s.HW / (a.s.patch * a.s.patch);
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     int b;
     size_t r;
     const float mu = ddpm_mean(a, i, CHW, rows, b, r);
     if (a.noise) {
       const size_t ni = a.noise_div == 1 ? i : (size_t)(b / a.noise_div) * CHW + r;
-      a.out[i] = mu + a.noise[ni] * a.sd;
+      a.s.out[i] = mu + a.noise[ni] * a.sd;
     } else {
-      a.out[i] = fminf(fmaxf(mu, -1.f), 1.f);                                    // last pass: the clipped mean
+      a.s.out[i] = fminf(fmaxf(mu, -1.f), 1.f);                                  // last pass: the clipped mean
     }
   }
 }
@@ -283,103 +313,79 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
 // x_next's buffer: a thread reads its element before it writes it, and no other thread touches that element.
 __global__ __launch_bounds__(256) void ddpm_noise_map_kernel(const DdpmArgs a, const float* x_next) {
 #pragma clang fp contract(off)
-  const size_t CHW = (size_t)a.C * a.HW, total = CHW * a.n;
-  const size_t rows = a.patch > 1 ? (size_t)a.HW / (a.patch * a.patch) : (size_t)a.HW;
+  const size_t CHW = (size_t)a.s.C * a.s.HW, total = CHW * a.s.n;
+  const size_t rows = (size_t)a.s.HW / (a.s.patch * a.s.patch);
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     int b;
     size_t r;
     const float mu = ddpm_mean(a, i, CHW, rows, b, r);
-    a.out[i] = (x_next[i] - mu) / a.sd;
+    a.s.out[i] = (x_next[i] - mu) / a.sd;
   }
 }
 
-// Argument checks and launch shape shared by the step and its noise map (x_next NULL: the step).
-static int ddpm_step_launch(const char* who, const DdpmArgs& a, int H, dc_stream stream, const float* x_next = nullptr) {
-  DC_REQUIRE(a.z && a.pred && a.out, DC_ERR_ARG, "%s: null pointer", who);
-  DC_REQUIRE(a.noise_div >= 1 && a.n % a.noise_div == 0, DC_ERR_ARG, "%s: noise_div=%d must be >= 1 and divide n=%d", who, a.noise_div, a.n);
-  DC_REQUIRE(a.n > 0 && a.C > 0 && H > 0 && a.W > 0 && a.ld >= a.C * a.patch * a.patch, DC_ERR_SHAPE, "%s: extents", who);
-  DC_REQUIRE(H % a.patch == 0 && a.W % a.patch == 0, DC_ERR_SHAPE, "%s: patch=%d does not tile %dx%d", who, a.patch, H, a.W);
-  const size_t total = (size_t)a.n * a.C * a.HW;
-  const unsigned grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-  if (x_next)
-    hipLaunchKernelGGL(ddpm_noise_map_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, x_next);
-  else
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+template <typename P>
+static int ddpm_step_entry(const char* who, const P* p, int noise_div, dc_stream stream) {
+  DdpmArgs a;
+  unsigned grid;
+  if (const int rc = step_args(who, p, a.s, grid)) return rc;
+  DC_REQUIRE(noise_div >= 1 && p->n % noise_div == 0, DC_ERR_ARG, "%s: noise_div=%d must be >= 1 and divide n=%d", who, noise_div, p->n);
+  a.noise = p->noise, a.alpha_s = p->alpha_s, a.c = p->c, a.sd = p->sd, a.noise_div = noise_div;
+  hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   return dc_check_launch(who);
 }
 
-extern "C" int dc_ddpm_step(const dc_ddpm_step_params* p, dc_stream stream) {
-  DC_REQUIRE(p, DC_ERR_ARG, "dc_ddpm_step: null pointer");
-  DdpmArgs a{p->z, p->pred, p->noise, p->out, p->C, p->H * p->W, p->W, p->ld, p->patch > 1 ? p->patch : 1, p->v_param, p->n,
-             p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd, 1};
-  return ddpm_step_launch("dc_ddpm_step", a, p->H, stream);
-}
+extern "C" int dc_ddpm_step(const dc_ddpm_step_params* p, dc_stream stream) { return ddpm_step_entry("dc_ddpm_step", p, 1, stream); }
 
 extern "C" int dc_ddpm_step_shared(const dc_ddpm_step_shared_params* p, dc_stream stream) {
-  DC_REQUIRE(p, DC_ERR_ARG, "dc_ddpm_step_shared: null pointer");
-  DdpmArgs a{p->z, p->pred, p->noise, p->out, p->C, p->H * p->W, p->W, p->ld, p->patch > 1 ? p->patch : 1, p->v_param, p->n,
-             p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd, p->noise_div};
-  return ddpm_step_launch("dc_ddpm_step_shared", a, p->H, stream);
+  return ddpm_step_entry("dc_ddpm_step_shared", p, p ? p->noise_div : 1, stream);
 }
 
 extern "C" int dc_ddpm_noise_map(const dc_ddpm_noise_map_params* p, dc_stream stream) {
-  DC_REQUIRE(p && p->x_next, DC_ERR_ARG, "dc_ddpm_noise_map: null pointer");
+  DdpmArgs a;
+  unsigned grid;
+  if (const int rc = step_args("dc_ddpm_noise_map", p, a.s, grid)) return rc;
+  DC_REQUIRE(p->x_next, DC_ERR_ARG, "dc_ddpm_noise_map: null pointer");
   DC_REQUIRE(p->sd > 0.f && p->sd < __builtin_huge_valf(), DC_ERR_ARG,      // NaN fails both comparisons
              "dc_ddpm_noise_map: sd=%g must be finite and > 0", (double)p->sd);
-  DdpmArgs a{p->z, p->pred, nullptr, p->out, p->C, p->H * p->W, p->W, p->ld, p->patch > 1 ? p->patch : 1, p->v_param, p->n,
-             p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->alpha_s, p->c, p->sd, 1};
-  return ddpm_step_launch("dc_ddpm_noise_map", a, p->H, stream, p->x_next);
+  a.noise = nullptr, a.alpha_s = p->alpha_s, a.c = p->c, a.sd = p->sd, a.noise_div = 1;
+  hipLaunchKernelGGL(ddpm_noise_map_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, p->x_next);
+  return dc_check_launch("dc_ddpm_noise_map");
 }
 
 // ------------------------------------------------------------------ solver step ----
 // One pass of a deterministic data-prediction solver on the same prediction pair (include/dcamd.h dc_solver_step): the guidance mix and
-// the x-prediction are ddpm_step_kernel's, then the update z_s = k1 z + k2 D with D = x (DDIM) or x + k3 (x - xprev) (DPM-Solver++ 2M).
-// Same indexing as ddpm_step_kernel, the operation order of the header's expressions, no contraction.  xhat may be xprev's buffer: a
-// thread reads its element of xprev before it writes the same element of xhat, and no other thread touches that element.
+// the x-prediction are step_xpred's, then the update z_s = k1 z + k2 D with D = x (DDIM) or x + k3 (x - xprev) (DPM-Solver++ 2M).
+// The operation order of the header's expressions, no contraction.  xhat may be xprev's buffer: a thread reads its element of xprev
+// before it writes the same element of xhat, and no other thread touches that element.
 struct SolverArgs {
-  const float* z; const float* pred; const float* xprev; float* xhat; float* out;
-  int C, HW, W, ld, patch, v_param, clamp, final_pass, n;
-  float w, one_plus_w, alpha_t, sigma_t, k1, k2, k3;
+  StepArgs s;
+  const float* xprev; float* xhat;
+  int clamp, final_pass;
+  float k1, k2, k3;
 };
 
 __global__ __launch_bounds__(256) void solver_step_kernel(const SolverArgs a) {
 #pragma clang fp contract(off)
-  const size_t CHW = (size_t)a.C * a.HW, total = CHW * a.n;
-  const size_t rows = a.patch > 1 ? (size_t)a.HW / (a.patch * a.patch) : (size_t)a.HW;
+  const size_t CHW = (size_t)a.s.C * a.s.HW, total = CHW * a.s.n;
+  const size_t rows = (size_t)a.s.HW / (a.s.patch * a.s.patch);
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int b = (int)(i / CHW);
-    const size_t r = i - (size_t)b * CHW;
-    const int c = (int)(r / a.HW), p = (int)(r - (size_t)c * a.HW);
-    size_t pi;
-    if (a.patch > 1) {
-      const int y = p / a.W, xw = p - y * a.W, pp = a.patch;
-      pi = ((size_t)(y / pp) * (a.W / pp) + xw / pp) * a.ld + (size_t)((y % pp) * pp + xw % pp) * a.C + c;
-    } else {
-      pi = (size_t)p * a.ld + c;
-    }
-    const float pc = a.pred[(size_t)(2 * b) * rows * a.ld + pi], pu = a.pred[(size_t)(2 * b + 1) * rows * a.ld + pi];
-    const float zt = a.z[i];
-    const float pr = a.one_plus_w * pc - a.w * pu;
-    float x = a.v_param ? a.alpha_t * zt - a.sigma_t * pr : (zt - a.sigma_t * pr) / a.alpha_t;
-    if (a.clamp) x = fminf(fmaxf(x, -1.f), 1.f);
+    int b;
+    size_t r;
+    float zt;
+    const float x = step_xpred(a.s, i, CHW, rows, a.clamp, b, r, zt);
     float D = x;
     if (a.xprev) D = x + a.k3 * (x - a.xprev[i]);                                // read before the write below: xhat may be xprev
     if (a.xhat) a.xhat[i] = x;
-    a.out[i] = a.final_pass ? fminf(fmaxf(D, -1.f), 1.f) : a.k1 * zt + a.k2 * D;
+    a.s.out[i] = a.final_pass ? fminf(fmaxf(D, -1.f), 1.f) : a.k1 * zt + a.k2 * D;
   }
 }
 
 extern "C" int dc_solver_step(const dc_solver_step_params* p, dc_stream stream) {
-  DC_REQUIRE(p, DC_ERR_ARG, "dc_solver_step: null pointer");
-  DC_REQUIRE(p->z && p->pred && p->out, DC_ERR_ARG, "dc_solver_step: null pointer");
+  SolverArgs a;
+  unsigned grid;
+  if (const int rc = step_args("dc_solver_step", p, a.s, grid)) return rc;
   DC_REQUIRE(p->out != p->z, DC_ERR_ARG, "dc_solver_step: out must not alias z");
-  const int pp = p->patch > 1 ? p->patch : 1;
-  DC_REQUIRE(p->n > 0 && p->C > 0 && p->H > 0 && p->W > 0 && p->ld >= p->C * pp * pp, DC_ERR_SHAPE, "dc_solver_step: extents");
-  DC_REQUIRE(p->H % pp == 0 && p->W % pp == 0, DC_ERR_SHAPE, "dc_solver_step: patch=%d does not tile %dx%d", pp, p->H, p->W);
-  SolverArgs a{p->z, p->pred, p->xprev, p->xhat, p->out, p->C, p->H * p->W, p->W, p->ld, pp, p->v_param, p->clamp, p->final_pass, p->n,
-               p->w, p->one_plus_w, p->alpha_t, p->sigma_t, p->k1, p->k2, p->k3};
-  const size_t total = (size_t)p->n * p->C * a.HW;
-  const unsigned grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+  a.xprev = p->xprev, a.xhat = p->xhat, a.clamp = p->clamp, a.final_pass = p->final_pass, a.k1 = p->k1, a.k2 = p->k2, a.k3 = p->k3;
   hipLaunchKernelGGL(solver_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   return dc_check_launch("dc_solver_step");
 }

@@ -11,16 +11,17 @@ is the rounding of (x_{i+1} - mu_i) / sd_i * sd_i + mu_i.  Under another class t
 structure.  The sampler's last pass (the clipped mean from x_n) is kept and draws nothing.
 
 `run_eager` is the written statement — two backbone calls per pass and `ddpm_sampler_step` — and the path of a foreign nn.Module.  HIP
-backbones run pass i as one step of a pair session per chunk of images and one `dc_ddpm_noise_map` (include/dcamd.h) per pass and chunk;
-nothing is copied to the host inside the loop.  The n passes do not depend on one another: only two latents are alive at a time.
+backbones run pass i over a `trajectory.Walk` (`run_hip`): one step of a pair session per chunk of images and one `dc_ddpm_noise_map`
+(include/dcamd.h) per pass and chunk; nothing is copied to the host inside the loop.  The n passes do not depend on one another: only
+two latents are alive at a time.
 """
-import ctypes as C
 from collections import namedtuple
 
 import torch
 
 from . import _lib as L
 from . import solver as S
+from . import trajectory as TJ
 
 DEFAULT_MAX_BYTES = 2 << 30
 
@@ -73,78 +74,31 @@ def run_eager(dc, x, lab, from_t, w):
     return start.to(torch.float32), noise
 
 
-def run_hip(dc, backbone, x, lab, from_t, w, rng, seed, units):
-    """The same on a HIP backbone: image b is one unit pair (class token || null token) of a pair session per chunk of images, pass i is
-    one session step at (x_i, lam_i) and one `dc_ddpm_noise_map` per chunk that writes noise[i] in place."""
-    from . import counterfactual as CF
-    lib = L.require_gpu()
-    if not x.is_cuda:
-        raise L.DcamdError("invert_ddpm on a HIP backbone needs a CUDA/HIP tensor (as sample does; no CPU fallback)")
+def run_hip(walk, x, scal, alsg, noise):
+    """The same on a HIP backbone: image b is the one trajectory of its unit pair in `walk` (trajectory.py), pass i is one session step
+    at (x_i, lam_i) and one `dc_ddpm_noise_map` per chunk that writes noise[i] in place.  The latents take draws i = 0 .. n of `noise`."""
     dev = x.device
-    BS, Cc, H, W = x.shape
-    CHW = Cc * H * W
-    patch = int(getattr(backbone.config, "patch_size", 0) or 0)
-    oc = int(getattr(backbone.config, "out_channels", Cc) or Cc)
-    if oc != Cc:                 # the kernel indexes the prediction with z's channel count as the feature stride
-        raise L.DcamdError(f"fused noise map needs out_channels == in_channels (got {oc} vs {Cc})")
-    philox = rng == "philox"
-    if philox and CHW % 4:
-        raise L.DcamdError(f"rng='philox' needs C * H * W to be a multiple of 4, got {CHW}")
-    lams, scal, alsg = grid(dc, from_t)
-    n = len(lams) - 1
-    lam_dev = torch.stack([v.detach().float().reshape(()) for v in lams]).to(dev)
+    n = len(scal)
     alsg = [(a.to(dev), s.to(dev)) for a, s in alsg]
-    one_plus_w, v_param = float(1.0 + w), int(dc.pred_param == 'v')
     xf = x.detach().to(torch.float32).contiguous()
-    if philox:                   # row i * BS + b: counterfactual's convention (row b the start, (step + 1) * BS + b after it)
-        row_ids = torch.arange((n + 1) * BS, dtype=torch.int64, device=dev)
-        nbuf = torch.empty_like(xf)
-
-    def latent(i):
-        if philox:
-            L.check(lib.dc_philox_normal(nbuf.data_ptr(), BS, CHW, row_ids[i * BS:(i + 1) * BS].data_ptr(), int(seed), L.stream_ptr()), "dc_philox_normal")
-            e = nbuf
-        else:
-            e = torch.randn_like(x).to(torch.float32)
-        return (alsg[i][0] * xf + alsg[i][1] * e).contiguous()
-
-    chunks = CF.image_chunks(BS, 1, units)
-    sessions = CF.pair_sessions(dc, backbone, lab.view(-1, 1), chunks, dev)
-    noise = torch.empty((n, BS, Cc, H, W), dtype=torch.float32, device=dev)
+    latent = lambda i: (alsg[i][0] * xf + alsg[i][1] * noise(i)).contiguous()              # noqa: E731
+    maps = torch.empty((n,) + tuple(x.shape), dtype=torch.float32, device=dev)
     start = z = latent(0)
     for i in range(n):                                                        # no device -> host copy
         z_next = latent(i + 1)
         c, alpha_t, sigma_t, alpha_s, sd = scal[i]
-        for (b0, b1), ses in zip(chunks, sessions):
-            pair = ses.step(z[b0:b1], lam_dev[i:i + 1])
-            p = L.DdpmNoiseMapParams(z=z[b0:b1].data_ptr(), pred=pair.data_ptr(), x_next=z_next[b0:b1].data_ptr(),
-                                     out=noise[i, b0:b1].data_ptr(), n=b1 - b0, C=Cc, H=H, W=W, ld=pair.shape[-1], patch=patch,
-                                     v_param=v_param, w=w, one_plus_w=one_plus_w, alpha_t=alpha_t, sigma_t=sigma_t,
-                                     alpha_s=alpha_s, c=c, sd=sd)
-            L.check(lib.dc_ddpm_noise_map(C.byref(p), L.stream_ptr()), "dc_ddpm_noise_map")
+        for _, imgs, f in walk.run(i, z):
+            TJ.launch("dc_ddpm_noise_map", L.DdpmNoiseMapParams(
+                x_next=z_next[imgs].data_ptr(), out=maps[i, imgs].data_ptr(), alpha_t=alpha_t, sigma_t=sigma_t, alpha_s=alpha_s, c=c, sd=sd, **f))
         z = z_next
-    return start, noise
+    return start, maps
 
 
 @torch.no_grad()
-def invert(dc, x, text, from_t, guidance, rng, seed, units_per_launch, name="text"):
+def invert(dc, x, text, from_t, guidance, rng, seed, name="text"):
     """`DiffusionClassifier.invert_ddpm` (its docstring is the interface).  Every refusal comes before the first draw."""
-    from_t = float(from_t)
-    if not 0.0 < from_t <= 1.0:
-        raise ValueError(f"from_t must lie in (0, 1], got {from_t}")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [BS, C, H, W], got {tuple(x.shape)}")
-    assert dc.encoder_type is not None, "Encoder must be provided for inversion."
-    dc._require_prompts()
+    from_t, hip = TJ.check_entry(dc, x, from_t, "from_t", "inversion", rng)
     lab = S.label_rows(text, x.shape[0], dc.config.classes, name)
-    if rng not in ("reference", "philox"):
-        raise ValueError(f"rng must be 'reference' or 'philox', got {rng!r}")
-    backbone = dc.ema.ema_model
-    hip = hasattr(backbone, "pair_session")
-    if not hip:
-        if rng == "philox":
-            raise L.DcamdError("rng='philox' needs a HIP backbone (UNetCondition2D / DiT)")
-        dc._refuse_ragged_on_foreign()
     w = float(dc.cfg_w if guidance is None else guidance)
     n = int(dc.config.sampling_steps)
     size, cap = 4 * n * x.numel(), max_bytes_of(dc.config)
@@ -152,7 +106,9 @@ def invert(dc, x, text, from_t, guidance, rng, seed, units_per_launch, name="tex
         raise ValueError(f"invert_ddpm stores one noise map per step: {n} x {tuple(x.shape)} f32 = {size} bytes, more than "
                          f"config.ddpm_invert_max_bytes = {cap} (fewer sampling_steps, a smaller batch, or raise the key)")
     if hip:
-        start, noise = run_hip(dc, backbone, x, lab, from_t, w, rng, seed, units_per_launch(x.shape[2], x.shape[3], 2))
+        lams, scal, alsg = grid(dc, from_t)
+        walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), lams, w, who="invert_ddpm", noun="fused noise map")
+        start, noise = run_hip(walk, x, scal, alsg, TJ.NoiseSource(x, rng, seed, n + 1))
     else:
         start, noise = run_eager(dc, x, lab, from_t, w)
     return DdpmInversion(start, noise, from_t, w)

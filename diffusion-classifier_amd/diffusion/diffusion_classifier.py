@@ -102,6 +102,7 @@ from .. import ddpm_invert as DI
 from .. import posterior as P
 from .. import evidence as EV
 from .. import solver as S
+from .. import trajectory as TJ
 from .._ema import EMA
 
 
@@ -614,16 +615,11 @@ class DiffusionClassifier(nn.Module):
         """`ddpm_sampler_step` + the update `z = mu + noise * sqrt(var)` (noise None: the clipped mean of the last pass) on the
         prediction pair of `forward_pair`, as one kernel.  The step's scalars are formed by the same fp32 torch ops as above."""
         c, alpha_t, sigma_t, alpha_s, sd = self._sampler_step_scalars(lam_t, lam_s)
-        N, Cc, H, W = z_t.shape
         z = z_t.detach().to(torch.float32).contiguous()
         out = torch.empty_like(z)
-        patch = int(getattr(backbone.config, "patch_size", 0) or 0)
-        oc = int(getattr(backbone.config, "out_channels", Cc) or Cc)
-        if oc != Cc:        # dc_ddpm_step indexes the prediction with z's channel count as the feature stride (ADVICE r3)
-            raise L.DcamdError(f"fused sampler step needs out_channels == in_channels (got {oc} vs {Cc})")
         p = L.DdpmStepParams(z=z.data_ptr(), pred=pair.data_ptr(), noise=None if noise is None else noise.data_ptr(), out=out.data_ptr(),
-                             n=N, C=Cc, H=H, W=W, ld=pair.shape[-1], patch=patch, v_param=int(self.pred_param == 'v'),
-                             w=float(self.cfg_w), one_plus_w=float(1.0 + float(self.cfg_w)), alpha_t=float(alpha_t), sigma_t=float(sigma_t), alpha_s=float(alpha_s), c=float(c), sd=float(sd))
+                             n=z.shape[0], ld=pair.shape[-1], alpha_t=alpha_t, sigma_t=sigma_t, alpha_s=alpha_s, c=c, sd=sd,
+                             **TJ.step_fields(self, backbone, z.shape, self.cfg_w))
         L.check(L.lib().dc_ddpm_step(p, L.stream_ptr()), "dc_ddpm_step")
         return out
 
@@ -636,43 +632,23 @@ class DiffusionClassifier(nn.Module):
         With config.vae_path, x and the result are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
         sampler = S.sampler_of(self.config)
         if sampler is not None:
-            return S.sample(self, x, text, from_t, sampler, lambda H, W, k: _units_per_launch(self.config, H, W, k))
+            return S.sample(self, x, text, from_t, sampler)
         dev = x.device
-        if from_t == 1:
-            z_t = torch.randn(x.shape).to(dev)
-        else:
-            lam = self.schedule(torch.ones(x.shape[0]) * from_t).to(dev)
-            z_t, _ = self.diffuse(x, torch.sqrt(torch.sigmoid(lam)).view(-1, 1, 1, 1), torch.sqrt(torch.sigmoid(-lam)).view(-1, 1, 1, 1))
-        cond = null = None
-        if text is not None and self.encoder_type is not None:
-            cond = self.encode_text_prompt(text).to(dev)
-            null = self.encode_text_prompt(torch.full_like(text, self.null_token)).to(dev)
+        z_t = TJ.initial_latent(self, x, from_t)
         backbone = self.ema.ema_model
-        fused = hasattr(backbone, "forward_pair") and cond is not None and z_t.is_cuda
-        lens = {}                                                             # prompts of different lengths: the rows' token counts
-        if cond is not None and self._ragged_table():
-            if not hasattr(backbone, "make_plan"):
-                self._refuse_ragged_on_foreign()
-            ln = self.encoder.lengths.cpu()
-            lens = dict(cond=ln[text.detach().cpu()], null=ln[torch.full_like(text, self.null_token).cpu()])
+        cond, null, lens = TJ.contexts(self, text, dev, backbone)             # lens: the rows' token counts of a ragged prompt table
+        if not (hasattr(backbone, "forward_pair") and cond is not None and z_t.is_cuda):
+            return TJ.ancestral_eager(self, z_t, [cond], null, from_t, lens)[0]
+        kw = {"cond_lengths": lens["cond"], "null_lengths": lens["null"]} if lens else {}
         steps = torch.linspace(from_t, 0.0, self.config.sampling_steps + 1)
         n = len(steps) - 1
         for i in range(n + 1):                                                # the last pass repeats step n-1 and keeps the mean
             u_t, u_s = (steps[i], steps[i + 1]) if i < n else (steps[-2], steps[-1])
             lam_t, lam_s = self.schedule(u_t).to(dev).unsqueeze(0), self.schedule(u_s).to(dev).unsqueeze(0)
-            if fused:
-                pair = backbone.forward_pair(z_t, lam_t, cond, null, **({"cond_lengths": lens["cond"], "null_lengths": lens["null"]} if lens else {}))
-                if i == n:
-                    return self._fused_sampler_step(backbone, z_t, pair, lam_t, lam_s, None).to(z_t.dtype)
-                noise = torch.randn_like(z_t).to(torch.float32).contiguous()
-                z_t = self._fused_sampler_step(backbone, z_t, pair, lam_t, lam_s, noise).to(z_t.dtype)
-                continue
-            pred = self.ema(z_t, lam_t, encoder_hidden_states=cond, **({"encoder_lengths": lens["cond"]} if lens else {}))
-            u_pred = self.ema(z_t, lam_t, encoder_hidden_states=null, **({"encoder_lengths": lens["null"]} if lens else {}))
-            mu, var = self.ddpm_sampler_step(z_t, pred, u_pred, lam_t.clone().detach(), lam_s.clone().detach())
-            if i == n:
-                return self.clip(mu)
-            z_t = mu + torch.randn_like(mu) * torch.sqrt(var)
+            pair = backbone.forward_pair(z_t, lam_t, cond, null, **kw)
+            noise = torch.randn_like(z_t).to(torch.float32).contiguous() if i < n else None
+            z_t = self._fused_sampler_step(backbone, z_t, pair, lam_t, lam_s, noise).to(z_t.dtype)
+        return z_t
 
     @torch.no_grad()
     def counterfactual(self, x, classes=None, from_t=0.5, *, against="input", rng="reference", seed=0, pixel_space=False,
@@ -714,8 +690,7 @@ class DiffusionClassifier(nn.Module):
         holds no solver error; another class's map is the label's effect.  rng / seed govern the inversion's n + 1 draws; the decode
         draws nothing.  Costs one more backbone pass per step and the maps' memory (config.ddpm_invert_max_bytes)
         With config.vae_path, x, the samples and the maps are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
-        return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space,
-                      lambda H, W, k: _units_per_launch(self.config, H, W, k), start=start, invert_class=invert_class)
+        return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class)
 
     @torch.no_grad()
     def invert(self, x, text=None, to_t=0.5, *, guidance=0.0):
@@ -728,7 +703,7 @@ class DiffusionClassifier(nn.Module):
         Works whatever config.sampler says (always DDIM).  HIP backbones run a pair session per chunk of images and one `dc_solver_step`
         per step and chunk; a foreign nn.Module takes the eager form (solver.py).
         With config.vae_path, x and the result are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
-        return S.invert(self, x, text, to_t, guidance, lambda H, W, k: _units_per_launch(self.config, H, W, k))
+        return S.invert(self, x, text, to_t, guidance)
 
     @torch.no_grad()
     def invert_ddpm(self, x, text=None, from_t=0.5, *, guidance=None, rng="reference", seed=0):
@@ -750,7 +725,7 @@ class DiffusionClassifier(nn.Module):
         and one `dc_ddpm_noise_map` per pass and chunk, nothing is copied to the host inside the loop; a foreign nn.Module takes the
         eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`.
         With config.vae_path, x, start and noise are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
-        return DI.invert(self, x, text, from_t, guidance, rng, seed, lambda H, W, k: _units_per_launch(self.config, H, W, k))
+        return DI.invert(self, x, text, from_t, guidance, rng, seed)
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----
     @torch.no_grad()
@@ -927,17 +902,6 @@ class _ForeignRunner:
                     EV.err_map_torch(eps_pred, e, bs.to(x.device) * dc.config.classes + lab, self.ev[0][self.ev_stage], self.ev[1][self.ev_stage])
 
 
-def _units_per_launch(config, H, W, k):
-    """Work units one plan launch should hold (k: the units that must stay together); config.units_per_launch overrides the rule."""
-    u = config.units_per_launch
-    if u is None:
-        # ~8M output pixel rows per launch at full resolution (measured on cfg2: 1M -> 4M = +13 %, 4M -> 8M = +2.4 %), but never fewer than 192
-        # units: the deep levels of a 256x256 UNet see only units x 64 rows, and 64-unit launches left their GEMMs at
-        # 0.2-0.35 PF (IPMSA: 1.14 -> 1.27 img/s; ~200 MB of arena per unit, far inside 288 GB)
-        u = max(192, (1 << 23) // (H * W))
-    return max(k, int(u))
-
-
 class _HipRunner:
     """Micro-batched execution of the (image, trial, class) grid through libdcamd plans."""
 
@@ -954,9 +918,6 @@ class _HipRunner:
         self.dt = dt
         if draws["philox"]:
             assert (x.shape[1] * x.shape[2] * x.shape[3]) % 4 == 0
-
-    def _units_per_launch(self, H, W, k):
-        return _units_per_launch(self.dc.config, H, W, k)
 
     def _plan(self, n_bj, k):
         dc, dev = self.dc, self.dev
@@ -1078,7 +1039,7 @@ class _HipRunner:
         BS, Cc, H, W = self.x.shape
         ncls, k = dc.config.classes, classes.shape[1]
         on_dev = classes.is_cuda                         # stages >= 1: the surviving classes never left the device
-        cap = max(1, self._units_per_launch(H, W, k) // k)
+        cap = max(1, TJ.units_per_launch(self.dc.config, H, W, k) // k)
         if rows is None:
             n_bj = min(len(pairs), cap)
             # equal micro-batches: 800 pairs at a cap of 256 run as 4 x 200, not 3 x 256 + 32 padded to 256 (slots past the last pair

@@ -97,11 +97,7 @@ class CLIPTextEncoder(_HipBackbone):
         return model
 
     # ---- engine ---------------------------------------------------------------------------------
-    def packed_weights(self, dt, device):
-        key = (dt, str(device))
-        if key not in self._packed:
-            self._packed[key] = EC.ClipWeights(self, dt, device)
-        return self._packed[key]
+    weights_class = EC.ClipWeights
 
     @torch.no_grad()
     def forward(self, input_ids, attention_mask=None):

@@ -94,33 +94,24 @@ class DiT(_HipBackbone):
             self.transformer_blocks.append(b)
         self.proj_out_1 = nn.Linear(D, 2 * D)
         self.proj_out_2 = nn.Linear(D, patch_size * patch_size * out_channels)
+        self.patch = patch_size
         self._init_engine()
 
-    def packed_weights(self, dt, device):
-        key = (dt, str(device))
-        if key not in self._packed:
-            self._packed[key] = ED.DiTWeights(self, dt, device)
-        return self._packed[key]
+    weights_class, im2col = ED.DiTWeights, 2                   # `patch` is the instance's patch_size
 
     def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None):
         dt = E.DT[self.compute_dtype]
         return ED.DiTPlan(self, self.packed_weights(dt, device), n_bj, n_cls, n_ctx, score=score, device=device)
 
-    def _feed(self, plan, x, noise_labels):
-        """lambda and the patch-embedding GEMM operand (p x p patches of x) of a plain forward."""
-        lib = L.lib()
-        dev = x.device
-        N, Cin, H, W = x.shape
-        lam = noise_labels if torch.is_tensor(noise_labels) else torch.tensor([noise_labels])
-        lam = lam.to(dev, torch.float32).reshape(-1)
-        plan.lam.copy_(lam.expand(N) if lam.numel() == 1 else lam)
-        xf = x.detach().to(torch.float32).contiguous()
-        ones = torch.ones(N, dtype=torch.float32, device=dev)
-        zeros = torch.zeros(N, dtype=torch.float32, device=dev)
-        q = L.QsampleParams(x=xf.data_ptr(), eps=xf.data_ptr(), alpha=ones.data_ptr(), sigma=zeros.data_ptr(), img_of_bj=None,
-                            out=plan.a0_buf.data_ptr(), out_dtype=plan.dt, n_bj=N, C=Cin, H=H, W=W,
-                            ld=plan.a0_buf.shape[-1], im2col=2, patch=self.config.patch_size)
-        L.check(lib.dc_qsample(q, L.stream_ptr()), "dc_qsample")
+    def _label_plan(self, kind, N, dev, labels):
+        """What `forward`, `forward_pair` and `pair_session` share: the plan cached under kind + (N, device, dtype) (built on first use)
+        with the labels — one int tensor of N per unit of an image, unit n_cls * b + u = labels[u][b] — copied into its `ctx_of_unit`."""
+        key = kind + (N, str(dev), self.compute_dtype)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self.make_plan(N, len(labels), None, dev)
+        plan.ctx_of_unit.copy_(torch.stack([lab.reshape(-1) for lab in labels], dim=1).reshape(-1).to(dev, torch.int32))
+        return plan
 
     @torch.no_grad()
     def forward_pair(self, x, noise_labels, cond, null):
@@ -130,14 +121,8 @@ class DiT(_HipBackbone):
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError("DiT.forward_pair needs CUDA/HIP tensors (no CPU fallback)")
-        dev = x.device
-        N = x.shape[0]
-        key = ("pair", N, str(dev), self.compute_dtype)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 2, None, dev)
+        plan = self._label_plan(("pair",), x.shape[0], x.device, (cond, null))
         self._feed(plan, x, noise_labels)
-        plan.ctx_of_unit.copy_(torch.stack([cond.reshape(-1), null.reshape(-1)], dim=1).reshape(-1).to(dev, torch.int32))
         plan.run()
         return plan.pred_view()
 
@@ -147,32 +132,20 @@ class DiT(_HipBackbone):
         belongs to `slot`.  Returns a `PairSession` (nets/unet.py) whose `step(x, lam)` gives what `forward_pair(x, lam, cond, null)`
         gives."""
         L.require_gpu()
-        dev = torch.device(device)
         if cond.numel() != N or null.numel() != N:
             raise L.DcamdError(f"a pair session of {N} images needs {N} labels per side, got {cond.numel()} and {null.numel()}")
-        key = ("pair_session", slot, N, str(dev), self.compute_dtype)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 2, None, dev)
-        plan.ctx_of_unit.copy_(torch.stack([cond.reshape(-1), null.reshape(-1)], dim=1).reshape(-1).to(dev, torch.int32))
-        return PairSession(self, plan, N)
+        return PairSession(self, self._label_plan(("pair_session", slot), N, torch.device(device), (cond, null)), N)
 
     @torch.no_grad()
     def forward(self, x, noise_labels, encoder_hidden_states=None):
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError("DiT.forward needs CUDA/HIP tensors (no CPU fallback)")
-        dev = x.device
         N, Cin, H, W = x.shape
-        cfg = self.config
-        p = cfg.patch_size
-        key = ("fwd", N, str(dev), self.compute_dtype)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 1, None, dev)
+        p, oc = self.patch, self.config.out_channels
+        plan = self._label_plan(("fwd",), N, x.device, (encoder_hidden_states,))
         self._feed(plan, x, noise_labels)
-        plan.ctx_of_unit.copy_(encoder_hidden_states.reshape(-1).to(dev, torch.int32))
         plan.run()
-        g, oc = H // p, cfg.out_channels
+        g = H // p
         out = plan.pred_view().reshape(N, g, g, p, p, oc)          # un-patchify: nhwpqc -> nchpwq
         return out.permute(0, 5, 1, 3, 2, 4).reshape(N, oc, g * p, g * p).contiguous().to(x.dtype)

@@ -100,11 +100,7 @@ class T5Encoder(_HipBackbone):
         return model
 
     # ---- engine ---------------------------------------------------------------------------------
-    def packed_weights(self, dt, device):
-        key = (dt, str(device))
-        if key not in self._packed:
-            self._packed[key] = ET.T5Weights(self, dt, device)
-        return self._packed[key]
+    weights_class = ET.T5Weights
 
     @torch.no_grad()
     def forward(self, input_ids, attention_mask=None):

@@ -111,6 +111,30 @@ class _HipBackbone(nn.Module):
                 new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
+    # ---- engine hooks: a subclass names `weights_class`; one that is fed images also `im2col` and `patch` (dc_qsample's fields) ----
+    def packed_weights(self, dt, device):
+        key = (dt, str(device))
+        if key not in self._packed:
+            self._packed[key] = self.weights_class(self, dt, device)
+        return self._packed[key]
+
+    def _feed(self, plan, x, noise_labels):
+        """lambda and the first GEMM's operand of a plain forward: the 3x3 patches of x for conv_in (im2col 1), its p x p patches for
+        the patch embedding (im2col 2)."""
+        lib = L.lib()
+        dev = x.device
+        N, Cin, H, W = x.shape
+        lam = noise_labels if torch.is_tensor(noise_labels) else torch.tensor([noise_labels])
+        lam = lam.to(dev, torch.float32).reshape(-1)
+        plan.lam.copy_(lam.expand(N) if lam.numel() == 1 else lam)
+        xf = x.detach().to(torch.float32).contiguous()
+        ones = torch.ones(N, dtype=torch.float32, device=dev)
+        zeros = torch.zeros(N, dtype=torch.float32, device=dev)
+        p = L.QsampleParams(x=xf.data_ptr(), eps=xf.data_ptr(), alpha=ones.data_ptr(), sigma=zeros.data_ptr(), img_of_bj=None,
+                            out=plan.a0_buf.data_ptr(), out_dtype=plan.dt, n_bj=N, C=Cin, H=H, W=W,
+                            ld=plan.a0_buf.shape[-1], im2col=self.im2col, patch=self.patch)
+        L.check(lib.dc_qsample(p, L.stream_ptr()), "dc_qsample")
+
 
 class PairSession:
     """`forward_pair` cut into "once per call" and "once per step", for a sampling loop whose contexts do not change from step to step.
@@ -267,11 +291,7 @@ class UNetCondition2D(_HipBackbone):
         self._init_engine()
 
     # ---- engine hooks -----------------------------------------------------------------
-    def packed_weights(self, dt, device):
-        key = (dt, str(device))
-        if key not in self._packed:
-            self._packed[key] = E.UNetWeights(self, dt, device)
-        return self._packed[key]
+    weights_class, im2col, patch = E.UNetWeights, 1, 0
 
     def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None, S=1, varlen=False):
         """S: tokens per context (1: the class token; more: a prompt, attended by dc_cross_attention).  varlen (S > 1 only): the
@@ -307,6 +327,24 @@ class UNetCondition2D(_HipBackbone):
             raise L.DcamdError(f"prompt lengths must lie in [1, {S}], got {ln.tolist()}")
         return ln.to(torch.int32)
 
+    def _ctx_plan(self, kind, N, dev, S, ctxs, lengths):
+        """What `forward`, `forward_pair` and `pair_session` share: the plan cached under kind + (N, device, dtype, share_trunk, S[,
+        "varlen"]) (built on first use), the contexts `ctxs` — one [N, S, hid] per unit of an image, context n_cls * b + u = ctxs[u][b]
+        — and their `lengths` (any of them given: a "varlen" plan; None on a side: all S) copied in, the context plan run."""
+        key = kind + (N, str(dev), self.compute_dtype, self.share_trunk, S)
+        varlen = any(ln is not None for ln in lengths)
+        if varlen:
+            lens = torch.stack([self._context_lengths(ln, N, S) for ln in lengths], dim=1)
+            key += ("varlen",)
+        plan = self._plans.get(key)
+        if plan is None:                                                      # ctx_of_unit = unit index: one context per unit
+            plan = self._plans[key] = self.make_plan(N, len(ctxs), len(ctxs) * N, dev, S=S, varlen=varlen)
+        plan.ctx.copy_(torch.stack(ctxs, dim=1).to(dev, torch.float32).reshape(plan.ctx.shape))
+        if varlen:
+            plan.ctx_len.copy_(lens.reshape(-1))                              # interleaved as the contexts
+        plan.run_ctx()
+        return plan
+
     @torch.no_grad()
     def forward(self, x, noise_labels, downblock_additional_residuals=None, midblock_additional_residuals=None,
                 encoder_hidden_states=None, encoder_lengths=None):
@@ -317,25 +355,11 @@ class UNetCondition2D(_HipBackbone):
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError("UNetCondition2D.forward needs CUDA/HIP tensors (no CPU fallback)")
-        dev = x.device
-        N, Cin, H, W = x.shape
         S = self._context_tokens(encoder_hidden_states)
-        key = ("fwd", N, str(dev), self.compute_dtype, self.share_trunk, S)
-        varlen = encoder_lengths is not None
-        if varlen:
-            lens = self._context_lengths(encoder_lengths, N, S)
-            key += ("varlen",)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 1, N, dev, S=S, varlen=varlen)
+        plan = self._ctx_plan(("fwd",), x.shape[0], x.device, S, (encoder_hidden_states,), (encoder_lengths,))
         self._feed(plan, x, noise_labels)
-        plan.ctx.copy_(encoder_hidden_states.to(dev, torch.float32).reshape(plan.ctx.shape))
-        if varlen:
-            plan.ctx_len.copy_(lens)
-        plan.run_ctx()
         plan.run()
         return plan.pred_view().permute(0, 3, 1, 2).contiguous().to(x.dtype)
-
 
     @torch.no_grad()
     def forward_pair(self, x, noise_labels, cond, null, cond_lengths=None, null_lengths=None):
@@ -349,23 +373,9 @@ class UNetCondition2D(_HipBackbone):
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError("UNetCondition2D.forward_pair needs CUDA/HIP tensors (no CPU fallback)")
-        dev = x.device
-        N, Cin, H, W = x.shape
         S = self._context_tokens(cond, null)
-        key = ("pair", N, str(dev), self.compute_dtype, self.share_trunk, S)
-        varlen = cond_lengths is not None or null_lengths is not None
-        if varlen:
-            lens = torch.stack([self._context_lengths(cond_lengths, N, S), self._context_lengths(null_lengths, N, S)], dim=1)
-            key += ("varlen",)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 2, 2 * N, dev, S=S, varlen=varlen)   # ctx_of_unit = unit index: one context per unit
+        plan = self._ctx_plan(("pair",), x.shape[0], x.device, S, (cond, null), (cond_lengths, null_lengths))
         self._feed(plan, x, noise_labels)
-        ctx = torch.stack([cond, null], dim=1)                                # [N, 2, S, hid]: context 2b = cond[b], 2b + 1 = null[b]
-        plan.ctx.copy_(ctx.to(dev, torch.float32).reshape(plan.ctx.shape))
-        if varlen:
-            plan.ctx_len.copy_(lens.reshape(-1))                              # interleaved as the contexts: 2b = cond[b], 2b + 1 = null[b]
-        plan.run_ctx()
         plan.run()
         return plan.pred_view()
 
@@ -375,40 +385,11 @@ class UNetCondition2D(_HipBackbone):
         `slot`, the context plan run once.  Returns a `PairSession`; its `step(x, lam)` gives what `forward_pair(x, lam, cond, null)`
         gives, without projecting the prompts again."""
         L.require_gpu()
-        dev = torch.device(device)
         S = self._context_tokens(cond, null)
         if cond.shape[0] != N or null.shape[0] != N:
             raise L.DcamdError(f"a pair session of {N} images needs {N} contexts per side, got {cond.shape[0]} and {null.shape[0]}")
-        key = ("pair_session", slot, N, str(dev), self.compute_dtype, self.share_trunk, S)
-        varlen = cond_lengths is not None or null_lengths is not None
-        if varlen:
-            lens = torch.stack([self._context_lengths(cond_lengths, N, S), self._context_lengths(null_lengths, N, S)], dim=1)
-            key += ("varlen",)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self.make_plan(N, 2, 2 * N, dev, S=S, varlen=varlen)   # as forward_pair: one context per unit
-        ctx = torch.stack([cond, null], dim=1)                                # [N, 2, S, hid]: context 2b = cond[b], 2b + 1 = null[b]
-        plan.ctx.copy_(ctx.to(dev, torch.float32).reshape(plan.ctx.shape))
-        if varlen:
-            plan.ctx_len.copy_(lens.reshape(-1))
-        plan.run_ctx()
+        plan = self._ctx_plan(("pair_session", slot), N, torch.device(device), S, (cond, null), (cond_lengths, null_lengths))
         return PairSession(self, plan, N)
-
-    def _feed(self, plan, x, noise_labels):
-        """lambda and the conv_in GEMM operand (3x3 patches of x) of a plain forward."""
-        lib = L.lib()
-        dev = x.device
-        N, Cin, H, W = x.shape
-        lam = noise_labels if torch.is_tensor(noise_labels) else torch.tensor([noise_labels])
-        lam = lam.to(dev, torch.float32).reshape(-1)
-        plan.lam.copy_(lam.expand(N) if lam.numel() == 1 else lam)
-        xf = x.detach().to(torch.float32).contiguous()
-        ones = torch.ones(N, dtype=torch.float32, device=dev)
-        zeros = torch.zeros(N, dtype=torch.float32, device=dev)
-        p = L.QsampleParams(x=xf.data_ptr(), eps=xf.data_ptr(), alpha=ones.data_ptr(), sigma=zeros.data_ptr(), img_of_bj=None,
-                            out=plan.a0_buf.data_ptr(), out_dtype=plan.dt, n_bj=N, C=Cin, H=H, W=W,
-                            ld=plan.a0_buf.shape[-1], im2col=1)
-        L.check(lib.dc_qsample(p, L.stream_ptr()), "dc_qsample")
 
 
 class UNet2D(nn.Module):

@@ -134,11 +134,7 @@ class VAEEncoder(_HipBackbone):
         return model
 
     # ---- engine ---------------------------------------------------------------------------------
-    def packed_weights(self, dt, device):
-        key = (dt, str(device))
-        if key not in self._packed:
-            self._packed[key] = EV.VaeWeights(self, dt, device)
-        return self._packed[key]
+    weights_class = EV.VaeWeights
 
     def check_image_shape(self, shape):
         f = self.downscale

@@ -10,10 +10,14 @@ The last denoising pass returns clip(x) at the last grid point, so n steps are n
 Inversion walks the grid upwards (h < 0), first order throughout, and starts from z = alpha(lam(0)) x.
 
 `eager_pass` / `run_eager` are the written statement — two backbone calls per pass and the expressions above in fp32 torch — and the
-path of a foreign nn.Module.  HIP backbones run the same passes as `counterfactual.run_hip`'s loop with one `dc_solver_step` per step
-and chunk.
+path of a foreign nn.Module.  HIP backbones run the same passes as `run_walk` over a `trajectory.Walk`, one `dc_solver_step` per step and
+chunk: the decode of `sample` (K = 1) and `counterfactual`, and DDIM inversion — the same loop on the upward grid with "invert" scalars.
 """
 import torch
+
+from . import _lib as L
+from . import trajectory as TJ
+from .trajectory import contexts, initial_latent      # noqa: F401  (shared with `sample`; importable here as ever)
 
 SAMPLERS = ("ddim", "dpmpp_2m")
 
@@ -87,30 +91,6 @@ def run_eager(dc, z, lams, scal, w, cond, null, lens=None):
     return z
 
 
-def initial_latent(dc, x, from_t):
-    """`sample`'s start: randn for from_t == 1, else diffuse(x) to from_t — one draw from torch's generator."""
-    dev = x.device
-    if from_t == 1:
-        return torch.randn(x.shape).to(dev)
-    lam = dc.schedule(torch.ones(x.shape[0]) * from_t).to(dev)
-    return dc.diffuse(x, torch.sqrt(torch.sigmoid(lam)).view(-1, 1, 1, 1), torch.sqrt(torch.sigmoid(-lam)).view(-1, 1, 1, 1))[0]
-
-
-def contexts(dc, text, dev, backbone):
-    """(cond, null, lens) of `sample`: the encoded labels, the encoded null token and, for a ragged prompt table, the rows' token counts."""
-    cond = null = None
-    lens = None
-    if text is not None and dc.encoder_type is not None:
-        cond = dc.encode_text_prompt(text).to(dev)
-        null = dc.encode_text_prompt(torch.full_like(text, dc.null_token)).to(dev)
-        if dc._ragged_table():
-            if not hasattr(backbone, "make_plan"):
-                dc._refuse_ragged_on_foreign()
-            ln = dc.encoder.lengths.cpu()
-            lens = dict(cond=ln[text.detach().cpu()], null=ln[torch.full_like(text, dc.null_token).cpu()])
-    return cond, null, lens
-
-
 def decode_eager(dc, z, text, from_t, sampler):
     """The latent z at from_t decoded under the labels `text` in eager torch on any backbone: n passes on
     linspace(from_t, 0, sampling_steps + 1) with config.cfg_w."""
@@ -124,15 +104,31 @@ def sample_eager(dc, x, text, from_t, sampler):
     return decode_eager(dc, initial_latent(dc, x, from_t), text, from_t, sampler)
 
 
-def sample(dc, x, text, from_t, sampler, units_per_launch):
-    """`DiffusionClassifier.sample` with config.sampler set.  A HIP backbone with labels runs the trajectories as a pair session
-    (`counterfactual.run_hip` with one class per image); everything else takes the eager form."""
+def run_walk(walk, z0, scal):
+    """The passes `scal` of all trajectories of `walk` (trajectory.py) from z0 [BS, C, H, W]: one `dc_solver_step` per pass and chunk,
+    no draw, one history buffer of data predictions for the second-order passes -> [BS, K, C, H, W].  The direction is in the scalars
+    and in the grid the walk was built on: the deterministic decode, or DDIM inversion on the upward grid."""
+    za, zb = walk.buffers(z0)
+    hist = torch.empty_like(za) if any(sc[4] is not None for sc in scal) else None       # x of the pass before
+    for t, (alpha_t, sigma_t, k1, k2, k3, final) in enumerate(scal):
+        for rows, _, f in walk.run(t, za):
+            # 2M: pass 0 writes the history, a second-order pass reads its element and writes it again; the final pass needs none
+            hc = None if hist is None or final else hist[rows].data_ptr()
+            TJ.launch("dc_solver_step", L.SolverStepParams(
+                xprev=hc if k3 is not None else None, xhat=hc, out=zb[rows].data_ptr(), clamp=1, final_pass=int(final), alpha_t=alpha_t,
+                sigma_t=sigma_t, k1=k1, k2=k2, k3=0.0 if k3 is None else k3, **f))
+        za, zb = zb, za
+    return walk.view(za)
+
+
+def sample(dc, x, text, from_t, sampler):
+    """`DiffusionClassifier.sample` with config.sampler set.  A HIP backbone with labels runs the trajectories as a walk with one
+    class per image; everything else takes the eager form."""
     backbone = dc.ema.ema_model
     if hasattr(backbone, "pair_session") and text is not None and dc.encoder_type is not None and x.is_cuda:
-        from . import counterfactual as CF
-        cl = text.detach().cpu().reshape(-1, 1).to(torch.int64)
-        out = CF.run_hip(dc, backbone, x, cl, from_t, "reference", 0, units_per_launch(x.shape[2], x.shape[3], 2), sampler=sampler)
-        return out[:, 0]
+        lams = grid_lams(dc, from_t, 0.0)
+        walk = TJ.Walk(dc, backbone, x, text.detach().cpu().reshape(-1, 1).to(torch.int64), lams, dc.cfg_w)
+        return run_walk(walk, initial_latent(dc, x, from_t), step_scalars(lams, sampler, "denoise"))[:, 0]
     return sample_eager(dc, x, text, from_t, sampler)
 
 
@@ -160,20 +156,12 @@ def invert_eager(dc, x, lab, to_t, guidance):
 
 
 @torch.no_grad()
-def invert(dc, x, text, to_t, guidance, units_per_launch):
+def invert(dc, x, text, to_t, guidance):
     """`DiffusionClassifier.invert` (its docstring is the interface)."""
-    to_t = float(to_t)
-    if not 0.0 < to_t <= 1.0:
-        raise ValueError(f"to_t must lie in (0, 1], got {to_t}")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [BS, C, H, W], got {tuple(x.shape)}")
-    assert dc.encoder_type is not None, "Encoder must be provided for inversion."
-    dc._require_prompts()
+    to_t, hip = TJ.check_entry(dc, x, to_t, "to_t", "inversion")
     lab = label_rows(text, x.shape[0], dc.config.classes, "text")
-    backbone = dc.ema.ema_model
-    if hasattr(backbone, "pair_session"):
-        from . import counterfactual as CF
-        units = units_per_launch(x.shape[2], x.shape[3], 2)
-        return CF.run_hip(dc, backbone, x, lab.view(-1, 1), to_t, "reference", 0, units, sampler="ddim", invert=True, w=float(guidance))[:, 0]
-    dc._refuse_ragged_on_foreign()
-    return invert_eager(dc, x, lab, to_t, guidance).to(torch.float32)
+    if not hip:
+        return invert_eager(dc, x, lab, to_t, guidance).to(torch.float32)
+    lams = grid_lams(dc, 0.0, to_t)
+    walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), lams, guidance)
+    return run_walk(walk, torch.sqrt(torch.sigmoid(lams[0])).to(x.device) * x, step_scalars(lams, "ddim", "invert"))[:, 0]

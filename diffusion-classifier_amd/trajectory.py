@@ -1,0 +1,200 @@
+"""What `sample`, `counterfactual`, `invert` and `invert_ddpm` share: the entry checks, the start latent, the contexts, the step kernels'
+geometry, the noise of a call, and the walk of all trajectories of a call over a HIP backbone.
+
+The loops themselves live with their arithmetic and none takes a mode flag: the ancestral decode in counterfactual.py (`decode_hip`),
+the solver walk in solver.py (`run_walk`: the deterministic decode and, on the upward grid, DDIM inversion), the noise-map inversion in
+ddpm_invert.py (`run_hip`).  Each is `for pass: for chunk in walk.run(t, z): one step kernel`.  `ancestral_eager` is the reference's
+ancestral loop in eager torch, the path of a foreign nn.Module and the written statement of the kernels.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+
+
+def units_per_launch(config, H, W, k):
+    """Work units one plan launch should hold (k: the units that must stay together); config.units_per_launch overrides the rule."""
+    u = config.units_per_launch
+    if u is None:
+        # ~8M output pixel rows per launch at full resolution (measured on cfg2: 1M -> 4M = +13 %, 4M -> 8M = +2.4 %), but never fewer than 192
+        # units: the deep levels of a 256x256 UNet see only units x 64 rows, and 64-unit launches left their GEMMs at
+        # 0.2-0.35 PF (IPMSA: 1.14 -> 1.27 img/s; ~200 MB of arena per unit, far inside 288 GB)
+        u = max(192, (1 << 23) // (H * W))
+    return max(k, int(u))
+
+
+def check_entry(dc, x, t, name, purpose, rng="reference"):
+    """The refusals of an entry point, all before its first draw: the range of `t` (`name`: "from_t" / "to_t"), x's rank, the encoder
+    (`purpose` ends the assertion's sentence), the prompt table, the value of `rng`, and Philox or a ragged table in front of a foreign
+    module -> (float(t), is the backbone a HIP one)."""
+    t = float(t)
+    if not 0.0 < t <= 1.0:
+        raise ValueError(f"{name} must lie in (0, 1], got {t}")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [BS, C, H, W], got {tuple(x.shape)}")
+    assert dc.encoder_type is not None, f"Encoder must be provided for {purpose}."
+    dc._require_prompts()
+    if rng not in ("reference", "philox"):
+        raise ValueError(f"rng must be 'reference' or 'philox', got {rng!r}")
+    hip = hasattr(dc.ema.ema_model, "pair_session")
+    if not hip:
+        if rng == "philox":
+            raise L.DcamdError("rng='philox' needs a HIP backbone (UNetCondition2D / DiT)")
+        dc._refuse_ragged_on_foreign()
+    return t, hip
+
+
+def initial_latent(dc, x, from_t, noise=None):
+    """`sample`'s start: randn for from_t == 1, else diffuse(x) to from_t — one draw from torch's generator, or draw 0 of a Philox
+    `NoiseSource` (cloned out of its buffer when it is the start itself)."""
+    dev = x.device
+    philox = noise is not None and noise.philox
+    if from_t == 1:
+        return noise(0).clone() if philox else torch.randn(x.shape).to(dev)
+    lam = dc.schedule(torch.ones(x.shape[0]) * from_t).to(dev)
+    al, sg = torch.sqrt(torch.sigmoid(lam)).view(-1, 1, 1, 1), torch.sqrt(torch.sigmoid(-lam)).view(-1, 1, 1, 1)
+    return al * x + sg * noise(0) if philox else dc.diffuse(x, al, sg)[0]
+
+
+def contexts(dc, text, dev, backbone):
+    """(cond, null, lens) of `sample`: the encoded labels, the encoded null token and, for a ragged prompt table, the rows' token counts."""
+    cond = null = None
+    lens = None
+    if text is not None and dc.encoder_type is not None:
+        cond = dc.encode_text_prompt(text).to(dev)
+        null = dc.encode_text_prompt(torch.full_like(text, dc.null_token)).to(dev)
+        if dc._ragged_table():
+            if not hasattr(backbone, "make_plan"):
+                dc._refuse_ragged_on_foreign()
+            ln = dc.encoder.lengths.cpu()
+            lens = dict(cond=ln[text.detach().cpu()], null=ln[torch.full_like(text, dc.null_token).cpu()])
+    return cond, null, lens
+
+
+def ancestral_eager(dc, z0, conds, null, from_t, lens=None, noise_maps=None):
+    """The reference's ancestral loop from z0 under the K label columns `conds`: per step and column one conditional and one null call
+    at z0's batch and `ddpm_sampler_step`, every column adding the step's one `randn_like` (or noise_maps[i] in its place) — op for op
+    what K calls of `sample` with the seed reset in front of each compute -> the K clipped means of the last pass.
+    lens: `contexts`' token counts for a ragged table (K = 1)."""
+    dev = z0.device
+    kc = {"encoder_lengths": lens["cond"]} if lens else {}
+    kn = {"encoder_lengths": lens["null"]} if lens else {}
+    steps = torch.linspace(from_t, 0.0, dc.config.sampling_steps + 1)
+    n = len(steps) - 1
+    zs = [z0] * len(conds)
+    for i in range(n + 1):                                                    # the last pass repeats step n-1 and keeps the mean
+        u_t, u_s = (steps[i], steps[i + 1]) if i < n else (steps[-2], steps[-1])
+        lam_t, lam_s = dc.schedule(u_t).to(dev).unsqueeze(0), dc.schedule(u_s).to(dev).unsqueeze(0)
+        mus, var = [], None
+        for z, cond in zip(zs, conds):
+            pred = dc.ema(z, lam_t, encoder_hidden_states=cond, **kc)
+            u_pred = dc.ema(z, lam_t, encoder_hidden_states=null, **kn)
+            mu, var = dc.ddpm_sampler_step(z, pred, u_pred, lam_t.clone().detach(), lam_s.clone().detach())
+            mus.append(mu)
+        if i == n:
+            return [dc.clip(mu) for mu in mus]
+        noise = torch.randn_like(mus[0]) if noise_maps is None else noise_maps[i]
+        zs = [mu + noise * torch.sqrt(var) for mu in mus]
+
+
+def step_fields(dc, backbone, shape, w, noun="fused sampler step"):
+    """The fields every step struct shares but n and ld, for latents of `shape` [*, C, H, W] under guidance weight w.  `patch` is the
+    backbone's; the kernels index the prediction with z's channel count as the feature stride, so out_channels must equal C."""
+    _, Cc, H, W = shape
+    oc = int(getattr(backbone.config, "out_channels", Cc) or Cc)
+    if oc != Cc:
+        raise L.DcamdError(f"{noun} needs out_channels == in_channels (got {oc} vs {Cc})")
+    w = float(w)
+    return dict(C=Cc, H=H, W=W, patch=int(getattr(backbone.config, "patch_size", 0) or 0), v_param=int(dc.pred_param == 'v'),
+                w=w, one_plus_w=float(1.0 + w))
+
+
+class NoiseSource:
+    """noise(i): draw i of a call on a HIP backbone, [BS, C, H, W] f32 contiguous on x's device.
+    "reference": `torch.randn_like(like)` in call order (like: x until the caller sets another, its dtype is the draw's).
+    "philox": `dc_philox_normal` rows i * BS + b keyed by `seed` into ONE reused buffer — row b the start, (step + 1) * BS + b after it."""
+
+    def __init__(self, x, rng, seed, n_draws):
+        self.like, self.philox, self.seed = x, rng == "philox", int(seed)
+        self.BS, self.CHW = x.shape[0], x[0].numel()
+        if self.philox:
+            if self.CHW % 4:
+                raise L.DcamdError(f"rng='philox' needs C * H * W to be a multiple of 4, got {self.CHW}")
+            self.rows = torch.arange(n_draws * self.BS, dtype=torch.int64, device=x.device)
+            self.buf = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+
+    def __call__(self, i):
+        if not self.philox:
+            return torch.randn_like(self.like).to(torch.float32).contiguous()
+        rows = self.rows[i * self.BS:(i + 1) * self.BS]
+        L.check(L.lib().dc_philox_normal(self.buf.data_ptr(), self.BS, self.CHW, rows.data_ptr(), self.seed, L.stream_ptr()), "dc_philox_normal")
+        return self.buf
+
+
+def image_chunks(BS, K, units):
+    """Whole images per launch: 2 * K units an image, at most `units` a launch (one image at least), in equal chunks -> [(b0, b1)]."""
+    per = max(1, int(units) // (2 * K))
+    n_chunks = -(-BS // per)
+    per = -(-BS // n_chunks)
+    return [(b0, min(BS, b0 + per)) for b0 in range(0, BS, per)]
+
+
+def pair_sessions(dc, backbone, cl, chunks, dev):
+    """One pair session per chunk (b0, b1) of images for the labels cl [BS, K]: unit pair b * K + k is class token cl[b, k] || null
+    token; contexts, lengths and the context plan once per call and chunk, session ci in slot ci."""
+    table = dc.encoder is not None
+    lab_dev = dc.encoder.weight.device if table else dev
+    ln = dc.encoder.lengths.cpu() if dc._ragged_table() else None
+    sessions = []
+    for ci, (b0, b1) in enumerate(chunks):
+        lab = cl[b0:b1].reshape(-1)
+        nul = torch.full_like(lab, dc.null_token)
+        cond, null = dc.encode_text_prompt(lab.to(lab_dev)).to(dev), dc.encode_text_prompt(nul.to(lab_dev)).to(dev)
+        kw = dict(cond_lengths=ln[lab], null_lengths=ln[nul]) if ln is not None else {}
+        sessions.append(backbone.pair_session(lab.numel(), dev, cond, null, slot=ci, **kw))
+    return sessions
+
+
+class Walk:
+    """The BS x K trajectories of one call on a HIP backbone: trajectory b * K + k is image b under label cl[b, k], one unit pair
+    (class token || null token) of a pair session.  Built once per call — the images cut into chunks by classify's launch-size rule,
+    one pair session per chunk (the prompts projected once), lambda of the grid `lams` on the device, the step structs' common fields
+    — and walked step-major, chunk-minor by the caller's loop; nothing is copied to the host inside it.
+    who / noun: the caller's words in the two refusals."""
+
+    def __init__(self, dc, backbone, x, cl, lams, w, who="counterfactual", noun="fused sampler step"):
+        L.require_gpu()
+        if not x.is_cuda:
+            raise L.DcamdError(f"{who} on a HIP backbone needs a CUDA/HIP tensor (as sample does; no CPU fallback)")
+        self.BS, self.K = cl.shape
+        self.shape = tuple(x.shape[1:])
+        self.fields = step_fields(dc, backbone, x.shape, w, noun)
+        self.chunks = image_chunks(self.BS, self.K, units_per_launch(dc.config, x.shape[2], x.shape[3], 2 * self.K))
+        self.lam = torch.stack([v.detach().float().reshape(()) for v in lams]).to(x.device)
+        # opened at the first pass, behind the caller's draws and blocking host-to-device copies: the context plans then run on the
+        # device while the host prepares pass 0, instead of being waited for by the next such copy
+        self.sessions, self._open = None, lambda: pair_sessions(dc, backbone, cl, self.chunks, x.device)
+
+    def buffers(self, z0):
+        """(za, zb): the trajectories' latents, trajectory b * K + k starting from z0[b], and the buffer the first pass writes."""
+        za = z0.detach().to(torch.float32).repeat_interleave(self.K, dim=0).contiguous()
+        return za, torch.empty_like(za)
+
+    def view(self, z):
+        return z.view((self.BS, self.K) + self.shape)
+
+    def run(self, t, z):
+        """Pass t over z [BS * K, C, H, W]: per chunk one session step at (z[rows], lam_t), then -> (rows: the chunk's trajectories,
+        imgs: its images, f: the step struct's fields z, pred, n, ld and the common ones) for the caller's one kernel."""
+        if self.sessions is None:
+            self.sessions = self._open()
+        for (b0, b1), ses in zip(self.chunks, self.sessions):
+            rows = slice(b0 * self.K, b1 * self.K)
+            pair = ses.step(z[rows], self.lam[t:t + 1])
+            yield rows, slice(b0, b1), dict(self.fields, z=z[rows].data_ptr(), pred=pair.data_ptr(), n=(b1 - b0) * self.K, ld=pair.shape[-1])
+
+
+def launch(entry, params):
+    """One step kernel on the current stream: entry "dc_solver_step" | "dc_ddpm_step_shared" | "dc_ddpm_noise_map"."""
+    L.check(getattr(L.lib(), entry)(C.byref(params), L.stream_ptr()), entry)

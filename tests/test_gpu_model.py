@@ -502,3 +502,32 @@ def test_classify_f32_schedule_corners_match_oracle(variant):
     assert torch.equal(torch.isfinite(got_e), fin)
     assert ((got_e[fin] - ref_e[fin]).abs() / ref_e[fin]).max().item() < 1e-4
     assert got_l.cpu().tolist() == ref_l.tolist()
+
+
+@pytest.mark.parametrize("case", ["unet_f32_token", "unet_bf16_token", "unet_f32_ragged", "unet_bf16_ragged", "dit_f32"])
+def test_pair_session_step_returns_the_bits_of_forward_pair(case):
+    """`forward_pair(x, lam, cond, null)` and `pair_session(N, dev, cond, null).step(x, lam)` share one body (the plan lookup, the
+    contexts copied in, the context plan) and differ in the plan's cache key, so in its arena only: the same ops on the same operands,
+    `torch.equal` predictions.  N = 3 on the small UNet in fp32 and bf16, under class tokens (S = 1) and under 3-token prompts of
+    lengths cond [2, 3, 1] / null [1, 1, 1], and on the small DiT (labels).  The session's second step gives the same bits again."""
+    torch.manual_seed(61)
+    N, kw_len = 3, {}
+    if case == "dit_f32":
+        m = dca.DiT(num_attention_heads=2, attention_head_dim=32, in_channels=4, num_layers=2, sample_size=16, patch_size=4, num_embeds_ada_norm=10)
+        x, cond, null = torch.randn(N, 4, 16, 16), torch.tensor([1, 9, 3]), torch.tensor([10, 10, 10])
+    else:
+        kw = dca.small_unet_kwargs()
+        m, _ = make_pair(kw, seed=61)
+        S = 3 if case.endswith("ragged") else 1
+        x, cond, null = torch.randn(N, 3, 32, 32) * 0.5, torch.randn(N, S, kw["encoder_hid_dim"]), torch.randn(N, S, kw["encoder_hid_dim"])
+        if S > 1:
+            kw_len = dict(cond_lengths=torch.tensor([2, 3, 1]), null_lengths=torch.tensor([1, 1, 1]))
+    m = m.to(DEV).set_compute_dtype("bf16" if "bf16" in case else "f32")
+    x, lam, cond, null = x.to(DEV), torch.tensor([0.5, -3.0, 1.5]).to(DEV), cond.to(DEV), null.to(DEV)
+    want = m.forward_pair(x, lam, cond, null, **kw_len).clone()
+    ses = m.pair_session(N, DEV, cond, null, **kw_len)
+    got = ses.step(x, lam).clone()
+    assert want.shape[0] == 2 * N and torch.isfinite(want).all()
+    assert torch.equal(got, want), (got - want).abs().max().item()
+    assert torch.equal(ses.step(x, lam), want)
+    assert {k[0] for k in m._plans} == {"pair", "pair_session"}
