@@ -20,36 +20,17 @@ shards the (trial, image) grid of ONE replicated batch over the default process 
 `vae_path` (a LOCAL diffusers AutoencoderKL directory: `classify` encodes images to latents on the device first, nets/vae.py;
 `vae_dtype` its compute dtype, default the backbone's; `encode_latents(x)`; `classify(..., latents=True)` takes latents as they are).
 
-What differs is HOW classify runs.  The reference walks a Python double loop — T trials x C
-classes sequential eager backbone calls at batch BS (:686-714).  Here the (image, trial, class)
-grid is flattened into micro-batches of work units; each micro-batch is ONE native call
-(`dc_run_plan`) that enqueues q_sample -> backbone -> eps-MSE on the HIP stream, with z_t / eps
-materialised once per (image, trial), class-independent layers computed once per (image,
-trial), and errors scattered straight into `errors[b, class, j]`.  The stage end (mean over
-trials, top-k smallest, :718-721) runs ON THE DEVICE for the HIP backbones (`dc_stage_topk`,
-`dc_reduce_argmin`: fixed summation order, ties to the lower class id, NaN last — identical on
-every rank), and so do the next stage's work-unit maps (`dc_stage_maps`): nothing is copied to
-the host between stages as long as `stop_margin_z` is unset.  A foreign `nn.Module` backbone takes the reference's own torch ops
-(`_ForeignRunner.stage_end`).
+What differs is HOW classify runs: the (image, trial, class) grid is flattened into micro-batches of work units, one native call each,
+with the stage ends on the device — scoring.py (`_HipRunner`; a foreign `nn.Module` backbone takes `_ForeignRunner`, eager torch).
 
 Per-image early stopping (`config.stop_margin_z` = a float > 0; +inf: never stop; anything else, or the key together with
 `simulate_rank`, raises ValueError): stage pruning drops classes, never images — with two classes every image pays all T trials.
 With the key set, the stages are checkpoints: after stage i < n_stages - 1 (and after its top-k pruning) every image still active
-gets winner, runner-up and margin_z over its cells j < t_end exactly as the posterior defines them (posterior.py); it stops iff
-margin_z >= stop_margin_z and its winner's mean is not NaN (a NaN z-score, e.g. at t_end = 1, never stops; no runner-up — margin_z =
-+inf — does).  A stopped image keeps label = winner and t_done = t_end, its cells j >= t_done stay +inf for good, and it is in no
+stops iff the posterior's margin_z over its cells j < t_end is >= stop_margin_z (posterior.py has the rule).  A stopped image keeps label = winner and t_done = t_end, its cells j >= t_done stay +inf for good, and it is in no
 later stage's pairs: the work of a batch is sum_b t_done[b] (trial, image) pairs instead of BS * T.  The last stage ends as always,
 the images that got there take its label and t_done = T; if no image is left after a checkpoint the remaining stages are skipped.
-HIP backbones decide on the device (`dc_stage_stop`: the posterior's own device code, so the z-score an image stopped on is the one
-the posterior reports; the undecided ids compacted in ascending order without atomics) and build the next stage's maps over the
-undecided images there (`dc_stage_maps_rows`); the PRICE is one pinned device-to-host copy of BS + 1 int32 (the ids and their
-count) and a wait for it at every stage end but the last — the host needs the count to size the launches.  A stage over a subset of
-the images takes its launch size from a short ladder (cap, cap/2, ... cap/32 pairs, padded with dump-cell slots), so that the
-changing number of undecided images does not build a plan per count.  A foreign backbone applies the same rule as torch statements
-(`posterior.stop_rule_torch`).  Under grid sharding every rank holds the same errors after each gather, takes the same decisions and
-builds the same image list: no extra collective.  With +inf labels, errors and posterior are bit-identical to the key unset.
-The rule looks at the data at every checkpoint: `stop_margin_z` is NOT a one-shot significance level (sequential testing) — a z
-reached at one of several looks is weaker evidence than the same z at a fixed T; calibrate the threshold on held-out data.
+With +inf labels, errors and posterior are bit-identical to the key unset.  `stop_margin_z` is NOT a one-shot significance level
+(sequential testing, posterior.py): calibrate the threshold on held-out data.  How and at what price the device decides: scoring.py.
 
 Extra keyword-only arguments (defaults keep the reference behaviour):
   t, eps         inject the per-trial draws ([T,BS] and [T,BS,C,H,W]) — parity tests
@@ -90,7 +71,6 @@ decodes the image back exactly — and `counterfactual(..., start="ddpm_invert")
 """
 import math
 import os
-import time
 
 import torch
 import torch.nn as nn
@@ -103,6 +83,7 @@ from .. import posterior as P
 from .. import evidence as EV
 from .. import solver as S
 from .. import trajectory as TJ
+from ..scoring import _ForeignRunner, _HipRunner      # (tests and tools reach the runners through this module)
 from .._ema import EMA
 
 
@@ -371,7 +352,7 @@ class DiffusionClassifier(nn.Module):
         assert rng in ("reference", "philox")
         backbone = self.ema.ema_model
         ends = [0] + list(cfg.evaluation_per_stage)
-        T, ncls = ends[-1], cfg.classes
+        T = ends[-1]
         BS = x.shape[0]
         if return_evidence:
             EV.check_trials(T)
@@ -387,17 +368,85 @@ class DiffusionClassifier(nn.Module):
         elif ws > 1:
             D.assert_replicated(x, group)
 
-        # candidate classes per image (host, exactly the reference's ops :671-679)
+        classes = self._candidate_classes(text, fast, fast_select, BS)
+        draws = self._trial_draws(x, T, t, eps, rng, seed)
+        if hasattr(backbone, "make_plan"):
+            runner = _HipRunner(self, backbone, x, T, draws)           # libdcamd; raises without GPU / library
+        else:
+            runner = _ForeignRunner(self, backbone, x, T, draws)       # user-supplied nn.Module, eager torch
+        # per-image early stopping (config.stop_margin_z): t_done[b] = 0 while image b is undecided, else the trials it was decided on;
+        # `rows` = the undecided images (ascending ids; None: all of them, the plain path), the same list on every rank
+        t_done = frozen = rows = None
+        if z_stop is not None:
+            t_done, frozen = runner.stop_state()
+        if return_evidence:
+            runner.evidence_begin(cfg.n_stages)      # per-stage int64 accumulators; the plans of this call carry the map op
+        for i in range(cfg.n_stages):
+            last = i == cfg.n_stages - 1
+            if return_evidence:
+                runner.ev_stage = i
+            pairs = D.local_pairs(ends[i], ends[i + 1], BS, rank, ws) if rows is None else D.local_pairs_rows(ends[i], ends[i + 1], rows, rank, ws)
+            runner.run_stage(pairs, classes, stage=(ends[i], rank, ws), rows=rows)
+            errors = runner.errors()
+            if not sim:
+                D.gather_stage_errors(errors, ends[i], ends[i + 1], rank, ws, group=group,
+                                      **({} if rows is None else {"rows": runner.rows_on_device(rows)}))
+            # stage end (:718-721), identically on every rank: mean over the trials so far, the k smallest classes per image (HIP
+            # backbones: on the device, scoring.py).  (A stopped image's cells past t_done stay +inf: its class list is meaningless
+            # from then on and never used.)
+            classes = runner.stage_end(errors, ends[i + 1], cfg.n_keep_per_stage[i], last=last)
+            if z_stop is not None and not last:
+                active = runner.stage_stop(errors, ends[i + 1], z_stop, t_done, frozen)
+                rows = None if len(active) == BS else active
+                if not active:
+                    break                        # every image is decided: the remaining stages have nothing to score
+        if z_stop is None or last:
+            assert classes.shape[1] == 1, "Only one class should be selected at the end of the classification process."
+        if z_stop is None:
+            out = classes[:, 0].to(device=x.device, dtype=torch.int64)
+        elif last:                               # the images that ran to T take the last stage's label, the others keep theirs
+            out = torch.where(t_done == 0, classes[:, 0].to(device=frozen.device, dtype=torch.int64), frozen).to(x.device)
+            t_done = torch.where(t_done == 0, torch.full_like(t_done, T), t_done)
+        else:
+            out = frozen.to(x.device)
+        # the posterior reads the errors every rank holds after the last gather: the same bits everywhere
+        post = evid = None
+        t_end, t_values = (T, None) if z_stop is None else (t_done, ends[1:i + 2])
+        if return_evidence:
+            # the maps are paired to the posterior's winner over the posterior's trial counts: its parts are computed either way
+            post, winner, means, _ = runner.posterior(errors, t_end, 1.0 if tau is None else tau, t_values=t_values, return_parts=True)
+            acc, bad = runner.ev
+            if ws > 1:
+                D.reduce_evidence(acc, bad, ws, group=group)     # exact integer sums: the same bits on every rank and for every world size
+            evid = runner.evidence(ends[1:], post.n_trials, EV.winner_or_none(winner, means))
+        elif return_posterior:
+            post = runner.posterior(errors, t_end, tau, t_values=t_values)
+        res = (out,)
+        if return_errors:
+            res += (errors.cpu(),)               # (synchronises: the cheap moment to look at the device-side failure counter)
+            self.check_device_errors()
+        if return_posterior:
+            res += (post,)
+        if return_evidence:
+            res += (evid,)
+        if return_trials:
+            res += (t_done if t_done is not None else torch.full((BS,), T, dtype=torch.int32, device=errors.device),)
+        return res if len(res) > 1 else out
+
+    def _candidate_classes(self, text, fast, fast_select, BS):
+        """Candidate classes per image (host, exactly the reference's ops :671-679)."""
+        cfg, ncls = self.config, self.config.classes
         if fast:
             text_c = text.detach().cpu().view(-1, 1)
             classes = torch.arange(ncls).repeat(BS, 1)
             wrong = classes[(classes == text_c) == False].view(BS, -1)  # noqa: E712
             sel = fast_select.cpu() if fast_select is not None else torch.randint(0, wrong.shape[1], (BS, cfg.n_fast_classes - 1))
-            classes = torch.cat((text_c, torch.gather(wrong, 1, sel)), dim=1)
-        else:
-            classes = torch.arange(ncls).repeat(BS, 1)
+            return torch.cat((text_c, torch.gather(wrong, 1, sel)), dim=1)
+        return torch.arange(ncls).repeat(BS, 1)
 
-        # per-trial draws.  reference order: t = rand(BS) then eps = randn_like(x), trial by trial (:688-692, :113)
+    def _trial_draws(self, x, T, t, eps, rng, seed):
+        """Per-trial draws.  reference order: t = rand(BS) then eps = randn_like(x), trial by trial (:688-692, :113)."""
+        BS = x.shape[0]
         eps_of = {}
         if t is not None:
             t_all = torch.as_tensor(t, dtype=torch.float32).cpu().reshape(T, BS)
@@ -426,77 +475,8 @@ class DiffusionClassifier(nn.Module):
             logsnr = torch.stack([self.schedule(t_all[j].clone()) for j in range(T)])
             alpha_all = torch.stack([torch.sqrt(torch.sigmoid(logsnr[j].clone())) for j in range(T)])
             sigma_all = torch.stack([torch.sqrt(torch.sigmoid(-logsnr[j].clone())) for j in range(T)])
-        draws = dict(logsnr=logsnr, alpha=alpha_all, sigma=sigma_all,
-                     eps_of=eps_of, philox=(rng == "philox" and eps is None), seed=int(seed))
-
-        if hasattr(backbone, "make_plan"):
-            runner = _HipRunner(self, backbone, x, T, draws)           # libdcamd; raises without GPU / library
-        else:
-            runner = _ForeignRunner(self, backbone, x, T, draws)       # user-supplied nn.Module, eager torch
-        # per-image early stopping (config.stop_margin_z): t_done[b] = 0 while image b is undecided, else the trials it was decided on;
-        # `rows` = the undecided images (ascending ids; None: all of them, the plain path), the same list on every rank
-        t_done = frozen = rows = None
-        if z_stop is not None:
-            t_done, frozen = runner.stop_state()
-        if return_evidence:
-            runner.evidence_begin(cfg.n_stages)      # per-stage int64 accumulators; the plans of this call carry the map op
-        for i in range(cfg.n_stages):
-            last = i == cfg.n_stages - 1
-            if return_evidence:
-                runner.ev_stage = i
-            if rows is None:
-                pairs = D.local_pairs(ends[i], ends[i + 1], BS, rank, ws)
-                runner.run_stage(pairs, classes, stage=(ends[i], rank, ws))
-            else:
-                pairs = D.local_pairs_rows(ends[i], ends[i + 1], rows, rank, ws)
-                runner.run_stage(pairs, classes, stage=(ends[i], rank, ws), rows=rows)
-            errors = runner.errors()
-            if not sim:
-                D.gather_stage_errors(errors, ends[i], ends[i + 1], rank, ws, group=group,
-                                      **({} if rows is None else {"rows": runner.rows_on_device(rows)}))
-            # stage end (:718-721), identically on every rank: mean over the trials so far, the k smallest classes per image.
-            # HIP backbones: on the device (dc_stage_topk / dc_reduce_argmin; the next stage's work-unit maps are built
-            # there too), so a multi-stage / fast classify never copies errors to the host between stages — unless stop_margin_z
-            # is set: the stop rule then hands the number and the ids of the undecided images to the host at every boundary.
-            # (A stopped image's cells past t_done stay +inf: its class list is meaningless from then on and never used.)
-            classes = runner.stage_end(errors, ends[i + 1], cfg.n_keep_per_stage[i], last=last)
-            if z_stop is not None and not last:
-                active = runner.stage_stop(errors, ends[i + 1], z_stop, t_done, frozen)
-                rows = None if len(active) == BS else active
-                if not active:
-                    break                        # every image is decided: the remaining stages have nothing to score
-        if z_stop is None or last:
-            assert classes.shape[1] == 1, "Only one class should be selected at the end of the classification process."
-        if z_stop is None:
-            out = classes[:, 0].to(device=x.device, dtype=torch.int64)
-        elif last:                               # the images that ran to T take the last stage's label, the others keep theirs
-            out = torch.where(t_done == 0, classes[:, 0].to(device=frozen.device, dtype=torch.int64), frozen).to(x.device)
-            t_done = torch.where(t_done == 0, torch.full_like(t_done, T), t_done)
-        else:
-            out = frozen.to(x.device)
-        # the posterior reads the errors every rank holds after the last gather: the same bits everywhere
-        post = evid = None
-        if return_evidence:
-            # the maps are paired to the posterior's winner over the posterior's trial counts: its parts are computed either way
-            pk = dict(return_parts=True) if z_stop is None else dict(return_parts=True, t_values=ends[1:i + 2])
-            post, winner, means, _ = runner.posterior(errors, T if z_stop is None else t_done, 1.0 if tau is None else tau, **pk)
-            acc, bad = runner.ev
-            if ws > 1:
-                D.reduce_evidence(acc, bad, ws, group=group)     # exact integer sums: the same bits on every rank and for every world size
-            evid = runner.evidence(ends[1:], post.n_trials, EV.winner_or_none(winner, means))
-        elif return_posterior:
-            post = runner.posterior(errors, T, tau) if z_stop is None else runner.posterior(errors, t_done, tau, t_values=ends[1:i + 2])
-        res = (out,)
-        if return_errors:
-            res += (errors.cpu(),)               # (synchronises: the cheap moment to look at the device-side failure counter)
-            self.check_device_errors()
-        if return_posterior:
-            res += (post,)
-        if return_evidence:
-            res += (evid,)
-        if return_trials:
-            res += (t_done if t_done is not None else torch.full((BS,), T, dtype=torch.int32, device=errors.device),)
-        return res if len(res) > 1 else out
+        return dict(logsnr=logsnr, alpha=alpha_all, sigma=sigma_all,
+                    eps_of=eps_of, philox=(rng == "philox" and eps is None), seed=int(seed))
 
     def check_device_errors(self):
         """Raise if a producer-side-GroupNorm launch (csrc/epi_pn.h) gave up waiting for the other workgroups of a sample since the last
@@ -829,340 +809,3 @@ class DiffusionClassifier(nn.Module):
             save_file(cpu(self.encoder.state_dict()), os.path.join(checkpoint_dir, "model_2.safetensors"))
         torch.save({"epoch": epoch + 1, "best_metric": best_metric, "experiment_key": experiment_key},
                    os.path.join(checkpoint_dir, "experiment_state.pth"))
-
-
-class _ForeignRunner:
-    """Backbones that are plain nn.Modules (not this package's HIP backbones): the reference's
-    semantics in eager torch on x.device, one backbone call per (trial, class column) at batch BS
-    (reference :686-714).  This is NOT a fallback for UNetCondition2D / DiT — those always take
-    _HipRunner and raise when libdcamd or the GPU is missing."""
-
-    def __init__(self, dc, backbone, x, T, draws):
-        if draws["philox"]:
-            raise L.DcamdError("rng='philox' needs a HIP backbone (UNetCondition2D / DiT)")
-        dc._refuse_ragged_on_foreign()
-        self.dc, self.bb, self.x, self.T, self.d = dc, backbone, x, T, draws
-        self.err = torch.full((x.shape[0], dc.config.classes, T), float("inf"), device=x.device)
-
-    def errors(self):
-        return self.err
-
-    def stage_end(self, errors, t_end, num_keep, last=False):
-        # identical torch ops to the reference (:718-721)
-        end_of_stage_errors = errors.cpu()[:, :, :t_end].mean(dim=2)
-        _, keep_indices = torch.topk(end_of_stage_errors, num_keep, dim=1, largest=False)
-        return keep_indices
-
-    def posterior(self, errors, t_end, temperature, t_values=None, return_parts=False):
-        return P.class_posterior_torch(errors, t_end, temperature, t_values=t_values, return_parts=return_parts)
-
-    ev = None            # (acc, bad) per-stage evidence accumulators of a return_evidence call (evidence.py), `ev_stage` the running stage
-
-    def evidence_begin(self, n_stages):
-        BS, _, H, W = self.x.shape
-        self.ev, self.ev_stage = EV.new_slabs(n_stages, BS * self.dc.config.classes, H * W, self.x.device), 0
-
-    def evidence(self, stage_ends, n_eval, winner):
-        return EV.evidence_maps_torch(self.ev[0], self.ev[1], stage_ends, n_eval, winner, self.x.shape[2], self.x.shape[3])
-
-    def stop_state(self):
-        BS, dev = self.x.shape[0], self.x.device
-        return torch.zeros(BS, dtype=torch.int32, device=dev), torch.zeros(BS, dtype=torch.int64, device=dev)
-
-    def stage_stop(self, errors, t_end, z_stop, t_done, labels):
-        """The stop rule at a stage boundary as torch statements (posterior.stop_rule_torch), in place; the undecided image ids as a list."""
-        ids, n, _ = P.stop_rule_torch(errors, t_end, z_stop, t_done, labels)
-        return ids[:int(n)].tolist()
-
-    def rows_on_device(self, rows):
-        return rows
-
-    def run_stage(self, pairs, classes, stage=None, rows=None):
-        dc, x, d = self.dc, self.x, self.d
-        by_trial = {}
-        for j, b in pairs:
-            by_trial.setdefault(j, []).append(b)
-        for j, bl in by_trial.items():
-            bs = torch.tensor(bl)
-            full = bl == list(range(x.shape[0]))       # the reference's own batch: use the tensors as they are
-            al = (d["alpha"][j] if full else d["alpha"][j, bs]).view(-1, 1, 1, 1).to(x.device)
-            sg = (d["sigma"][j] if full else d["sigma"][j, bs]).view(-1, 1, 1, 1).to(x.device)
-            lam = (d["logsnr"][j] if full else d["logsnr"][j, bs]).to(x.device)
-            e = d["eps_of"][j]
-            e = (e if full else e[bs.to(e.device)]).to(x.device)
-            z = al * (x if full else x[bs.to(x.device)]) + sg * e
-            for c in range(classes.shape[1]):
-                lab = classes[bs, c].to(x.device)
-                emb = dc.encode_text_prompt(lab)
-                pred = self.bb(x=z, noise_labels=lam, encoder_hidden_states=emb)
-                eps_pred = sg * z + al * pred if dc.pred_param == 'v' else pred
-                err = torch.norm((eps_pred - e).view(len(bl), -1), dim=1, p=2) ** 2
-                self.err[bs.to(x.device), lab, j] = err
-                if self.ev is not None:
-                    EV.err_map_torch(eps_pred, e, bs.to(x.device) * dc.config.classes + lab, self.ev[0][self.ev_stage], self.ev[1][self.ev_stage])
-
-
-class _HipRunner:
-    """Micro-batched execution of the (image, trial, class) grid through libdcamd plans."""
-
-    def __init__(self, dc, backbone, x, T, draws):
-        self.lib = L.require_gpu()
-        self.dc, self.bb, self.x, self.T, self.d = dc, backbone, x, T, draws
-        self.dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self.x_dev = x.detach().to(self.dev, torch.float32).contiguous()
-        self.err_dev = None
-        cfg = dc.config
-        dt = cfg.compute_dtype or "bf16"
-        if getattr(backbone, "compute_dtype", None) != dt:
-            backbone.set_compute_dtype(dt)
-        self.dt = dt
-        if draws["philox"]:
-            assert (x.shape[1] * x.shape[2] * x.shape[3]) % 4 == 0
-
-    def _plan(self, n_bj, k):
-        dc, dev = self.dc, self.dev
-        cfg = dc.config
-        BS, Cc, H, W = self.x.shape
-        wver = getattr(self.bb, "_wver", 0)
-        S = int(dc.encoder.weight.shape[1]) if dc._table_mode() else 1                 # tokens per context
-        varlen = dc._ragged_table()                                                    # prompts of different lengths: a plan with ctx_len
-        key = (BS, n_bj, k, self.dt, str(dev), (Cc, H, W), bool(getattr(self.bb, "share_trunk", True)), id(self.bb),
-               self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ()) + (("evidence",) if self.ev is not None else ())
-        sp = dc._score_plans.get(key)
-        if sp is not None:
-            dc._score_plans[key] = dc._score_plans.pop(key)      # most recently used last
-            return sp
-        # plans hold raw pointers into the packed weights they were built from: entries of an older weights version of this
-        # backbone (load_state_dict / .to() / EMA.update since) are stale — drop them so their arenas are freed
-        for old in [k_ for k_ in dc._score_plans if k_[7] == id(self.bb) and k_[10] != wver]:
-            del dc._score_plans[old]
-        U, T = n_bj * k, self.T
-        # one int32 control block: | pair_id (int64 x n_bj) | lam | alpha | sigma | img_of_bj | ctx_of_unit | out_index |
-        words = 2 * n_bj + 4 * n_bj + 2 * U
-        ctl = torch.zeros(words, dtype=torch.int32, device=dev)
-        o = [0]
-
-        def take(n):
-            v = ctl[o[0]:o[0] + n]
-            o[0] += n
-            return v
-        pair_id = take(2 * n_bj).view(torch.int64)
-        lam, alpha, sigma = (take(n_bj).view(torch.float32) for _ in range(3))
-        img_of_bj, ctx_of_unit, out_index = take(n_bj), take(U), take(U)
-        score = dict(
-            x=torch.zeros((BS, Cc, H, W), dtype=torch.float32, device=dev),
-            eps=torch.zeros((n_bj, Cc, H, W), dtype=torch.float32, device=dev),
-            errors=torch.full((BS * cfg.classes * T + 1,), float("inf"), dtype=torch.float32, device=dev),
-            lam=lam, alpha=alpha, sigma=sigma, img_of_bj=img_of_bj, ctx_of_unit=ctx_of_unit, out_index=out_index,
-            v_param=dc.pred_param == 'v')
-        if self.ev is not None:          # such plans own the accumulators their map op adds into (one stage at a time: run_stage)
-            score["emap_acc"], score["emap_bad"] = (v[0] for v in EV.new_slabs(1, BS * cfg.classes, H * W, dev))
-            score["emap_T"] = T
-        plan = self.bb.make_plan(n_bj, k, cfg.classes, dev, score=score, **({"S": S} if S > 1 else {}), **({"varlen": True} if varlen else {}))
-        sp = dict(plan=plan, score=score, ctl=ctl, pair_id=pair_id, words=words, n_bj=n_bj, k=k, U=U)
-        dc._score_plans[key] = sp
-        # each entry owns an arena, a workspace and an errors buffer in HBM, and n_bj follows the pair count (per rank, per stage, per
-        # last batch of a dataloader): keep the most recently used few (a multi-stage classify alternates between one plan per stage).
-        # (Scores that do not depend on n_bj — i.e. on the world size or the micro-batch split — rest on every kernel giving a sample the
-        # same bits wherever it sits in a launch and whichever tile shape the launch size selects; tests/test_gpu_dist.py and
-        # test_cfg2_full_grid_properties_at_bench_size hold that, and caught the one epilogue branch that did not in round 4.)
-        cap = int(getattr(cfg, "score_plan_cache", None) or 6)
-        while len(dc._score_plans) > max(cap, 1):
-            del dc._score_plans[next(iter(dc._score_plans))]
-        return sp
-
-    def errors(self):
-        BS, ncls = self.x.shape[0], self.dc.config.classes
-        if self.err_dev is None:   # this rank owned no trial so far
-            self.err_dev = torch.full((BS * ncls * self.T + 1,), float("inf"), dtype=torch.float32, device=self.dev)
-        return self.err_dev[:-1].view(BS, ncls, self.T)
-
-    def stage_end(self, errors, t_end, num_keep, last=False):
-        """Mean over trials [0, t_end) and the num_keep smallest classes per image, on the device.  Returns [BS, num_keep]:
-        int64 labels for the last stage (dc_reduce_argmin), else the int32 class lists the next stage's maps are built from."""
-        BS, ncls, T = errors.shape
-        assert errors.is_contiguous() and errors.dtype == torch.float32
-        if last and num_keep == 1:
-            keep = torch.empty((BS, 1), dtype=torch.int64, device=errors.device)
-            L.check(self.lib.dc_reduce_argmin(errors.data_ptr(), BS, ncls, T, t_end, keep.data_ptr(), None, L.stream_ptr()), "dc_reduce_argmin")
-        else:
-            keep = torch.empty((BS, num_keep), dtype=torch.int32, device=errors.device)
-            L.check(self.lib.dc_stage_topk(errors.data_ptr(), BS, ncls, T, t_end, num_keep, keep.data_ptr(), None, L.stream_ptr()), "dc_stage_topk")
-        return keep
-
-    def posterior(self, errors, t_end, temperature, t_values=None, return_parts=False):
-        return P.class_posterior_hip(errors, t_end, temperature, t_values=t_values, return_parts=return_parts)
-
-    ev = None            # (acc, bad) per-stage evidence accumulators of a return_evidence call (evidence.py), `ev_stage` the running stage
-
-    def evidence_begin(self, n_stages):
-        BS, _, H, W = self.x.shape
-        self.ev, self.ev_stage = EV.new_slabs(n_stages, BS * self.dc.config.classes, H * W, self.dev), 0
-
-    def evidence(self, stage_ends, n_eval, winner):
-        return EV.evidence_maps_hip(self.ev[0], self.ev[1], stage_ends, n_eval, winner, self.x.shape[2], self.x.shape[3])
-
-    def stop_state(self):
-        BS = self.x.shape[0]
-        return torch.zeros(BS, dtype=torch.int32, device=self.dev), torch.zeros(BS, dtype=torch.int64, device=self.dev)
-
-    def stage_stop(self, errors, t_end, z_stop, t_done, labels):
-        """The stop rule at a stage boundary on the device (dc_stage_stop), in place on t_done / labels.  Returns the undecided image
-        ids (ascending) as a list: ONE pinned device-to-host copy of BS + 1 int32 (the ids and their count) and a wait for it — the
-        host needs the count to size the next stage's launches.  The ids stay on the device for dc_stage_maps_rows."""
-        BS = errors.shape[0]
-        block = torch.empty(BS + 1, dtype=torch.int32, device=self.dev)          # | active ids [BS] | their count |
-        ids, _, _ = P.stop_rule_hip(errors, t_end, z_stop, t_done, labels, out=block)
-        host = getattr(self.dc, "_stop_host", None)          # pinned staging kept across calls (pin_memory() is slow); free again after the wait
-        if host is None or host.numel() != BS + 1:
-            host = self.dc._stop_host = torch.zeros(BS + 1, dtype=torch.int32).pin_memory()
-        host.copy_(block, non_blocking=True)
-        torch.cuda.current_stream(self.dev).synchronize()
-        n = int(host[BS])
-        active = host[:n].tolist()
-        self._rows = (active, ids[:n])
-        return active
-
-    def rows_on_device(self, rows):
-        """The int32 device tensor of an image list: the one dc_stage_stop wrote when it is the list it returned."""
-        have = getattr(self, "_rows", None)
-        if have is not None and have[0] == list(rows):
-            return have[1]
-        return torch.tensor(list(rows), dtype=torch.int32).to(self.dev)
-
-    def run_stage(self, pairs, classes, stage=None, rows=None):
-        """pairs: this rank's (trial, image) pairs of the stage = D.local_pairs(t0, t1, BS, rank, world); stage = (t0, rank, world).
-        rows (per-image early stopping): the stage runs over these images only — pairs = D.local_pairs_rows(t0, t1, rows, rank, world)."""
-        if not pairs:
-            return
-        dc, d, dev, T = self.dc, self.d, self.dev, self.T
-        BS, Cc, H, W = self.x.shape
-        ncls, k = dc.config.classes, classes.shape[1]
-        on_dev = classes.is_cuda                         # stages >= 1: the surviving classes never left the device
-        cap = max(1, TJ.units_per_launch(self.dc.config, H, W, k) // k)
-        if rows is None:
-            n_bj = min(len(pairs), cap)
-            # equal micro-batches: 800 pairs at a cap of 256 run as 4 x 200, not 3 x 256 + 32 padded to 256 (slots past the last pair
-            # repeat a pair into the dump cell: 28 % wasted work on the CheXpert workload at 8 images per step)
-            n_bj = -(-len(pairs) // -(-len(pairs) // n_bj))
-        else:
-            # a stage over the undecided images: their number changes from batch to batch, and every n_bj is a plan with an arena of
-            # its own — take the smallest rung of cap, cap/2, ... cap/32 that holds the pairs (cap when there are more) and pad the
-            # last micro-batch with dump-cell slots: at most 6 plan sizes per k, the default score_plan_cache
-            n_bj = cap
-            for _ in range(5):
-                if n_bj == 1 or -(-n_bj // 2) < len(pairs):
-                    break
-                n_bj = -(-n_bj // 2)
-        sp = self._plan(n_bj, k)
-        plan, score, U = sp["plan"], sp["score"], sp["U"]
-        if self.err_dev is None:
-            score["errors"].fill_(float("inf"))
-        elif score["errors"] is not self.err_dev:
-            score["errors"].copy_(self.err_dev)
-        self.err_dev = score["errors"]
-        if self.ev is not None:
-            score["emap_acc"].zero_()
-            score["emap_bad"].zero_()
-        score["x"].copy_(self.x_dev)
-        if dc.encoder is not None:
-            plan.ctx.copy_(dc.encoder.weight[:ncls].detach().to(dev, torch.float32).reshape(plan.ctx.shape))
-            if plan.varlen:                              # the same on every rank: grid sharding needs nothing else
-                plan.ctx_len.copy_(dc.encoder.lengths[:ncls].to(dev, torch.int32))
-        plan.run_ctx()                                   # per-class vectors: once per stage, not per micro-batch
-        n_mb = -(-len(pairs) // n_bj)
-        host = sp.get("host")                            # pinned staging, reused across calls (pin_memory() is slow)
-        ev = sp.get("host_ev")
-        if ev is not None:
-            ev.synchronize()                             # the previous call's asynchronous control-block copies have left `host`
-        if host is None or host.shape[0] < n_mb:
-            host = sp["host"] = torch.zeros((n_mb, sp["words"]), dtype=torch.int32).pin_memory()
-        dump = BS * ncls * T
-        # the index part of every control block (pair ids, image / class / output maps) depends on (pairs, classes) only:
-        # built once and kept (stage 0 of every call sees the same pairs and the full class list); per call only the
-        # three float rows (lambda, alpha, sigma of this call's t draws) are gathered.  Host time here is GPU idle time.
-        # (pairs over a subset of the images: two subsets can agree in length, first and last pair — the ids are part of the key; a
-        # caller that hands over pairs without naming their stage is keyed by the pairs themselves)
-        ck = (n_bj, len(pairs), pairs[0], pairs[-1], T, ncls, b"dev" if on_dev else classes.numpy().tobytes(),
-              tuple(rows) if rows is not None else (None if stage is not None else tuple(pairs)))
-        cache = sp.setdefault("idx_cache", {})
-        ent = cache.get(ck)
-        if ent is None:
-            if len(cache) > 8:
-                cache.clear()
-            tmpl = torch.zeros((n_mb, sp["words"]), dtype=torch.int32)
-            jsb = []
-            for m in range(n_mb):
-                chunk = pairs[m * n_bj:(m + 1) * n_bj]
-                row = tmpl[m]
-                pad = n_bj - len(chunk)
-                js = torch.tensor([p[0] for p in chunk] + [chunk[0][0]] * pad)
-                bs = torch.tensor([p[1] for p in chunk] + [chunk[0][1]] * pad)
-                o = 2 * n_bj
-                row[0:o].view(torch.int64).copy_(bs * T + js)
-                o += 3 * n_bj
-                row[o:o + n_bj].copy_(bs.to(torch.int32)); o += n_bj
-                if not on_dev:
-                    cl = classes[bs]                                       # [n_bj, k] class id of every unit
-                    oi = (bs[:, None] * ncls + cl) * T + js[:, None]       # errors[b, class, j], flat
-                    if pad:
-                        oi[len(chunk):] = dump
-                    row[o:o + U].copy_(cl.reshape(-1).to(torch.int32)); o += U
-                    row[o:o + U].copy_(oi.reshape(-1).to(torch.int32))
-                jsb.append((js, bs))
-            ent = cache[ck] = (tmpl, jsb)
-        tmpl, jsb = ent
-        host[:n_mb].copy_(tmpl)
-        for m in range(n_mb):
-            js, bs = jsb[m]
-            o = 2 * n_bj
-            for src in (d["logsnr"], d["alpha"], d["sigma"]):
-                host[m, o:o + n_bj].view(torch.float32).copy_(src[js, bs])
-                o += n_bj
-        CHW = Cc * H * W
-        hw = 6 * n_bj                                    # words of a control block the host owns (pair ids, lambda / alpha / sigma, image map)
-        if on_dev:
-            # class-dependent maps of every micro-batch of the stage, built on the device from the surviving classes
-            t0, rank, ws = stage
-            maps = torch.empty((n_mb, 2 * U), dtype=torch.int32, device=dev)
-            if rows is None:
-                L.check(self.lib.dc_stage_maps(classes.data_ptr(), BS, ncls, T, k, t0, len(pairs), rank, ws, n_bj, n_mb, dump,
-                                               maps.data_ptr(), L.stream_ptr()), "dc_stage_maps")
-            else:
-                rd = self.rows_on_device(rows)
-                L.check(self.lib.dc_stage_maps_rows(classes.data_ptr(), rd.data_ptr(), len(rows), BS, ncls, T, k, t0, len(pairs), rank, ws,
-                                                    n_bj, n_mb, dump, maps.data_ptr(), L.stream_ptr()), "dc_stage_maps_rows")
-        for m in range(n_mb):
-            chunk = pairs[m * n_bj:(m + 1) * n_bj]
-            if on_dev:
-                sp["ctl"][:hw].copy_(host[m, :hw], non_blocking=True)
-                sp["ctl"][hw:].copy_(maps[m], non_blocking=True)
-            else:
-                sp["ctl"].copy_(host[m], non_blocking=True)
-            if d["philox"]:
-                L.check(self.lib.dc_philox_normal(score["eps"].data_ptr(), n_bj, CHW, sp["pair_id"].data_ptr(),
-                                                  d["seed"], L.stream_ptr()), "dc_philox_normal")
-            else:
-                r = 0
-                while r < len(chunk):                                  # runs of consecutive images of one trial
-                    j, b0 = chunk[r]
-                    r1 = r
-                    while r1 < len(chunk) and chunk[r1][0] == j and chunk[r1][1] == b0 + (r1 - r):
-                        r1 += 1
-                    score["eps"][r:r1].copy_(d["eps_of"][j][b0:b0 + (r1 - r)].to(torch.float32), non_blocking=True)
-                    r = r1
-                if len(chunk) < n_bj:
-                    score["eps"][len(chunk):].copy_(score["eps"][0:1].expand(n_bj - len(chunk), -1, -1, -1))
-            if dc._timed_sink is not None:
-                dc._timed_sink.append((plan, plan.pb.run_timed()))
-            else:
-                plan.run()
-        # `host` (pinned) must outlive the asynchronous copies: instead of draining the stream here (the GPU then idles while the
-        # host prepares the next call) an event marks the last copy, and the next user of the buffer waits for it — by then it has
-        # long fired, and the host side of call i+1 runs under the kernels of call i
-        if ev is None:
-            ev = sp["host_ev"] = torch.cuda.Event()
-        ev.record()
-        if self.ev is not None:          # the stage's sums into the call's slab (int64 adds on the stream: exact)
-            self.ev[0][self.ev_stage] += score["emap_acc"]
-            self.ev[1][self.ev_stage] += score["emap_bad"]

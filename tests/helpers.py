@@ -32,7 +32,7 @@ def standin_from(g, cfg):
 def hip_preds(dc, T, BS):
     """Backbone outputs of the LAST classify call of `dc` on the HIP path, as [T, BS, class columns, C, H, W] (the layout of the
     oracle's `return_preds`): read from the score plan's prediction buffer.  Needs a single-stage grid that fitted ONE
-    micro-batch (pairs trial-major, units = pair x class: diffusion_classifier.py _HipRunner.run_stage)."""
+    micro-batch (pairs trial-major, units = pair x class: scoring.py _HipRunner.run_stage)."""
     (sp,) = list(dc._score_plans.values())
     assert sp["n_bj"] == T * BS, "the grid must fit one micro-batch"
     plan, k = sp["plan"], sp["k"]
@@ -46,6 +46,26 @@ def hip_preds(dc, T, BS):
     else:
         img = pv[..., :bb.config.out_channels].permute(0, 3, 1, 2)
     return img.reshape(T, BS, k, *img.shape[1:])
+
+
+def expected_unit_maps(pairs, keep, n_bj, ncls, T, dump):
+    """What a stage's class-dependent control-block maps must hold, unit by unit -> (ctx_of_unit, out_index), int64 [n_mb, n_bj * k]:
+    unit (m, slot, class column c) belongs to pair m * n_bj + slot of `pairs` = (j, b), is class keep[b][c] and writes its error to
+    cell (b * ncls + class) * T + j of errors[BS, ncls, T]; a slot past the last pair repeats the micro-batch's first pair and
+    writes to `dump`.  A plain loop on purpose: the product builds these maps vectorised on the host (scoring.py `index_blocks`)
+    and in kernels (`dc_stage_maps`, `dc_stage_maps_rows`)."""
+    k = len(keep[0])
+    n_mb = -(-len(pairs) // n_bj)
+    cls = torch.zeros((n_mb, n_bj * k), dtype=torch.int64)
+    out = torch.zeros((n_mb, n_bj * k), dtype=torch.int64)
+    for m in range(n_mb):
+        for slot in range(n_bj):
+            g = m * n_bj + slot
+            j, b = pairs[g] if g < len(pairs) else pairs[m * n_bj]
+            for c in range(k):
+                cls[m, slot * k + c] = int(keep[b][c])
+                out[m, slot * k + c] = (b * ncls + int(keep[b][c])) * T + j if g < len(pairs) else dump
+    return cls, out
 
 
 def pred_rel_l2(got, ref):

@@ -16,6 +16,7 @@ from diffusion_classifier_amd import dist as D
 from diffusion_classifier_amd import posterior as P
 from diffusion_classifier_amd.diffusion import diffusion_classifier as DCM
 import early_stop_oracle as O
+from helpers import expected_unit_maps
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -93,7 +94,7 @@ def test_stage_stop_is_the_same_from_launch_to_launch_and_refuses_bad_arguments(
 # ------------------------------------------------------------------------------------------------ dc_stage_maps_rows
 @pytest.mark.parametrize("world,rank", [(1, 0), (2, 0), (2, 1), (3, 0), (3, 1), (3, 2)])
 def test_stage_maps_rows_match_the_host_built_control_blocks(world, rank):
-    """The index arithmetic classify does on the host for stage 0 (diffusion_classifier.py _HipRunner.run_stage), over the images
+    """The index arithmetic classify does on the host for stage 0 (scoring.py `index_blocks`, from _HipRunner.run_stage), over the images
     rows = [1, 3, 4] of 5; every n_mb * n_bj leaves a padded tail."""
     BS, Cn, T, k, t0, t1, n_bj = 5, 9, 12, 2, 4, 12, 7
     rows = [1, 3, 4]
@@ -108,16 +109,9 @@ def test_stage_maps_rows_match_the_host_built_control_blocks(world, rank):
     L.check(L.lib().dc_stage_maps_rows(kd.data_ptr(), rd.data_ptr(), len(rows), BS, Cn, T, k, t0, len(pairs), rank, world, n_bj, n_mb, dump,
                                        maps.data_ptr(), L.stream_ptr()), "dc_stage_maps_rows")
     got = maps.cpu()
+    cl, oi = expected_unit_maps(pairs, keep, n_bj, Cn, T, dump)
     for m in range(n_mb):
-        chunk = pairs[m * n_bj:(m + 1) * n_bj]
-        pad = n_bj - len(chunk)
-        js = torch.tensor([p[0] for p in chunk] + [chunk[0][0]] * pad)
-        bs = torch.tensor([p[1] for p in chunk] + [chunk[0][1]] * pad)
-        cl = keep[bs].long()
-        oi = (bs[:, None] * Cn + cl) * T + js[:, None]
-        if pad:
-            oi[len(chunk):] = dump
-        assert torch.equal(got[m, :U].long(), cl.reshape(-1)) and torch.equal(got[m, U:].long(), oi.reshape(-1))
+        assert torch.equal(got[m, :U].long(), cl[m]) and torch.equal(got[m, U:].long(), oi[m])
     if world == 1:
         # all images as rows: dc_stage_maps; an id outside [0, BS) is clamped, not followed
         allr = torch.arange(BS, dtype=torch.int32, device=DEV)

@@ -1436,8 +1436,9 @@ def test_ddpm_step_equals_the_torch_expressions(w):
 @pytest.mark.parametrize("world,rank", [(1, 0), (3, 1)])
 def test_stage_maps_match_the_host_built_control_blocks(world, rank):
     """dc_stage_maps: next stage's (pair, class) -> work-unit maps from the surviving classes, against the index arithmetic
-    classify does on the host for stage 0 (diffusion_classifier.py _HipRunner.run_stage)."""
+    classify does on the host for stage 0 (scoring.py `index_blocks`, from _HipRunner.run_stage)."""
     from diffusion_classifier_amd import dist as D
+    from helpers import expected_unit_maps
     BS, Cn, T, k, t0, t1, n_bj = 5, 9, 12, 3, 4, 12, 7
     torch.manual_seed(43)
     keep = torch.stack([torch.randperm(Cn)[:k] for _ in range(BS)]).to(torch.int32)
@@ -1448,16 +1449,9 @@ def test_stage_maps_match_the_host_built_control_blocks(world, rank):
     kd = keep.to(DEV)
     L.check(L.lib().dc_stage_maps(ptr(kd), BS, Cn, T, k, t0, len(pairs), rank, world, n_bj, n_mb, dump, ptr(maps), L.stream_ptr()), "dc_stage_maps")
     got = maps.cpu()
+    cl, oi = expected_unit_maps(pairs, keep, n_bj, Cn, T, dump)
     for m in range(n_mb):
-        chunk = pairs[m * n_bj:(m + 1) * n_bj]
-        pad = n_bj - len(chunk)
-        js = torch.tensor([p[0] for p in chunk] + [chunk[0][0]] * pad)
-        bs = torch.tensor([p[1] for p in chunk] + [chunk[0][1]] * pad)
-        cl = keep[bs].long()
-        oi = (bs[:, None] * Cn + cl) * T + js[:, None]
-        if pad:
-            oi[len(chunk):] = dump
-        assert torch.equal(got[m, :U].long(), cl.reshape(-1)) and torch.equal(got[m, U:].long(), oi.reshape(-1))
+        assert torch.equal(got[m, :U].long(), cl[m]) and torch.equal(got[m, U:].long(), oi[m])
 
 
 @pytest.mark.parametrize("dt", [L.DC_F32, L.DC_BF16, L.DC_F16])
