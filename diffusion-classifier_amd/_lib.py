@@ -24,6 +24,7 @@ OP_ERR_MAP = 19
 EVIDENCE_FRAC_BITS, EVIDENCE_VMAX = 30, 16384.0      # include/dcamd.h DC_EVIDENCE_FRAC_BITS / DC_EVIDENCE_VMAX
 OP_ATTENTION_WIDE, OP_IM2COL_S2 = 20, 21
 ATTENTION_WIDE_DIMS = (256, 512)     # head widths of dc_attention_wide
+OP_CONV3_PN_TAIL = 22
 
 i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -54,6 +55,15 @@ class IgemmParams(C.Structure):
                 ("ln_eps", f32), ("up4", i32), ("qstats", vp),
                 ("pn_out", vp), ("pn_gamma", vp), ("pn_beta", vp), ("pn_cnt", vp),
                 ("pn_ld", i32), ("pn_groups", i32), ("pn_silu", i32), ("pn_eps", f32)]
+
+
+class PnTailParams(C.Structure):
+    _fields_ = [("Wt", vp), ("bias", vp), ("pred", vp), ("ring", vp), ("gamma", vp), ("beta", vp), ("cnt", vp),
+                ("Co", i32), ("pred_ld", i32), ("groups", i32), ("silu", i32), ("eps", f32), ("pad_", i32)]
+
+
+class Conv3PnTailOp(C.Structure):
+    _fields_ = [("conv", C.POINTER(IgemmParams)), ("tail", C.POINTER(PnTailParams))]
 
 
 class GroupnormParams(C.Structure):
@@ -202,7 +212,7 @@ class Op(C.Structure):
 
 # every symbol include/dcamd.h declares (tests check that the library exports all of them)
 EXPORTS = ["dc_abi_version", "dc_last_error", "dc_arch", "dc_qsample", "dc_philox_normal", "dc_sinusoid",
-           "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_instance", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
+           "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_instance", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_conv3_pn_tail", "dc_conv3_pn_tail_ok", "dc_conv3_pn_tail_variant", "dc_conv3_pn_tail_ring_floats", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
            "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_attention_wide", "dc_attention_wide_variant", "dc_im2col_s2", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_err_map", "dc_evidence_maps", "dc_ddpm_step", "dc_ddpm_step_shared", "dc_solver_step", "dc_ddpm_noise_map", "dc_abs_diff_map", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_stage_maps_rows", "dc_stage_stop", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
            "dc_packed_bytes", "dc_pack_weights_matrix", "dc_pack_weights_conv3x3", "dc_pack_weights_up4", "dc_pack_weights_geglu",
            "dc_fold_layernorm_bias", "dc_workspace_bytes_groupnorm", "dc_workspace_bytes_igemm", "dc_workspace_bytes_attention",
@@ -286,6 +296,14 @@ def lib():
     L.dc_tblock_front_ok.restype = C.c_int32
     L.dc_pn_timeouts.argtypes = []
     L.dc_pn_timeouts.restype = C.c_int32
+    L.dc_conv3_pn_tail.argtypes = [C.POINTER(IgemmParams), C.POINTER(PnTailParams), vp]
+    L.dc_conv3_pn_tail.restype = i32
+    L.dc_conv3_pn_tail_ok.argtypes = [C.POINTER(IgemmParams), C.POINTER(PnTailParams)]
+    L.dc_conv3_pn_tail_ok.restype = i32
+    L.dc_conv3_pn_tail_variant.argtypes = [C.POINTER(IgemmParams), C.POINTER(PnTailParams)]
+    L.dc_conv3_pn_tail_variant.restype = C.c_char_p
+    L.dc_conv3_pn_tail_ring_floats.argtypes = [C.POINTER(IgemmParams), C.POINTER(PnTailParams)]
+    L.dc_conv3_pn_tail_ring_floats.restype = i64
     L.dc_igemm_side_ok.argtypes = [C.POINTER(IgemmParams)]
     L.dc_igemm_side_ok.restype = C.c_int32
     L.dc_igemm_variant.argtypes = [C.POINTER(IgemmParams)]

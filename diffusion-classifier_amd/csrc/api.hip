@@ -84,6 +84,11 @@ static int run_one(const dc_op* ops, int i, dc_stream s) {
       case DC_OP_EPS_MSE: rc = dc_eps_mse(static_cast<const dc_eps_mse_params*>(ops[i].params), s); break;
       case DC_OP_ERR_MAP: rc = dc_err_map(static_cast<const dc_err_map_params*>(ops[i].params), s); break;
       case DC_OP_ATTENTION_WIDE: rc = dc_attention_wide(static_cast<const dc_attention_wide_params*>(ops[i].params), s); break;
+      case DC_OP_CONV3_PN_TAIL: {
+        const dc_conv3_pn_tail_op* t = static_cast<const dc_conv3_pn_tail_op*>(ops[i].params);
+        rc = dc_conv3_pn_tail(t->conv, t->tail, s);
+        break;
+      }
       case DC_OP_IM2COL_S2: rc = dc_im2col_s2(static_cast<const dc_im2col_s2_params*>(ops[i].params), s); break;
       default: dc_set_error("dc_run_plan: op %d has unknown kind %d", i, ops[i].kind); return DC_ERR_ARG;
     }

@@ -101,3 +101,20 @@ template <int V> struct IC { static constexpr int value = V; };
 #define HALO_XDEPTH 3
 #endif
 
+// ---- tail fold of the producer-side GroupNorm epilogue (epi_pn.h): kernel argument and ring layout, shared with the host and with
+// the combine kernel (elementwise.hip)
+struct PnTail {            // kernel argument of the TAIL instance
+  const void* Wt;          // [32][128] in the compute type: row tap * Co + co, rows >= 9 Co zero
+  const float* bias;       // [Co] or null
+  float* pred;             // [n_img * H * W][pred_ld] fp32
+  float* ring;             // [n_img][tiles per image][PN_TAIL_RING(tw, th)][Co] fp32: a tile's sums for the pixels just outside it
+  int Co, pred_ld;
+};
+#define PN_TAIL_RING(tw, th) (2 * ((tw) + 2) + 2 * (th))
+// ring slot of the position (oy, ox) just outside a th x tw tile (oy = -1 | th, or ox = -1 | tw)
+__host__ __device__ __forceinline__ int pn_tail_ring_slot(int oy, int ox, int tw, int th) {
+  if (oy < 0) return ox + 1;
+  if (oy >= th) return tw + 2 + ox + 1;
+  return 2 * (tw + 2) + (ox < 0 ? 0 : th) + oy;
+}
+

@@ -71,8 +71,13 @@ DC_CLOCK_DECL(conv3_halo)
 // One accumulator gets one MFMA per step in both loops: results are bit-identical.
 // PN (one image per patch, 4 waves, 3x3): producer-side GroupNorm — the output is stored normalised for the GroupNorm that consumes it
 // (epi_pn.h).  The workgroups of one (sample, N tile) then sit on consecutive block indices (see there).
-template <typename T, int NW, int NTAP = 9, int MODE = 0, bool STG = false, bool PN = false>
-__global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs a, const HaloGeom g) {
+// TL (one PnTail, PN one-image-per-patch 3x3 form only): the TAIL instance — the thin 3x3 conv that is this tensor's only reader is
+// folded into the epilogue and the normalised tensor is never stored (epi_pn.h, tail fold).  An empty pack everywhere else: those
+// instances keep their arguments and their code.
+template <typename T, int NW, int NTAP = 9, int MODE = 0, bool STG = false, bool PN = false, typename... TL>
+__global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs a, const HaloGeom g, const TL... tl) {
+  constexpr bool TAIL = sizeof...(TL) == 1;
+  static_assert(sizeof...(TL) <= 1 && (!TAIL || (PN && NW == 4 && NTAP == 9 && MODE == 1 && sizeof(T) == 2)), "tail fold: the 16-bit 4-wave exchange form");
   // PN with NW = 4: images that span workgroups (statistics exchanged through memory, epi_pn.h).  PN with NW = 8 (8x8 images, staggered loop):
   // every image lies inside one wave, the statistics never leave it (igemm_epilogue.h, EpiPnLocal8x8).
   static_assert(!PN || (MODE == 1 && NW == 4 && !STG) || ((MODE == 0 || MODE == 2) && NW == 8 && STG && NTAP == 9), "producer-side GroupNorm: one-image-per-patch forms, or 8x8 / 4x4 images");
@@ -632,6 +637,13 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3_halo_kernel(const IgemmArgs 
     pc.scr = reinterpret_cast<float2*>(pc.tiles > 1 ? smem + wave * 4096 : smem + wn * 256);
     pc.flag = reinterpret_cast<int*>(brv + 384);
     pc.eps = a.pn_eps; pc.silu = a.pn_silu;
+    if constexpr (TAIL) {
+      PnTailCtx tc;
+      tc.p = [](const PnTail& p, auto...) { return p; }(tl...);
+      tc.zs = reinterpret_cast<float*>(smem);
+      tc.wm = wm; tc.ltw = g.ltw; tc.lth = g.lth; tc.tx = tx; tc.ty = ty; tc.tiles_x = g.tiles_x; tc.lpt = g.lpt; tc.H = g.H; tc.W = g.W;
+      epi_halo_pn<T>(a, acc, tile_n, wn, lq, rowfn, brv + wn * 64 + lq * 8, pc, tc);
+    } else
     epi_halo_pn<T>(a, acc, tile_n, wn, lq, rowfn, brv + wn * 64 + lq * 8, pc);
   } else if constexpr (STAGE_BRV) {
     epi_direct_act<T, TM, DC_ACT_NONE, false, true>(a, acc, tile_n, wn, lq, nw0, nw1, rowfn, EpiNoPre(), qsfn, HaloLdsBias{brv + wn * 64 + lq * 8});
@@ -958,6 +970,36 @@ int dc_conv3_halo_launch(const HaloPlan& pl, const IgemmArgs& a0, int dtype, boo
   if (!kern) { dc_set_error("conv3_halo: no instance <%d,%d,%d,%d,%d>", k.NW, k.NTAP, k.MODE, (int)k.STG, (int)k.PN); return DC_ERR_UNSUPPORTED; }
   hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(k.NW * 64), k.NW == 4 ? HaloCfg<4>::LDS : HaloCfg<8>::LDS, s, a, pl.g);
   return dc_check_launch("dc_igemm(conv3_halo)");
+}
+
+// Tail fold (epi_pn.h): the one extra instance per 16-bit dtype, conv3_halo_kernel<T, 4, 9, 1, false, true, PnTail>.  pl: a plan whose key
+// is that PN form (4 waves, 3x3, buffer-descriptor loaders); a: Cout = 128 — one N tile, so a workgroup holds every channel of its pixels
+template <typename T>
+static int launch_tail(const HaloPlan& pl, const IgemmArgs& a, const PnTail& tl, hipStream_t s) {
+  static bool attr_done = false;
+  void (*kern)(const IgemmArgs, const HaloGeom, const PnTail) = conv3_halo_kernel<T, 4, 9, 1, false, true, PnTail>;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, HaloCfg<4>::LDS);
+    attr_done = true;
+  }
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(256), HaloCfg<4>::LDS, s, a, pl.g, tl);
+  return dc_check_launch("dc_conv3_pn_tail(conv3_halo)");
+}
+
+static_assert(2 * 256 * PN_TAIL_ZLD * 4 <= 2 * HaloCfg<4>::XBUF + HaloCfg<4>::WR * HALO_WST, "tail fold: the z image must fit the halo buffers and the W ring");
+
+bool dc_conv3_halo_tail_ok(const IgemmArgs& a, const HaloPlan& pl, int dtype, int Co) {
+  const HaloKey& k = pl.key;
+  return pl.status == DC_OK && k.NW == 4 && k.NTAP == 9 && k.MODE == 1 && !k.STG && k.PN && (dtype == DC_BF16 || dtype == DC_F16) &&
+         a.Cout == 128 && a.tiles_n == 1 && Co >= 1 && 9 * Co <= 32 && Co <= 3 && !a.out;
+}
+
+int dc_conv3_halo_tail_launch(const HaloPlan& pl, const IgemmArgs& a0, int dtype, const PnTail& tl, hipStream_t s) {
+  if (pl.status != DC_OK) { dc_set_error("%s", pl.message); return pl.status; }
+  if (!dc_conv3_halo_tail_ok(a0, pl, dtype, tl.Co)) { dc_set_error("dc_conv3_pn_tail: no tail instance for this problem"); return DC_ERR_UNSUPPORTED; }
+  IgemmArgs a = a0;
+  a.tiles_m = pl.tiles_m;
+  return dtype == DC_BF16 ? launch_tail<__bf16>(pl, a, tl, s) : launch_tail<_Float16>(pl, a, tl, s);
 }
 
 // producer-side GroupNorm (epi_pn.h): the plan has a PN form for the problem (the 4-wave one-image-per-patch form, power-of-two images

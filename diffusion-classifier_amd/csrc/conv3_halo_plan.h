@@ -79,5 +79,12 @@ HaloPlan dc_conv3_halo_plan(const IgemmArgs& walked, int dtype, int n_img, bool 
 int dc_conv3_halo_launch(const HaloPlan& pl, const IgemmArgs& a, int dtype, bool up4, hipStream_t s);
 bool dc_conv3_halo_pn_ok(const IgemmArgs& a, const HaloPlan& pl, bool up4);   // producer-side GroupNorm possible (epi_pn.h)
 HaloPlan dc_conv3_thin_plan(const IgemmArgs& a, int n_img);
+// tail fold (epi_pn.h): the thin 3x3 conv of Co channels that is the only reader of a PN conv's normalised output, inside that conv.
+// a: the conv as dc_igemm filled it (no raw output), pl: its plan
+bool dc_conv3_halo_tail_ok(const IgemmArgs& a, const HaloPlan& pl, int dtype, int Co);
+int dc_conv3_halo_tail_launch(const HaloPlan& pl, const IgemmArgs& a, int dtype, const PnTail& tl, hipStream_t s);
+// elementwise.hip: the border sums of the tail fold (second, stream-ordered launch)
+int dc_pn_tail_combine_launch(float* pred, const float* ring, int n_img, int ltw, int lth, int tiles_x, int tiles_y, int H, int W, int Co, int ld,
+                              hipStream_t s);
 // conv3_ws.hip
 HaloPlan dc_conv3_ws_plan(const IgemmArgs& a, int n_img);

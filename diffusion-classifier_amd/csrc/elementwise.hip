@@ -598,3 +598,51 @@ extern "C" int dc_im2col_s2(const dc_im2col_s2_params* p, dc_stream stream) {
   }
   return dc_check_launch("dc_im2col_s2");
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Second launch of the tail fold (epi_pn.h): every tile of the last ResNet conv wrote the thin conv's sums of its OWN pixels (+ bias) into
+// pred and its sums for the positions just around it into its ring slots (conv3_halo.h).  A pixel on a tile's border also gets what the
+// (at most three) neighbouring tiles hold for it: added here in ascending tile index, one lane per (sample, tile, border pixel), so the
+// result is the same bits at every launch.  Stream order is the only synchronisation between the two kernels.
+#include "conv3_halo.h"
+__global__ __launch_bounds__(256) void pn_tail_combine_kernel(float* pred, const float* ring, int total, int ltw, int lth, int tiles_x, int tiles_y,
+                                                              int H, int W, int Co, int ld) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int tw = 1 << ltw, th = 1 << lth, tiles = tiles_x * tiles_y;
+  const int nb = 2 * tw + 2 * (th - 2);                     // border pixels of a tile: its first and last row, then the two outer columns between
+  const int b = idx % nb, rest = idx / nb, tile = rest % tiles, n = rest / tiles;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  int py, px;
+  if (b < 2 * tw) { py = b < tw ? 0 : th - 1; px = b & (tw - 1); }
+  else { const int c = b - 2 * tw; py = 1 + (c >> 1); px = (c & 1) ? tw - 1 : 0; }
+  const int gy = ty * th + py, gx = tx * tw + px;
+  float s[3] = {0.f, 0.f, 0.f};
+  float* o = pred + ((size_t)n * H * W + (size_t)gy * W + gx) * ld;
+  bool any = false;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      if (!dy && !dx) continue;
+      const int ny = ty + dy, nx = tx + dx;
+      if ((unsigned)ny >= (unsigned)tiles_y || (unsigned)nx >= (unsigned)tiles_x) continue;
+      // the pixel in the neighbour's coordinates: inside its one-pixel surround?
+      const int oy = gy - ny * th, ox = gx - nx * tw;
+      if (oy < -1 || oy > th || ox < -1 || ox > tw) continue;
+      const float* r = ring + (((size_t)n * tiles + ny * tiles_x + nx) * PN_TAIL_RING(tw, th) + pn_tail_ring_slot(oy, ox, tw, th)) * Co;
+      if (!any) { for (int co = 0; co < 3; ++co) if (co < Co) s[co] = o[co]; any = true; }
+      for (int co = 0; co < 3; ++co) if (co < Co) s[co] += r[co];
+    }
+  if (any)
+    for (int co = 0; co < 3; ++co) if (co < Co) o[co] = s[co];
+}
+
+int dc_pn_tail_combine_launch(float* pred, const float* ring, int n_img, int ltw, int lth, int tiles_x, int tiles_y, int H, int W, int Co, int ld,
+                              hipStream_t s) {
+  if (tiles_x * tiles_y == 1) return DC_OK;                 // a sample that is one tile has no neighbour: pred is final
+  const int tw = 1 << ltw, th = 1 << lth;
+  const long long total = (long long)n_img * tiles_x * tiles_y * (2 * tw + 2 * (th - 2));
+  if (total <= 0 || total > 0x7fffffffLL) { dc_set_error("dc_conv3_pn_tail: bad combine extent %lld", total); return DC_ERR_SHAPE; }
+  hipLaunchKernelGGL(pn_tail_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pred, ring, (int)total, ltw, lth, tiles_x, tiles_y,
+                     H, W, Co, ld);
+  return dc_check_launch("dc_conv3_pn_tail(combine)");
+}

@@ -32,6 +32,7 @@
 // whatever records are there — wrong numbers and an error, never a hang.
 #pragma once
 #include "igemm_epilogue.h"
+#include "conv3_halo.h"
 
 #ifndef PN_TIMEOUT_TICKS
 #define PN_TIMEOUT_TICKS 3000000ull          // 30 ms at 100 MHz; a real wait is the dispatch skew inside one group (microseconds)
@@ -53,6 +54,60 @@ struct PnCtx {
   float eps;
   int silu;
 };
+
+// Tail fold (TAIL instance of conv3_halo_kernel: the last ResNet conv of a UNet, Cout = 128 = ONE N tile, so the workgroup holds every
+// channel of its 256 pixels): instead of storing y = act(gn(v)) for a thin 3x3 conv (conv_out, Co <= 3) to read back, the epilogue
+// multiplies y by that conv's weights itself.  The chunk f_to_chunk makes of a lane's run of 8 channels IS the B fragment of the 16x16x32
+// MFMA (pixel lr, k = 8 lq + e), so z[tap * Co + co][pixel] = sum_c Wt[tap * Co + co][c] * y[pixel][c] is 32 MFMAs per wave on the very
+// bits the normalised store would have written; what is left of the 3x3 conv is a shift-and-add of z over the nine tap offsets
+// (pn_tail_finish).  Sums that need pixels of a neighbouring tile go to a ring buffer and are added by a second launch
+// (elementwise.hip, pn_tail_combine_kernel): no workgroup waits for another one here.
+#define PN_TAIL_ZLD 36     // floats per pixel of the z image in LDS (32 rows + 4: the 16-byte writes of 16 pixels cover all 64 banks)
+struct PnNoTail { static constexpr bool on = false; };
+struct PnTailCtx {
+  static constexpr bool on = true;
+  PnTail p;
+  float* zs;               // LDS: [2 channel halves][256 pixels][PN_TAIL_ZLD] — the halo buffers and the W ring, dead after the tap loop
+  int wm, ltw, lth, tx, ty, tiles_x, lpt, H, W;
+};
+// z (both channel halves, in LDS) -> the tile's (th + 2) x (tw + 2) partial sums of the thin conv, one position per lane and round: the two
+// halves are added first, then the nine taps in order.  Own pixels: + bias, straight into pred (final for every pixel whose 3x3
+// neighbourhood lies inside the tile); the positions around the tile: into the tile's ring slots; positions outside the image are
+// padding of the NORMALISED tensor and are dropped.
+__device__ __forceinline__ void pn_tail_finish(const PnTailCtx& t, int sample) {
+  const int tw = 1 << t.ltw, th = 1 << t.lth, hw = tw + 2, npos = (th + 2) * hw;
+  const int Co = t.p.Co;
+  const int tile = t.ty * t.tiles_x + t.tx;
+  for (int pos = threadIdx.x; pos < npos; pos += 256) {
+    const int hy = pos / hw, hx = pos - hy * hw;
+    const int oy = hy - 1, ox = hx - 1;
+    const int gy = (t.ty << t.lth) + oy, gx = (t.tx << t.ltw) + ox;
+    if ((unsigned)gy >= (unsigned)t.H || (unsigned)gx >= (unsigned)t.W) continue;
+    float s[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int py = oy + tap / 3 - 1, px = ox + tap % 3 - 1;
+      if ((unsigned)py < (unsigned)th && (unsigned)px < (unsigned)tw) {
+        const float* z0 = t.zs + ((py << t.ltw) + px) * PN_TAIL_ZLD + tap * Co;
+        const float* z1 = z0 + 256 * PN_TAIL_ZLD;
+#pragma unroll
+        for (int co = 0; co < 3; ++co)
+          if (co < Co) s[co] += z0[co] + z1[co];
+      }
+    }
+    if ((unsigned)oy < (unsigned)th && (unsigned)ox < (unsigned)tw) {
+      float* o = t.p.pred + ((size_t)sample * t.H * t.W + (size_t)gy * t.W + gx) * t.p.pred_ld;
+#pragma unroll
+      for (int co = 0; co < 3; ++co)
+        if (co < Co) o[co] = s[co] + (t.p.bias ? t.p.bias[co] : 0.f);
+    } else {
+      float* o = t.p.ring + ((((size_t)sample << t.lpt) + tile) * PN_TAIL_RING(tw, th) + pn_tail_ring_slot(oy, ox, tw, th)) * Co;
+#pragma unroll
+      for (int co = 0; co < 3; ++co)
+        if (co < Co) o[co] = s[co];
+    }
+  }
+}
 
 // Fold the records of one GroupNorm group — local quads [q0, q0 + qpg) of every part, in scr[part * 16 + quad] — with the 16 lanes of a
 // row sharing the parts (lane lr takes parts lr, lr + 16, ...): equal counts, means shifted by the first record's (gn_fold_rec's form:
@@ -84,9 +139,10 @@ __device__ __forceinline__ void pn_fold_row(const float2* scr, int parts, int q0
 }
 
 // acc[i][j]: cout fragment i, pixel fragment j of the wave (128 pixels x 64 couts); brv: bias (+ row vector) of the lane's run 0 in LDS
-template <typename T, typename RowFn>
+// tl: PnTailCtx — the tail fold above replaces the normalised store
+template <typename T, typename RowFn, typename TL = PnNoTail>
 __device__ __forceinline__ void epi_halo_pn(const IgemmArgs& a, f32x4 (&acc)[4][8], int tile_n, int wn, int lq, RowFn rowfn,
-                                            const float* brv, const PnCtx& c) {
+                                            const float* brv, const PnCtx& c, const TL& tl = TL()) {
   constexpr int TM = 8, NK = 2;
   constexpr bool res16 = sizeof(T) == 2;
   const int abl = DC_HALO_ABL();                             // 0 outside diagnostic builds (timing-only ablations: 16 no wait, 32 no SiLU)
@@ -284,6 +340,15 @@ __device__ __forceinline__ void epi_halo_pn(const IgemmArgs& a, f32x4 (&acc)[4][
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);                        // lgkmcnt(0): the wave's own LDS writes (its lanes read each other's records)
   __builtin_amdgcn_wave_barrier();
+  // tail fold: the lane's A fragments of Wt (rows 16 mf + lr, the 8 channels of its run k), from L2 while the statistics are folded
+  chunk16 wt[2][NK];
+  if constexpr (TL::on) {
+#pragma unroll
+    for (int mf = 0; mf < 2; ++mf)
+#pragma unroll
+      for (int k = 0; k < NK; ++k)
+        wt[mf][k] = *reinterpret_cast<const chunk16*>(reinterpret_cast<const T*>(tl.p.Wt) + (mf * 16 + lrp) * 128 + wn * 64 + 32 * k + lq * 8);
+  }
   float ga[NK][8], gb[NK][8];
   {
     const float nq = 512.0f;                                 // values per record: 128 pixels x 4 channels
@@ -316,6 +381,46 @@ __device__ __forceinline__ void epi_halo_pn(const IgemmArgs& a, f32x4 (&acc)[4][
     }
   }
   DC_STAMP(6);
+  if constexpr (TL::on) {
+    // ---- 4'. tail fold: y exactly as the normalised store rounds it, times Wt; j-major, so acc[.][j] dies as z[.][j] is born ----
+    f32x4 z[2][TM];
+    auto tail_mma = [&](auto actc) {
+      constexpr bool ACT = decltype(actc)::value;
+#pragma unroll
+      for (int j = 0; j < TM; ++j) {
+        chunk16 y[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+          float v[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float x = acc[2 * k + (e >> 2)][j][e & 3] * ga[k][e] + gb[k][e];
+            if (ACT) x = silu_t<T>(x);
+            v[e] = x;
+          }
+          y[k] = f_to_chunk<T>(v);
+        }
+#pragma unroll
+        for (int mf = 0; mf < 2; ++mf) {
+          z[mf][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int k = 0; k < NK; ++k) z[mf][j] = Mma<T>::run(wt[mf][k], y[k], z[mf][j]);
+        }
+      }
+    };
+    if (c.silu && !(abl & 32)) tail_mma(EpiIC<1>{});
+    else tail_mma(EpiIC<0>{});
+    __syncthreads();                                         // every wave has folded its records: the whole of LDS below the tables is free
+    // lane: rows 16 mf + 4 lq + r of pixel lr of fragment j
+#pragma unroll
+    for (int j = 0; j < TM; ++j)
+#pragma unroll
+      for (int mf = 0; mf < 2; ++mf)
+        *reinterpret_cast<f32x4*>(tl.zs + (wn * 256 + tl.wm * 128 + j * 16 + lrp) * PN_TAIL_ZLD + mf * 16 + 4 * lq) = z[mf][j];
+    __syncthreads();
+    pn_tail_finish(tl, c.sample);
+    return;
+  }
   // ---- 4. the normalised tensor (the raw one, if it has a reader, went out while the workgroup waited) ----
   // (the activation switch sits OUTSIDE the unrolled loops: a taken scalar branch per element costs ~20 cycles on this core)
   auto store_norm = [&](auto actc) {

@@ -445,6 +445,67 @@ extern "C" int32_t dc_igemm_pn_ok(const dc_igemm_params* p) {
 
 extern "C" int32_t dc_pn_timeouts(void) { return (int32_t)dc_conv3_halo_pn_timeouts(); }
 
+// ---- tail fold: the last ResNet conv + conv_norm_out + SiLU + conv_out as one op (epi_pn.h) ----------------------------------------
+// The conv goes the way of every dc_igemm call with pn_out — validate, choose — and must come out as the 4-wave exchange form of
+// conv3_halo; what the tail adds is checked here.  Probes (no launch) may leave pointers out: dummies stand in, as in the probes above.
+struct TailChoice { IgemmArgs a; IgemmChoice c; int status = DC_OK; const char* tag = nullptr; const char* message = nullptr; };
+
+static TailChoice tail_choose(const dc_igemm_params* conv, const dc_pn_tail_params* tail, bool probe) {
+  TailChoice t;
+  auto fail = [&](int st, const char* tag, const char* msg) -> TailChoice& { t.status = st; t.tag = tag; t.message = msg; return t; };
+  if (!conv || !tail) return fail(DC_ERR_ARG, "invalid", "dc_conv3_pn_tail: null params");
+  if (conv->out || conv->pn_out) return fail(DC_ERR_UNSUPPORTED, "tail-raw-output", "dc_conv3_pn_tail: the conv's own output (out / pn_out) is never stored; leave both null");
+  dc_igemm_params q = *conv;
+  q.pn_out = g_probe_dummy;                                   // never written: the TAIL instance has no normalised store
+  q.pn_gamma = tail->gamma; q.pn_beta = tail->beta; q.pn_cnt = tail->cnt;
+  q.pn_ld = 0; q.pn_groups = tail->groups; q.pn_silu = tail->silu; q.pn_eps = tail->eps;
+  if (probe) {
+    if (!q.qstats) q.qstats = g_probe_dummy;
+    if (!q.pn_gamma) q.pn_gamma = g_probe_dummy;
+    if (!q.pn_beta) q.pn_beta = g_probe_dummy;
+    if (!q.pn_cnt) q.pn_cnt = reinterpret_cast<uint32_t*>(g_probe_dummy);
+    if (!(q.pn_eps > 0.f)) q.pn_eps = 1e-5f;
+  } else if (!tail->Wt || !tail->pred || !tail->ring || ((uintptr_t)tail->Wt & 15) || (((uintptr_t)tail->pred | (uintptr_t)tail->ring | (uintptr_t)tail->bias) & 3)) {
+    return fail(DC_ERR_ARG, "invalid", "dc_conv3_pn_tail: Wt (16-byte aligned), pred and ring must be given");
+  }
+  if (q.pn_groups <= 0) return fail(DC_ERR_ARG, "invalid", "dc_conv3_pn_tail: groups");
+  if (igemm_validate_and_fill(&q, t.a) != DC_OK) return fail(DC_ERR_ARG, "invalid", nullptr);      // (the text is already in place)
+  t.c = igemm_choose(&q, t.a);
+  if (t.c.status != DC_OK) return fail(t.c.status, t.c.tag, t.c.message);
+  if (t.c.kernel != IG_HALO || !t.c.pn || !dc_conv3_halo_tail_ok(t.a, t.c.halo, q.dtype, tail->Co) || tail->pred_ld < tail->Co)
+    return fail(DC_ERR_UNSUPPORTED, "tail-unsupported",
+                "dc_conv3_pn_tail: needs a 16-bit 3x3 conv with Cout = 128 on the 4-wave producer-GroupNorm form and 1 <= Co <= 3 (see dc_conv3_pn_tail_ok)");
+  return t;
+}
+
+extern "C" int32_t dc_conv3_pn_tail_ok(const dc_igemm_params* conv, const dc_pn_tail_params* tail) {
+  return tail_choose(conv, tail, true).status == DC_OK ? 1 : 0;
+}
+
+extern "C" const char* dc_conv3_pn_tail_variant(const dc_igemm_params* conv, const dc_pn_tail_params* tail) {
+  const TailChoice t = tail_choose(conv, tail, true);
+  if (t.status != DC_OK) return t.tag;
+  return conv->dtype == DC_BF16 ? "conv3_halo<bf16,4w,pn,tail>" : "conv3_halo<f16,4w,pn,tail>";
+}
+
+extern "C" int64_t dc_conv3_pn_tail_ring_floats(const dc_igemm_params* conv, const dc_pn_tail_params* tail) {
+  const TailChoice t = tail_choose(conv, tail, true);
+  if (t.status != DC_OK) return 0;
+  const HaloGeom& g = t.c.halo.g;
+  return (long long)conv->n_img * g.tiles_x * g.tiles_y * PN_TAIL_RING(1 << g.ltw, 1 << g.lth) * tail->Co;
+}
+
+extern "C" int dc_conv3_pn_tail(const dc_igemm_params* conv, const dc_pn_tail_params* tail, dc_stream stream) {
+  const TailChoice t = tail_choose(conv, tail, false);
+  if (t.status != DC_OK) { if (t.message) dc_set_error("%s", t.message); return t.status; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const PnTail tl{tail->Wt, tail->bias, tail->pred, tail->ring, tail->Co, tail->pred_ld};
+  const int rc = dc_conv3_halo_tail_launch(t.c.halo, t.a, conv->dtype, tl, s);
+  if (rc != DC_OK) return rc;
+  const HaloGeom& g = t.c.halo.g;
+  return dc_pn_tail_combine_launch(tail->pred, tail->ring, conv->n_img, g.ltw, g.lth, g.tiles_x, g.tiles_y, g.H, g.W, tail->Co, tail->pred_ld, s);
+}
+
 extern "C" int32_t dc_igemm_up4_ok(const dc_igemm_params* p) {
   if (!p) return 0;
   dc_igemm_params q = *p;

@@ -220,6 +220,58 @@ class PlanBuilder:
         x.prod = None
         return y
 
+    def pn_tail(self, name, x, gamma, beta, groups, eps, silu, Wt, bias, Co):
+        """Tail fold (dc_conv3_pn_tail; csrc/epi_pn.h): ask the 3x3 conv that produced x to compute act(GroupNorm(x)) AND the bias-only
+        3x3 conv of Co <= 3 channels that is its only reader, so that neither x nor the normalised tensor is ever stored.  Wt: that
+        conv's weights as pack_tail lays them out.  Returns the fp32 prediction tensor, or None when the library does not serve the
+        pair (the caller then takes pn_claim / the fused loader / the GroupNorm pass).  x must be unread so far and stays unreadable."""
+        if x is None or x.prod is None or x.base is not x or self.pn_off:
+            return None
+        idx = x.prod
+        kind, cls, f = self.ops[idx]
+        b = x.base
+        if kind != L.OP_IGEMM or f.get("pn_out") is not None or f["Cout"] % groups or b.ext is not None or b.first != idx or b.last != idx:
+            return None
+        dom = x.dom
+        pred = self.tensor(name, dom, x.H, x.W, Co, L.DC_F32)
+        t = dict(tail_Wt=Wt, tail_bias=bias, tail_pred=pred, tail_Co=Co, tail_pred_ld=pred.ld,
+                 pn_gamma=gamma, pn_beta=beta, pn_groups=groups, pn_silu=int(silu), pn_eps=float(eps))
+        probe = dict(f, out=None, **t)
+        conv_p, tail_p = self._tail_structs(probe, lambda v: FAKE_PTR if isinstance(v, TRef) else v)
+        ring_floats = int(L.lib().dc_conv3_pn_tail_ring_floats(conv_p, tail_p))
+        if ring_floats <= 0 or not L.lib().dc_conv3_pn_tail_ok(conv_p, tail_p):
+            return None
+        # ring and arrival counters belong to this call site: never part of the (reused) arena
+        t["tail_ring"] = self.const(torch.zeros(ring_floats, dtype=torch.float32, device=self.dev))
+        t["pn_cnt"] = self.const(torch.zeros(self.n[dom], dtype=torch.int32, device=self.dev))
+        f.update(t, out=None)
+        self.ops[idx] = (L.OP_CONV3_PN_TAIL, L.Conv3PnTailOp, f)
+        pred.first = pred.last = idx
+        M = self.n[dom] * x.H * x.W
+        m = self.meta[idx]
+        m.update(kind=L.OP_CONV3_PN_TAIL, tail=True, pn=True)
+        # no store of the conv's own output; the folded conv's MACs, its prediction, the ring (written by the conv, read by the combine
+        # launch, which also re-reads and re-writes the border pixels: counted as twice the ring) and the packed weights
+        m["flops"] += 2.0 * M * x.C * 9 * Co
+        m["bytes"] += float(-M * x.C * DT_SIZE[x.dt] + M * Co * 4 + 2 * ring_floats * 4 + 32 * x.C * DT_SIZE[x.dt])
+        x.prod = None
+        return pred
+
+    @staticmethod
+    def _tail_structs(f, ptr):
+        """(dc_igemm_params, dc_pn_tail_params) of a DC_OP_CONV3_PN_TAIL op: the conv's pn_* fields travel in the tail struct."""
+        conv, tail = L.IgemmParams(), L.PnTailParams()
+        for name, ctype in L.IgemmParams._fields_:
+            if name in f and f[name] is not None and not name.startswith("pn_"):
+                setattr(conv, name, ptr(f[name]) if ctype is L.vp else f[name])
+        src = dict(Wt="tail_Wt", bias="tail_bias", pred="tail_pred", ring="tail_ring", gamma="pn_gamma", beta="pn_beta", cnt="pn_cnt",
+                   Co="tail_Co", pred_ld="tail_pred_ld", groups="pn_groups", silu="pn_silu", eps="pn_eps")
+        for name, ctype in L.PnTailParams._fields_:
+            v = f.get(src.get(name))
+            if v is not None:
+                setattr(tail, name, ptr(v) if ctype is L.vp else v)
+        return conv, tail
+
     def up4_ok(self, src0, Cout):
         """Can the upsample conv of src0 run as four 2x2-tap phases on the low-resolution image (dc_igemm_up4_ok)?"""
         H2, W2 = 2 * src0.H, 2 * src0.W
@@ -466,6 +518,14 @@ class PlanBuilder:
         self.structs = []
         arr = (L.Op * nops)()
         for i, (kind, cls, f) in enumerate(self.ops):
+            if kind == L.OP_CONV3_PN_TAIL:      # two structs behind one op record
+                conv, tail = self._tail_structs(f, ptr)
+                s = cls(C.pointer(conv), C.pointer(tail))
+                self.structs.append((s, conv, tail))
+                self.meta[i]["family"] = L.lib().dc_conv3_pn_tail_variant(conv, tail).decode()
+                arr[i].kind = kind
+                arr[i].params = C.cast(C.pointer(s), C.c_void_p)
+                continue
             s = cls()
             for name, ctype in cls._fields_:
                 if name not in f:
@@ -560,6 +620,17 @@ def pack_up4(w, dt, device, tile_n=128):
     cout, cin = wd.shape[0], wd.shape[1]
     out = _packed(L.lib().dc_igemm_cout_pad(cout, tile_n), 4 * cin, dt, device, lead=(4,))
     L.check(L.lib().dc_pack_weights_up4(wd.data_ptr(), cout, cin, out.data_ptr(), dt, tile_n, L.stream_ptr()), "dc_pack_weights_up4")
+    return out
+
+
+def pack_tail(w, dt, device):
+    """Conv2d weight [Co <= 3, 128, 3, 3] -> [32, 128] in dt, row (3 ky + kx) * Co + co, the other rows zero: the A operand of the tail
+    fold (dc_pn_tail_params.Wt).  Depends on the weights only."""
+    wd = _dev32(w, device)
+    co, cin = wd.shape[0], wd.shape[1]
+    assert 9 * co <= 32 and cin == 128 and tuple(wd.shape[2:]) == (3, 3), tuple(wd.shape)
+    out = torch.zeros(32, cin, dtype=TORCH_DT[dt], device=device)
+    out[:9 * co] = wd.permute(2, 3, 0, 1).reshape(9 * co, cin).to(TORCH_DT[dt])
     return out
 
 
@@ -846,6 +917,8 @@ class UNetPlan:
         # the attention half of a transformer block (proj_in ... to_out) as one launch where libdcamd serves the shape (tblock.hip)
         fuse_tb = os.environ.get("DCAMD_NO_TBLOCK") is None
         fold_po = os.environ.get("DCAMD_NO_PO_FOLD") is None
+        # conv_norm_out + SiLU + conv_out inside the last ResNet conv's epilogue (csrc/epi_pn.h, tail fold)
+        fold_tail = os.environ.get("DCAMD_NO_TAIL_FOLD") is None
         # GroupNorm(+SiLU) applied by the consuming 3x3 conv's loader waves (conv3_ws.hip) from the producer's quad records: no
         # GroupNorm launch, the normalised tensor never exists (DCAMD_NO_GN_WS: the GroupNorm pass + the plain conv, for A/B runs)
         fuse_ws = os.environ.get("DCAMD_NO_GN_WS") is None and use_qs
@@ -1108,8 +1181,17 @@ class UNetPlan:
                 else:
                     h = pb.igemm(key, h, pb.const(P[key + ".w"]), h.C, taps=9, upsample=1, bias=pb.const(P[key + ".b"]), qstats=use_qs)
         tn_out = 32 if cfg.out_channels <= 32 else 128
-        hn = pb.pn_claim(h, pb.const(P["conv_norm_out.g"]), pb.const(P["conv_norm_out.b"]), G, eps, True)
-        if hn is not None:      # the last ResNet's conv2 stored conv_norm_out + SiLU of its output: conv_out is a plain thin conv
+        pred = None
+        if fold_tail and cfg.out_channels <= 3 and h.C == 128 and dt != L.DC_F32:
+            # the last ResNet's conv2 normalises its output and multiplies it by conv_out's weights itself: no normalised tensor, no thin conv
+            if "conv_out.wt" not in P:
+                P["conv_out.wt"] = pack_tail(weights._sd["conv_out.weight"], weights.dt, weights.dev)
+            pred = pb.pn_tail("conv_out", h, pb.const(P["conv_norm_out.g"]), pb.const(P["conv_norm_out.b"]), G, eps, True,
+                              pb.const(P["conv_out.wt"]), pb.const(P["conv_out.b"]), cfg.out_channels)
+        hn = None if pred is not None else pb.pn_claim(h, pb.const(P["conv_norm_out.g"]), pb.const(P["conv_norm_out.b"]), G, eps, True)
+        if pred is not None:
+            pass
+        elif hn is not None:      # the last ResNet's conv2 stored conv_norm_out + SiLU of its output: conv_out is a plain thin conv
             pred = pb.igemm("conv_out", hn, pb.const(P["conv_out.w"]), cfg.out_channels, taps=9, bias=pb.const(P["conv_out.b"]),
                             out_dt=L.DC_F32, tile_n=tn_out)
         elif (fuse_gn_out and pb.qstats_ok(h, None, G, h.dom) and pb.gn_fusable(h, None, cfg.out_channels, tile_n=tn_out, out_dt=L.DC_F32)):

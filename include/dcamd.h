@@ -84,7 +84,9 @@ extern "C" {
  * (dc_solver_step and dc_solver_step_params — called directly — are additive within 5 likewise)
  * (dc_ddpm_noise_map and dc_ddpm_noise_map_params — called directly — likewise)
  * (the AutoencoderKL encoder's entries — dc_attention_wide, dc_attention_wide_variant, dc_im2col_s2, their structs and
- *  DC_OP_ATTENTION_WIDE / DC_OP_IM2COL_S2 — likewise) */
+ *  DC_OP_ATTENTION_WIDE / DC_OP_IM2COL_S2 — likewise)
+ * (dc_conv3_pn_tail, dc_conv3_pn_tail_ok, dc_conv3_pn_tail_variant, dc_conv3_pn_tail_ring_floats, dc_pn_tail_params, dc_conv3_pn_tail_op
+ *  and DC_OP_CONV3_PN_TAIL — likewise) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -225,6 +227,35 @@ int32_t dc_igemm_pn_ok(const dc_igemm_params* p);
 int32_t dc_pn_timeouts(void);
 /* 1 when dc_igemm can take up4 = 1 (four-phase upsample conv) for this problem. */
 int32_t dc_igemm_up4_ok(const dc_igemm_params* p);
+
+/* Tail fold: a 3x3 conv with a producer-side GroupNorm whose normalised output has ONE reader, a bias-only 3x3 stride-1 conv of at most
+ * 3 output channels (a UNet's last ResNet conv -> conv_norm_out -> SiLU -> conv_out), computes that reader itself:
+ *   pred[row, co] = bias[co] + sum over the 9 taps and 128 channels of Wt[tap * Co + co][c] * y[row + tap offset, c],
+ *   y = act(GroupNorm(v)) rounded to the compute type exactly as pn_out would have held it (zero outside the image),
+ * and neither v nor y is ever stored.  `conv` describes the producing conv as for dc_igemm with out = pn_out = NULL and its pn_* fields
+ * unused (qstats must be given: the workgroups of a sample exchange their records through it); the GroupNorm and the folded conv are
+ * described here.  Wt: the folded conv's weights in the compute type, [32][128], row tap * Co + co (tap = 3 ky + kx) over the 128 input
+ * channels, rows from 9 * Co on zero; packed once, it depends on the weights only.  pred: fp32, row stride pred_ld >= Co.  ring: fp32
+ * scratch of as many floats as the ring_floats query below returns (each tile's sums for the pixels just outside it; a second,
+ * stream-ordered launch inside the call adds them to the border pixels in ascending tile order, so results are bit-identical from
+ * call to call).  cnt: as dc_igemm_params.pn_cnt (n_img counters, zeroed once, owned by this call site).  Neither ring nor cnt may
+ * live in memory that other ops of the same stream reuse.  Served: 16-bit compute types, Cout = 128, 1 <= Co <= 3, whatever
+ * dc_igemm_pn_ok accepts for the conv on images of 16x16 ... 64x64; everything else keeps the separate thin conv.  Additive within
+ * version 5. */
+typedef struct {
+  const void* Wt; const float* bias; float* pred; float* ring;
+  const float* gamma; const float* beta; uint32_t* cnt;
+  int32_t Co, pred_ld, groups, silu; float eps; int32_t pad_;
+} dc_pn_tail_params;
+int dc_conv3_pn_tail(const dc_igemm_params* conv, const dc_pn_tail_params* tail, dc_stream s);
+/* 1 when dc_conv3_pn_tail serves this pair (pointers may be NULL: nothing is touched). */
+int32_t dc_conv3_pn_tail_ok(const dc_igemm_params* conv, const dc_pn_tail_params* tail);
+/* "conv3_halo<bf16,4w,pn,tail>" / "conv3_halo<f16,4w,pn,tail>", or the reason of the refusal (static string). */
+const char* dc_conv3_pn_tail_variant(const dc_igemm_params* conv, const dc_pn_tail_params* tail);
+/* Floats of `ring` for this pair (0: not served): n_img x tiles per image x (2 (tw + 2) + 2 th) x Co for th x tw tiles. */
+int64_t dc_conv3_pn_tail_ring_floats(const dc_igemm_params* conv, const dc_pn_tail_params* tail);
+/* what DC_OP_CONV3_PN_TAIL points to */
+typedef struct { const dc_igemm_params* conv; const dc_pn_tail_params* tail; } dc_conv3_pn_tail_op;
 
 /* ---------------------------------------------------------------- weight packing - */
 /* dc_igemm consumes weights as [Cout_pad][K] in the compute dtype, K contiguous, rows zero-padded to the N tile
@@ -718,7 +749,8 @@ typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GRO
                DC_OP_LAYERNORM = 5, DC_OP_ATTENTION = 6, DC_OP_EPS_MSE = 7, DC_OP_TBLOCK_FRONT = 8,
                DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10, DC_OP_ATTENTION_BIAS = 11, DC_OP_RMSNORM = 12,
                DC_OP_EMBED_ROWS = 13, DC_OP_RELU = 14, DC_OP_ATTENTION_CAUSAL = 15, DC_OP_LAYERNORM_ROWS = 16, DC_OP_EMBED_ROWS_POS = 17,
-               DC_OP_ACT_PASS = 18, DC_OP_ERR_MAP = 19, DC_OP_ATTENTION_WIDE = 20, DC_OP_IM2COL_S2 = 21 } dc_op_kind;
+               DC_OP_ACT_PASS = 18, DC_OP_ERR_MAP = 19, DC_OP_ATTENTION_WIDE = 20, DC_OP_IM2COL_S2 = 21,
+               DC_OP_CONV3_PN_TAIL = 22 /* params: dc_conv3_pn_tail_op */ } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */
