@@ -12,7 +12,7 @@ All arithmetic of the scoring path runs in `libdcamd.so` (HIP kernels + C-ABI, c
 from . import _lib  # noqa: F401
 from .nets.unet import UNetCondition2D, UNet2D  # noqa: F401
 from .nets.dit import DiT  # noqa: F401
-from .nets.vae import VAEEncoder  # noqa: F401
+from .nets.vae import VAEEncoder, VAEDecoder  # noqa: F401
 from .diffusion.diffusion_classifier import DiffusionClassifier  # noqa: F401
 from .utils.wavelet import wavelet_dec_2, wavelet_enc_2  # noqa: F401
 from .posterior import ClassPosterior  # noqa: F401
@@ -130,7 +130,7 @@ def ipmsa_experiment_unet_kwargs(image_channels=10, image_size=256, wavelet_tran
 
 
 def sd_vae_kwargs():
-    # the published Stable Diffusion AutoencoderKL (sd-vae-ft-mse / -ema, the `vae/` of SD 1.x): encoder side, 8x downsampling
+    # the published Stable Diffusion AutoencoderKL (sd-vae-ft-mse / -ema, the `vae/` of SD 1.x), 8x downsampling; VAEEncoder and VAEDecoder both take it
     return dict(in_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2, norm_num_groups=32,
                 scaling_factor=0.18215)
 

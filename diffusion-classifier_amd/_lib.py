@@ -25,6 +25,7 @@ EVIDENCE_FRAC_BITS, EVIDENCE_VMAX = 30, 16384.0      # include/dcamd.h DC_EVIDEN
 OP_ATTENTION_WIDE, OP_IM2COL_S2 = 20, 21
 ATTENTION_WIDE_DIMS = (256, 512)     # head widths of dc_attention_wide
 OP_CONV3_PN_TAIL = 22
+OP_LATENT_IM2COL = 23
 
 i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -93,6 +94,11 @@ class AttentionWideParams(C.Structure):
 
 class Im2colS2Params(C.Structure):
     _fields_ = [("x", vp), ("out", vp), ("dtype", i32), ("n", i32), ("H", i32), ("W", i32), ("C", i32), ("ld", i32)]
+
+
+class LatentIm2colParams(C.Structure):
+    _fields_ = [("z", vp), ("Q", vp), ("bias", vp), ("out", vp),
+                ("out_dtype", i32), ("n", i32), ("Z", i32), ("H", i32), ("W", i32), ("Kpad", i32), ("inv_scale", f32), ("shift", f32)]
 
 
 class CrossAttentionParams(C.Structure):
@@ -213,7 +219,7 @@ class Op(C.Structure):
 # every symbol include/dcamd.h declares (tests check that the library exports all of them)
 EXPORTS = ["dc_abi_version", "dc_last_error", "dc_arch", "dc_qsample", "dc_philox_normal", "dc_sinusoid",
            "dc_igemm", "dc_igemm_cout_pad", "dc_igemm_variant", "dc_igemm_instance", "dc_igemm_gn_fusable", "dc_igemm_side_ok", "dc_igemm_ln_ok", "dc_igemm_qstats_parts", "dc_igemm_up4_ok", "dc_igemm_pn_ok", "dc_pn_timeouts", "dc_conv3_pn_tail", "dc_conv3_pn_tail_ok", "dc_conv3_pn_tail_variant", "dc_conv3_pn_tail_ring_floats", "dc_groupnorm", "dc_groupnorm_variant", "dc_groupnorm_ws_floats", "dc_groupnorm_splits",
-           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_attention_wide", "dc_attention_wide_variant", "dc_im2col_s2", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_err_map", "dc_evidence_maps", "dc_ddpm_step", "dc_ddpm_step_shared", "dc_solver_step", "dc_ddpm_noise_map", "dc_abs_diff_map", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_stage_maps_rows", "dc_stage_stop", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
+           "dc_layernorm", "dc_layernorm_variant", "dc_attention", "dc_attention_variant", "dc_attention_wide", "dc_attention_wide_variant", "dc_im2col_s2", "dc_latent_im2col", "dc_cross_attention", "dc_cross_attention_variant", "dc_cross_attention_len", "dc_cross_attention_len_variant", "dc_attention_bias", "dc_attention_bias_variant", "dc_rmsnorm", "dc_embed_rows", "dc_relu", "dc_attention_causal", "dc_attention_causal_variant", "dc_layernorm_rows", "dc_embed_rows_pos", "dc_act_pass", "dc_tblock_front", "dc_tblock_front_ok", "dc_eps_mse", "dc_err_map", "dc_evidence_maps", "dc_ddpm_step", "dc_ddpm_step_shared", "dc_solver_step", "dc_ddpm_noise_map", "dc_abs_diff_map", "dc_haar_dwt2", "dc_haar_idwt2", "dc_stage_topk", "dc_reduce_argmin", "dc_stage_maps", "dc_stage_maps_rows", "dc_stage_stop", "dc_class_posterior", "dc_run_plan", "dc_run_plan_timed",
            "dc_packed_bytes", "dc_pack_weights_matrix", "dc_pack_weights_conv3x3", "dc_pack_weights_up4", "dc_pack_weights_geglu",
            "dc_fold_layernorm_bias", "dc_workspace_bytes_groupnorm", "dc_workspace_bytes_igemm", "dc_workspace_bytes_attention",
            "dc_workspace_bytes_layernorm"]
@@ -246,6 +252,7 @@ def lib():
                        ("dc_attention", [C.POINTER(AttentionParams), vp]),
                        ("dc_attention_wide", [C.POINTER(AttentionWideParams), vp]),
                        ("dc_im2col_s2", [C.POINTER(Im2colS2Params), vp]),
+                       ("dc_latent_im2col", [C.POINTER(LatentIm2colParams), vp]),
                        ("dc_cross_attention", [C.POINTER(CrossAttentionParams), vp]),
                        ("dc_cross_attention_len", [C.POINTER(CrossAttentionLenParams), vp]),
                        ("dc_attention_bias", [C.POINTER(AttentionBiasParams), vp]),

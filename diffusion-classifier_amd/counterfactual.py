@@ -28,7 +28,7 @@ from .trajectory import image_chunks      # noqa: F401  (its home is the walk; i
 
 Counterfactuals = namedtuple("Counterfactuals", ["samples", "classes", "maps"])
 Counterfactuals.__doc__ = """Result of `DiffusionClassifier.counterfactual` (tensors on the input's device).
-samples [BS, K, C, H, W] f32 (pixel_space: [BS, K, C / 4, 2H, 2W]), classes [BS, K] int64 (the label of every trajectory),
+samples [BS, K, C, H, W] f32 (pixel_space: [BS, K, C / 4, 2H, 2W]; decode: [BS, K, out_channels, f H, f W], images), classes [BS, K] int64 (the label of every trajectory),
 maps [BS, K, H', W'] f32 (the channel-summed absolute difference to the base image, at the resolution of `samples`)."""
 
 
@@ -128,8 +128,9 @@ def decode_hip(dc, walk, z0, lams, noise):
 
 
 @torch.no_grad()
-def run(dc, x, classes, from_t, against, rng, seed, pixel_space, start="noise", invert_class=None):
+def run(dc, x, classes, from_t, against, rng, seed, pixel_space, start="noise", invert_class=None, decode=False):
     """`DiffusionClassifier.counterfactual` (its docstring is the interface)."""
+    TJ.check_decode(dc, decode, pixel_space)
     sampler = S.sampler_of(dc.config)
     if start not in ("noise", "invert", "ddpm_invert"):
         raise ValueError(f"start must be 'noise', 'invert' or 'ddpm_invert', got {start!r}")
@@ -180,6 +181,11 @@ def run(dc, x, classes, from_t, against, rng, seed, pixel_space, start="noise", 
         # models trained on wavelet_dec_2(image) / 2: back to the image, as the reference's plotters do before they look at a sample
         from .utils.wavelet import wavelet_enc_2
         flat, xb = wavelet_enc_2(flat * 2), wavelet_enc_2(xb * 2)
+    if decode:
+        # latents -> images (config.vae_path); against="input": the base is the VAE's own reconstruction of x, so the map holds the
+        # label's effect and no reconstruction error
+        flat = dc.decode_latents(flat)
+        xb = dc.decode_latents(xb) if base is None else xb
     r, r_of_a = (xb, torch.arange(BS).repeat_interleave(K)) if base is None else (flat, base)
     maps = abs_diff_map_hip(flat, r, r_of_a) if hip else abs_diff_map_torch(flat, r, r_of_a)
     return Counterfactuals(flat.view((BS, K) + tuple(flat.shape[1:])), cl.to(x.device), maps.view((BS, K) + tuple(maps.shape[1:])))

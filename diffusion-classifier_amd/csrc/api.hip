@@ -90,6 +90,7 @@ static int run_one(const dc_op* ops, int i, dc_stream s) {
         break;
       }
       case DC_OP_IM2COL_S2: rc = dc_im2col_s2(static_cast<const dc_im2col_s2_params*>(ops[i].params), s); break;
+      case DC_OP_LATENT_IM2COL: rc = dc_latent_im2col(static_cast<const dc_latent_im2col_params*>(ops[i].params), s); break;
       default: dc_set_error("dc_run_plan: op %d has unknown kind %d", i, ops[i].kind); return DC_ERR_ARG;
     }
     if (rc != DC_OK) {

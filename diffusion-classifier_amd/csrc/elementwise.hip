@@ -599,6 +599,73 @@ extern "C" int dc_im2col_s2(const dc_im2col_s2_params* p, dc_stream stream) {
   return dc_check_launch("dc_im2col_s2");
 }
 
+// ------------------------------------------------------------------ latent im2col ----
+// The head of the AutoencoderKL decoder (include/dcamd.h dc_latent_im2col): per pixel u = Q (z inv_scale + shift) + bias in fp32, channels
+// ascending and no contraction, written as the 3x3 patches of u in dc_qsample's im2col column order (tap * Z + c), zero for taps outside
+// the image and for the columns [9 Z, Kpad).  One lane per 16-byte chunk of the output, consecutive lanes on consecutive chunks; z is read
+// inside the image only.  Kpad is a multiple of the K granule, so every row is whole chunks and every store is 16 bytes.
+struct LatentArgs {
+  const float* z; const float* Q; const float* bias; void* out;
+  int n, Z, H, W, Kpad;
+  float inv_scale, shift;
+};
+
+template <typename TO>
+__global__ __launch_bounds__(256) void latent_im2col_kernel(const LatentArgs a) {
+#pragma clang fp contract(off)
+  constexpr int EPC = Elem<TO>::EPC;
+  const int cpr = a.Kpad / EPC;
+  const int HW = a.H * a.W;
+  const long long total = (long long)a.n * HW * cpr;
+  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const int ch = (int)(idx % cpr);
+    const long long row = idx / cpr;
+    const int p = (int)(row % HW);
+    const long long i = row / HW;
+    const int y = p / a.W, xw = p - y * a.W;
+    const float* zi = a.z + (size_t)i * a.Z * HW;
+    float f[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+      const int k = ch * EPC + e;
+      float v = 0.f;
+      if (k < 9 * a.Z) {
+        const int tap = k / a.Z, c = k - tap * a.Z;
+        const int iy = y + tap / 3 - 1, ix = xw + tap % 3 - 1;
+        if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) {
+          const float* zp = zi + (size_t)iy * a.W + ix;
+          const float* q = a.Q + (size_t)c * a.Z;
+          float s = 0.f;
+          for (int j = 0; j < a.Z; ++j) s += q[j] * (zp[(size_t)j * HW] * a.inv_scale + a.shift);
+          v = s + a.bias[c];
+        }
+      }
+      f[e] = v;
+    }
+    reinterpret_cast<chunk16*>(a.out)[idx] = f_to_chunk<TO>(f);
+  }
+}
+
+extern "C" int dc_latent_im2col(const dc_latent_im2col_params* p, dc_stream stream) {
+  DC_REQUIRE(p && p->z && p->Q && p->bias && p->out, DC_ERR_ARG, "dc_latent_im2col: null pointer");
+  DC_REQUIRE(p->out_dtype == DC_F32 || p->out_dtype == DC_BF16 || p->out_dtype == DC_F16, DC_ERR_DTYPE, "dc_latent_im2col: out_dtype %d", p->out_dtype);
+  DC_REQUIRE(p->n > 0 && p->Z >= 1 && p->H > 0 && p->W > 0, DC_ERR_SHAPE, "dc_latent_im2col: extents n=%d Z=%d H=%d W=%d", p->n, p->Z, p->H, p->W);
+  const int granule = 128 / dc_dtype_size(p->out_dtype);      // the K granule of dc_igemm: one 128-byte LDS row
+  DC_REQUIRE(p->Z <= 0x7fffffff / 9 && p->Kpad >= 9 * p->Z && p->Kpad % granule == 0, DC_ERR_SHAPE,
+             "dc_latent_im2col: Kpad=%d (need >= 9 Z = %lld, a multiple of %d)", p->Kpad, 9LL * p->Z, granule);
+  DC_REQUIRE((((uintptr_t)p->z | (uintptr_t)p->Q | (uintptr_t)p->bias) & 3) == 0 && ((uintptr_t)p->out & 15) == 0, DC_ERR_ALIGN,
+             "dc_latent_im2col: z / Q / bias must be 4-byte aligned, out 16-byte aligned");
+  LatentArgs a{p->z, p->Q, p->bias, p->out, p->n, p->Z, p->H, p->W, p->Kpad, p->inv_scale, p->shift};
+  const int epc = 16 / dc_dtype_size(p->out_dtype);
+  const long long total = (long long)p->n * p->H * p->W * (p->Kpad / epc);
+  const unsigned grid = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return dc_by_dtype(p->out_dtype, "dc_latent_im2col: out_dtype", [&](auto t) {
+    hipLaunchKernelGGL((latent_im2col_kernel<decltype(t)>), dim3(grid), dim3(256), 0, s, a);
+    return dc_check_launch("dc_latent_im2col");
+  });
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Second launch of the tail fold (epi_pn.h): every tile of the last ResNet conv wrote the thin conv's sums of its OWN pixels (+ bias) into
 // pred and its sums for the positions just around it into its ring slots (conv3_halo.h).  A pixel on a tile's border also gets what the

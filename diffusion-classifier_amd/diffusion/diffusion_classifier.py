@@ -18,7 +18,9 @@ shards the (trial, image) grid of ONE replicated batch over the default process 
 `simulate_rank` ((r, N), bench.py only: time rank r's share of an N-rank sharded call on one GPU),
 `stop_margin_z` (opt-in per-image early stopping, see below; None: off, none of its code runs),
 `vae_path` (a LOCAL diffusers AutoencoderKL directory: `classify` encodes images to latents on the device first, nets/vae.py;
-`vae_dtype` its compute dtype, default the backbone's; `encode_latents(x)`; `classify(..., latents=True)` takes latents as they are).
+`vae_dtype` its compute dtype, default the backbone's; `encode_latents(x)`; `classify(..., latents=True)` takes latents as they are;
+`decode_latents(z)` is the way back through the same directory's decoder, loaded at its first call, at most `vae_decode_batch` (default 8)
+images per launch plan; `sample(..., decode=True)` and `counterfactual(..., decode=True)` return images instead of latents).
 
 What differs is HOW classify runs: the (image, trial, class) grid is flattened into micro-batches of work units, one native call each,
 with the stage ends on the device — scoring.py (`_HipRunner`; a foreign `nn.Module` backbone takes `_ForeignRunner`, eager torch).
@@ -246,6 +248,7 @@ class DiffusionClassifier(nn.Module):
             zc, ic = self.vae.config.latent_channels, getattr(backbone.config, "in_channels", None)
             if ic != zc:
                 raise ValueError(f"backbone.config.in_channels = {ic} but the VAE under {self.config.vae_path} has latent_channels = {zc}")
+        object.__setattr__(self, "_vae_decoder", None)      # decode_latents loads it; never a submodule: state_dict stays as it is
         self._score_plans = {}
         self._timed_sink = None      # bench.py: list collecting (plan, per-op event ms) instead of plain runs
 
@@ -327,6 +330,35 @@ class DiffusionClassifier(nn.Module):
         if self.vae is None:
             raise RuntimeError("encode_latents needs config.vae_path: a LOCAL diffusers AutoencoderKL directory")
         return self.vae(x.to(device=self.vae.encoder.conv_in.weight.device, dtype=torch.float32))
+
+    @torch.no_grad()
+    def decode_latents(self, z):
+        """config.vae_path set: latents [B, latent_channels, h, w] as `encode_latents` returns them (scaled) -> images
+        [B, out_channels, f h, f w] fp32, `AutoencoderKL.decode(z / scaling_factor + shift_factor).sample`, unclamped, on the VAE's device
+        (nets/vae.py VAEDecoder: all of it in libdcamd).  The decoder is read from config.vae_path at the first call, at config.vae_dtype
+        (a directory that holds the encoder only is refused then, by the first key it lacks); at most config.vae_decode_batch (additive,
+        default 8) images go through one launch plan, plans are kept per chunk size.  fp16 is known to overflow in published VAE
+        decoders (upstream's `force_upcast`): prefer bf16, the default, or f32."""
+        if self.vae is None:
+            raise RuntimeError("decode_latents needs config.vae_path: a LOCAL diffusers AutoencoderKL directory")
+        dev = self.vae.encoder.conv_in.weight.device
+        dec = self._vae_decoder
+        if dec is None:
+            from ..nets.vae import VAEDecoder
+            dec = VAEDecoder.from_directory(self.config.vae_path)
+            object.__setattr__(self, "_vae_decoder", dec)
+        if dec.compute_dtype != self.vae.compute_dtype:        # follows the encoder's at every call (plans are kept per dtype)
+            dec.set_compute_dtype(self.vae.compute_dtype)
+        if dec.decoder.conv_in.weight.device != dev:
+            dec.to(dev)
+        step = self.config.vae_decode_batch
+        step = 8 if step is None else int(step)
+        if step < 1:
+            raise ValueError(f"config.vae_decode_batch must be an int >= 1, got {self.config.vae_decode_batch!r}")
+        z = z.to(device=dev, dtype=torch.float32)
+        dec.check_latent_shape(z.shape)
+        out = [dec(z[i:i + step].contiguous()) for i in range(0, z.shape[0], step)]
+        return out[0] if len(out) == 1 else torch.cat(out, 0)
 
     # ---- the hot path ---------------------------------------------------------------------
     @torch.no_grad()
@@ -604,12 +636,19 @@ class DiffusionClassifier(nn.Module):
         return out
 
     @torch.no_grad()
-    def sample(self, x, text=None, from_t=1):
+    def sample(self, x, text=None, from_t=1, decode=False):
         """Ancestral DDPM sampling with classifier-free guidance (reference :210-293), same RNG consumption order as the reference.
-        config.sampler = "ddim" | "dpmpp_2m" (additive; unset or "ddpm": everything below, untouched): the start is drawn as ever, then
+        config.sampler = "ddim" | "dpmpp_2m" (additive; unset or "ddpm": the ancestral loop, untouched): the start is drawn as ever, then
         sampling_steps deterministic passes on linspace(from_t, 0, sampling_steps + 1) (solver.py) — only the initial draw is taken
         from torch's generator.
-        With config.vae_path, x and the result are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
+        With config.vae_path, x and the result are LATENTS (`encode_latents`), unless decode=True (additive; ValueError without
+        config.vae_path): the result is then `decode_latents` of those latents, images [BS, out_channels, f H, f W]."""
+        TJ.check_decode(self, decode)
+        z = self._sample_latents(x, text, from_t)
+        return self.decode_latents(z) if decode else z
+
+    def _sample_latents(self, x, text, from_t):
+        """`sample` before any decoding: the solver's loop under a deterministic config.sampler, else the ancestral loop below."""
         sampler = S.sampler_of(self.config)
         if sampler is not None:
             return S.sample(self, x, text, from_t, sampler)
@@ -632,7 +671,7 @@ class DiffusionClassifier(nn.Module):
 
     @torch.no_grad()
     def counterfactual(self, x, classes=None, from_t=0.5, *, against="input", rng="reference", seed=0, pixel_space=False,
-                       start="noise", invert_class=None):
+                       start="noise", invert_class=None, decode=False):
         """Every class from shared noise in one call (reference experiments/ipmsa/explain.py: noise to `from_t`, denoise once per label
         with the seed reset in front of each run, look at where the results differ) -> `Counterfactuals(samples, classes, maps)`.
           classes      None: all config.classes; an int tensor [K] (the same for every image) or [BS, K]; K >= 1, duplicates allowed
@@ -669,8 +708,12 @@ class DiffusionClassifier(nn.Module):
         error, at any sampling_steps and cfg_w), so that class's sample is the last pass applied to the image's own x_n and its map
         holds no solver error; another class's map is the label's effect.  rng / seed govern the inversion's n + 1 draws; the decode
         draws nothing.  Costs one more backbone pass per step and the maps' memory (config.ddpm_invert_max_bytes)
-        With config.vae_path, x, the samples and the maps are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
-        return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class)
+        With config.vae_path, x, the samples and the maps are LATENTS (`encode_latents`), unless
+          decode       True (config.vae_path only; ValueError without it or together with pixel_space): samples are the decoded images
+                       [BS, K, out_channels, f H, f W] (`decode_latents`) and maps [BS, K, f H, f W] are taken on them by
+                       `dc_abs_diff_map`; against="input": the base is `decode_latents(x)`, the VAE's own reconstruction, so the map
+                       holds no reconstruction error; class ids: the base is that class's decoded trajectory.  False: nothing changes"""
+        return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class, decode=decode)
 
     @torch.no_grad()
     def invert(self, x, text=None, to_t=0.5, *, guidance=0.0):
@@ -682,7 +725,7 @@ class DiffusionClassifier(nn.Module):
                     inversion is known to be unstable
         Works whatever config.sampler says (always DDIM).  HIP backbones run a pair session per chunk of images and one `dc_solver_step`
         per step and chunk; a foreign nn.Module takes the eager form (solver.py).
-        With config.vae_path, x and the result are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
+        With config.vae_path, x and the result are LATENTS (`encode_latents` / `decode_latents`)."""
         return S.invert(self, x, text, to_t, guidance)
 
     @torch.no_grad()
@@ -704,7 +747,7 @@ class DiffusionClassifier(nn.Module):
         Every refusal comes before the first draw.  HIP backbones run a pair session per chunk of images (classify's launch-size rule)
         and one `dc_ddpm_noise_map` per pass and chunk, nothing is copied to the host inside the loop; a foreign nn.Module takes the
         eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`.
-        With config.vae_path, x, start and noise are LATENTS (`encode_latents`): the VAE decoder is not part of this library."""
+        With config.vae_path, x, start and noise are LATENTS (`encode_latents` / `decode_latents`)."""
         return DI.invert(self, x, text, from_t, guidance, rng, seed)
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----

@@ -1,4 +1,4 @@
-"""AutoencoderKL encoder as ONE launch plan for libdcamd — see engine.py for the plan model.
+"""AutoencoderKL encoder and decoder, each as ONE launch plan for libdcamd — see engine.py for the plan model.
 
 Restated: the encoder half of diffusers' `AutoencoderKL` (0.31 layout) and the mean of its posterior, scaled:
     conv_in -> per level [layers_per_block x ResNet, then (all but the last level) pad (0, 1, 0, 1) + 3x3 stride-2 conv]
@@ -18,13 +18,24 @@ What runs where:
   tail             quant_conv's mean rows, scaling_factor and shift_factor are folded into conv_out on the host in fp64 (fold_tail): the
                    plan's last conv writes latent_channels fp32 channels and nothing of the log-variance half is computed
 The residual stream is in the compute dtype, as in the UNet plan.
+
+The decoder half (`VaeDecoderWeights`, `VaeDecoderPlan`), `AutoencoderKL.decode(z / scaling_factor + shift_factor).sample`:
+    post_quant_conv -> conv_in -> mid block [ResNet, attention, ResNet]
+            -> per level [(layers_per_block + 1) x ResNet, then (all but the last level) nearest 2x + 3x3 conv] -> GroupNorm + SiLU -> conv_out
+  head             dc_latent_im2col: u = Q (z / scaling_factor + shift_factor) + b per pixel in fp32 (Q, b: post_quant_conv), written as the
+                   3x3 patches conv_in reads, then a 1x1 dc_igemm over Kpad.  No host fold: a biased 1x1 conv in front of a zero-padded
+                   3x3 conv is not a 3x3 conv at the border, and folding Q / s into 16-bit weights rounds products the reference never rounds
+  ResNet, attention  the encoder's builders (resnet_ops, attention_ops)
+  upsampler        dc_igemm upsample = 1: the four-phase form (pack_up4, up4) where dc_igemm_up4_ok says so, else the plain upsample route
+  tail             dc_groupnorm (+ SiLU) -> dc_igemm taps = 9 with an fp32 output, on the 32-wide tile when out_channels <= 32
+The producer-side GroupNorm hand-off, the fused GroupNorm prologue and the tail fold are not claimed here either.
 """
 import os
 
 import torch
 
 from . import _lib as L
-from .engine import DT_SIZE, PlanBuilder, bke, f32c, pack_conv3x3, pack_matrix, round_up
+from .engine import DT_SIZE, PlanBuilder, bke, f32c, pack_conv3x3, pack_matrix, pack_up4, round_up
 
 GN_EPS = 1e-6
 MID_WIDTHS = (64, 128) + L.ATTENTION_WIDE_DIMS      # dc_attention / dc_attention_wide, and a multiple of the GEMMs' K granule
@@ -51,6 +62,37 @@ def pack_down(w, dt, device):
     return pack_matrix(w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1), dt, device)
 
 
+class _Packer:
+    """The packing steps the two halves share: fills P with the packed form of the state-dict entries of a 3x3 conv, a GroupNorm, a ResNet
+    and the mid block's attention under the plans' key names."""
+
+    def __init__(self, sd, dt, device):
+        self.sd, self.dt, self.dev, self.P = sd, dt, device, {}
+
+    def conv3(self, key, **kw):
+        self.P[key + ".w"] = pack_conv3x3(self.sd[key + ".weight"], self.dt, self.dev, **kw)
+        self.P[key + ".b"] = f32c(self.sd[key + ".bias"], self.dev)
+
+    def norm(self, key):
+        self.P[key + ".g"], self.P[key + ".b"] = f32c(self.sd[key + ".weight"], self.dev), f32c(self.sd[key + ".bias"], self.dev)
+
+    def resnet(self, key):
+        sd, P = self.sd, self.P
+        self.norm(key + ".norm1"); self.conv3(key + ".conv1"); self.norm(key + ".norm2"); self.conv3(key + ".conv2")
+        if key + ".conv_shortcut.weight" in sd:
+            P[key + ".conv_shortcut.w"] = pack_matrix(sd[key + ".conv_shortcut.weight"], self.dt, self.dev)
+            P[key + ".conv_shortcut.b"] = f32c(sd[key + ".conv_shortcut.bias"], self.dev)
+
+    def attention(self, a):
+        sd, P = self.sd, self.P
+        self.norm(a + "group_norm")
+        # q | k | v as one [3 C, C] GEMM with the stacked bias
+        P[a + "qkv.w"] = pack_matrix(torch.cat([sd[a + f"to_{n}.weight"] for n in "qkv"], 0), self.dt, self.dev)
+        P[a + "qkv.b"] = f32c(torch.cat([sd[a + f"to_{n}.bias"] for n in "qkv"], 0), self.dev)
+        P[a + "to_out.0.w"] = pack_matrix(sd[a + "to_out.0.weight"], self.dt, self.dev)
+        P[a + "to_out.0.b"] = f32c(sd[a + "to_out.0.bias"], self.dev)
+
+
 class VaeWeights:
     """Device-resident packed weights of a VAEEncoder for one compute dtype."""
 
@@ -59,40 +101,21 @@ class VaeWeights:
         cfg = model.config
         sd = model.state_dict()
         self.kin = round_up(9 * cfg.in_channels, bke(dt))
-        P = {}
-
-        def conv3(key, **kw):
-            P[key + ".w"] = pack_conv3x3(sd[key + ".weight"], dt, device, **kw)
-            P[key + ".b"] = f32c(sd[key + ".bias"], device)
-
-        def norm(key):
-            P[key + ".g"], P[key + ".b"] = f32c(sd[key + ".weight"], device), f32c(sd[key + ".bias"], device)
-
-        def resnet(key):
-            norm(key + ".norm1"); conv3(key + ".conv1"); norm(key + ".norm2"); conv3(key + ".conv2")
-            if key + ".conv_shortcut.weight" in sd:
-                P[key + ".conv_shortcut.w"] = pack_matrix(sd[key + ".conv_shortcut.weight"], dt, device)
-                P[key + ".conv_shortcut.b"] = f32c(sd[key + ".conv_shortcut.bias"], device)
-
-        conv3("encoder.conv_in", kpad=self.kin)
+        pk = _Packer(sd, dt, device)
+        P = pk.P
+        pk.conv3("encoder.conv_in", kpad=self.kin)
         nb = len(cfg.block_out_channels)
         for i in range(nb):
             for j in range(cfg.layers_per_block):
-                resnet(f"encoder.down_blocks.{i}.resnets.{j}")
+                pk.resnet(f"encoder.down_blocks.{i}.resnets.{j}")
             if i != nb - 1:
                 key = f"encoder.down_blocks.{i}.downsamplers.0.conv"
                 P[key + ".w"] = pack_down(sd[key + ".weight"], dt, device)
                 P[key + ".b"] = f32c(sd[key + ".bias"], device)
-        resnet("encoder.mid_block.resnets.0")
-        resnet("encoder.mid_block.resnets.1")
-        a = "encoder.mid_block.attentions.0."
-        norm(a + "group_norm")
-        # q | k | v as one [3 C, C] GEMM with the stacked bias
-        P[a + "qkv.w"] = pack_matrix(torch.cat([sd[a + f"to_{n}.weight"] for n in "qkv"], 0), dt, device)
-        P[a + "qkv.b"] = f32c(torch.cat([sd[a + f"to_{n}.bias"] for n in "qkv"], 0), device)
-        P[a + "to_out.0.w"] = pack_matrix(sd[a + "to_out.0.weight"], dt, device)
-        P[a + "to_out.0.b"] = f32c(sd[a + "to_out.0.bias"], device)
-        norm("encoder.conv_norm_out")
+        pk.resnet("encoder.mid_block.resnets.0")
+        pk.resnet("encoder.mid_block.resnets.1")
+        pk.attention("encoder.mid_block.attentions.0.")
+        pk.norm("encoder.conv_norm_out")
         qc = cfg.use_quant_conv
         w, b = fold_tail(sd["encoder.conv_out.weight"], sd["encoder.conv_out.bias"], sd["quant_conv.weight"] if qc else None,
                          sd["quant_conv.bias"] if qc else None, cfg.latent_channels, cfg.scaling_factor, cfg.shift_factor)
@@ -100,6 +123,49 @@ class VaeWeights:
         P["tail.w"] = pack_conv3x3(w.float(), dt, device, tile_n=self.tail_tile_n)
         P["tail.b"] = f32c(b.float(), device)
         self.P = P
+
+
+# ---- the op builders the two plans share: P holds the packed weights under the keys _Packer writes, G the GroupNorm group count -----------
+def gn_ops(pb, P, G, name, x, key, silu):
+    return pb.groupnorm(name, x, pb.const(P[key + ".g"]), pb.const(P[key + ".b"]), G, GN_EPS, silu)
+
+
+def resnet_ops(pb, P, G, use_qs, key, x):
+    Cout = P[key + ".conv1.b"].shape[0]
+    h = gn_ops(pb, P, G, key + ".gn1", x, key + ".norm1", True)
+    h = pb.igemm(key + ".conv1", h, pb.const(P[key + ".conv1.w"]), Cout, taps=9, bias=pb.const(P[key + ".conv1.b"]), qstats=use_qs)
+    h = gn_ops(pb, P, G, key + ".gn2", h, key + ".norm2", True)
+    sc = x
+    if key + ".conv_shortcut.w" in P:
+        sc = pb.igemm(key + ".short", x, pb.const(P[key + ".conv_shortcut.w"]), Cout, bias=pb.const(P[key + ".conv_shortcut.b"]))
+    return pb.igemm(key + ".conv2", h, pb.const(P[key + ".conv2.w"]), Cout, taps=9, bias=pb.const(P[key + ".conv2.b"]),
+                    residual=sc, qstats=use_qs)
+
+
+def attention_ops(pb, P, G, key, x):
+    """One head as wide as the level over the H W tokens, with the residual: dc_attention up to 128 channels, dc_attention_wide above."""
+    Cc, Lq, B, dt = x.C, x.H * x.W, pb.n[x.dom], x.dt
+    es = DT_SIZE[dt]
+    hn = gn_ops(pb, P, G, key + "gn", x, key + "group_norm", False)
+    qkv = pb.igemm(key + "qkv", hn, pb.const(P[key + "qkv.w"]), 3 * Cc, bias=pb.const(P[key + "qkv.b"]))
+    q, k, v = qkv.view(0, Cc), qkv.view(Cc, Cc), qkv.view(2 * Cc, Cc)
+    if Cc <= 128:
+        o = pb.attention(key + "attn", q, k, v, 1, Cc)
+    else:
+        o = pb.tensor(key + "attn", "bj", x.H, x.W, Cc, dt)
+        pb._emit(L.OP_ATTENTION_WIDE, L.AttentionWideParams,
+                 dict(q=q, k=k, v=v, out=o, dtype=dt, n=B, L=Lq, heads=1, d=Cc, ld_qkv=qkv.ld, ld_out=o.ld, scale=float(Cc) ** -0.5),
+                 [q, k, v], [o], dict(name=key + "attn", family="attention_wide", flops=4.0 * B * Lq * Lq * Cc, bytes=4.0 * B * Lq * Cc * es))
+    return pb.igemm(key + "to_out", o, pb.const(P[key + "to_out.0.w"]), Cc, bias=pb.const(P[key + "to_out.0.b"]), residual=x)
+
+
+def check_served(pb, who, what):
+    """Names dc_attention_wide's variant and raises DcamdError for the first op the library refuses."""
+    for i, (kd, _, _) in enumerate(pb.ops):
+        if kd == L.OP_ATTENTION_WIDE:
+            pb.meta[i]["variant"] = L.lib().dc_attention_wide_variant(pb.structs[i]).decode()
+        if pb.meta[i].get("variant") == "invalid" or pb.meta[i]["family"] == "invalid":
+            raise L.DcamdError(f"{who}: libdcamd refuses {pb.meta[i]['name']} at {what}")
 
 
 class VaePlan:
@@ -123,18 +189,10 @@ class VaePlan:
         es = DT_SIZE[dt]
 
         def gn(name, x, key, silu):
-            return pb.groupnorm(name, x, pb.const(P[key + ".g"]), pb.const(P[key + ".b"]), G, GN_EPS, silu)
+            return gn_ops(pb, P, G, name, x, key, silu)
 
         def resnet(key, x):
-            Cout = P[key + ".conv1.b"].shape[0]
-            h = gn(key + ".gn1", x, key + ".norm1", True)
-            h = pb.igemm(key + ".conv1", h, pb.const(P[key + ".conv1.w"]), Cout, taps=9, bias=pb.const(P[key + ".conv1.b"]), qstats=use_qs)
-            h = gn(key + ".gn2", h, key + ".norm2", True)
-            sc = x
-            if key + ".conv_shortcut.w" in P:
-                sc = pb.igemm(key + ".short", x, pb.const(P[key + ".conv_shortcut.w"]), Cout, bias=pb.const(P[key + ".conv_shortcut.b"]))
-            return pb.igemm(key + ".conv2", h, pb.const(P[key + ".conv2.w"]), Cout, taps=9, bias=pb.const(P[key + ".conv2.b"]),
-                            residual=sc, qstats=use_qs)
+            return resnet_ops(pb, P, G, use_qs, key, x)
 
         def downsample(key, x):
             col = pb.tensor(key + ".col", "bj", x.H // 2, x.W // 2, 9 * x.C, dt)
@@ -143,18 +201,7 @@ class VaePlan:
             return pb.igemm(key, col, pb.const(P[key + ".w"]), x.C, bias=pb.const(P[key + ".b"]))
 
         def attention(key, x):
-            Cc, Lq = x.C, x.H * x.W
-            hn = gn(key + "gn", x, key + "group_norm", False)
-            qkv = pb.igemm(key + "qkv", hn, pb.const(P[key + "qkv.w"]), 3 * Cc, bias=pb.const(P[key + "qkv.b"]))
-            q, k, v = qkv.view(0, Cc), qkv.view(Cc, Cc), qkv.view(2 * Cc, Cc)
-            if Cc <= 128:
-                o = pb.attention(key + "attn", q, k, v, 1, Cc)
-            else:
-                o = pb.tensor(key + "attn", "bj", x.H, x.W, Cc, dt)
-                pb._emit(L.OP_ATTENTION_WIDE, L.AttentionWideParams,
-                         dict(q=q, k=k, v=v, out=o, dtype=dt, n=B, L=Lq, heads=1, d=Cc, ld_qkv=qkv.ld, ld_out=o.ld, scale=float(Cc) ** -0.5),
-                         [q, k, v], [o], dict(name=key + "attn", family="attention_wide", flops=4.0 * B * Lq * Lq * Cc, bytes=4.0 * B * Lq * Cc * es))
-            return pb.igemm(key + "to_out", o, pb.const(P[key + "to_out.0.w"]), Cc, bias=pb.const(P[key + "to_out.0.b"]), residual=x)
+            return attention_ops(pb, P, G, key, x)
 
         h = pb.igemm("encoder.conv_in", a0, pb.const(P["encoder.conv_in.w"]), boc[0], bias=pb.const(P["encoder.conv_in.b"]),
                      k_real=9 * cfg.in_channels)
@@ -170,11 +217,92 @@ class VaePlan:
         self.out = pb.igemm("encoder.conv_out", h, pb.const(P["tail.w"]), cfg.latent_channels, taps=9, bias=pb.const(P["tail.b"]),
                             out_dt=L.DC_F32, tile_n=weights.tail_tile_n)
         pb.finalize(keep_alive=[self.out])
-        for i, (kd, _, _) in enumerate(pb.ops):
-            if kd == L.OP_ATTENTION_WIDE:
-                pb.meta[i]["variant"] = L.lib().dc_attention_wide_variant(pb.structs[i]).decode()
-            if pb.meta[i].get("variant") == "invalid" or pb.meta[i]["family"] == "invalid":
-                raise L.DcamdError(f"VaePlan: libdcamd refuses {pb.meta[i]['name']} at {B} x {H} x {W} in {model.compute_dtype}")
+        check_served(pb, "VaePlan", f"{B} x {H} x {W} in {model.compute_dtype}")
+
+    def run(self):
+        self.pb.run()
+
+    def run_timed(self):
+        return self.pb.run_timed()
+
+    def out_view(self):
+        return self.pb.tensor_view(self.out)
+
+
+class VaeDecoderWeights:
+    """Device-resident packed weights of a VAEDecoder for one compute dtype."""
+
+    def __init__(self, model, dt, device):
+        self.dt, self.dev = dt, device
+        cfg = model.config
+        sd = self._sd = model.state_dict()
+        Z = cfg.latent_channels
+        self.kin = round_up(9 * Z, bke(dt))
+        pk = _Packer(sd, dt, device)
+        P = pk.P
+        # post_quant_conv stays fp32: dc_latent_im2col applies it (the identity and zeros when the VAE has none)
+        if cfg.use_post_quant_conv:
+            P["head.Q"], P["head.b"] = f32c(sd["post_quant_conv.weight"].reshape(Z, Z), device), f32c(sd["post_quant_conv.bias"], device)
+        else:
+            P["head.Q"], P["head.b"] = torch.eye(Z, dtype=torch.float32, device=device), torch.zeros(Z, dtype=torch.float32, device=device)
+        pk.conv3("decoder.conv_in", kpad=self.kin)
+        pk.resnet("decoder.mid_block.resnets.0")
+        pk.resnet("decoder.mid_block.resnets.1")
+        pk.attention("decoder.mid_block.attentions.0.")
+        nb = len(cfg.block_out_channels)
+        for i in range(nb):
+            for j in range(cfg.layers_per_block + 1):
+                pk.resnet(f"decoder.up_blocks.{i}.resnets.{j}")
+            if i != nb - 1:
+                pk.conv3(f"decoder.up_blocks.{i}.upsamplers.0.conv")        # the four-phase form is packed when a plan takes it
+        pk.norm("decoder.conv_norm_out")
+        self.tail_tile_n = 32 if cfg.out_channels <= 32 else 128
+        pk.conv3("decoder.conv_out", tile_n=self.tail_tile_n)
+        self.P = P
+
+
+class VaeDecoderPlan:
+    """input: z [B, latent_channels, h, w] fp32, scaled latents (a device buffer of the plan: copy into it, then run()).
+    output: images [B, f h, f w, out_channels] fp32 NHWC (out_view), f = 2^(levels - 1)."""
+
+    def __init__(self, model, weights, B, h, w):
+        cfg = model.config
+        dev, dt, P = weights.dev, weights.dt, weights.P
+        boc, G, Z = cfg.block_out_channels, cfg.norm_num_groups, cfg.latent_channels
+        use_qs = os.environ.get("DCAMD_NO_QSTATS") is None
+        use_up4 = os.environ.get("DCAMD_NO_UP4") is None
+        self.B, self.h, self.w, self.dt = B, h, w, dt
+        pb = self.pb = PlanBuilder(dev, B, 1, 1)
+        self.z = torch.zeros(B, Z, h, w, dtype=torch.float32, device=dev)
+        zt = pb.external("z", self.z, "bj", 1, 1, 1, L.DC_F32)
+        es = DT_SIZE[dt]
+        a0 = pb.tensor("a0", "bj", h, w, weights.kin, dt)
+        pb._emit(L.OP_LATENT_IM2COL, L.LatentIm2colParams,
+                 dict(z=zt, Q=pb.const(P["head.Q"]), bias=pb.const(P["head.b"]), out=a0, out_dtype=dt, n=B, Z=Z, H=h, W=w, Kpad=weights.kin,
+                      inv_scale=1.0 / cfg.scaling_factor, shift=float(cfg.shift_factor or 0.0)), [zt], [a0],
+                 dict(name="a0", family="latent_im2col", flops=2.0 * B * h * w * 9 * Z * Z, bytes=float(B * h * w * (Z * 4 + weights.kin * es))))
+        rev = boc[::-1]
+        x = pb.igemm("decoder.conv_in", a0, pb.const(P["decoder.conv_in.w"]), rev[0], bias=pb.const(P["decoder.conv_in.b"]), k_real=9 * Z)
+        x = resnet_ops(pb, P, G, use_qs, "decoder.mid_block.resnets.0", x)
+        x = attention_ops(pb, P, G, "decoder.mid_block.attentions.0.", x)
+        x = resnet_ops(pb, P, G, use_qs, "decoder.mid_block.resnets.1", x)
+        for i in range(len(boc)):
+            for j in range(cfg.layers_per_block + 1):
+                x = resnet_ops(pb, P, G, use_qs, f"decoder.up_blocks.{i}.resnets.{j}", x)
+            if i != len(boc) - 1:
+                key = f"decoder.up_blocks.{i}.upsamplers.0.conv"
+                if use_up4 and pb.up4_ok(x, x.C):
+                    # nearest-2x upsample + 3x3 conv == four 2x2-tap convs of the low-resolution tensor (phase-summed weights): 4/9 of the MACs
+                    if key + ".w4" not in P:
+                        P[key + ".w4"] = pack_up4(weights._sd[key + ".weight"], dt, dev)
+                    x = pb.igemm(key, x, pb.const(P[key + ".w4"]), x.C, taps=9, upsample=1, bias=pb.const(P[key + ".b"]), qstats=use_qs, up4=True)
+                else:
+                    x = pb.igemm(key, x, pb.const(P[key + ".w"]), x.C, taps=9, upsample=1, bias=pb.const(P[key + ".b"]), qstats=use_qs)
+        x = gn_ops(pb, P, G, "decoder.conv_norm_out", x, "decoder.conv_norm_out", True)
+        self.out = pb.igemm("decoder.conv_out", x, pb.const(P["decoder.conv_out.w"]), cfg.out_channels, taps=9,
+                            bias=pb.const(P["decoder.conv_out.b"]), out_dt=L.DC_F32, tile_n=weights.tail_tile_n)
+        pb.finalize(keep_alive=[self.out])
+        check_served(pb, "VaeDecoderPlan", f"{B} x {h} x {w} latents in {model.compute_dtype}")
 
     def run(self):
         self.pb.run()

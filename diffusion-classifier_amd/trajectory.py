@@ -45,6 +45,17 @@ def check_entry(dc, x, t, name, purpose, rng="reference"):
     return t, hip
 
 
+def check_decode(dc, decode, pixel_space=False):
+    """The refusals of `decode=True` (sample / counterfactual), before the first draw: it needs config.vae_path, and the wavelet form of
+    `pixel_space` belongs to models trained on wavelet coefficients, not on VAE latents."""
+    if not decode:
+        return
+    if dc.vae is None:
+        raise ValueError("decode=True needs config.vae_path: a LOCAL diffusers AutoencoderKL directory whose decoder turns the latents into images")
+    if pixel_space:
+        raise ValueError("decode=True cannot be combined with pixel_space=True: a model on VAE latents is not one on wavelet coefficients")
+
+
 def initial_latent(dc, x, from_t, noise=None):
     """`sample`'s start: randn for from_t == 1, else diffuse(x) to from_t — one draw from torch's generator, or draw 0 of a Philox
     `NoiseSource` (cloned out of its buffer when it is the start itself)."""

@@ -29,6 +29,9 @@
  *                       nothing in the reference: the encoder half of diffusers' AutoencoderKL in front of a latent-space backbone
  *                       (config key vae_path) — its mid-block attention over one head of 256 / 512 channels, and the A operand of its
  *                       bottom/right-padded stride-2 downsampling conv; every other layer of the encoder is dc_igemm / dc_groupnorm
+ *   dc_latent_im2col    nothing in the reference: the decoder half of the same AutoencoderKL (decode_latents, sample / counterfactual with
+ *                       decode=True) — post_quant_conv and the un-scaling of the latents in fp32, written as the A operand of the
+ *                       decoder's conv_in; every other layer of the decoder is dc_igemm / dc_groupnorm / dc_attention(_wide)
  *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
@@ -86,7 +89,8 @@ extern "C" {
  * (the AutoencoderKL encoder's entries — dc_attention_wide, dc_attention_wide_variant, dc_im2col_s2, their structs and
  *  DC_OP_ATTENTION_WIDE / DC_OP_IM2COL_S2 — likewise)
  * (dc_conv3_pn_tail, dc_conv3_pn_tail_ok, dc_conv3_pn_tail_variant, dc_conv3_pn_tail_ring_floats, dc_pn_tail_params, dc_conv3_pn_tail_op
- *  and DC_OP_CONV3_PN_TAIL — likewise) */
+ *  and DC_OP_CONV3_PN_TAIL — likewise)
+ * (the AutoencoderKL decoder's head — dc_latent_im2col, dc_latent_im2col_params and DC_OP_LATENT_IM2COL — likewise) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -370,6 +374,23 @@ const char* dc_attention_wide_variant(const dc_attention_wide_params* p);
  * are multiples of 16 bytes, element moves otherwise. */
 typedef struct { const void* x; void* out; int32_t dtype, n, H, W, C, ld; } dc_im2col_s2_params;
 int dc_im2col_s2(const dc_im2col_s2_params* p, dc_stream s);
+
+/* ---------------------------------------------------------------- latent im2col    */
+/* The head of the AutoencoderKL decoder, one pass from the scaled latents to the A operand of decoder.conv_in as a GEMM.  Per pixel
+ *   u[i, :, y, x] = Q (z[i, :, y, x] * inv_scale + shift) + bias        fp32, channels ascending, no contraction
+ * (Q, bias: post_quant_conv; the identity and zeros for a VAE without one), then
+ *   out[i, y, x, tap*Z + c] = u[i, c, y + tap/3 - 1, x + tap%3 - 1]     in out_dtype, tap = 0..8
+ * with exact zeros for taps outside the image and for the columns [9 Z, Kpad): the column order of dc_qsample's im2col = 1, so
+ * dc_pack_weights_conv3x3(..., kpad = Kpad) serves conv_in.  A 1x1 conv with a bias in front of a zero-padded 3x3 conv is not a 3x3
+ * conv (the padded taps carry no bias), hence a kernel and no weight fold; the operand is rounded to out_dtype once.
+ * z [n, Z, H, W] f32 NCHW, Q [Z, Z] f32 row-major, bias [Z] f32, out [n, H, W, Kpad] dense, 16-byte aligned.  Kpad >= 9 Z and a
+ * multiple of dc_igemm's K granule (32 for DC_F32, 64 for the 16-bit types), else DC_ERR_SHAPE.  16-byte stores, no atomics; the rows
+ * of sample i depend on sample i only. */
+typedef struct {
+  const float* z; const float* Q; const float* bias; void* out;
+  int32_t out_dtype, n, Z, H, W, Kpad; float inv_scale, shift;
+} dc_latent_im2col_params;
+int dc_latent_im2col(const dc_latent_im2col_params* p, dc_stream s);
 
 /* ---------------------------------------------------------------- cross-attention */
 /* out[i] = softmax(q[q_map[i]] k[kv_map[i]]^T * scale) v[kv_map[i]] per head, for i < n: attention whose keys and values come from
@@ -750,7 +771,7 @@ typedef enum { DC_OP_QSAMPLE = 1, DC_OP_SINUSOID = 2, DC_OP_IGEMM = 3, DC_OP_GRO
                DC_OP_CROSS_ATTENTION = 9, DC_OP_CROSS_ATTENTION_LEN = 10, DC_OP_ATTENTION_BIAS = 11, DC_OP_RMSNORM = 12,
                DC_OP_EMBED_ROWS = 13, DC_OP_RELU = 14, DC_OP_ATTENTION_CAUSAL = 15, DC_OP_LAYERNORM_ROWS = 16, DC_OP_EMBED_ROWS_POS = 17,
                DC_OP_ACT_PASS = 18, DC_OP_ERR_MAP = 19, DC_OP_ATTENTION_WIDE = 20, DC_OP_IM2COL_S2 = 21,
-               DC_OP_CONV3_PN_TAIL = 22 /* params: dc_conv3_pn_tail_op */ } dc_op_kind;
+               DC_OP_CONV3_PN_TAIL = 22 /* params: dc_conv3_pn_tail_op */, DC_OP_LATENT_IM2COL = 23 } dc_op_kind;
 typedef struct { int32_t kind; int32_t pad_; const void* params; } dc_op;
 /* Launch ops[0..n) in order on the stream; stops at the first failure and returns its
  * status (failed index via dc_last_error text). */
