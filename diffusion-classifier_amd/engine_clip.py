@@ -1,4 +1,4 @@
-"""CLIP text transformer as ONE launch plan for libdcamd — see engine.py for the plan model and engine_t5.py for the sibling encoder.
+"""CLIP text transformer as ONE launch plan for libdcamd — see plan.py for the plan model and engine_t5.py for the sibling encoder.
 
 Restated: transformers' `CLIPTextModel.last_hidden_state`: token + position embedding -> per layer [LayerNorm -> q | k | v (with bias)
 -> softmax(q k^T d^-1/2 over keys k <= q) v -> out_proj + bias + residual; LayerNorm -> fc1 + bias -> quick-GELU or erf-GELU -> fc2 +
@@ -9,7 +9,8 @@ which rows are computed (dc_attention_causal's / dc_layernorm_rows' row_len) and
 import torch
 
 from . import _lib as L
-from .engine import PlanBuilder, f32c, pack_matrix
+from .packing import f32c, pack_matrix
+from .plan import Plan, PlanBuilder
 
 MAX_LENGTH = L.ATTENTION_CAUSAL_MAX_L
 HEAD_DIMS = (16, 32, 64, 128)            # dc_attention_causal
@@ -42,7 +43,7 @@ class ClipWeights:
         self.P = P
 
 
-class ClipPlan:
+class ClipPlan(Plan):
     """inputs: ids [B, L] int64 and lens [B] int32 (device buffers of the plan: copy into them, then run()).
     output: out [B, L, hidden] fp32, rows at or past a prompt's length zero.  8 * layers + 2 ops."""
 
@@ -63,54 +64,45 @@ class ClipPlan:
 
         def layernorm(name, x, g, b, out_dt):
             y = pb.tensor(name, "bj", 1, Lq, D, out_dt)
-            pb._emit(L.OP_LAYERNORM_ROWS, L.LayernormRowsParams,
-                     dict(x=x, y=y, gamma=pb.const(g), beta=pb.const(b), row_len=lens, dtype=x.dt, out_dtype=out_dt, rows=rows, C=D,
-                          rows_per_sample=Lq, eps=eps),
-                     [x], [y], dict(name=name, family="layernorm_rows", flops=0.0, bytes=float(rows * D * (4 + (4 if out_dt == L.DC_F32 else 2)))))
+            pb.emit(L.OP_LAYERNORM_ROWS, L.LayernormRowsParams,
+                    dict(x=x, y=y, gamma=pb.const(g), beta=pb.const(b), row_len=lens, dtype=x.dt, out_dtype=out_dt, rows=rows, C=D,
+                         rows_per_sample=Lq, eps=eps),
+                    [x], [y], dict(name=name, family="layernorm_rows", flops=0.0, bytes=float(rows * D * (4 + (4 if out_dt == L.DC_F32 else 2)))))
             return y
 
         def gemm(name, x, w, b, cout, **kw):
             y = pb.igemm(name, x, pb.const(P[w]), cout, bias=pb.const(P[b]), **kw)
-            v = L.lib().dc_igemm_variant(pb._probe(**pb.ops[-1][2])).decode()
+            v = L.lib().dc_igemm_variant(pb.probe(**pb.ops[-1][2])).decode()
             if v == "invalid":
                 raise L.DcamdError(f"ClipPlan: dc_igemm refuses {name} ({rows} x {x.C} -> {cout})")
             pb.meta[-1]["variant"] = v
             return y
 
         h = pb.tensor("embed", "bj", 1, Lq, D, L.DC_F32)
-        pb._emit(L.OP_EMBED_ROWS_POS, L.EmbedRowsPosParams,
-                 dict(table=pb.const(P["tok"]), pos=pb.const(P["pos"]), ids=ids, out=h, out_dtype=L.DC_F32, rows=rows, C=D,
-                      vocab=cfg.vocab_size, L=Lq),
-                 [], [h], dict(name="embed", family="embed_rows_pos", flops=0.0, bytes=12.0 * rows * D))
+        pb.emit(L.OP_EMBED_ROWS_POS, L.EmbedRowsPosParams,
+                dict(table=pb.const(P["tok"]), pos=pb.const(P["pos"]), ids=ids, out=h, out_dtype=L.DC_F32, rows=rows, C=D,
+                     vocab=cfg.vocab_size, L=Lq),
+                [], [h], dict(name="embed", family="embed_rows_pos", flops=0.0, bytes=12.0 * rows * D))
         for i in range(cfg.num_hidden_layers):
             k = f"{PREFIX}encoder.layers.{i}."
             hn = layernorm(k + "ln1", h, P[k + "layer_norm1.g"], P[k + "layer_norm1.b"], dt)
             qkv = gemm(k + "qkv", hn, k + "qkv.w", k + "qkv.b", 3 * D)
             o = pb.tensor(k + "attn", "bj", 1, Lq, D, dt)
             q, kk, v = qkv.view(0, D), qkv.view(D, D), qkv.view(2 * D, D)
-            pb._emit(L.OP_ATTENTION_CAUSAL, L.AttentionCausalParams,
-                     dict(q=q, k=kk, v=v, out=o, row_len=lens, dtype=dt, n=B, L=Lq, heads=heads, d=dh, ld_qkv=qkv.ld, ld_out=o.ld,
-                          scale=float(dh) ** -0.5),
-                     [q, kk, v], [o], dict(name=k + "attn", family="attention_causal", flops=2.0 * B * heads * Lq * (Lq + 1) * dh,
-                                           bytes=4.0 * rows * D * es))
+            pb.emit(L.OP_ATTENTION_CAUSAL, L.AttentionCausalParams,
+                    dict(q=q, k=kk, v=v, out=o, row_len=lens, dtype=dt, n=B, L=Lq, heads=heads, d=dh, ld_qkv=qkv.ld, ld_out=o.ld,
+                         scale=float(dh) ** -0.5),
+                    [q, kk, v], [o], dict(name=k + "attn", family="attention_causal", flops=2.0 * B * heads * Lq * (Lq + 1) * dh,
+                                          bytes=4.0 * rows * D * es))
             # fp32 residual stream: the GEMM reads the old stream as its residual and writes a new one (never in place)
             h = gemm(k + "out", o, k + "out.w", k + "out.b", D, residual=h, out_dt=L.DC_F32)
             hn = layernorm(k + "ln2", h, P[k + "layer_norm2.g"], P[k + "layer_norm2.b"], dt)
             ff = gemm(k + "fc1", hn, k + "fc1.w", k + "fc1.b", dff)
-            pb._emit(L.OP_ACT_PASS, L.ActPassParams, dict(x=ff, n=rows * dff, dtype=dt, kind=kind), [ff], [ff],
-                     dict(name=k + "act", family="act_pass", flops=0.0, bytes=2.0 * rows * dff * es))
+            pb.emit(L.OP_ACT_PASS, L.ActPassParams, dict(x=ff, n=rows * dff, dtype=dt, kind=kind), [ff], [ff],
+                    dict(name=k + "act", family="act_pass", flops=0.0, bytes=2.0 * rows * dff * es))
             h = gemm(k + "fc2", ff, k + "fc2.w", k + "fc2.b", D, residual=h, out_dt=L.DC_F32)
         self.out = layernorm("final.ln", h, P["final.g"], P["final.b"], L.DC_F32)
         pb.finalize(keep_alive=[self.out])
-        for i, (kd, _, _) in enumerate(pb.ops):
-            if kd == L.OP_ATTENTION_CAUSAL:
-                pb.meta[i]["variant"] = L.lib().dc_attention_causal_variant(pb.structs[i]).decode()
-
-    def run(self):
-        self.pb.run()
-
-    def run_timed(self):
-        return self.pb.run_timed()
 
     def out_view(self):
-        return self.pb.tensor_view(self.out).view(self.B, self.L, -1)
+        return super().out_view().view(self.B, self.L, -1)

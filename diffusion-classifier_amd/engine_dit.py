@@ -1,4 +1,4 @@
-"""DiT (adaLN-Zero transformer) scoring plan for libdcamd — see engine.py for the plan model.
+"""DiT (adaLN-Zero transformer) scoring plan for libdcamd — see plan.py for the plan model.
 
 Backbone restated: diffusers 0.31.0 `DiTTransformer2DModel` behind reference nets/dit.py:8-51
 (instance: models/chexpert-256-dit-b4.py).  Class conditioning enters every block through
@@ -8,7 +8,8 @@ the per-class part of the conditioning is a table row added in a GEMM epilogue.
 import torch
 
 from . import _lib as L
-from .engine import PlanBuilder, TORCH_DT, bke, f32c, pack_matrix, pad_head_cols, pad_head_rows, padded_head_dim, round_up
+from .packing import f32c, pack_matrix, pad_head_cols, pad_head_rows, padded_head_dim
+from .plan import TORCH_DT, Plan, PlanBuilder, bke, round_up
 
 
 class DiTWeights:
@@ -52,7 +53,7 @@ class DiTWeights:
         self.P = P
 
 
-class DiTPlan:
+class DiTPlan(Plan):
     """inputs: lam [n_bj]; ctx_of_unit [U] = class label per unit (row of the embedding tables);
     a0 = patch tokens [n_bj, g, g, kin].  output: pred [U, g, g, p*p*out_ch] f32 (un-patchify is
     folded into dc_eps_mse / done by the caller)."""
@@ -84,11 +85,7 @@ class DiTPlan:
         lam = pb.external("lam", self.lam, "bj", 1, 1, 1, L.DC_F32)
         kin = weights.kin
         if score is not None:
-            eps_t = pb.external("eps", score["eps"], "bj", 1, 1, 1, L.DC_F32)
-            al = pb.external("alpha", score["alpha"], "bj", 1, 1, 1, L.DC_F32)
-            sg = pb.external("sigma", score["sigma"], "bj", 1, 1, 1, L.DC_F32)
-            a0 = pb.qsample("a0", pb.const(score["x"]), eps_t, al, sg, pb.const(score["img_of_bj"]),
-                            cfg.in_channels, H, W, kin, dt, im2col=2, patch=p)
+            a0, noise = pb.score_head(score, cfg.in_channels, H, W, kin, dt, im2col=2, patch=p)
         else:
             self.a0_buf = torch.zeros(n_bj, g, g, kin, dtype=TORCH_DT[dt], device=dev)
             a0 = pb.external("a0", self.a0_buf, "bj", g, g, kin, dt)
@@ -125,23 +122,8 @@ class DiTPlan:
                         tile_n=32 if p * p * oc <= 32 else 128)
         self.pred = pred
         if score is not None:
-            pb.eps_mse(pred, eps_t, pb.const(score["x"]), al, sg, pb.const(self.bj_of_unit), pb.const(score["img_of_bj"]),
-                       pb.const(score["out_index"]), pb.const(score["errors"]), cfg.in_channels, score["v_param"], patch=p)
-            if score.get("emap_acc") is not None:
-                pb.err_map(pred, eps_t, pb.const(score["x"]), al, sg, pb.const(self.bj_of_unit), pb.const(score["img_of_bj"]),
-                           pb.const(score["out_index"]), pb.const(score["emap_acc"]), pb.const(score["emap_bad"]), cfg.in_channels,
-                           score["v_param"], score["emap_T"], score["emap_acc"].shape[0] - 1, patch=p)
+            pb.score_tail(pred, score, noise, self.bj_of_unit, cfg.in_channels, patch=p)
         pb.finalize(keep_alive=[pred])
-
-    def run(self):
-        self.pb.run()
 
     def run_ctx(self):
         pass   # class conditioning is a table row picked inside the plan
-
-    def pred_view(self):
-        return self.pb.tensor_view(self.pred)
-
-    @property
-    def arena_bytes(self):
-        return self.pb.arena_bytes

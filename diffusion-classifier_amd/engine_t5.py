@@ -1,4 +1,4 @@
-"""T5 (v1.0) encoder stack as ONE launch plan for libdcamd — see engine.py for the plan model.
+"""T5 (v1.0) encoder stack as ONE launch plan for libdcamd — see plan.py for the plan model.
 
 Restated: transformers' `T5EncoderModel` behind the reference's `encoder_type='t5'` (diffusion/diffusion_classifier.py:59-74, :93-98):
 token embedding -> per block [RMS norm -> q | k | v (no bias) -> softmax(q k^T + relative-position bias, keys below the prompt's length)
@@ -12,7 +12,8 @@ import math
 import torch
 
 from . import _lib as L
-from .engine import PlanBuilder, f32c, pack_matrix
+from .packing import f32c, pack_matrix
+from .plan import Plan, PlanBuilder
 
 MAX_LENGTH = L.ATTENTION_BIAS_MAX_L      # the reference tokenises with max_length=512 (:95)
 HEAD_DIMS = (16, 32, 64, 128)            # dc_attention_bias
@@ -87,7 +88,7 @@ class T5Weights:
         self.P = P
 
 
-class T5Plan:
+class T5Plan(Plan):
     """inputs: ids [B, L] int64 and lens [B] int32 (device buffers of the plan: copy into them, then run()).
     output: out [B, L, d_model] fp32, rows at or past a prompt's length zero."""
 
@@ -107,44 +108,35 @@ class T5Plan:
 
         def rmsnorm(name, x, w, out_dt):
             y = pb.tensor(name, "bj", 1, Lq, D, out_dt)
-            pb._emit(L.OP_RMSNORM, L.RmsnormParams,
-                     dict(x=x, y=y, weight=pb.const(w), row_len=lens, dtype=x.dt, out_dtype=out_dt, rows=rows, C=D, rows_per_sample=Lq, eps=eps),
-                     [x], [y], dict(name=name, family="rmsnorm", flops=0.0, bytes=float(rows * D * (4 + (4 if out_dt == L.DC_F32 else 2)))))
+            pb.emit(L.OP_RMSNORM, L.RmsnormParams,
+                    dict(x=x, y=y, weight=pb.const(w), row_len=lens, dtype=x.dt, out_dtype=out_dt, rows=rows, C=D, rows_per_sample=Lq, eps=eps),
+                    [x], [y], dict(name=name, family="rmsnorm", flops=0.0, bytes=float(rows * D * (4 + (4 if out_dt == L.DC_F32 else 2)))))
             return y
 
         h = pb.tensor("embed", "bj", 1, Lq, D, L.DC_F32)
-        pb._emit(L.OP_EMBED_ROWS, L.EmbedRowsParams,
-                 dict(table=pb.const(P["shared"]), ids=ids, out=h, out_dtype=L.DC_F32, rows=rows, C=D, vocab=cfg.vocab_size),
-                 [], [h], dict(name="embed", family="embed_rows", flops=0.0, bytes=8.0 * rows * D))
+        pb.emit(L.OP_EMBED_ROWS, L.EmbedRowsParams,
+                dict(table=pb.const(P["shared"]), ids=ids, out=h, out_dtype=L.DC_F32, rows=rows, C=D, vocab=cfg.vocab_size),
+                [], [h], dict(name="embed", family="embed_rows", flops=0.0, bytes=8.0 * rows * D))
         for i in range(cfg.num_layers):
             a, f = f"encoder.block.{i}.layer.0.", f"encoder.block.{i}.layer.1."
             hn = rmsnorm(a + "ln", h, P[a + "ln"], dt)
             qkv = pb.igemm(a + "qkv", hn, pb.const(P[a + "qkv"]), 3 * inner)
             o = pb.tensor(a + "attn", "bj", 1, Lq, inner, dt)
             q, k, v = qkv.view(0, inner), qkv.view(inner, inner), qkv.view(2 * inner, inner)
-            pb._emit(L.OP_ATTENTION_BIAS, L.AttentionBiasParams,
-                     dict(q=q, k=k, v=v, out=o, bias=bias, kv_len=lens, dtype=dt, n=B, L=Lq, heads=heads, d=dkv, ld_qkv=qkv.ld, ld_out=o.ld,
-                          scale=1.0),       # T5 does not scale its scores: the factor lives in the initialisation of q
-                     [q, k, v], [o], dict(name=a + "attn", family="attention_bias", flops=4.0 * B * heads * Lq * Lq * dkv,
-                                          bytes=4.0 * rows * inner * (4 if dt == L.DC_F32 else 2)))
+            pb.emit(L.OP_ATTENTION_BIAS, L.AttentionBiasParams,
+                    dict(q=q, k=k, v=v, out=o, bias=bias, kv_len=lens, dtype=dt, n=B, L=Lq, heads=heads, d=dkv, ld_qkv=qkv.ld, ld_out=o.ld,
+                         scale=1.0),       # T5 does not scale its scores: the factor lives in the initialisation of q
+                    [q, k, v], [o], dict(name=a + "attn", family="attention_bias", flops=4.0 * B * heads * Lq * Lq * dkv,
+                                         bytes=4.0 * rows * inner * (4 if dt == L.DC_F32 else 2)))
             # fp32 residual stream: the GEMM reads the old stream as its residual and writes a new one (never in place)
             h = pb.igemm(a + "o", o, pb.const(P[a + "o"]), D, residual=h, out_dt=L.DC_F32)
             hn = rmsnorm(f + "ln", h, P[f + "ln"], dt)
             ff = pb.igemm(f + "wi", hn, pb.const(P[f + "wi"]), dff)
-            pb._emit(L.OP_RELU, L.ReluParams, dict(x=ff, n=rows * dff, dtype=dt), [ff], [ff],
-                     dict(name=f + "relu", family="relu", flops=0.0, bytes=2.0 * rows * dff * (4 if dt == L.DC_F32 else 2)))
+            pb.emit(L.OP_RELU, L.ReluParams, dict(x=ff, n=rows * dff, dtype=dt), [ff], [ff],
+                    dict(name=f + "relu", family="relu", flops=0.0, bytes=2.0 * rows * dff * (4 if dt == L.DC_F32 else 2)))
             h = pb.igemm(f + "wo", ff, pb.const(P[f + "wo"]), D, residual=h, out_dt=L.DC_F32)
         self.out = rmsnorm("final.ln", h, P["final.ln"], L.DC_F32)
         pb.finalize(keep_alive=[self.out])
-        for i, (kind, _, _) in enumerate(pb.ops):
-            if kind == L.OP_ATTENTION_BIAS:
-                pb.meta[i]["variant"] = L.lib().dc_attention_bias_variant(pb.structs[i]).decode()
-
-    def run(self):
-        self.pb.run()
-
-    def run_timed(self):
-        return self.pb.run_timed()
 
     def out_view(self):
-        return self.pb.tensor_view(self.out).view(self.B, self.L, -1)
+        return super().out_view().view(self.B, self.L, -1)

@@ -1,4 +1,4 @@
-"""AutoencoderKL encoder and decoder, each as ONE launch plan for libdcamd — see engine.py for the plan model.
+"""AutoencoderKL encoder and decoder, each as ONE launch plan for libdcamd — see plan.py for the plan model.
 
 Restated: the encoder half of diffusers' `AutoencoderKL` (0.31 layout) and the mean of its posterior, scaled:
     conv_in -> per level [layers_per_block x ResNet, then (all but the last level) pad (0, 1, 0, 1) + 3x3 stride-2 conv]
@@ -30,12 +30,11 @@ The decoder half (`VaeDecoderWeights`, `VaeDecoderPlan`), `AutoencoderKL.decode(
   tail             dc_groupnorm (+ SiLU) -> dc_igemm taps = 9 with an fp32 output, on the 32-wide tile when out_channels <= 32
 The producer-side GroupNorm hand-off, the fused GroupNorm prologue and the tail fold are not claimed here either.
 """
-import os
-
 import torch
 
 from . import _lib as L
-from .engine import DT_SIZE, PlanBuilder, bke, f32c, pack_conv3x3, pack_matrix, pack_up4, round_up
+from .packing import LazyPacks, f32c, pack_conv3x3, pack_matrix
+from .plan import DT_SIZE, Plan, PlanBuilder, bke, round_up, switches
 
 GN_EPS = 1e-6
 MID_WIDTHS = (64, 128) + L.ATTENTION_WIDE_DIMS      # dc_attention / dc_attention_wide, and a multiple of the GEMMs' K granule
@@ -153,22 +152,13 @@ def attention_ops(pb, P, G, key, x):
         o = pb.attention(key + "attn", q, k, v, 1, Cc)
     else:
         o = pb.tensor(key + "attn", "bj", x.H, x.W, Cc, dt)
-        pb._emit(L.OP_ATTENTION_WIDE, L.AttentionWideParams,
-                 dict(q=q, k=k, v=v, out=o, dtype=dt, n=B, L=Lq, heads=1, d=Cc, ld_qkv=qkv.ld, ld_out=o.ld, scale=float(Cc) ** -0.5),
-                 [q, k, v], [o], dict(name=key + "attn", family="attention_wide", flops=4.0 * B * Lq * Lq * Cc, bytes=4.0 * B * Lq * Cc * es))
+        pb.emit(L.OP_ATTENTION_WIDE, L.AttentionWideParams,
+                dict(q=q, k=k, v=v, out=o, dtype=dt, n=B, L=Lq, heads=1, d=Cc, ld_qkv=qkv.ld, ld_out=o.ld, scale=float(Cc) ** -0.5),
+                [q, k, v], [o], dict(name=key + "attn", family="attention_wide", flops=4.0 * B * Lq * Lq * Cc, bytes=4.0 * B * Lq * Cc * es))
     return pb.igemm(key + "to_out", o, pb.const(P[key + "to_out.0.w"]), Cc, bias=pb.const(P[key + "to_out.0.b"]), residual=x)
 
 
-def check_served(pb, who, what):
-    """Names dc_attention_wide's variant and raises DcamdError for the first op the library refuses."""
-    for i, (kd, _, _) in enumerate(pb.ops):
-        if kd == L.OP_ATTENTION_WIDE:
-            pb.meta[i]["variant"] = L.lib().dc_attention_wide_variant(pb.structs[i]).decode()
-        if pb.meta[i].get("variant") == "invalid" or pb.meta[i]["family"] == "invalid":
-            raise L.DcamdError(f"{who}: libdcamd refuses {pb.meta[i]['name']} at {what}")
-
-
-class VaePlan:
+class VaePlan(Plan):
     """input: x [B, in_channels, H, W] fp32 (a device buffer of the plan: copy into it, then run()).
     output: latents [B, H / f, W / f, latent_channels] fp32 NHWC (out_view), f = 2^(levels - 1)."""
 
@@ -176,7 +166,7 @@ class VaePlan:
         cfg = model.config
         dev, dt, P = weights.dev, weights.dt, weights.P
         boc, G = cfg.block_out_channels, cfg.norm_num_groups
-        use_qs = os.environ.get("DCAMD_NO_QSTATS") is None
+        use_qs = switches().qstats
         self.B, self.H, self.W, self.dt = B, H, W, dt
         pb = self.pb = PlanBuilder(dev, B, 1, 1)
         f32 = dict(dtype=torch.float32, device=dev)
@@ -188,48 +178,30 @@ class VaePlan:
         a0 = pb.qsample("a0", pb.const(self.x), xt, one, zero, None, cfg.in_channels, H, W, weights.kin, dt, im2col=True)
         es = DT_SIZE[dt]
 
-        def gn(name, x, key, silu):
-            return gn_ops(pb, P, G, name, x, key, silu)
-
-        def resnet(key, x):
-            return resnet_ops(pb, P, G, use_qs, key, x)
-
         def downsample(key, x):
             col = pb.tensor(key + ".col", "bj", x.H // 2, x.W // 2, 9 * x.C, dt)
-            pb._emit(L.OP_IM2COL_S2, L.Im2colS2Params, dict(x=x, out=col, dtype=dt, n=B, H=x.H, W=x.W, C=x.C, ld=x.ld), [x], [col],
-                     dict(name=key + ".col", family="im2col_s2", flops=0.0, bytes=float(B * x.H * x.W * x.C * es + B * col.H * col.W * col.C * es)))
+            pb.emit(L.OP_IM2COL_S2, L.Im2colS2Params, dict(x=x, out=col, dtype=dt, n=B, H=x.H, W=x.W, C=x.C, ld=x.ld), [x], [col],
+                    dict(name=key + ".col", family="im2col_s2", flops=0.0, bytes=float(B * x.H * x.W * x.C * es + B * col.H * col.W * col.C * es)))
             return pb.igemm(key, col, pb.const(P[key + ".w"]), x.C, bias=pb.const(P[key + ".b"]))
-
-        def attention(key, x):
-            return attention_ops(pb, P, G, key, x)
 
         h = pb.igemm("encoder.conv_in", a0, pb.const(P["encoder.conv_in.w"]), boc[0], bias=pb.const(P["encoder.conv_in.b"]),
                      k_real=9 * cfg.in_channels)
         for i in range(len(boc)):
             for j in range(cfg.layers_per_block):
-                h = resnet(f"encoder.down_blocks.{i}.resnets.{j}", h)
+                h = resnet_ops(pb, P, G, use_qs, f"encoder.down_blocks.{i}.resnets.{j}", h)
             if i != len(boc) - 1:
                 h = downsample(f"encoder.down_blocks.{i}.downsamplers.0.conv", h)
-        h = resnet("encoder.mid_block.resnets.0", h)
-        h = attention("encoder.mid_block.attentions.0.", h)
-        h = resnet("encoder.mid_block.resnets.1", h)
-        h = gn("encoder.conv_norm_out", h, "encoder.conv_norm_out", True)
+        h = resnet_ops(pb, P, G, use_qs, "encoder.mid_block.resnets.0", h)
+        h = attention_ops(pb, P, G, "encoder.mid_block.attentions.0.", h)
+        h = resnet_ops(pb, P, G, use_qs, "encoder.mid_block.resnets.1", h)
+        h = gn_ops(pb, P, G, "encoder.conv_norm_out", h, "encoder.conv_norm_out", True)
         self.out = pb.igemm("encoder.conv_out", h, pb.const(P["tail.w"]), cfg.latent_channels, taps=9, bias=pb.const(P["tail.b"]),
                             out_dt=L.DC_F32, tile_n=weights.tail_tile_n)
         pb.finalize(keep_alive=[self.out])
-        check_served(pb, "VaePlan", f"{B} x {H} x {W} in {model.compute_dtype}")
-
-    def run(self):
-        self.pb.run()
-
-    def run_timed(self):
-        return self.pb.run_timed()
-
-    def out_view(self):
-        return self.pb.tensor_view(self.out)
+        pb.check_served("VaePlan", f"{B} x {H} x {W} in {model.compute_dtype}")
 
 
-class VaeDecoderWeights:
+class VaeDecoderWeights(LazyPacks):
     """Device-resident packed weights of a VAEDecoder for one compute dtype."""
 
     def __init__(self, model, dt, device):
@@ -261,7 +233,7 @@ class VaeDecoderWeights:
         self.P = P
 
 
-class VaeDecoderPlan:
+class VaeDecoderPlan(Plan):
     """input: z [B, latent_channels, h, w] fp32, scaled latents (a device buffer of the plan: copy into it, then run()).
     output: images [B, f h, f w, out_channels] fp32 NHWC (out_view), f = 2^(levels - 1)."""
 
@@ -269,18 +241,18 @@ class VaeDecoderPlan:
         cfg = model.config
         dev, dt, P = weights.dev, weights.dt, weights.P
         boc, G, Z = cfg.block_out_channels, cfg.norm_num_groups, cfg.latent_channels
-        use_qs = os.environ.get("DCAMD_NO_QSTATS") is None
-        use_up4 = os.environ.get("DCAMD_NO_UP4") is None
+        sw = switches()
+        use_qs = sw.qstats
         self.B, self.h, self.w, self.dt = B, h, w, dt
         pb = self.pb = PlanBuilder(dev, B, 1, 1)
         self.z = torch.zeros(B, Z, h, w, dtype=torch.float32, device=dev)
         zt = pb.external("z", self.z, "bj", 1, 1, 1, L.DC_F32)
         es = DT_SIZE[dt]
         a0 = pb.tensor("a0", "bj", h, w, weights.kin, dt)
-        pb._emit(L.OP_LATENT_IM2COL, L.LatentIm2colParams,
-                 dict(z=zt, Q=pb.const(P["head.Q"]), bias=pb.const(P["head.b"]), out=a0, out_dtype=dt, n=B, Z=Z, H=h, W=w, Kpad=weights.kin,
-                      inv_scale=1.0 / cfg.scaling_factor, shift=float(cfg.shift_factor or 0.0)), [zt], [a0],
-                 dict(name="a0", family="latent_im2col", flops=2.0 * B * h * w * 9 * Z * Z, bytes=float(B * h * w * (Z * 4 + weights.kin * es))))
+        pb.emit(L.OP_LATENT_IM2COL, L.LatentIm2colParams,
+                dict(z=zt, Q=pb.const(P["head.Q"]), bias=pb.const(P["head.b"]), out=a0, out_dtype=dt, n=B, Z=Z, H=h, W=w, Kpad=weights.kin,
+                     inv_scale=1.0 / cfg.scaling_factor, shift=float(cfg.shift_factor or 0.0)), [zt], [a0],
+                dict(name="a0", family="latent_im2col", flops=2.0 * B * h * w * 9 * Z * Z, bytes=float(B * h * w * (Z * 4 + weights.kin * es))))
         rev = boc[::-1]
         x = pb.igemm("decoder.conv_in", a0, pb.const(P["decoder.conv_in.w"]), rev[0], bias=pb.const(P["decoder.conv_in.b"]), k_real=9 * Z)
         x = resnet_ops(pb, P, G, use_qs, "decoder.mid_block.resnets.0", x)
@@ -290,25 +262,9 @@ class VaeDecoderPlan:
             for j in range(cfg.layers_per_block + 1):
                 x = resnet_ops(pb, P, G, use_qs, f"decoder.up_blocks.{i}.resnets.{j}", x)
             if i != len(boc) - 1:
-                key = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-                if use_up4 and pb.up4_ok(x, x.C):
-                    # nearest-2x upsample + 3x3 conv == four 2x2-tap convs of the low-resolution tensor (phase-summed weights): 4/9 of the MACs
-                    if key + ".w4" not in P:
-                        P[key + ".w4"] = pack_up4(weights._sd[key + ".weight"], dt, dev)
-                    x = pb.igemm(key, x, pb.const(P[key + ".w4"]), x.C, taps=9, upsample=1, bias=pb.const(P[key + ".b"]), qstats=use_qs, up4=True)
-                else:
-                    x = pb.igemm(key, x, pb.const(P[key + ".w"]), x.C, taps=9, upsample=1, bias=pb.const(P[key + ".b"]), qstats=use_qs)
+                x = pb.upsample_conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", x, weights, sw.up4, use_qs)
         x = gn_ops(pb, P, G, "decoder.conv_norm_out", x, "decoder.conv_norm_out", True)
         self.out = pb.igemm("decoder.conv_out", x, pb.const(P["decoder.conv_out.w"]), cfg.out_channels, taps=9,
                             bias=pb.const(P["decoder.conv_out.b"]), out_dt=L.DC_F32, tile_n=weights.tail_tile_n)
         pb.finalize(keep_alive=[self.out])
-        check_served(pb, "VaeDecoderPlan", f"{B} x {h} x {w} latents in {model.compute_dtype}")
-
-    def run(self):
-        self.pb.run()
-
-    def run_timed(self):
-        return self.pb.run_timed()
-
-    def out_view(self):
-        return self.pb.tensor_view(self.out)
+        pb.check_served("VaeDecoderPlan", f"{B} x {h} x {w} latents in {model.compute_dtype}")

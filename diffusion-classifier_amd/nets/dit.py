@@ -59,7 +59,7 @@ class DiT(_HipBackbone):
                                    norm_elementwise_affine=(norm_elementwise_affine, False)).items():
             if got != want:
                 raise NotImplementedError(f"DiT({k}={got!r}) is outside the scoring path built here (supported: {want!r})")
-        E.padded_head_dim(attention_head_dim)      # heads wider than 128 are refused here; narrower ones run zero-padded (engine.py)
+        E.padded_head_dim(attention_head_dim)      # heads wider than 128 are refused here; narrower ones run zero-padded (packing.py)
         D = num_attention_heads * attention_head_dim
         out_channels = in_channels if out_channels is None else out_channels
         self.D = D

@@ -232,7 +232,7 @@ class UNetCondition2D(_HipBackbone):
         lpb = (layers_per_block,) * nb if isinstance(layers_per_block, int) else tuple(layers_per_block)
         assert len(down_block_types) == nb and len(up_block_types) == nb and len(lpb) == nb
         G, eps, xdim = norm_num_groups, norm_eps, cross_attention_dim
-        # self-attention heads of C / attention_head_dim channels run zero-padded to a width dc_attention serves (engine.padded_head_dim):
+        # self-attention heads of C / attention_head_dim channels run zero-padded to a width dc_attention serves (packing.padded_head_dim):
         # a level whose heads are wider than 128 is refused here, not at its first launch
         rboc = boc[::-1]
         for C in {boc[-1]} | {boc[i] for i, k in enumerate(down_block_types) if k == "CrossAttnDownBlock2D"} \
