@@ -64,7 +64,7 @@ class ClipPlan(Plan):
 
         def layernorm(name, x, g, b, out_dt):
             y = pb.tensor(name, "bj", 1, Lq, D, out_dt)
-            pb.emit(L.OP_LAYERNORM_ROWS, L.LayernormRowsParams,
+            pb.emit(L.OP_LAYERNORM_ROWS,
                     dict(x=x, y=y, gamma=pb.const(g), beta=pb.const(b), row_len=lens, dtype=x.dt, out_dtype=out_dt, rows=rows, C=D,
                          rows_per_sample=Lq, eps=eps),
                     [x], [y], dict(name=name, family="layernorm_rows", flops=0.0, bytes=float(rows * D * (4 + (4 if out_dt == L.DC_F32 else 2)))))
@@ -79,7 +79,7 @@ class ClipPlan(Plan):
             return y
 
         h = pb.tensor("embed", "bj", 1, Lq, D, L.DC_F32)
-        pb.emit(L.OP_EMBED_ROWS_POS, L.EmbedRowsPosParams,
+        pb.emit(L.OP_EMBED_ROWS_POS,
                 dict(table=pb.const(P["tok"]), pos=pb.const(P["pos"]), ids=ids, out=h, out_dtype=L.DC_F32, rows=rows, C=D,
                      vocab=cfg.vocab_size, L=Lq),
                 [], [h], dict(name="embed", family="embed_rows_pos", flops=0.0, bytes=12.0 * rows * D))
@@ -89,7 +89,7 @@ class ClipPlan(Plan):
             qkv = gemm(k + "qkv", hn, k + "qkv.w", k + "qkv.b", 3 * D)
             o = pb.tensor(k + "attn", "bj", 1, Lq, D, dt)
             q, kk, v = qkv.view(0, D), qkv.view(D, D), qkv.view(2 * D, D)
-            pb.emit(L.OP_ATTENTION_CAUSAL, L.AttentionCausalParams,
+            pb.emit(L.OP_ATTENTION_CAUSAL,
                     dict(q=q, k=kk, v=v, out=o, row_len=lens, dtype=dt, n=B, L=Lq, heads=heads, d=dh, ld_qkv=qkv.ld, ld_out=o.ld,
                          scale=float(dh) ** -0.5),
                     [q, kk, v], [o], dict(name=k + "attn", family="attention_causal", flops=2.0 * B * heads * Lq * (Lq + 1) * dh,
@@ -98,7 +98,7 @@ class ClipPlan(Plan):
             h = gemm(k + "out", o, k + "out.w", k + "out.b", D, residual=h, out_dt=L.DC_F32)
             hn = layernorm(k + "ln2", h, P[k + "layer_norm2.g"], P[k + "layer_norm2.b"], dt)
             ff = gemm(k + "fc1", hn, k + "fc1.w", k + "fc1.b", dff)
-            pb.emit(L.OP_ACT_PASS, L.ActPassParams, dict(x=ff, n=rows * dff, dtype=dt, kind=kind), [ff], [ff],
+            pb.emit(L.OP_ACT_PASS, dict(x=ff, n=rows * dff, dtype=dt, kind=kind), [ff], [ff],
                     dict(name=k + "act", family="act_pass", flops=0.0, bytes=2.0 * rows * dff * es))
             h = gemm(k + "fc2", ff, k + "fc2.w", k + "fc2.b", D, residual=h, out_dt=L.DC_F32)
         self.out = layernorm("final.ln", h, P["final.g"], P["final.b"], L.DC_F32)

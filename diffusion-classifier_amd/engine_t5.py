@@ -108,13 +108,13 @@ class T5Plan(Plan):
 
         def rmsnorm(name, x, w, out_dt):
             y = pb.tensor(name, "bj", 1, Lq, D, out_dt)
-            pb.emit(L.OP_RMSNORM, L.RmsnormParams,
+            pb.emit(L.OP_RMSNORM,
                     dict(x=x, y=y, weight=pb.const(w), row_len=lens, dtype=x.dt, out_dtype=out_dt, rows=rows, C=D, rows_per_sample=Lq, eps=eps),
                     [x], [y], dict(name=name, family="rmsnorm", flops=0.0, bytes=float(rows * D * (4 + (4 if out_dt == L.DC_F32 else 2)))))
             return y
 
         h = pb.tensor("embed", "bj", 1, Lq, D, L.DC_F32)
-        pb.emit(L.OP_EMBED_ROWS, L.EmbedRowsParams,
+        pb.emit(L.OP_EMBED_ROWS,
                 dict(table=pb.const(P["shared"]), ids=ids, out=h, out_dtype=L.DC_F32, rows=rows, C=D, vocab=cfg.vocab_size),
                 [], [h], dict(name="embed", family="embed_rows", flops=0.0, bytes=8.0 * rows * D))
         for i in range(cfg.num_layers):
@@ -123,7 +123,7 @@ class T5Plan(Plan):
             qkv = pb.igemm(a + "qkv", hn, pb.const(P[a + "qkv"]), 3 * inner)
             o = pb.tensor(a + "attn", "bj", 1, Lq, inner, dt)
             q, k, v = qkv.view(0, inner), qkv.view(inner, inner), qkv.view(2 * inner, inner)
-            pb.emit(L.OP_ATTENTION_BIAS, L.AttentionBiasParams,
+            pb.emit(L.OP_ATTENTION_BIAS,
                     dict(q=q, k=k, v=v, out=o, bias=bias, kv_len=lens, dtype=dt, n=B, L=Lq, heads=heads, d=dkv, ld_qkv=qkv.ld, ld_out=o.ld,
                          scale=1.0),       # T5 does not scale its scores: the factor lives in the initialisation of q
                     [q, k, v], [o], dict(name=a + "attn", family="attention_bias", flops=4.0 * B * heads * Lq * Lq * dkv,
@@ -132,7 +132,7 @@ class T5Plan(Plan):
             h = pb.igemm(a + "o", o, pb.const(P[a + "o"]), D, residual=h, out_dt=L.DC_F32)
             hn = rmsnorm(f + "ln", h, P[f + "ln"], dt)
             ff = pb.igemm(f + "wi", hn, pb.const(P[f + "wi"]), dff)
-            pb.emit(L.OP_RELU, L.ReluParams, dict(x=ff, n=rows * dff, dtype=dt), [ff], [ff],
+            pb.emit(L.OP_RELU, dict(x=ff, n=rows * dff, dtype=dt), [ff], [ff],
                     dict(name=f + "relu", family="relu", flops=0.0, bytes=2.0 * rows * dff * (4 if dt == L.DC_F32 else 2)))
             h = pb.igemm(f + "wo", ff, pb.const(P[f + "wo"]), D, residual=h, out_dt=L.DC_F32)
         self.out = rmsnorm("final.ln", h, P["final.ln"], L.DC_F32)

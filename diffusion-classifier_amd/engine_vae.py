@@ -152,7 +152,7 @@ def attention_ops(pb, P, G, key, x):
         o = pb.attention(key + "attn", q, k, v, 1, Cc)
     else:
         o = pb.tensor(key + "attn", "bj", x.H, x.W, Cc, dt)
-        pb.emit(L.OP_ATTENTION_WIDE, L.AttentionWideParams,
+        pb.emit(L.OP_ATTENTION_WIDE,
                 dict(q=q, k=k, v=v, out=o, dtype=dt, n=B, L=Lq, heads=1, d=Cc, ld_qkv=qkv.ld, ld_out=o.ld, scale=float(Cc) ** -0.5),
                 [q, k, v], [o], dict(name=key + "attn", family="attention_wide", flops=4.0 * B * Lq * Lq * Cc, bytes=4.0 * B * Lq * Cc * es))
     return pb.igemm(key + "to_out", o, pb.const(P[key + "to_out.0.w"]), Cc, bias=pb.const(P[key + "to_out.0.b"]), residual=x)
@@ -180,7 +180,7 @@ class VaePlan(Plan):
 
         def downsample(key, x):
             col = pb.tensor(key + ".col", "bj", x.H // 2, x.W // 2, 9 * x.C, dt)
-            pb.emit(L.OP_IM2COL_S2, L.Im2colS2Params, dict(x=x, out=col, dtype=dt, n=B, H=x.H, W=x.W, C=x.C, ld=x.ld), [x], [col],
+            pb.emit(L.OP_IM2COL_S2, dict(x=x, out=col, dtype=dt, n=B, H=x.H, W=x.W, C=x.C, ld=x.ld), [x], [col],
                     dict(name=key + ".col", family="im2col_s2", flops=0.0, bytes=float(B * x.H * x.W * x.C * es + B * col.H * col.W * col.C * es)))
             return pb.igemm(key, col, pb.const(P[key + ".w"]), x.C, bias=pb.const(P[key + ".b"]))
 
@@ -249,7 +249,7 @@ class VaeDecoderPlan(Plan):
         zt = pb.external("z", self.z, "bj", 1, 1, 1, L.DC_F32)
         es = DT_SIZE[dt]
         a0 = pb.tensor("a0", "bj", h, w, weights.kin, dt)
-        pb.emit(L.OP_LATENT_IM2COL, L.LatentIm2colParams,
+        pb.emit(L.OP_LATENT_IM2COL,
                 dict(z=zt, Q=pb.const(P["head.Q"]), bias=pb.const(P["head.b"]), out=a0, out_dtype=dt, n=B, Z=Z, H=h, W=w, Kpad=weights.kin,
                      inv_scale=1.0 / cfg.scaling_factor, shift=float(cfg.shift_factor or 0.0)), [zt], [a0],
                 dict(name="a0", family="latent_im2col", flops=2.0 * B * h * w * 9 * Z * Z, bytes=float(B * h * w * (Z * 4 + weights.kin * es))))

@@ -132,26 +132,18 @@ class TRef:
         return v
 
 
-# op kind -> (the library function that names the kernel chosen for the op's params, the meta key the name is stored under).
-# bench.py groups timings by an igemm's `family`; the others keep the family their builder wrote and get a `variant`.
-VARIANT_OF = {
-    L.OP_IGEMM: ("dc_igemm_variant", "family"),
-    L.OP_ATTENTION: ("dc_attention_variant", "variant"),
-    L.OP_ATTENTION_WIDE: ("dc_attention_wide_variant", "variant"),
-    L.OP_ATTENTION_CAUSAL: ("dc_attention_causal_variant", "variant"),
-    L.OP_ATTENTION_BIAS: ("dc_attention_bias_variant", "variant"),
-    L.OP_CROSS_ATTENTION: ("dc_cross_attention_variant", "variant"),
-    L.OP_CROSS_ATTENTION_LEN: ("dc_cross_attention_len_variant", "variant"),
-    L.OP_GROUPNORM: ("dc_groupnorm_variant", "variant"),
-    L.OP_LAYERNORM: ("dc_layernorm_variant", "variant"),
-}
+# op kind -> (the library function that names the kernel chosen for the op's params, the meta key the name is stored under): every
+# kind whose entry dc_<op> has a dc_<op>_variant beside it in the header.  bench.py groups timings by an igemm's `family`; the others
+# keep the family their builder wrote and get a `variant`.  (DC_OP_CONV3_PN_TAIL's variant takes two structs: finalize() asks it.)
+VARIANT_OF = {kind: (fn + "_variant", "family" if kind == L.OP_IGEMM else "variant") for kind, fn in L.OP_ENTRY.items()
+              if fn + "_variant" in L.EXPORTS and kind != L.OP_CONV3_PN_TAIL}
 
 
 class PlanBuilder:
     def __init__(self, device, n_bj, n_cls, n_ctx):
         self.dev = device
         self.n = {"bj": n_bj, "unit": n_bj * n_cls, "ctx": n_ctx}
-        self.ops = []        # (kind, struct_cls, fields{name: value | TRef | ("ptr", TRef)}, reads, writes)
+        self.ops = []        # (kind, struct_cls = L.OP_PARAMS[kind], fields{name: value | TRef | ("ptr", TRef)}, reads, writes)
         self.keep = []       # torch tensors kept alive (weights, maps, inputs)
         self.maps = {}       # (src_dom, dst_dom) -> external int32 TRef
         self.arena = None
@@ -192,7 +184,7 @@ class PlanBuilder:
             return "unit"
         return doms.pop()
 
-    def emit(self, kind, cls, fields, reads, writes, meta=None):
+    def emit(self, kind, fields, reads, writes, meta=None):
         idx = len(self.ops)
         self.meta.append(dict(meta or {}, kind=kind))
         for t in reads + writes:
@@ -203,7 +195,7 @@ class PlanBuilder:
                 if b.first is None:
                     b.first = idx
                 b.last = idx
-        self.ops.append((kind, cls, fields))
+        self.ops.append((kind, L.OP_PARAMS[kind], fields))
 
     # ---- ops -----------------------------------------------------------------------
     def igemm(self, name, src0, W, Cout, *, taps=1, stride=1, upsample=0, src1=None, bias=None, rowvec=None,
@@ -265,7 +257,7 @@ class PlanBuilder:
             meta["flops"] += 2.0 * M * side[0].C * Cout
             meta["K"] = kreal + side[0].C
             meta["bytes"] += float(nsrc.get(side[0].dom, 1) * side[0].H * side[0].W * side[0].C * DT_SIZE[side[0].dt] + side[0].C * Cout * es)
-        self.emit(L.OP_IGEMM, L.IgemmParams, f, [src0, src1, rowvec, gate, residual] + (list(gn[:2]) if gn else []) + ([side[0]] if side else []), [out] + ([qs] if qs else []), meta)
+        self.emit(L.OP_IGEMM, f, [src0, src1, rowvec, gate, residual] + (list(gn[:2]) if gn else []) + ([side[0]] if side else []), [out] + ([qs] if qs else []), meta)
         if qstats and gn is None and (qs is not None or (taps == 9 and stride == 1 and not upsample and Hin == 4 and Win == 4)):
             out.prod = len(self.ops) - 1       # (4x4 images: no quad records, but the conv can still normalise its output inside the wave)
         return out
@@ -351,7 +343,7 @@ class PlanBuilder:
         t["tail_ring"] = self.const(torch.zeros(ring_floats, dtype=torch.float32, device=self.dev))
         t["pn_cnt"] = self.const(torch.zeros(self.n[dom], dtype=torch.int32, device=self.dev))
         f.update(t, out=None)
-        self.ops[idx] = (L.OP_CONV3_PN_TAIL, L.Conv3PnTailOp, f)
+        self.ops[idx] = (L.OP_CONV3_PN_TAIL, L.OP_PARAMS[L.OP_CONV3_PN_TAIL], f)
         pred.first = pred.last = idx
         M = self.n[dom] * x.H * x.W
         m = self.meta[idx]
@@ -433,7 +425,7 @@ class PlanBuilder:
         sweep = 1.0 * n * HW * Cc * DT_SIZE[x0.dt]
         meta = dict(name=name, family="groupnorm_stats", flops=0.0, bytes=0.0 if qs is not None else sweep) if stats else \
             dict(name=name, family="groupnorm", flops=0.0, bytes=2.0 * sweep)
-        self.emit(L.OP_GROUPNORM, L.GroupnormParams, f, [x0, x1, qs], res + [ws], meta)
+        self.emit(L.OP_GROUPNORM, f, [x0, x1, qs], res + [ws], meta)
         return res
 
     def groupnorm(self, name, x0, gamma, beta, groups, eps, silu, x1=None):
@@ -450,7 +442,7 @@ class PlanBuilder:
         f = dict(x=x, y=out, dtype=x.dt, out_dtype=x.dt, rows=self.n[x.dom] * x.H * x.W, C=x.C,
                  rows_per_sample=x.H * x.W, mod_ld=scale.ld if scale is not None else 0, eps=eps,
                  gamma=gamma, beta=beta, scale=scale, shift=shift, mod_map=self.map(scale, x.dom))
-        self.emit(L.OP_LAYERNORM, L.LayernormParams, f, [x, scale, shift], [out],
+        self.emit(L.OP_LAYERNORM, f, [x, scale, shift], [out],
                   dict(name=name, family="layernorm", flops=0.0, bytes=2.0 * f["rows"] * x.C * DT_SIZE[x.dt]))
         return out
 
@@ -464,7 +456,7 @@ class PlanBuilder:
         f = dict(q=q, k=k, v=v, out=out, dtype=q.dt, n=self.n[q.dom], L=q.H * q.W, heads=heads, d=dp,
                  ld_qkv=q.ld, ld_out=out.ld, scale=float(d) ** -0.5)
         Lq = q.H * q.W
-        self.emit(L.OP_ATTENTION, L.AttentionParams, f, [q, k, v], [out],
+        self.emit(L.OP_ATTENTION, f, [q, k, v], [out],
                   dict(name=name, family="attention", flops=4.0 * self.n[q.dom] * heads * Lq * Lq * dp,
                        bytes=4.0 * self.n[q.dom] * Lq * q.C * DT_SIZE[q.dt]))
         return out
@@ -486,9 +478,9 @@ class PlanBuilder:
                  d=dp, ld_q=q.ld, ld_kv=k.ld, ld_out=out.ld, scale=float(d) ** -0.5)
         meta = dict(name=name, family="cross_attention", flops=4.0 * n * heads * Lq * S * dp, bytes=2.0 * n * Lq * q.C * DT_SIZE[q.dt])
         if kv_len is None:
-            self.emit(L.OP_CROSS_ATTENTION, L.CrossAttentionParams, f, [q, k, v], [out], meta)
+            self.emit(L.OP_CROSS_ATTENTION, f, [q, k, v], [out], meta)
         else:
-            self.emit(L.OP_CROSS_ATTENTION_LEN, L.CrossAttentionLenParams, dict(f, kv_len=kv_len), [q, k, v], [out], meta)
+            self.emit(L.OP_CROSS_ATTENTION_LEN, dict(f, kv_len=kv_len), [q, k, v], [out], meta)
         return out
 
     def tblock_front_ok(self, x, heads):
@@ -509,7 +501,7 @@ class PlanBuilder:
                  rowvec_ld=rowvec.ld if rowvec is not None else 0, out=out, dtype=x.dt, n=self.n[dom], L=Lq, C=Cc, heads=heads,
                  ldx=x.ld, ld_out=out.ld, ln_eps=float(eps), scale=float(d) ** -0.5)
         M, es = self.n[dom] * Lq, DT_SIZE[x.dt]
-        self.emit(L.OP_TBLOCK_FRONT, L.TblockFrontParams, f, [x, rowvec], [out],
+        self.emit(L.OP_TBLOCK_FRONT, f, [x, rowvec], [out],
                   dict(name=name, family="tblock_front", flops=2.0 * M * Cc * 5 * Cc + 4.0 * self.n[dom] * heads * Lq * Lq * d,
                        bytes=float(2 * M * Cc * es + 5 * Cc * Cc * es), M=M, N=Cc, K=Cc))
         return out
@@ -517,7 +509,7 @@ class PlanBuilder:
     def sinusoid(self, name, lam, dim, flip, shift):
         out = self.tensor(name, lam.dom, 1, 1, dim, L.DC_F32)
         f = dict(lam=lam, out=out, n=self.n[lam.dom], dim=dim, flip_sin_to_cos=int(flip), freq_shift=float(shift))
-        self.emit(L.OP_SINUSOID, L.SinusoidParams, f, [lam], [out], dict(name=name, family="sinusoid", flops=0.0, bytes=0.0))
+        self.emit(L.OP_SINUSOID, f, [lam], [out], dict(name=name, family="sinusoid", flops=0.0, bytes=0.0))
         return out
 
     def qsample(self, name, x_ptr, eps, alpha, sigma, img_of_bj, Cin, H, W, ld, dt, im2col, patch=0):
@@ -525,7 +517,7 @@ class PlanBuilder:
         out = self.tensor(name, "bj", H // g, W // g, ld, dt)
         f = dict(x=x_ptr, eps=eps, alpha=alpha, sigma=sigma, img_of_bj=img_of_bj, out=out, out_dtype=dt,
                  n_bj=self.n["bj"], C=Cin, H=H, W=W, ld=ld, im2col=int(im2col), patch=int(patch))
-        self.emit(L.OP_QSAMPLE, L.QsampleParams, f, [eps, alpha, sigma], [out],
+        self.emit(L.OP_QSAMPLE, f, [eps, alpha, sigma], [out],
                   dict(name=name, family="qsample", flops=0.0,
                        bytes=float(self.n["bj"] * (2 * Cin * H * W * 4 + (H // g) * (W // g) * ld * DT_SIZE[dt]))))
         return out
@@ -546,11 +538,11 @@ class PlanBuilder:
         f = dict(pred=pred, eps=noise[0], x=self.const(score["x"]), alpha=noise[1], sigma=noise[2], bj_of_unit=self.const(bj_of_unit),
                  img_of_bj=self.const(score["img_of_bj"]), out_index=self.const(score["out_index"]), n_units=self.n["unit"], C=Cin,
                  H=pred.H * g, W=pred.W * g, ld=pred.ld, v_param=int(score["v_param"]), patch=int(patch))
-        self.emit(L.OP_EPS_MSE, L.EpsMseParams, dict(f, out=self.const(score["errors"])), [pred, *noise], [],
+        self.emit(L.OP_EPS_MSE, dict(f, out=self.const(score["errors"])), [pred, *noise], [],
                   dict(name="eps_mse", family="eps_mse", flops=0.0, bytes=8.0 * Cin * px))
         if score.get("emap_acc") is not None:
             acc = score["emap_acc"]
-            self.emit(L.OP_ERR_MAP, L.ErrMapParams, dict(f, acc=self.const(acc), bad=self.const(score["emap_bad"]), T=int(score["emap_T"]), cells=acc.shape[0] - 1),
+            self.emit(L.OP_ERR_MAP, dict(f, acc=self.const(acc), bad=self.const(score["emap_bad"]), T=int(score["emap_T"]), cells=acc.shape[0] - 1),
                       [pred, *noise], [], dict(name="err_map", family="err_map", flops=0.0, bytes=(8.0 * Cin + 8.0) * px))
 
     # ---- finalize: liveness-based arena + ctypes records ----------------------------
