@@ -11,6 +11,7 @@ All arithmetic of the scoring path runs in `libdcamd.so` (HIP kernels + C-ABI, c
 """
 from . import _lib  # noqa: F401
 from .nets.unet import UNetCondition2D, UNet2D  # noqa: F401
+from .nets.sd_unet import StableDiffusionUNet  # noqa: F401
 from .nets.dit import DiT  # noqa: F401
 from .nets.vae import VAEEncoder, VAEDecoder  # noqa: F401
 from .diffusion.diffusion_classifier import DiffusionClassifier  # noqa: F401
@@ -133,6 +134,22 @@ def sd_vae_kwargs():
     # the published Stable Diffusion AutoencoderKL (sd-vae-ft-mse / -ema, the `vae/` of SD 1.x), 8x downsampling; VAEEncoder and VAEDecoder both take it
     return dict(in_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2, norm_num_groups=32,
                 scaling_factor=0.18215)
+
+
+def sd15_unet_kwargs():
+    # the published Stable Diffusion 1.x UNet (the `unet/config.json` of v1-4 / v1-5): 64x64 latents, 8 heads at every level (head widths
+    # 40 / 80 / 160 / 160), the CLIP ViT-L/14 context of 768 channels, 1x1-conv projections; StableDiffusionUNet takes it
+    return dict(sample_size=64, in_channels=4, out_channels=4, layers_per_block=2, block_out_channels=(320, 640, 1280, 1280),
+                down_block_types=("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+                up_block_types=("UpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "CrossAttnUpBlock2D"),
+                mid_block_type="UNetMidBlock2DCrossAttn", norm_num_groups=32, cross_attention_dim=768, attention_head_dim=8,
+                use_linear_projection=False)
+
+
+def sd21_unet_kwargs():
+    # the published Stable Diffusion 2.1 UNet (2.1-base: 64x64 latents; the 768-pixel model differs in sample_size = 96 alone): heads
+    # (5, 10, 20, 20), i.e. 64 channels per head everywhere, the OpenCLIP ViT-H context of 1024 channels, linear projections
+    return dict(sd15_unet_kwargs(), cross_attention_dim=1024, attention_head_dim=(5, 10, 20, 20), use_linear_projection=True)
 
 
 def chexpert_dit_b4_kwargs(wavelet_transform=True):

@@ -6,14 +6,16 @@
 // tokens; the one-token context needs no kernel (softmax over one key is 1: the class vector of the attn1.to_out epilogue).
 //
 // Both kernels are the bodies of attn_strip.h; this file adds the addressing (q_map / kv_map, separate ld_q / ld_kv) and the mode:
-// 16-bit, d = 32 / 64 / 96 / 128: attn_strip_run with raw scores (the scale folded into the exponent's FMA), key blocks of 32 (d >= 64)
-// or 64 keys.  K / V of a launch are small (n_ctx * S rows) and stay in L2: the stream that costs is q in and out back, so the unit of
+// 16-bit, d = 32 / 64 / 96 / 128 / 160: attn_strip_run with raw scores (the scale folded into the exponent's FMA), key blocks of 32
+// (d >= 64) or 64 keys.  K / V of a launch are small (n_ctx * S rows) and stay in L2: the stream that costs is q in and out back, so the unit of
 // work is a query tile.  The last block is ragged: keys >= S are staged as zeros and masked, never read (behind them lies the next
 // context, or a gap).  A sample's bits depend on its own q rows and its own context only, not on n or on the position.
 // LEN instantiations (dc_cross_attention_len): context c holds kv_len[c] <= S keys in its S rows; the length, uniform over the wave (over
 // the workgroup in the fp32 kernel), replaces S in the block count, the prefetch condition, the staging bound and the ragged mask, so
 // blocks wholly past it cost nothing and the surviving keys keep their blocks: the bits are those of a context of kv_len[c] rows.
 // fp32 and d = 16: attn_exact_run (FMA chain over the keys in order).
+// Self-attention is the same problem with q / k / v the three column offsets of a fused QKV tensor, Lq = S = L, ld_q = ld_kv and no
+// maps: heads of 160 channels (Stable Diffusion 1.x: 1280 channels in 8 heads, L <= 256), which dc_attention does not serve, run here.
 #include <stdio.h>
 #include "attn_strip.h"
 
@@ -25,7 +27,9 @@ struct CrossArgs {
   const int32_t* kv_len;   // LEN instantiations only: keys per context, clamped into [1, S] by the kernel
 };
 
-// keys per block: 8 staging chunks per lane and operand at most, and an LDS strip small enough for 2 - 4 workgroups per CU
+// keys per block: an LDS strip small enough for 2 - 4 workgroups per CU and 8 staging chunks per lane and operand at most — but
+// for D = 160: 32 keys are 32 * 20 / 64 = 10 chunks per lane, and four waves' K and V strips 4 * 2 * 32 * 168 * 2 B = 86 KB, one
+// workgroup per CU (at 64 keys they would take 172 KB, more than the CU's 160 KB)
 static constexpr int cross_kb(int D) { return D <= 32 ? 64 : 32; }
 
 // output sample i, head h (of width d): q rows through q_map, the context's k / v rows through kv_map, its S rows apart whatever its length
@@ -61,7 +65,8 @@ static int launch_cross(const CrossArgs& a, hipStream_t s, const char* fn) {
                       LEN ? "dc_cross_attention_len(mfma)" : "dc_cross_attention(mfma)");
 }
 
-// Exact fp32 kernel (f32, d = 16, and operands the matrix-core kernel's 16-byte loads cannot take): SW = 16; 24 for d = 96.  The length
+// Exact fp32 kernel (f32, d = 16, and operands the matrix-core kernel's 16-byte loads cannot take): SW = 16; 24 for d = 96 and 20 for
+// d = 160 (eight lanes a query: the xor-shuffle reduction needs a power-of-two lane count).  The length
 // is uniform over the workgroup, as the barriers need.
 template <typename T, int SW, bool LEN>
 __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) {
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) 
 static int cross_validate(const dc_cross_attention_params* p, const char* fn) {
   DC_REQUIRE(p && p->q && p->k && p->v && p->out, DC_ERR_ARG, "%s: null pointer", fn);
   DC_REQUIRE(p->dtype == DC_F32 || p->dtype == DC_BF16 || p->dtype == DC_F16, DC_ERR_DTYPE, "%s: dtype %d", fn, p->dtype);
-  DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128, DC_ERR_SHAPE, "%s: head dim %d (16/32/64/96/128)", fn, p->d);
+  DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128 || p->d == 160, DC_ERR_SHAPE, "%s: head dim %d (16/32/64/96/128/160)", fn, p->d);
   DC_REQUIRE(p->n > 0 && p->Lq > 0 && p->heads > 0, DC_ERR_SHAPE, "%s: n/Lq/heads", fn);
   DC_REQUIRE(p->S >= 1, DC_ERR_SHAPE, "%s: S=%d (at least one key)", fn, p->S);
   DC_REQUIRE(p->ld_q >= p->heads * p->d && p->ld_kv >= p->heads * p->d && p->ld_out >= p->heads * p->d, DC_ERR_SHAPE, "%s: ld", fn);
@@ -85,9 +90,9 @@ static int cross_validate(const dc_cross_attention_params* p, const char* fn) {
   return DC_OK;
 }
 
-// matrix cores: d = 32 / 64 / 96 / 128 on the strip route
+// matrix cores: d = 32 / 64 / 96 / 128 / 160 on the strip route
 static bool cross_mfma_ok(const dc_cross_attention_params* p) {
-  return (p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128) && strip_route_ok(p->dtype, p->q, p->k, p->v, p->out, p->ld_q, p->ld_kv, p->ld_out);
+  return (p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128 || p->d == 160) && strip_route_ok(p->dtype, p->q, p->k, p->v, p->out, p->ld_q, p->ld_kv, p->ld_out);
 }
 
 // validated parameters -> the launch; LEN: the instantiations that read a.kv_len
@@ -103,16 +108,17 @@ static int cross_launch(const dc_cross_attention_params* p, const int32_t* kv_le
       if (p->d == 32) return launch_cross<T, 32, LEN>(a, s, fn);
       if (p->d == 64) return launch_cross<T, 64, LEN>(a, s, fn);
       if (p->d == 96) return launch_cross<T, 96, LEN>(a, s, fn);
-      return launch_cross<T, 128, LEN>(a, s, fn);
+      if (p->d == 128) return launch_cross<T, 128, LEN>(a, s, fn);
+      return launch_cross<T, 160, LEN>(a, s, fn);
     });
-  const int SW = p->d == 96 ? 24 : 16;
+  const int SW = p->d == 96 ? 24 : p->d == 160 ? 20 : 16;
   ExactPlan e;
   const int rc = exact_plan(p->n, p->heads, p->Lq, p->S, p->d, SW, fn, e);
   if (rc != DC_OK) return rc;
   a.KB = e.KB;
   return dc_by_dtype(p->dtype, what, [&](auto t) {
     using T = decltype(t);
-    void (*kern)(const CrossArgs) = SW == 24 ? attn_cross_f32_kernel<T, 24, LEN> : attn_cross_f32_kernel<T, 16, LEN>;
+    void (*kern)(const CrossArgs) = SW == 24 ? attn_cross_f32_kernel<T, 24, LEN> : SW == 20 ? attn_cross_f32_kernel<T, 20, LEN> : attn_cross_f32_kernel<T, 16, LEN>;
     hipLaunchKernelGGL(kern, dim3(e.nb), dim3(256), e.lds, s, a);
     return dc_check_launch(fn);
   });

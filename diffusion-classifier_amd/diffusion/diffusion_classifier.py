@@ -10,6 +10,10 @@ per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text
 't5' (with `config.t5_path`, a LOCAL Hugging Face directory, and `config.prompt_tokens = S`) runs the T5 encoder on the device
 (nets/t5.py) and fills the same table: `set_class_prompts(input_ids, attention_mask)`, then everything is the 'prompt' path.
 'clip' (additive, with `config.clip_path` and `config.prompt_tokens = S`) does the same with a CLIP text transformer (nets/clip.py).
+`config.schedule`: 'cosine' and 'shifted_cosine' as in the reference; 'scaled_linear' (additive) is the discrete DDPM schedule a Stable
+Diffusion UNet is trained on — `train_timesteps` (1000) steps, `beta_start` / `beta_end` (0.00085 / 0.012), optionally read from
+`scheduler_path` (a local diffusers scheduler_config.json).  `schedule(t)` is then the log-SNR of the step t falls into, and the backbone
+is fed `noise_labels(t)`, that step as a float, instead of the log-SNR; classify only (the generation entry points raise).
 `config` is the reference's attribute bag (missing keys read as None).  Additive keys read
 here: `compute_dtype` ("bf16" default | "f16" | "f32"), `units_per_launch`, `score_plan_cache` (launch plans kept, LRU;
 default 6), `dwt_on_device` (True: `inference` applies `wavelet_dec_2(images) / 2` on the device to the batches its loader yields, on the
@@ -167,8 +171,13 @@ class DiffusionClassifier(nn.Module):
         assert pred_param in ['v', 'eps'], "Invalid prediction parameterization. Must be 'v' or 'eps'"
         self.pred_param = pred_param
         schedule = self.config.schedule
-        assert schedule in ['cosine', 'shifted_cosine'], "Invalid schedule. Must be 'cosine' or 'shifted_cosine'"
-        self.schedule = self.logsnr_schedule_cosine if schedule == 'cosine' else self.logsnr_schedule_cosine_shifted
+        assert schedule in ['cosine', 'shifted_cosine', 'scaled_linear'], "Invalid schedule. Must be 'cosine', 'shifted_cosine' or 'scaled_linear'"
+        self.discrete = schedule == 'scaled_linear'      # the backbone's time input is then the DDPM step, not the log-SNR (noise_labels)
+        if self.discrete:
+            self._init_scaled_linear()
+            self.schedule = self.logsnr_schedule_scaled_linear
+        else:
+            self.schedule = self.logsnr_schedule_cosine if schedule == 'cosine' else self.logsnr_schedule_cosine_shifted
         self.noise_d = self.config.noise_d
         self.image_d = self.config.image_size
         self.cfg_w = self.config.cfg_w
@@ -321,6 +330,57 @@ class DiffusionClassifier(nn.Module):
 
     def logsnr_schedule_cosine_shifted(self, t):
         return self.logsnr_schedule_cosine(t) + 2 * math.log(self.noise_d / self.image_d)
+
+    # ---- the discrete DDPM schedule of Stable Diffusion (additive: config.schedule = 'scaled_linear') ----
+    def _init_scaled_linear(self):
+        """N = config.train_timesteps (1000) steps of betas = linspace(sqrt(beta_start), sqrt(beta_end), N)^2 (0.00085, 0.012) ->
+        `self.ddpm_logsnr` [N] fp32, log(abar_k / (1 - abar_k)) with abar = cumprod(1 - betas) in fp64, once, on the host.
+        config.scheduler_path: a local diffusers scheduler_config.json that supplies num_train_timesteps / beta_start / beta_end (keys of
+        the config win over it where both are given), must say beta_schedule = scaled_linear and must agree with config.pred_param."""
+        cfg = self.config
+        sched = {}
+        if cfg.scheduler_path is not None:
+            import json
+            path = cfg.scheduler_path
+            if os.path.isdir(path):
+                path = os.path.join(path, "scheduler_config.json")
+            with open(path) as fh:
+                sched = json.load(fh)
+            if sched.get("beta_schedule", "scaled_linear") != "scaled_linear":
+                raise ValueError(f"{path}: beta_schedule = {sched['beta_schedule']!r}, but schedule='scaled_linear' is the only discrete schedule built here")
+            want = {"epsilon": "eps", "v_prediction": "v"}.get(sched.get("prediction_type", "epsilon"))
+            if want != self.pred_param:
+                raise ValueError(f"{path}: prediction_type = {sched.get('prediction_type')!r} but config.pred_param = {self.pred_param!r}")
+        pick = lambda own, key, default: own if own is not None else sched.get(key, default)
+        N = int(pick(cfg.train_timesteps, "num_train_timesteps", 1000))
+        b0, b1 = float(pick(cfg.beta_start, "beta_start", 0.00085)), float(pick(cfg.beta_end, "beta_end", 0.012))
+        if N < 1 or not 0.0 < b0 <= b1 < 1.0:
+            raise ValueError(f"schedule='scaled_linear' needs train_timesteps >= 1 and 0 < beta_start <= beta_end < 1, got {N}, {b0}, {b1}")
+        betas = torch.linspace(b0 ** 0.5, b1 ** 0.5, N, dtype=torch.float64) ** 2
+        abar = torch.cumprod(1.0 - betas, 0)
+        self.train_timesteps = N
+        self.ddpm_logsnr = torch.log(abar / (1.0 - abar)).to(torch.float32)      # plain attribute: host data, never part of a checkpoint
+
+    def ddpm_step(self, t):
+        """t in [0, 1] as the reference draws it -> the DDPM step k = min(floor(t N), N - 1) (int64; the product in fp64)."""
+        N = self.train_timesteps
+        t = torch.as_tensor(t)
+        return torch.clamp(torch.floor(t.detach().to("cpu", torch.float64) * N), 0, N - 1).to(torch.int64)
+
+    def logsnr_schedule_scaled_linear(self, t):
+        """log-SNR of the step t falls into, fp32 (on t's device)."""
+        return self.ddpm_logsnr[self.ddpm_step(t)].to(torch.as_tensor(t).device)
+
+    def noise_labels(self, t):
+        """What the backbone is fed as its time input at t: the log-SNR `schedule(t)` for the cosine schedules (the reference's
+        models), the DDPM step as fp32 for 'scaled_linear' (a Stable Diffusion UNet embeds the integer step)."""
+        if self.discrete:
+            return self.ddpm_step(t).to(torch.float32).to(torch.as_tensor(t).device)
+        return self.schedule(t)
+
+    def _refuse_discrete(self, what):
+        if self.discrete:
+            raise NotImplementedError(f"{what} under schedule='scaled_linear': generation on the discrete DDPM grid is not built (classify only)")
 
     @torch.no_grad()
     def encode_latents(self, x):
@@ -507,7 +567,9 @@ class DiffusionClassifier(nn.Module):
             logsnr = torch.stack([self.schedule(t_all[j].clone()) for j in range(T)])
             alpha_all = torch.stack([torch.sqrt(torch.sigmoid(logsnr[j].clone())) for j in range(T)])
             sigma_all = torch.stack([torch.sqrt(torch.sigmoid(-logsnr[j].clone())) for j in range(T)])
-        return dict(logsnr=logsnr, alpha=alpha_all, sigma=sigma_all,
+        # `label`: the backbone's time input per (trial, image) — the log-SNR tensor itself unless the schedule is discrete
+        label = torch.stack([self.noise_labels(t_all[j].clone()) for j in range(T)]) if self.discrete else logsnr
+        return dict(logsnr=logsnr, alpha=alpha_all, sigma=sigma_all, label=label,
                     eps_of=eps_of, philox=(rng == "philox" and eps is None), seed=int(seed))
 
     def check_device_errors(self):
@@ -643,6 +705,7 @@ class DiffusionClassifier(nn.Module):
         from torch's generator.
         With config.vae_path, x and the result are LATENTS (`encode_latents`), unless decode=True (additive; ValueError without
         config.vae_path): the result is then `decode_latents` of those latents, images [BS, out_channels, f H, f W]."""
+        self._refuse_discrete("sample")
         TJ.check_decode(self, decode)
         z = self._sample_latents(x, text, from_t)
         return self.decode_latents(z) if decode else z
@@ -713,6 +776,7 @@ class DiffusionClassifier(nn.Module):
                        [BS, K, out_channels, f H, f W] (`decode_latents`) and maps [BS, K, f H, f W] are taken on them by
                        `dc_abs_diff_map`; against="input": the base is `decode_latents(x)`, the VAE's own reconstruction, so the map
                        holds no reconstruction error; class ids: the base is that class's decoded trajectory.  False: nothing changes"""
+        self._refuse_discrete("counterfactual")
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class, decode=decode)
 
     @torch.no_grad()
@@ -726,6 +790,7 @@ class DiffusionClassifier(nn.Module):
         Works whatever config.sampler says (always DDIM).  HIP backbones run a pair session per chunk of images and one `dc_solver_step`
         per step and chunk; a foreign nn.Module takes the eager form (solver.py).
         With config.vae_path, x and the result are LATENTS (`encode_latents` / `decode_latents`)."""
+        self._refuse_discrete("invert")
         return S.invert(self, x, text, to_t, guidance)
 
     @torch.no_grad()
@@ -748,6 +813,7 @@ class DiffusionClassifier(nn.Module):
         and one `dc_ddpm_noise_map` per pass and chunk, nothing is copied to the host inside the loop; a foreign nn.Module takes the
         eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`.
         With config.vae_path, x, start and noise are LATENTS (`encode_latents` / `decode_latents`)."""
+        self._refuse_discrete("invert_ddpm")
         return DI.invert(self, x, text, from_t, guidance, rng, seed)
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----

@@ -1,4 +1,5 @@
-"""UNet scoring-step engine: the packed weights (`UNetWeights`) and the launch plan (`UNetPlan`) of a UNetCondition2D.
+"""UNet scoring-step engine: the packed weights (`UNetWeights`) and the launch plan (`UNetPlan`) of a UNetCondition2D or a
+StableDiffusionUNet (nets/sd_unet.py: heads per attention site, no `encoder_hid_proj`, heads of 160 channels).
 
 The plan model — ops, domains, the arena, `PlanBuilder`, the route switches — is plan.py; the weight packers are packing.py.  Their
 names that tests, tools and nets/ have always reached through this module are imported below.
@@ -9,6 +10,28 @@ from . import _lib as L
 from .packing import (HEAD_DIMS, LazyPacks, f32c, fold_layernorm_bias, geglu_perm, pack_conv3x3, pack_geglu, pack_matrix,  # noqa: F401
                       pack_tail, pack_up4, pad_head_cols, pad_head_rows, pad_vec, padded_head_dim)
 from .plan import DT, DT_SIZE, FAKE_PTR, TORCH_DT, Plan, PlanBuilder, TRef, bke, round_up, switches  # noqa: F401
+
+
+# The one head width above HEAD_DIMS a UNet plan runs, unpadded: Stable Diffusion 1.x's 1280 channels in 8 heads.  dc_attention and
+# dc_tblock_front do not serve it; attn1 and attn2 of such a site both go through dc_cross_attention (PlanBuilder.attention_strip).
+# UNetCondition2D refuses the width at construction (packing.padded_head_dim), so only a StableDiffusionUNet gets here with it.
+WIDE_HEAD = 160
+
+
+def site_head_dim(d):
+    """Channels per head q / k / v are packed with for heads of true width d: d itself at WIDE_HEAD, else padded_head_dim(d)."""
+    return d if d == WIDE_HEAD else padded_head_dim(d)
+
+
+def site_heads(cfg, key):
+    """Heads of the attention site `key` (`down_blocks.i.attentions.j`, `mid_block.attentions.0`, `up_blocks.i.attentions.j`).
+    cfg.attention_head_dim is diffusers' misnomer for that count: one int, or one entry per down block — the up blocks read it
+    reversed, the mid block takes the last."""
+    ahd = cfg.attention_head_dim
+    if isinstance(ahd, int):
+        return ahd
+    part, i = key.split(".")[:2]
+    return ahd[-1] if part == "mid_block" else ahd[int(i)] if part == "down_blocks" else ahd[::-1][int(i)]
 
 
 class UNetWeights(LazyPacks):
@@ -42,10 +65,11 @@ class UNetWeights(LazyPacks):
         conv3("conv_in", kpad=self.kin)
         lin("time_embedding.linear_1", L.DC_F32)
         lin("time_embedding.linear_2", L.DC_F32)
-        lin("encoder_hid_proj", L.DC_F32)
+        if "encoder_hid_proj.weight" in sd:      # (a StableDiffusionUNet has none: the context is attn2's input as it is)
+            lin("encoder_hid_proj", L.DC_F32)
         norm("conv_norm_out")
         conv3("conv_out", tile_n=32 if cfg.out_channels <= 32 else 128)
-        self.resnets, self.attns = [], []
+        self.resnets, self.attns, self.heads = [], [], {}      # heads: per attention site
         for k in sd:
             if k.endswith("samplers.0.conv.weight"):
                 conv3(k[: -len(".weight")])
@@ -69,8 +93,9 @@ class UNetWeights(LazyPacks):
             norm(key + ".norm"); conv1(key + ".proj_in"); conv1(key + ".proj_out")
             tb_ = key + ".transformer_blocks.0"
             norm(tb_ + ".norm1"); norm(tb_ + ".norm3")
-            d = sd[key + ".proj_in.weight"].shape[0] // cfg.attention_head_dim
-            dp = padded_head_dim(d)
+            heads = self.heads[key] = site_heads(cfg, key)
+            d = sd[key + ".proj_in.weight"].shape[0] // heads
+            dp = site_head_dim(d)
             qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0), d, dp)
             P[tb_ + ".qkv.w"] = pack_matrix(qkv, dt, device)
             P[tb_ + ".attn1.to_out.0.w"] = pack_matrix(pad_head_cols(sd[tb_ + ".attn1.to_out.0.weight"], d, dp), dt, device)
@@ -89,7 +114,6 @@ class UNetWeights(LazyPacks):
         P["attn2v.w"] = pack_matrix(vw, L.DC_F32, device)
         self.P = P
         self._sd = sd              # references only (no copy): split packing of skip-connection convs is lazy
-        self.heads = cfg.attention_head_dim
 
     def split_resnet(self, key, C0):
         """Packed halves of a skip-connection ResNet's input convs: `.conv1.wa/.wb` ([Cout, 9*C0] / [Cout, 9*C1], same
@@ -125,8 +149,8 @@ class UNetWeights(LazyPacks):
         sd = self._sd
 
         def make():
-            d = sd[tb_ + ".norm1.weight"].shape[0] // self.heads
-            qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0).float(), d, padded_head_dim(d))
+            d = sd[tb_ + ".norm1.weight"].shape[0] // self.heads[tb_[: -len(".transformer_blocks.0")]]
+            qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0).float(), d, site_head_dim(d))
             wf, bf = pack_geglu(sd[tb_ + ".ff.net.0.proj.weight"], sd[tb_ + ".ff.net.0.proj.bias"], self.dt, self.dev,
                                 ln_gamma=sd[tb_ + ".norm3.weight"], ln_beta=sd[tb_ + ".norm3.bias"])
             return {tb_ + ".qkv.wf": pack_matrix(qkv, self.dt, self.dev, col_scale=sd[tb_ + ".norm1.weight"]),
@@ -143,8 +167,8 @@ class UNetWeights(LazyPacks):
         sd = self._sd
 
         def site(key):
-            d = sd[key + ".proj_in.weight"].shape[0] // self.heads
-            return key + ".transformer_blocks.0", d, padded_head_dim(d)
+            d = sd[key + ".proj_in.weight"].shape[0] // self.heads[key]
+            return key + ".transformer_blocks.0", d, site_head_dim(d)
 
         def make():
             new, kv, self.ckv_off, o = {}, [], {}, 0
@@ -156,7 +180,7 @@ class UNetWeights(LazyPacks):
                 new[tb_ + ".attn2.to_out.0.bc"] = f32c(sd[tb_ + ".attn2.to_out.0.bias"], self.dev)
                 kv += [pad_head_rows(sd[tb_ + ".attn2.to_k.weight"], d, dp), pad_head_rows(sd[tb_ + ".attn2.to_v.weight"], d, dp)]
                 self.ckv_off[key] = o
-                o += 2 * self.heads * dp
+                o += 2 * self.heads[key] * dp
             self.ckv_total = o
             return dict(new, **{"attn2kv.w": pack_matrix(torch.cat(kv, 0), L.DC_F32, self.dev)})
 
@@ -196,14 +220,15 @@ class UNetPlan(Plan):
     """Static launch plan of one UNetCondition2D scoring step.
 
     inputs (plan-owned device buffers, refreshed per micro-batch by the caller):
-      lam [n_bj] f32;  ctx [n_ctx, hid] f32 (S = 1: one class token per context) or [n_ctx, S, hid] (S > 1: a prompt of S tokens);
+      lam [n_bj] f32 (what dc_sinusoid embeds: the log-SNR, or the DDPM step for a StableDiffusionUNet);
+      ctx [n_ctx, hid] f32 (S = 1: one class token per context) or [n_ctx, S, hid] (S > 1: a prompt of S tokens);
       varlen plans: ctx_len [n_ctx] int32, tokens of each prompt that are attended (1 ... S; S when built);  a0 = conv_in GEMM operand [n_bj, H, W, kin]
       (written by the q_sample op when `score=True`, else by the caller through `a0_view`);
       maps bj_of_unit / ctx_of_unit [U] int32.
     output: pred [U, H, W, out_channels] f32 (NHWC); with score=True also err -> errors buffer.
 
     The builders below share, on self: pb, weights and its P, sw (the route switches), cfg, G / eps (GroupNorm groups and epsilon),
-    heads, tproj (the stacked time_emb_proj output), cvec / ckv (per site: the class vector, S = 1, or the prompt's K | V) and ctx_len.
+    tproj (the stacked time_emb_proj output), cvec / ckv (per site: the class vector, S = 1, or the prompt's K | V) and ctx_len.
     """
 
     def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, share_trunk=True, score=None, device=None, S=1, varlen=False):
@@ -215,7 +240,7 @@ class UNetPlan(Plan):
         dt = weights.dt
         self.dt, self.n_bj, self.n_cls, self.n_ctx, self.S, self.varlen = dt, n_bj, n_cls, n_ctx, S, bool(varlen)
         self.weights, self.P, self.sw = weights, weights.P, switches()
-        self.G, self.eps, self.heads = cfg.norm_num_groups, cfg.norm_eps, cfg.attention_head_dim
+        self.G, self.eps = cfg.norm_num_groups, cfg.norm_eps
         U = n_bj * n_cls
         pb = self.pb = PlanBuilder(dev, n_bj, n_cls, n_ctx)
         H = W = cfg.sample_size
@@ -254,6 +279,8 @@ class UNetPlan(Plan):
         if score is not None:
             pb.score_tail(pred, score, noise, self.bj_of_unit, cfg.in_channels)
         pb.finalize(keep_alive=[pred])
+        for builder in (self.ctx_pb, pb):      # a shape libdcamd refuses is an error here, when the plan is built, never at a launch
+            builder.check_served(type(model).__name__, f"{n_bj} x {n_cls} units of {H}x{W}, S = {S}")
 
     def c(self, key):
         """Device pointer of the packed weight P[key], kept alive by the plan."""
@@ -266,8 +293,11 @@ class UNetPlan(Plan):
         pb, P, weights, cfg, S, n_ctx = self.pb, self.P, self.weights, self.cfg, self.S, self.n_ctx
         pc = self.ctx_pb = PlanBuilder(dev, 1, 1, n_ctx)
         cctx = pc.external("ctx", self.ctx, "ctx", 1, S, cfg.encoder_hid_dim, L.DC_F32)
-        hp = pc.igemm("ctx.hid_proj", cctx, pc.const(P["encoder_hid_proj.w"]), cfg.cross_attention_dim,
-                      bias=pc.const(P["encoder_hid_proj.b"]))
+        if "encoder_hid_proj.w" in P:
+            hp = pc.igemm("ctx.hid_proj", cctx, pc.const(P["encoder_hid_proj.w"]), cfg.cross_attention_dim,
+                          bias=pc.const(P["encoder_hid_proj.b"]))
+        else:
+            hp = cctx                  # no projection (StableDiffusionUNet): the context rows are the side path's input themselves
         self.cvec, self.ckv = {}, {}
         if S == 1:
             # one key: softmax = 1, attn2 is to_out(to_v(ctx)), a row vector of the attn1.to_out epilogue
@@ -288,7 +318,8 @@ class UNetPlan(Plan):
             pc.finalize(keep_alive=[kvall])
             kvx = pb.external("ctx.kv", pc.tensor_view(kvall), "ctx", 1, S, weights.ckv_total, self.dt)
             for k in weights.attns:
-                Cq = self.heads * padded_head_dim(P[k + ".norm.g"].shape[0] // self.heads)
+                heads = weights.heads[k]
+                Cq = heads * site_head_dim(P[k + ".norm.g"].shape[0] // heads)
                 self.ckv[k] = (kvx.view(weights.ckv_off[k], Cq), kvx.view(weights.ckv_off[k] + Cq, Cq))
 
     def walk(self, a0, share_trunk):
@@ -398,25 +429,25 @@ class UNetPlan(Plan):
         return pb.igemm(key + ".conv1", h, c(key + ".conv1.w"), Cout, taps=9, bias=c(key + ".conv1.b"), rowvec=tvec, qstats=qs)
 
     def transformer(self, key, x):
-        pb, c, heads = self.pb, self.c, self.heads
+        pb, c, heads = self.pb, self.c, self.weights.heads[key]
         tbk = key + ".transformer_blocks.0"
         d = x.C // heads
-        Cq = heads * padded_head_dim(d)    # q / k / v / attention width: heads of d channels padded to a served width
+        Cq = heads * site_head_dim(d)      # q / k / v / attention width: heads of d channels padded to a served width (160: as they are)
         h = pb.pn_claim(x, c(key + ".norm.g"), c(key + ".norm.b"), self.G, 1e-6, False)
         if h is None:
             h = pb.groupnorm(key + ".gn", x, c(key + ".norm.g"), c(key + ".norm.b"), self.G, 1e-6, False)
         if self.S > 1:
-            h = self.prompt_attention(key, tbk, self.self_attention(key, tbk, h, None, d, Cq), d, Cq)
+            h = self.prompt_attention(key, tbk, self.self_attention(key, tbk, h, None, heads, d, Cq), heads, d, Cq)
         elif self.sw.tblock and h.dom == pb.dom(h, self.cvec[key]) and pb.tblock_front_ok(h, heads):
             # proj_in -> LayerNorm -> q/k/v -> attention -> to_out + class vector + residual in ONE launch, the sample on chip
             assert Cq == x.C, "dc_tblock_front takes unpadded heads only"
             h = pb.tblock_front(tbk + ".front", h, c(key + ".proj_in.w"), c(key + ".proj_in.b"), c(tbk + ".norm1.g"), c(tbk + ".norm1.b"),
                                 c(tbk + ".qkv.w"), c(tbk + ".attn1.to_out.0.w"), c(tbk + ".attn1.to_out.0.b"), self.cvec[key], heads, 1e-5)
         else:
-            h = self.self_attention(key, tbk, h, self.cvec[key], d, Cq)
+            h = self.self_attention(key, tbk, h, self.cvec[key], heads, d, Cq)
         return self.feed_forward(key, tbk, x, h)
 
-    def self_attention(self, key, tbk, h, rowvec, d, Cq):
+    def self_attention(self, key, tbk, h, rowvec, heads, d, Cq):
         """proj_in -> LayerNorm -> q/k/v -> attention -> to_out + residual as a chain of launches.  rowvec: the class vector of a
         one-token context (attn2 of one key is a row vector of this epilogue); None in a prompt plan."""
         pb, c, Cc = self.pb, self.c, h.C
@@ -424,10 +455,12 @@ class UNetPlan(Plan):
         # (q/k/v keeps its LayerNorm launch: measured faster on the 256x256 tile + LayerNorm than on the row-standardising GEMM)
         hn = pb.layernorm(tbk + ".ln1", h, c(tbk + ".norm1.g"), c(tbk + ".norm1.b"), 1e-5)
         qkv = pb.igemm(tbk + ".qkv", hn, c(tbk + ".qkv.w"), 3 * Cq)
-        o = pb.attention(tbk + ".attn1", qkv.view(0, Cq), qkv.view(Cq, Cq), qkv.view(2 * Cq, Cq), self.heads, d)
+        # heads of 160 channels: dc_attention does not serve them; the strip kernel of dc_cross_attention in its self form does
+        attend = pb.attention_strip if d == WIDE_HEAD else pb.attention
+        o = attend(tbk + ".attn1", qkv.view(0, Cq), qkv.view(Cq, Cq), qkv.view(2 * Cq, Cq), heads, d)
         return pb.igemm(tbk + ".attn_out", o, c(tbk + ".attn1.to_out.0.w"), Cc, bias=c(tbk + ".attn1.to_out.0.b"), rowvec=rowvec, residual=h)
 
-    def prompt_attention(self, key, tbk, h, d, Cq):
+    def prompt_attention(self, key, tbk, h, heads, d, Cq):
         """attn2 over the S > 1 tokens of a prompt, behind the self-attention chain without a class vector (the one-launch front,
         dc_tblock_front, is built around that vector's epilogue and is not used in a prompt plan):
         norm2 -> to_q -> dc_cross_attention against this site's K | V of the context plan -> attn2.to_out + bias + residual.
@@ -439,7 +472,7 @@ class UNetPlan(Plan):
         else:
             hn = pb.layernorm(tbk + ".ln2", h, c(tbk + ".norm2.g"), c(tbk + ".norm2.b"), 1e-5)
             q2 = pb.igemm(tbk + ".attn2.to_q", hn, c(tbk + ".attn2.to_q.w"), Cq)
-        o2 = pb.cross_attention(tbk + ".attn2", q2, self.ckv[key][0], self.ckv[key][1], self.heads, d, kv_len=self.ctx_len_ptr)
+        o2 = pb.cross_attention(tbk + ".attn2", q2, self.ckv[key][0], self.ckv[key][1], heads, d, kv_len=self.ctx_len_ptr)
         return pb.igemm(tbk + ".attn2_out", o2, c(tbk + ".attn2.to_out.0.wc"), h.C, bias=c(tbk + ".attn2.to_out.0.bc"), residual=h)
 
     def feed_forward(self, key, tbk, x, h):

@@ -44,10 +44,12 @@ def _attention(qdim, ctx_dim, inner):
     return a
 
 
-def _transformer2d(ch, xdim, groups):
+def _transformer2d(ch, xdim, groups, linear=False):
+    """linear: proj_in / proj_out as nn.Linear [C, C] (diffusers' use_linear_projection) instead of 1x1 convs [C, C, 1, 1]: the same
+    arithmetic under another weight shape."""
     t = _Bag()
     t.norm = nn.GroupNorm(groups, ch, eps=1e-6)
-    t.proj_in = nn.Conv2d(ch, ch, 1)
+    t.proj_in = nn.Linear(ch, ch) if linear else nn.Conv2d(ch, ch, 1)
     b = _Bag()
     b.norm1 = nn.LayerNorm(ch)
     b.attn1 = _attention(ch, None, ch)
@@ -59,7 +61,7 @@ def _transformer2d(ch, xdim, groups):
     proj.proj = nn.Linear(ch, 8 * ch)
     b.ff.net = nn.ModuleList([proj, nn.Identity(), nn.Linear(4 * ch, ch)])
     t.transformer_blocks = nn.ModuleList([b])
-    t.proj_out = nn.Conv2d(ch, ch, 1)
+    t.proj_out = nn.Linear(ch, ch) if linear else nn.Conv2d(ch, ch, 1)
     return t
 
 
@@ -247,12 +249,23 @@ class UNetCondition2D(_HipBackbone):
             block_out_channels=boc, layers_per_block=lpb, norm_num_groups=G, norm_eps=eps, cross_attention_dim=xdim,
             encoder_hid_dim=encoder_hid_dim, encoder_hid_dim_type=encoder_hid_dim_type,
             attention_head_dim=attention_head_dim, flip_sin_to_cos=flip_sin_to_cos, freq_shift=freq_shift)
+        self._build_modules(in_channels, out_channels, encoder_hid_dim)
+        self._init_engine()
+
+    def _build_modules(self, in_channels, out_channels, hid_proj_dim, linear=False):
+        """The parameter-holding modules under diffusers' key names, from `self.config`.  hid_proj_dim None: no `encoder_hid_proj`;
+        linear: proj_in / proj_out as nn.Linear (both StableDiffusionUNet's)."""
+        cfg = self.config
+        boc, lpb, G, eps, xdim = cfg.block_out_channels, cfg.layers_per_block, cfg.norm_num_groups, cfg.norm_eps, cfg.cross_attention_dim
+        down_block_types, up_block_types = cfg.down_block_types, cfg.up_block_types
+        nb, rboc = len(boc), boc[::-1]
         temb = boc[0] * 4
         self.conv_in = nn.Conv2d(in_channels, boc[0], 3, padding=1)
         self.time_embedding = _Bag()
         self.time_embedding.linear_1 = nn.Linear(boc[0], temb)
         self.time_embedding.linear_2 = nn.Linear(temb, temb)
-        self.encoder_hid_proj = nn.Linear(encoder_hid_dim, xdim)
+        if hid_proj_dim is not None:
+            self.encoder_hid_proj = nn.Linear(hid_proj_dim, xdim)
         self.down_blocks = nn.ModuleList()
         out = boc[0]
         for i, kind in enumerate(down_block_types):
@@ -262,12 +275,12 @@ class UNetCondition2D(_HipBackbone):
             blk = _Bag()
             blk.resnets = nn.ModuleList([_resnet(cin if j == 0 else out, out, temb, G, eps) for j in range(lpb[i])])
             if kind == "CrossAttnDownBlock2D":
-                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G) for _ in range(lpb[i])])
+                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G, linear) for _ in range(lpb[i])])
             if i != nb - 1:
                 blk.downsamplers = nn.ModuleList([_sampler(out, 2)])
             self.down_blocks.append(blk)
         self.mid_block = _Bag()
-        self.mid_block.attentions = nn.ModuleList([_transformer2d(boc[-1], xdim, G)])
+        self.mid_block.attentions = nn.ModuleList([_transformer2d(boc[-1], xdim, G, linear)])
         self.mid_block.resnets = nn.ModuleList([_resnet(boc[-1], boc[-1], temb, G, eps) for _ in range(2)])
         self.up_blocks = nn.ModuleList()
         rlpb = lpb[::-1]
@@ -282,13 +295,12 @@ class UNetCondition2D(_HipBackbone):
             blk.resnets = nn.ModuleList(
                 [_resnet((prev if j == 0 else out) + (cin if j == n - 1 else out), out, temb, G, eps) for j in range(n)])
             if kind == "CrossAttnUpBlock2D":
-                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G) for _ in range(n)])
+                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G, linear) for _ in range(n)])
             if i != nb - 1:
                 blk.upsamplers = nn.ModuleList([_sampler(out, 1)])
             self.up_blocks.append(blk)
         self.conv_norm_out = nn.GroupNorm(G, boc[0], eps=eps)
         self.conv_out = nn.Conv2d(boc[0], out_channels, 3, padding=1)
-        self._init_engine()
 
     # ---- engine hooks -----------------------------------------------------------------
     weights_class, im2col, patch = E.UNetWeights, 1, 0

@@ -483,6 +483,20 @@ class PlanBuilder:
             self.emit(L.OP_CROSS_ATTENTION_LEN, dict(f, kv_len=kv_len), [q, k, v], [out], meta)
         return out
 
+    def attention_strip(self, name, q, k, v, heads, d):
+        """Self-attention as `attention` states it, launched through dc_cross_attention in its self form: q / k / v are the three
+        column offsets of one fused QKV tensor, the keys of a sample are its own L rows (Lq = S = L, ld_q = ld_kv, no maps).  For
+        heads of 160 channels, which dc_attention does not serve and the strip kernel does (csrc/attention_cross.hip)."""
+        out = self.tensor(name, q.dom, q.H, q.W, q.C, q.dt)
+        dp, Lq, n = q.C // heads, q.H * q.W, self.n[q.dom]
+        assert d <= dp and dp * heads == q.C and k.C == q.C and v.C == q.C and k.dom == q.dom and v.dom == q.dom, (d, dp, heads, q.C, k.C)
+        assert k.ld == q.ld and v.ld == q.ld and k.dt == q.dt and v.dt == q.dt
+        f = dict(q=q, k=k, v=v, out=out, q_map=None, kv_map=None, dtype=q.dt, n=n, Lq=Lq, S=Lq, heads=heads, d=dp,
+                 ld_q=q.ld, ld_kv=k.ld, ld_out=out.ld, scale=float(d) ** -0.5)
+        self.emit(L.OP_CROSS_ATTENTION, f, [q, k, v], [out],
+                  dict(name=name, family="attention", flops=4.0 * n * heads * Lq * Lq * dp, bytes=4.0 * n * Lq * q.C * DT_SIZE[q.dt]))
+        return out
+
     def tblock_front_ok(self, x, heads):
         """Can ONE launch take proj_in -> LayerNorm -> q/k/v -> attention -> to_out of this block input (dc_tblock_front_ok)?"""
         fn = getattr(L.lib(), "dc_tblock_front_ok", None)

@@ -111,6 +111,9 @@ class _Runner:
 
     def __init__(self, dc, backbone, x, T, draws, dev):
         self.dc, self.bb, self.x, self.T, self.d, self.dev = dc, backbone, x, T, draws, dev
+        # what the backbone is fed as its time input: the log-SNR itself, unless the draws carry a `label` of their own (the
+        # 'scaled_linear' schedule: the DDPM step; DiffusionClassifier.noise_labels)
+        self.label = draws.get("label", draws["logsnr"])
 
     def evidence_begin(self, n_stages):
         BS, _, H, W = self.x.shape
@@ -166,7 +169,7 @@ class _ForeignRunner(_Runner):
             full = bl == list(range(x.shape[0]))       # the reference's own batch: use the tensors as they are
             al = (d["alpha"][j] if full else d["alpha"][j, bs]).view(-1, 1, 1, 1).to(x.device)
             sg = (d["sigma"][j] if full else d["sigma"][j, bs]).view(-1, 1, 1, 1).to(x.device)
-            lam = (d["logsnr"][j] if full else d["logsnr"][j, bs]).to(x.device)
+            lam = (self.label[j] if full else self.label[j, bs]).to(x.device)
             e = d["eps_of"][j]
             e = (e if full else e[bs.to(e.device)]).to(x.device)
             z = al * (x if full else x[bs.to(x.device)]) + sg * e
@@ -325,7 +328,8 @@ class _HipRunner(_Runner):
             ent = cache[ck] = index_blocks(layout, pairs, None if classes.is_cuda else classes, ncls, T, dump)
         tmpl, jsb = ent
         host[:n_mb].copy_(tmpl)
-        rows3 = [(layout.fields[f][0], d[src]) for f, src in (("lam", "logsnr"), ("alpha", "alpha"), ("sigma", "sigma"))]
+        # (the block's `lam` slot feeds dc_sinusoid alone: it holds the backbone's time input, `self.label`)
+        rows3 = [(layout.fields["lam"][0], self.label)] + [(layout.fields[f][0], d[f]) for f in ("alpha", "sigma")]
         for m in range(n_mb):
             js, bs = jsb[m]
             for sl, src in rows3:

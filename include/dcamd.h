@@ -400,9 +400,11 @@ int dc_latent_im2col(const dc_latent_im2col_params* p, dc_stream s);
  * offset pointers), out [n, Lq, heads, d] with row stride ld_out; all in `dtype`.  Every one of the S keys is attended (the reference
  * passes no mask, so padded prompt rows take part; dc_cross_attention_len below takes a key count per context).  Rows behind the S-th
  * of a context are never read.
- * scale must be > 0 and S >= 1 (DC_ERR_ARG / DC_ERR_SHAPE); head dims d = 16, 32, 64, 96, 128, narrower heads zero-padded by the
- * caller exactly as for dc_attention (scale of the true width; the pad columns of the output are zero).
- * 16-bit with d = 32 / 64 / 96 / 128 and 16-byte aligned rows: the matrix-core kernel (one wave per 32 queries of a (sample, head),
+ * scale must be > 0 and S >= 1 (DC_ERR_ARG / DC_ERR_SHAPE); head dims d = 16, 32, 64, 96, 128, 160 (DC_ERR_SHAPE otherwise), narrower
+ * heads zero-padded by the caller exactly as for dc_attention (scale of the true width; the pad columns of the output are zero).
+ * 160 is Stable Diffusion 1.x's 1280-channel level in 8 heads; its self-attention is this function too: q / k / v the three column
+ * offsets of the fused QKV tensor, Lq = S = L, ld_q = ld_kv, both maps NULL (dc_attention serves no 160).
+ * 16-bit with d = 32 / 64 / 96 / 128 / 160 and 16-byte aligned rows: the matrix-core kernel (one wave per 32 queries of a (sample, head),
  * online softmax over key blocks, fp32 statistics); f32, d = 16 and unaligned operands: the exact fp32 kernel.  Fixed summation
  * order, no atomics: the bits of out[i] depend on its own q rows and its own context only, not on n or on i. */
 typedef struct {
