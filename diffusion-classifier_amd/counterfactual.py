@@ -22,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import ddpm_invert as DI
+from . import discrete as DG
 from . import solver as S
 from . import trajectory as TJ
 from .trajectory import image_chunks      # noqa: F401  (its home is the walk; importable here as ever)
@@ -97,15 +98,19 @@ def run_foreign(dc, z0, cl, from_t, noise_maps=None):
     """The reference's form from the start z0 [BS, C, H, W]: `trajectory.ancestral_eager` over the K columns of cl, every class adding
     the step's one `randn_like` — or, with noise_maps [n, BS, C, H, W] (ddpm_invert.py), noise_maps[i] in place of the draw."""
     conds, null = column_contexts(dc, cl, z0.device)
-    return torch.stack(TJ.ancestral_eager(dc, z0, conds, null, from_t, noise_maps=noise_maps), dim=1).to(torch.float32)
+    if dc.discrete:
+        mus = DG.ancestral_eager(dc, z0, conds, null, TJ.grid(dc, from_t, 0.0), noise_maps=noise_maps)
+    else:
+        mus = TJ.ancestral_eager(dc, z0, conds, null, from_t, noise_maps=noise_maps)
+    return torch.stack(mus, dim=1).to(torch.float32)
 
 
 def run_foreign_solver(dc, z0, cl, from_t, sampler):
     """The same under "ddim" / "dpmpp_2m": the K classes by `solver.run_eager` from the one start, no draw after it."""
     conds, null = column_contexts(dc, cl, z0.device)
-    lams = S.grid_lams(dc, from_t, 0.0)
-    scal = S.step_scalars(lams, sampler, "denoise")
-    return torch.stack([S.run_eager(dc, z0, lams, scal, dc.cfg_w, cond, null) for cond in conds], dim=1).to(torch.float32)
+    g = TJ.grid(dc, from_t, 0.0)
+    scal = S.step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete)
+    return torch.stack([S.run_eager(dc, z0, g, scal, dc.cfg_w, cond, null) for cond in conds], dim=1).to(torch.float32)
 
 
 def decode_hip(dc, walk, z0, lams, noise):
@@ -162,16 +167,18 @@ def run(dc, x, classes, from_t, against, rng, seed, pixel_space, start="noise", 
         z0, nmaps = inv.start, inv.noise
     if hip:
         # the walk's refusals before the first draw here; its sessions open at its first pass, after the inversions' (the same slots)
-        lams = S.grid_lams(dc, from_t, 0.0)
-        walk = TJ.Walk(dc, dc.ema.ema_model, x, cl, lams, dc.cfg_w)
-        noise = TJ.NoiseSource(x, rng, seed, len(lams))
+        g = TJ.grid(dc, from_t, 0.0)
+        walk = TJ.Walk(dc, dc.ema.ema_model, x, cl, g, dc.cfg_w)
+        noise = TJ.NoiseSource(x, rng, seed, len(g.lam))
         if z0 is None:
             z0 = S.initial_latent(dc, x, from_t, noise)
         if sampler is not None:
-            samples = S.run_walk(walk, z0, S.step_scalars(lams, sampler, "denoise"))
+            samples = S.run_walk(walk, z0, S.step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete))
         else:
             noise.like = z0                                              # the steps draw in the start's dtype, as `sample` does
-            samples = decode_hip(dc, walk, z0, lams, nmaps.__getitem__ if nmaps is not None else lambda i: noise(i + 1))
+            draw = nmaps.__getitem__ if nmaps is not None else lambda i: noise(i + 1)
+            # the discrete grid: the unclipped mean by dc_solver_step and the add in torch (discrete.py); otherwise the fused step
+            samples = DG.decode_hip(walk, z0, g, draw) if dc.discrete else decode_hip(dc, walk, z0, g.lam, draw)
     else:
         z0 = S.initial_latent(dc, x, from_t) if z0 is None else z0
         samples = run_foreign(dc, z0, cl, from_t, nmaps) if sampler is None else run_foreign_solver(dc, z0, cl, from_t, sampler)

@@ -20,6 +20,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from . import discrete as DG
 from . import solver as S
 from . import trajectory as TJ
 
@@ -42,19 +43,23 @@ def max_bytes_of(config):
 
 
 def grid(dc, from_t):
-    """(lams, scal, alsg): lambda of the n + 1 grid points, (c, alpha_t, sigma_t, alpha_s, sd) of pass i = 0 .. n - 1 and (alpha_i,
-    sigma_i) of every point as 0-dim fp32 tensors on the host."""
-    lams = S.grid_lams(dc, from_t, 0.0)
+    """(g, scal, alsg): the `trajectory.Grid` of the n + 1 points, (c, alpha_t, sigma_t, alpha_s, sd) of pass i = 0 .. n - 1 and
+    (alpha_i, sigma_i) of every point as 0-dim fp32 tensors on the host."""
+    g = TJ.grid(dc, from_t, 0.0)
+    lams = g.lam
     scal = [dc._sampler_step_scalars(lams[i], lams[i + 1]) for i in range(len(lams) - 1)]
     lam = [v.detach().float().cpu().reshape(()) for v in lams]
     alsg = [(torch.sqrt(torch.sigmoid(v)), torch.sqrt(torch.sigmoid(-v))) for v in lam]
-    return lams, scal, alsg
+    return g, scal, alsg
 
 
 def run_eager(dc, x, lab, from_t, w):
     """The statement on any backbone: -> (start, noise).  The draws are `randn_like(x)` in the order i = 0 .. n."""
+    if dc.discrete:
+        return DG.noise_maps_eager(dc, x, lab, TJ.grid(dc, from_t, 0.0), w)
     dev = x.device
-    lams, _, alsg = grid(dc, from_t)
+    g, _, alsg = grid(dc, from_t)
+    lams = g.lam
     n = len(lams) - 1
     lab_dev = dc.encoder.weight.device if dc.encoder is not None else dev
     cond, null, lens = S.contexts(dc, lab.to(lab_dev), dev, dc.ema.ema_model)
@@ -66,8 +71,9 @@ def run_eager(dc, x, lab, from_t, w):
     for i in range(n):
         z_next = latent(i + 1)
         lam_t, lam_s = lams[i].to(dev).unsqueeze(0), lams[i + 1].to(dev).unsqueeze(0)
-        pred = dc.ema(z, lam_t, encoder_hidden_states=cond, **kc)
-        u_pred = dc.ema(z, lam_t, encoder_hidden_states=null, **kn)
+        label = g.label[i].to(dev).unsqueeze(0)
+        pred = dc.ema(z, label, encoder_hidden_states=cond, **kc)
+        u_pred = dc.ema(z, label, encoder_hidden_states=null, **kn)
         mu, var = dc.ddpm_sampler_step(z, pred, u_pred, lam_t.clone().detach(), lam_s.clone().detach(), w=w)
         noise[i] = (z_next - mu) / torch.sqrt(var)
         z = z_next
@@ -106,9 +112,11 @@ def invert(dc, x, text, from_t, guidance, rng, seed, name="text"):
         raise ValueError(f"invert_ddpm stores one noise map per step: {n} x {tuple(x.shape)} f32 = {size} bytes, more than "
                          f"config.ddpm_invert_max_bytes = {cap} (fewer sampling_steps, a smaller batch, or raise the key)")
     if hip:
-        lams, scal, alsg = grid(dc, from_t)
-        walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), lams, w, who="invert_ddpm", noun="fused noise map")
-        start, noise = run_hip(walk, x, scal, alsg, TJ.NoiseSource(x, rng, seed, n + 1))
+        g, scal, alsg = grid(dc, from_t)
+        walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), g, w, who="invert_ddpm", noun="fused noise map")
+        draws = TJ.NoiseSource(x, rng, seed, n + 1)
+        # the discrete grid: the unclipped mean by dc_solver_step and the map in torch (discrete.py); otherwise the fused kernel
+        start, noise = DG.noise_maps_hip(walk, x, g, draws) if dc.discrete else run_hip(walk, x, scal, alsg, draws)
     else:
         start, noise = run_eager(dc, x, lab, from_t, w)
     return DdpmInversion(start, noise, from_t, w)

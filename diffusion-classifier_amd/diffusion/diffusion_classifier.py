@@ -13,7 +13,11 @@ per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text
 `config.schedule`: 'cosine' and 'shifted_cosine' as in the reference; 'scaled_linear' (additive) is the discrete DDPM schedule a Stable
 Diffusion UNet is trained on — `train_timesteps` (1000) steps, `beta_start` / `beta_end` (0.00085 / 0.012), optionally read from
 `scheduler_path` (a local diffusers scheduler_config.json).  `schedule(t)` is then the log-SNR of the step t falls into, and the backbone
-is fed `noise_labels(t)`, that step as a float, instead of the log-SNR; classify only (the generation entry points raise).
+is fed `noise_labels(t)`, that step as a float, instead of the log-SNR.  Generation on that grid is opt-in: with
+`config.timestep_spacing` = "trailing" | "leading" (additive; diffusers' two integer spacings, `steps_offset` an additive int read from
+`scheduler_path` too) `sample`, `counterfactual`, `invert` and `invert_ddpm` walk the integer steps k_0 > ... > k_n = 0 of
+`trajectory.discrete_steps`, feed the backbone float(k_i), take every scalar from the step's log-SNR and clip nothing (scaled VAE latents
+are not in [-1, 1]); without the key they raise NotImplementedError under this schedule, with it under a cosine schedule ValueError.
 `config` is the reference's attribute bag (missing keys read as None).  Additive keys read
 here: `compute_dtype` ("bf16" default | "f16" | "f32"), `units_per_launch`, `score_plan_cache` (launch plans kept, LRU;
 default 6), `dwt_on_device` (True: `inference` applies `wavelet_dec_2(images) / 2` on the device to the batches its loader yields, on the
@@ -85,6 +89,7 @@ from .. import _lib as L
 from .. import dist as D
 from .. import counterfactual as CF
 from .. import ddpm_invert as DI
+from .. import discrete as DG
 from .. import posterior as P
 from .. import evidence as EV
 from .. import solver as S
@@ -173,6 +178,13 @@ class DiffusionClassifier(nn.Module):
         schedule = self.config.schedule
         assert schedule in ['cosine', 'shifted_cosine', 'scaled_linear'], "Invalid schedule. Must be 'cosine', 'shifted_cosine' or 'scaled_linear'"
         self.discrete = schedule == 'scaled_linear'      # the backbone's time input is then the DDPM step, not the log-SNR (noise_labels)
+        spacing = self.config.timestep_spacing
+        if spacing not in (None, "trailing", "leading"):
+            raise ValueError(f"config.timestep_spacing must be None, 'trailing' or 'leading', got {spacing!r}")
+        if spacing is not None and not self.discrete:
+            raise ValueError(f"config.timestep_spacing = {spacing!r} belongs to the discrete grid of schedule='scaled_linear', "
+                             f"not to schedule={schedule!r}: the cosine schedules generate on linspace(from_t, 0, sampling_steps + 1)")
+        self.timestep_spacing = spacing
         if self.discrete:
             self._init_scaled_linear()
             self.schedule = self.logsnr_schedule_scaled_linear
@@ -359,6 +371,10 @@ class DiffusionClassifier(nn.Module):
         betas = torch.linspace(b0 ** 0.5, b1 ** 0.5, N, dtype=torch.float64) ** 2
         abar = torch.cumprod(1.0 - betas, 0)
         self.train_timesteps = N
+        off = pick(cfg.steps_offset, "steps_offset", 0)
+        if isinstance(off, bool) or not isinstance(off, int):
+            raise ValueError(f"steps_offset must be an int, got {off!r}")
+        self.steps_offset = off                                                  # added to every 'leading' step of the generation grid
         self.ddpm_logsnr = torch.log(abar / (1.0 - abar)).to(torch.float32)      # plain attribute: host data, never part of a checkpoint
 
     def ddpm_step(self, t):
@@ -378,9 +394,16 @@ class DiffusionClassifier(nn.Module):
             return self.ddpm_step(t).to(torch.float32).to(torch.as_tensor(t).device)
         return self.schedule(t)
 
-    def _refuse_discrete(self, what):
-        if self.discrete:
-            raise NotImplementedError(f"{what} under schedule='scaled_linear': generation on the discrete DDPM grid is not built (classify only)")
+    def _refuse_discrete(self, what, from_t):
+        """Generation under schedule='scaled_linear' is opt-in: without config.timestep_spacing there is no map from
+        linspace(from_t, 0, sampling_steps + 1) to DDPM steps.  With the key, the grid of this call is built once here so that an
+        impossible one (trajectory.discrete_steps) is refused before any draw."""
+        if not self.discrete:
+            return
+        if self.timestep_spacing is None:
+            raise NotImplementedError(f"{what} under schedule='scaled_linear' needs config.timestep_spacing = 'trailing' | 'leading': "
+                                      "how sampling_steps are laid on the discrete DDPM grid is the caller's choice (unset: classify only)")
+        TJ.discrete_steps(self, from_t)
 
     @torch.no_grad()
     def encode_latents(self, x):
@@ -704,8 +727,11 @@ class DiffusionClassifier(nn.Module):
         sampling_steps deterministic passes on linspace(from_t, 0, sampling_steps + 1) (solver.py) — only the initial draw is taken
         from torch's generator.
         With config.vae_path, x and the result are LATENTS (`encode_latents`), unless decode=True (additive; ValueError without
-        config.vae_path): the result is then `decode_latents` of those latents, images [BS, out_channels, f H, f W]."""
-        self._refuse_discrete("sample")
+        config.vae_path): the result is then `decode_latents` of those latents, images [BS, out_channels, f H, f W].
+        schedule='scaled_linear' (needs config.timestep_spacing): the grid is the integer steps of `trajectory.discrete_steps`, x is
+        diffused to its first point k_0, the backbone is fed float(k_i), and nothing is clipped — the ancestral mean is a z + b x
+        (discrete.py), the last deterministic pass returns the data prediction as it is."""
+        self._refuse_discrete("sample", from_t)
         TJ.check_decode(self, decode)
         z = self._sample_latents(x, text, from_t)
         return self.decode_latents(z) if decode else z
@@ -720,14 +746,18 @@ class DiffusionClassifier(nn.Module):
         backbone = self.ema.ema_model
         cond, null, lens = TJ.contexts(self, text, dev, backbone)             # lens: the rows' token counts of a ragged prompt table
         if not (hasattr(backbone, "forward_pair") and cond is not None and z_t.is_cuda):
+            if self.discrete:
+                return DG.ancestral_eager(self, z_t, [cond], null, TJ.grid(self, from_t, 0.0), lens)[0]
             return TJ.ancestral_eager(self, z_t, [cond], null, from_t, lens)[0]
         kw = {"cond_lengths": lens["cond"], "null_lengths": lens["null"]} if lens else {}
-        steps = torch.linspace(from_t, 0.0, self.config.sampling_steps + 1)
-        n = len(steps) - 1
+        g = TJ.grid(self, from_t, 0.0)
+        if self.discrete:                                                     # unclipped: the mean by dc_solver_step, the add in torch
+            return DG.sample_pair(self, backbone, z_t, cond, null, kw, g)
+        n = len(g.lam) - 1
         for i in range(n + 1):                                                # the last pass repeats step n-1 and keeps the mean
-            u_t, u_s = (steps[i], steps[i + 1]) if i < n else (steps[-2], steps[-1])
-            lam_t, lam_s = self.schedule(u_t).to(dev).unsqueeze(0), self.schedule(u_s).to(dev).unsqueeze(0)
-            pair = backbone.forward_pair(z_t, lam_t, cond, null, **kw)
+            t = min(i, n - 1)
+            lam_t, lam_s = g.lam[t].to(dev).unsqueeze(0), g.lam[t + 1].to(dev).unsqueeze(0)
+            pair = backbone.forward_pair(z_t, g.label[t].to(dev).unsqueeze(0), cond, null, **kw)
             noise = torch.randn_like(z_t).to(torch.float32).contiguous() if i < n else None
             z_t = self._fused_sampler_step(backbone, z_t, pair, lam_t, lam_s, noise).to(z_t.dtype)
         return z_t
@@ -775,8 +805,11 @@ class DiffusionClassifier(nn.Module):
           decode       True (config.vae_path only; ValueError without it or together with pixel_space): samples are the decoded images
                        [BS, K, out_channels, f H, f W] (`decode_latents`) and maps [BS, K, f H, f W] are taken on them by
                        `dc_abs_diff_map`; against="input": the base is `decode_latents(x)`, the VAE's own reconstruction, so the map
-                       holds no reconstruction error; class ids: the base is that class's decoded trajectory.  False: nothing changes"""
-        self._refuse_discrete("counterfactual")
+                       holds no reconstruction error; class ids: the base is that class's decoded trajectory.  False: nothing changes
+        schedule='scaled_linear' (needs config.timestep_spacing): all of the above on the integer grid of `sample`, unclipped — the
+        ancestral passes are one unclamped `dc_solver_step` (the posterior mean) and one torch add of the shared noise per pass and
+        chunk (discrete.py)"""
+        self._refuse_discrete("counterfactual", from_t)
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class, decode=decode)
 
     @torch.no_grad()
@@ -789,8 +822,10 @@ class DiffusionClassifier(nn.Module):
                     inversion is known to be unstable
         Works whatever config.sampler says (always DDIM).  HIP backbones run a pair session per chunk of images and one `dc_solver_step`
         per step and chunk; a foreign nn.Module takes the eager form (solver.py).
-        With config.vae_path, x and the result are LATENTS (`encode_latents` / `decode_latents`)."""
-        self._refuse_discrete("invert")
+        With config.vae_path, x and the result are LATENTS (`encode_latents` / `decode_latents`).
+        schedule='scaled_linear' (needs config.timestep_spacing): the grid is `sample`'s integer steps from to_t in reverse, so inversion
+        and decode visit the same points; the data prediction is not clipped."""
+        self._refuse_discrete("invert", to_t)
         return S.invert(self, x, text, to_t, guidance)
 
     @torch.no_grad()
@@ -812,8 +847,10 @@ class DiffusionClassifier(nn.Module):
         Every refusal comes before the first draw.  HIP backbones run a pair session per chunk of images (classify's launch-size rule)
         and one `dc_ddpm_noise_map` per pass and chunk, nothing is copied to the host inside the loop; a foreign nn.Module takes the
         eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`.
-        With config.vae_path, x, start and noise are LATENTS (`encode_latents` / `decode_latents`)."""
-        self._refuse_discrete("invert_ddpm")
+        With config.vae_path, x, start and noise are LATENTS (`encode_latents` / `decode_latents`).
+        schedule='scaled_linear' (needs config.timestep_spacing): the same on `sample`'s integer grid with the unclipped mean
+        mu_i = a z + b x — one unclamped `dc_solver_step` per pass and chunk, the map (x_{i+1} - mu_i) / sd_i in torch on that mean."""
+        self._refuse_discrete("invert_ddpm", from_t)
         return DI.invert(self, x, text, from_t, guidance, rng, seed)
 
     # ---- inference driver and checkpoint ingest (reference :581-655, :769-805; SURVEY §8f rows 1-2) ----

@@ -123,9 +123,15 @@ class _HipBackbone(nn.Module):
     def _feed(self, plan, x, noise_labels):
         """lambda and the first GEMM's operand of a plain forward: the 3x3 patches of x for conv_in (im2col 1), its p x p patches for
         the patch embedding (im2col 2)."""
+        N, Cin, H, W = x.shape
+        # a plan's buffers are sized for config.sample_size (engine.py): any other extent would write past the operand and read past the
+        # prediction, so it is refused before the first launch
+        side, chans = self.config.sample_size, self.config.in_channels
+        if side is not None and ((H, W) != (side, side) or Cin != chans):
+            raise L.DcamdError(f"{type(self).__name__}: x must be [N, {chans}, {side}, {side}] (config.in_channels, config.sample_size: "
+                               f"the launch plans are built for that extent), got {tuple(x.shape)}")
         lib = L.lib()
         dev = x.device
-        N, Cin, H, W = x.shape
         lam = noise_labels if torch.is_tensor(noise_labels) else torch.tensor([noise_labels])
         lam = lam.to(dev, torch.float32).reshape(-1)
         plan.lam.copy_(lam.expand(N) if lam.numel() == 1 else lam)

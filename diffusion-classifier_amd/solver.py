@@ -8,6 +8,9 @@ from grid point t to grid point s, on the guided prediction pr = (1 + w) pred_c 
   z_s = k1 z + k2 D                  k1 = sigma_s / sigma_t, k2 = -alpha_s expm1(-h) (= alpha_s - alpha_t sigma_s / sigma_t)
 The last denoising pass returns clip(x) at the last grid point, so n steps are n backbone passes (ancestral DDPM makes n + 1).
 Inversion walks the grid upwards (h < 0), first order throughout, and starts from z = alpha(lam(0)) x.
+On the discrete grid (schedule='scaled_linear' with config.timestep_spacing; `trajectory.Grid`) the backbone is fed the step float(k_i),
+nothing is clipped (scaled VAE latents are not in [-1, 1]) and the last pass is an ordinary first-order pass with k1 = 0, k2 = 1: its
+output 0 z + 1 D is the unclipped data prediction, still one backbone pass.
 
 `eager_pass` / `run_eager` are the written statement — two backbone calls per pass and the expressions above in fp32 torch — and the
 path of a foreign nn.Module.  HIP backbones run the same passes as `run_walk` over a `trajectory.Walk`, one `dc_solver_step` per step and
@@ -33,17 +36,17 @@ def sampler_of(config):
 
 
 def grid_lams(dc, u_from, u_to):
-    """lambda at the points of linspace(u_from, u_to, sampling_steps + 1): 0-dim evaluations of the schedule, as `sample` forms them."""
-    steps = torch.linspace(u_from, u_to, dc.config.sampling_steps + 1)
-    return [dc.schedule(steps[j]) for j in range(len(steps))]
+    """lambda at the points of the call's grid (`trajectory.grid`, which also says what the backbone is fed there): 0-dim tensors."""
+    return TJ.grid(dc, u_from, u_to).lam
 
 
-def step_scalars(lams, sampler, direction):
+def step_scalars(lams, sampler, direction, clip=True):
     """The per-pass scalars of a walk over the grid `lams` (n + 1 lambdas in the order they are visited) as Python floats, from fp32
     torch ops on 0-dim tensors on the host: [(alpha_t, sigma_t, k1, k2, k3 | None, final)] of n passes.
       direction "denoise": pass 0 is first order (k3 None); with "dpmpp_2m" passes 1 .. n-2 are second order; pass n-1 is `final` (first
                            order, it returns the clipped data prediction)
-      direction "invert":  first order throughout, no final pass"""
+      direction "invert":  first order throughout, no final pass
+      clip False (the discrete grid): the last denoising pass is (alpha_t, sigma_t, 0, 1, None, not final) — k1 z + k2 D = D unclipped"""
     if sampler not in SAMPLERS:
         raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     if direction not in ("denoise", "invert"):
@@ -61,6 +64,9 @@ def step_scalars(lams, sampler, direction):
         final = direction == "denoise" and i == n - 1
         second = sampler == "dpmpp_2m" and direction == "denoise" and 1 <= i <= n - 2
         k3 = float(0.5 * h / h_prev) if second else None
+        if final and not clip:
+            out.append((float(alpha_t), float(sigma_t), 0.0, 1.0, None, False))
+            break
         out.append((float(alpha_t), float(sigma_t), float(k1), float(k2), k3, final))
         h_prev = h
     return out
@@ -77,26 +83,26 @@ def eager_pass(dc, z, pred, u_pred, w, sc, x_prev, clamp=True):
     return (dc.clip(D) if final else k1 * z + k2 * D), x
 
 
-def run_eager(dc, z, lams, scal, w, cond, null, lens=None):
-    """The passes `scal` from z on the grid `lams`: per pass one conditional and one null backbone call at z's batch."""
+def run_eager(dc, z, g, scal, w, cond, null, lens=None):
+    """The passes `scal` from z on the grid `g`: per pass one conditional and one null backbone call at z's batch, fed g.label."""
     dev = z.device
     kc = {"encoder_lengths": lens["cond"]} if lens else {}
     kn = {"encoder_lengths": lens["null"]} if lens else {}
     x_prev = None
     for i, sc in enumerate(scal):
-        lam_t = lams[i].to(dev).unsqueeze(0)
-        pred = dc.ema(z, lam_t, encoder_hidden_states=cond, **kc)
-        u_pred = dc.ema(z, lam_t, encoder_hidden_states=null, **kn)
-        z, x_prev = eager_pass(dc, z, pred, u_pred, w, sc, x_prev)
+        label = g.label[i].to(dev).unsqueeze(0)
+        pred = dc.ema(z, label, encoder_hidden_states=cond, **kc)
+        u_pred = dc.ema(z, label, encoder_hidden_states=null, **kn)
+        z, x_prev = eager_pass(dc, z, pred, u_pred, w, sc, x_prev, clamp=not dc.discrete)
     return z
 
 
 def decode_eager(dc, z, text, from_t, sampler):
-    """The latent z at from_t decoded under the labels `text` in eager torch on any backbone: n passes on
-    linspace(from_t, 0, sampling_steps + 1) with config.cfg_w."""
+    """The latent z at from_t decoded under the labels `text` in eager torch on any backbone: n passes on the grid from from_t
+    down to 0 with config.cfg_w."""
     cond, null, lens = contexts(dc, text, z.device, dc.ema.ema_model)
-    lams = grid_lams(dc, from_t, 0.0)
-    return run_eager(dc, z, lams, step_scalars(lams, sampler, "denoise"), dc.cfg_w, cond, null, lens)
+    g = TJ.grid(dc, from_t, 0.0)
+    return run_eager(dc, z, g, step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete), dc.cfg_w, cond, null, lens)
 
 
 def sample_eager(dc, x, text, from_t, sampler):
@@ -115,7 +121,7 @@ def run_walk(walk, z0, scal):
             # 2M: pass 0 writes the history, a second-order pass reads its element and writes it again; the final pass needs none
             hc = None if hist is None or final else hist[rows].data_ptr()
             TJ.launch("dc_solver_step", L.SolverStepParams(
-                xprev=hc if k3 is not None else None, xhat=hc, out=zb[rows].data_ptr(), clamp=1, final_pass=int(final), alpha_t=alpha_t,
+                xprev=hc if k3 is not None else None, xhat=hc, out=zb[rows].data_ptr(), clamp=walk.clamp, final_pass=int(final), alpha_t=alpha_t,
                 sigma_t=sigma_t, k1=k1, k2=k2, k3=0.0 if k3 is None else k3, **f))
         za, zb = zb, za
     return walk.view(za)
@@ -126,9 +132,9 @@ def sample(dc, x, text, from_t, sampler):
     class per image; everything else takes the eager form."""
     backbone = dc.ema.ema_model
     if hasattr(backbone, "pair_session") and text is not None and dc.encoder_type is not None and x.is_cuda:
-        lams = grid_lams(dc, from_t, 0.0)
-        walk = TJ.Walk(dc, backbone, x, text.detach().cpu().reshape(-1, 1).to(torch.int64), lams, dc.cfg_w)
-        return run_walk(walk, initial_latent(dc, x, from_t), step_scalars(lams, sampler, "denoise"))[:, 0]
+        g = TJ.grid(dc, from_t, 0.0)
+        walk = TJ.Walk(dc, backbone, x, text.detach().cpu().reshape(-1, 1).to(torch.int64), g, dc.cfg_w)
+        return run_walk(walk, initial_latent(dc, x, from_t), step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete))[:, 0]
     return sample_eager(dc, x, text, from_t, sampler)
 
 
@@ -146,13 +152,14 @@ def label_rows(text, BS, n_classes, name):
 
 
 def invert_eager(dc, x, lab, to_t, guidance):
-    """DDIM inversion in eager torch: z = alpha(lam(0)) x, then n first-order passes up linspace(0, to_t, sampling_steps + 1)."""
+    """DDIM inversion in eager torch: z = alpha(lam(0)) x, then n first-order passes up the grid from 0 to to_t."""
     dev = x.device
-    lams = grid_lams(dc, 0.0, to_t)
+    g = TJ.grid(dc, 0.0, to_t)
+    lams = g.lam
     z = torch.sqrt(torch.sigmoid(lams[0])).to(dev) * x
     lab_dev = dc.encoder.weight.device if dc.encoder is not None else dev
     cond, null, lens = contexts(dc, lab.to(lab_dev), dev, dc.ema.ema_model)
-    return run_eager(dc, z, lams, step_scalars(lams, "ddim", "invert"), float(guidance), cond, null, lens)
+    return run_eager(dc, z, g, step_scalars(lams, "ddim", "invert"), float(guidance), cond, null, lens)
 
 
 @torch.no_grad()
@@ -162,6 +169,6 @@ def invert(dc, x, text, to_t, guidance):
     lab = label_rows(text, x.shape[0], dc.config.classes, "text")
     if not hip:
         return invert_eager(dc, x, lab, to_t, guidance).to(torch.float32)
-    lams = grid_lams(dc, 0.0, to_t)
-    walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), lams, guidance)
-    return run_walk(walk, torch.sqrt(torch.sigmoid(lams[0])).to(x.device) * x, step_scalars(lams, "ddim", "invert"))[:, 0]
+    g = TJ.grid(dc, 0.0, to_t)
+    walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), g, guidance)
+    return run_walk(walk, torch.sqrt(torch.sigmoid(g.lam[0])).to(x.device) * x, step_scalars(g.lam, "ddim", "invert"))[:, 0]

@@ -1,12 +1,15 @@
-"""What `sample`, `counterfactual`, `invert` and `invert_ddpm` share: the entry checks, the start latent, the contexts, the step kernels'
+"""What `sample`, `counterfactual`, `invert` and `invert_ddpm` share: the entry checks, the grid of a call (`Grid`: the log-SNR of every
+point and what the backbone is fed there; `discrete_steps`: the integer DDPM grid), the start latent, the contexts, the step kernels'
 geometry, the noise of a call, and the walk of all trajectories of a call over a HIP backbone.
 
 The loops themselves live with their arithmetic and none takes a mode flag: the ancestral decode in counterfactual.py (`decode_hip`),
 the solver walk in solver.py (`run_walk`: the deterministic decode and, on the upward grid, DDIM inversion), the noise-map inversion in
 ddpm_invert.py (`run_hip`).  Each is `for pass: for chunk in walk.run(t, z): one step kernel`.  `ancestral_eager` is the reference's
-ancestral loop in eager torch, the path of a foreign nn.Module and the written statement of the kernels.
+ancestral loop in eager torch, the path of a foreign nn.Module and the written statement of the kernels.  The ancestral loops of the
+discrete grid (unclipped, the mean by `dc_solver_step`) are their own functions in discrete.py.
 """
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -56,14 +59,70 @@ def check_decode(dc, decode, pixel_space=False):
         raise ValueError("decode=True cannot be combined with pixel_space=True: a model on VAE latents is not one on wavelet coefficients")
 
 
+Grid = namedtuple("Grid", ["lam", "label", "steps"])
+Grid.__doc__ = """The grid of one call, n + 1 points in the order they are visited.  lam[i]: the log-SNR, a 0-dim fp32 tensor on the host —
+every step scalar is a function of two of them.  label[i]: what the backbone is fed at the point — the same tensor on the cosine
+schedules, float(k_i) on the discrete grid.  steps: the DDPM steps k_i as Python ints (None on the cosine schedules)."""
+
+
+def discrete_steps(dc, from_t):
+    """schedule='scaled_linear': the DDPM steps k_0 > k_1 > ... > k_n = 0 of a downward walk from `from_t` in n = sampling_steps
+    passes, in Python integers only (the floor of an fp32 linspace value times N is off by one unpredictably).  With
+    k_top = ddpm_step(from_t), classify's map, and M = k_top + 1:
+      config.timestep_spacing = "trailing":  k_i = (M (n - i)) // n - 1                  i < n
+                                "leading":   k_i = (n - 1 - i) (M // n) + steps_offset   i < n
+    and k_n = 0 in both (abar_0: the published set_alpha_to_one = false).  A grid that is not strictly decreasing down to k_{n-1} >= 1
+    or that starts above N - 1 is refused: equal neighbours give c = 0 and sd = 0, and a noise map divides by sd."""
+    N, spacing, off = dc.train_timesteps, dc.timestep_spacing, dc.steps_offset
+    n = dc.config.sampling_steps
+    from_t = float(from_t)
+    if not 0.0 < from_t <= 1.0:
+        raise ValueError(f"from_t must lie in (0, 1], got {from_t}")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"config.sampling_steps must be an int >= 1, got {n!r}")
+    M = int(dc.ddpm_step(from_t)) + 1
+    if spacing == "trailing":
+        ks = [(M * (n - i)) // n - 1 for i in range(n)]
+    elif spacing == "leading":
+        ks = [(n - 1 - i) * (M // n) + off for i in range(n)]
+    else:
+        raise ValueError(f"the discrete grid needs config.timestep_spacing = 'trailing' | 'leading', got {spacing!r}")
+    ks.append(0)
+    if ks[0] > N - 1 or ks[n - 1] < 1 or any(a <= b for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"sampling_steps = {n} from from_t = {from_t} on N = {N} train steps with timestep_spacing = {spacing!r}"
+                         f"{f' (steps_offset = {off})' if spacing == 'leading' else ''} gives the steps {ks}: they must decrease strictly "
+                         f"from at most {N - 1} down to k_(n-1) >= 1 and end at 0 (fewer sampling_steps, a larger from_t, or for "
+                         "'leading' steps_offset = 1)")
+    return ks
+
+
+def grid(dc, u_from, u_to):
+    """The `Grid` of a call from u_from to u_to.  Cosine schedules: the schedule at the points of linspace(u_from, u_to,
+    sampling_steps + 1), 0-dim evaluations as `sample` forms them, lam and label the same tensors.  schedule='scaled_linear':
+    `discrete_steps` from max(u_from, u_to), reversed for an upward walk (inversion visits the points the decode visits),
+    lam = ddpm_logsnr[k_i] and label = float(k_i)."""
+    if not dc.discrete:
+        pts = torch.linspace(u_from, u_to, dc.config.sampling_steps + 1)
+        lam = [dc.schedule(pts[j]) for j in range(len(pts))]
+        return Grid(lam, lam, None)
+    ks = discrete_steps(dc, max(u_from, u_to))
+    if u_from < u_to:
+        ks = ks[::-1]
+    return Grid([dc.ddpm_logsnr[k] for k in ks], [torch.tensor(float(k), dtype=torch.float32) for k in ks], ks)
+
+
 def initial_latent(dc, x, from_t, noise=None):
     """`sample`'s start: randn for from_t == 1, else diffuse(x) to from_t — one draw from torch's generator, or draw 0 of a Philox
-    `NoiseSource` (cloned out of its buffer when it is the start itself)."""
+    `NoiseSource` (cloned out of its buffer when it is the start itself).  On the discrete grid x is diffused to grid point 0, which
+    under 'leading' spacing is not the step from_t falls into."""
     dev = x.device
     philox = noise is not None and noise.philox
     if from_t == 1:
         return noise(0).clone() if philox else torch.randn(x.shape).to(dev)
-    lam = dc.schedule(torch.ones(x.shape[0]) * from_t).to(dev)
+    if dc.discrete:
+        lam = grid(dc, from_t, 0.0).lam[0].expand(x.shape[0]).to(dev)
+    else:
+        lam = dc.schedule(torch.ones(x.shape[0]) * from_t).to(dev)
     al, sg = torch.sqrt(torch.sigmoid(lam)).view(-1, 1, 1, 1), torch.sqrt(torch.sigmoid(-lam)).view(-1, 1, 1, 1)
     return al * x + sg * noise(0) if philox else dc.diffuse(x, al, sg)[0]
 
@@ -87,20 +146,20 @@ def ancestral_eager(dc, z0, conds, null, from_t, lens=None, noise_maps=None):
     """The reference's ancestral loop from z0 under the K label columns `conds`: per step and column one conditional and one null call
     at z0's batch and `ddpm_sampler_step`, every column adding the step's one `randn_like` (or noise_maps[i] in its place) — op for op
     what K calls of `sample` with the seed reset in front of each compute -> the K clipped means of the last pass.
-    lens: `contexts`' token counts for a ragged table (K = 1)."""
+    lens: `contexts`' token counts for a ragged table (K = 1).  (schedule='scaled_linear': the callers take `discrete.ancestral_eager`.)"""
     dev = z0.device
     kc = {"encoder_lengths": lens["cond"]} if lens else {}
     kn = {"encoder_lengths": lens["null"]} if lens else {}
-    steps = torch.linspace(from_t, 0.0, dc.config.sampling_steps + 1)
-    n = len(steps) - 1
+    g = grid(dc, from_t, 0.0)
+    n = len(g.lam) - 1
     zs = [z0] * len(conds)
     for i in range(n + 1):                                                    # the last pass repeats step n-1 and keeps the mean
-        u_t, u_s = (steps[i], steps[i + 1]) if i < n else (steps[-2], steps[-1])
-        lam_t, lam_s = dc.schedule(u_t).to(dev).unsqueeze(0), dc.schedule(u_s).to(dev).unsqueeze(0)
+        t = min(i, n - 1)
+        lam_t, lam_s, label = g.lam[t].to(dev).unsqueeze(0), g.lam[t + 1].to(dev).unsqueeze(0), g.label[t].to(dev).unsqueeze(0)
         mus, var = [], None
         for z, cond in zip(zs, conds):
-            pred = dc.ema(z, lam_t, encoder_hidden_states=cond, **kc)
-            u_pred = dc.ema(z, lam_t, encoder_hidden_states=null, **kn)
+            pred = dc.ema(z, label, encoder_hidden_states=cond, **kc)
+            u_pred = dc.ema(z, label, encoder_hidden_states=null, **kn)
             mu, var = dc.ddpm_sampler_step(z, pred, u_pred, lam_t.clone().detach(), lam_s.clone().detach())
             mus.append(mu)
         if i == n:
@@ -170,11 +229,12 @@ def pair_sessions(dc, backbone, cl, chunks, dev):
 class Walk:
     """The BS x K trajectories of one call on a HIP backbone: trajectory b * K + k is image b under label cl[b, k], one unit pair
     (class token || null token) of a pair session.  Built once per call — the images cut into chunks by classify's launch-size rule,
-    one pair session per chunk (the prompts projected once), lambda of the grid `lams` on the device, the step structs' common fields
+    one pair session per chunk (the prompts projected once), lambda and the backbone's time input of the `Grid` on the device, the
+    step structs' common fields
     — and walked step-major, chunk-minor by the caller's loop; nothing is copied to the host inside it.
     who / noun: the caller's words in the two refusals."""
 
-    def __init__(self, dc, backbone, x, cl, lams, w, who="counterfactual", noun="fused sampler step"):
+    def __init__(self, dc, backbone, x, cl, grid, w, who="counterfactual", noun="fused sampler step"):
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError(f"{who} on a HIP backbone needs a CUDA/HIP tensor (as sample does; no CPU fallback)")
@@ -182,7 +242,10 @@ class Walk:
         self.shape = tuple(x.shape[1:])
         self.fields = step_fields(dc, backbone, x.shape, w, noun)
         self.chunks = image_chunks(self.BS, self.K, units_per_launch(dc.config, x.shape[2], x.shape[3], 2 * self.K))
-        self.lam = torch.stack([v.detach().float().reshape(()) for v in lams]).to(x.device)
+        self.lam = torch.stack([v.detach().float().reshape(()) for v in grid.lam]).to(x.device)
+        # the cosine schedules feed the backbone the log-SNR itself: one tensor, as ever
+        self.label = self.lam if grid.label is grid.lam else torch.stack([v.detach().float().reshape(()) for v in grid.label]).to(x.device)
+        self.clamp = int(not dc.discrete)                                     # dc_solver_step's clamp: nothing is clipped on the discrete grid
         # opened at the first pass, behind the caller's draws and blocking host-to-device copies: the context plans then run on the
         # device while the host prepares pass 0, instead of being waited for by the next such copy
         self.sessions, self._open = None, lambda: pair_sessions(dc, backbone, cl, self.chunks, x.device)
@@ -196,13 +259,13 @@ class Walk:
         return z.view((self.BS, self.K) + self.shape)
 
     def run(self, t, z):
-        """Pass t over z [BS * K, C, H, W]: per chunk one session step at (z[rows], lam_t), then -> (rows: the chunk's trajectories,
+        """Pass t over z [BS * K, C, H, W]: per chunk one session step at (z[rows], label_t), then -> (rows: the chunk's trajectories,
         imgs: its images, f: the step struct's fields z, pred, n, ld and the common ones) for the caller's one kernel."""
         if self.sessions is None:
             self.sessions = self._open()
         for (b0, b1), ses in zip(self.chunks, self.sessions):
             rows = slice(b0 * self.K, b1 * self.K)
-            pair = ses.step(z[rows], self.lam[t:t + 1])
+            pair = ses.step(z[rows], self.label[t:t + 1])
             yield rows, slice(b0, b1), dict(self.fields, z=z[rows].data_ptr(), pred=pair.data_ptr(), n=(b1 - b0) * self.K, ld=pair.shape[-1])
 
 
