@@ -7,13 +7,13 @@ reset in front of each run, and compares the generated images.  `DiffusionClassi
   maps [BS, K, H', W']       maps[b, k] = sum_c |samples[b, k, c] - base[b, c]|, c ascending, fp32; base = the input image or the
                              trajectory of one of the classes
 HIP backbones run all BS x K trajectories as the units of one pair session per chunk of images (a `trajectory.Walk`: the prompts are
-projected once per call, the step scalars are formed before the loop, nothing is copied to the host inside it); `decode_hip` is the
-ancestral loop on it (`dc_ddpm_step_shared`), the maps are `dc_abs_diff_map`.  A foreign nn.Module takes the reference's own form in
-eager torch (`run_foreign`, `run_foreign_solver`): it is the written statement.
+projected once per call, the step scalars are formed before the loop, nothing is copied to the host inside it); the ancestral loop on
+it is `ancestral.decode_hip` (`dc_ddpm_step_shared` on the cosine schedules), the maps are `dc_abs_diff_map`.  A foreign nn.Module takes
+the reference's own form in eager torch (`run_foreign`, `run_foreign_solver`): it is the written statement.
 With config.sampler = "ddim" | "dpmpp_2m" the trajectories are deterministic after their start (`solver.run_walk`), and
 start="invert" takes that start from DDIM inversion of the image instead of from noise.  Under the ancestral sampler
 start="ddpm_invert" takes the start AND the noise of every step from the image's edit-friendly DDPM inversion (ddpm_invert.py): the
-decode under the inversion's class is the image again, and the loop draws nothing: `run` hands `decode_hip` the maps as its noise.
+decode under the inversion's class is the image again, and the loop draws nothing: `run` hands the decode the maps as its noise.
 """
 import ctypes as C
 from collections import namedtuple
@@ -21,8 +21,8 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from . import ancestral as AN
 from . import ddpm_invert as DI
-from . import discrete as DG
 from . import solver as S
 from . import trajectory as TJ
 from .trajectory import image_chunks      # noqa: F401  (its home is the walk; importable here as ever)
@@ -89,47 +89,24 @@ def abs_diff_map_hip(a, r, r_of_a):
 
 def column_contexts(dc, cl, dev):
     """(conds, null) of a foreign module: the encoded labels of every column of cl [BS, K] and the encoded null token, at batch BS."""
-    lab_dev = dc.encoder.weight.device if dc.encoder is not None else dev
-    labs = [cl[:, k].to(lab_dev) for k in range(cl.shape[1])]
+    labs = [cl[:, k].to(TJ.label_device(dc, dev)) for k in range(cl.shape[1])]
     return [dc.encode_text_prompt(lab).to(dev) for lab in labs], dc.encode_text_prompt(torch.full_like(labs[0], dc.null_token)).to(dev)
 
 
 def run_foreign(dc, z0, cl, from_t, noise_maps=None):
-    """The reference's form from the start z0 [BS, C, H, W]: `trajectory.ancestral_eager` over the K columns of cl, every class adding
+    """The reference's form from the start z0 [BS, C, H, W]: `ancestral.ancestral_eager` over the K columns of cl, every class adding
     the step's one `randn_like` — or, with noise_maps [n, BS, C, H, W] (ddpm_invert.py), noise_maps[i] in place of the draw."""
     conds, null = column_contexts(dc, cl, z0.device)
-    if dc.discrete:
-        mus = DG.ancestral_eager(dc, z0, conds, null, TJ.grid(dc, from_t, 0.0), noise_maps=noise_maps)
-    else:
-        mus = TJ.ancestral_eager(dc, z0, conds, null, from_t, noise_maps=noise_maps)
-    return torch.stack(mus, dim=1).to(torch.float32)
+    kind = AN.step_kind(dc, TJ.grid(dc, from_t, 0.0), dc.cfg_w)
+    return torch.stack(AN.ancestral_eager(kind, z0, conds, null, noise_maps=noise_maps), dim=1).to(torch.float32)
 
 
 def run_foreign_solver(dc, z0, cl, from_t, sampler):
     """The same under "ddim" / "dpmpp_2m": the K classes by `solver.run_eager` from the one start, no draw after it."""
     conds, null = column_contexts(dc, cl, z0.device)
     g = TJ.grid(dc, from_t, 0.0)
-    scal = S.step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete)
+    scal = S.denoise_scalars(dc, g, sampler)
     return torch.stack([S.run_eager(dc, z0, g, scal, dc.cfg_w, cond, null) for cond in conds], dim=1).to(torch.float32)
-
-
-def decode_hip(dc, walk, z0, lams, noise):
-    """The ancestral decode of all trajectories of `walk` from z0 [BS, C, H, W] on the grid `lams`: n + 1 passes, one
-    `dc_ddpm_step_shared` per pass and chunk; pass i < n adds noise(i) [BS, C, H, W] f32, read by the K trajectories of an image
-    (noise_div = K); the last pass repeats step n - 1, takes no noise and keeps the clipped mean -> [BS, K, C, H, W]."""
-    n = len(lams) - 1
-    scal = [dc._sampler_step_scalars(lams[t], lams[t + 1]) for t in range(n)]
-    za, zb = walk.buffers(z0)
-    for i in range(n + 1):
-        t = min(i, n - 1)
-        c, alpha_t, sigma_t, alpha_s, sd = scal[t]
-        e = noise(i) if i < n else None
-        for rows, imgs, f in walk.run(t, za):
-            TJ.launch("dc_ddpm_step_shared", L.DdpmStepSharedParams(
-                noise=None if e is None else e[imgs].data_ptr(), out=zb[rows].data_ptr(), noise_div=walk.K, alpha_t=alpha_t,
-                sigma_t=sigma_t, alpha_s=alpha_s, c=c, sd=sd, pad_=0, **f))
-        za, zb = zb, za
-    return walk.view(za)
 
 
 @torch.no_grad()
@@ -173,12 +150,11 @@ def run(dc, x, classes, from_t, against, rng, seed, pixel_space, start="noise", 
         if z0 is None:
             z0 = S.initial_latent(dc, x, from_t, noise)
         if sampler is not None:
-            samples = S.run_walk(walk, z0, S.step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete))
+            samples = S.run_walk(walk, z0, S.denoise_scalars(dc, g, sampler))
         else:
             noise.like = z0                                              # the steps draw in the start's dtype, as `sample` does
             draw = nmaps.__getitem__ if nmaps is not None else lambda i: noise(i + 1)
-            # the discrete grid: the unclipped mean by dc_solver_step and the add in torch (discrete.py); otherwise the fused step
-            samples = DG.decode_hip(walk, z0, g, draw) if dc.discrete else decode_hip(dc, walk, z0, g.lam, draw)
+            samples = AN.decode_hip(AN.step_kind(dc, g, dc.cfg_w), walk, z0, draw)
     else:
         z0 = S.initial_latent(dc, x, from_t) if z0 is None else z0
         samples = run_foreign(dc, z0, cl, from_t, nmaps) if sampler is None else run_foreign_solver(dc, z0, cl, from_t, sampler)

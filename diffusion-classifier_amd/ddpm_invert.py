@@ -10,17 +10,16 @@ steps, the guidance weight and the clip of the data prediction: mu_i is a determ
 is the rounding of (x_{i+1} - mu_i) / sd_i * sd_i + mu_i.  Under another class the same maps give an edit that keeps the image's
 structure.  The sampler's last pass (the clipped mean from x_n) is kept and draws nothing.
 
-`run_eager` is the written statement — two backbone calls per pass and `ddpm_sampler_step` — and the path of a foreign nn.Module.  HIP
-backbones run pass i over a `trajectory.Walk` (`run_hip`): one step of a pair session per chunk of images and one `dc_ddpm_noise_map`
-(include/dcamd.h) per pass and chunk; nothing is copied to the host inside the loop.  The n passes do not depend on one another: only
-two latents are alive at a time.
+This module is the entry point: the refusals, the size cap and the result.  The loops are ancestral.py's: `noise_maps_eager` is the
+written statement — two backbone calls per pass and the step kind's mean — and the path of a foreign nn.Module; HIP backbones run pass
+i over a `trajectory.Walk` (`noise_maps_hip`): one step of a pair session per chunk of images and one map per pass and chunk
+(`dc_ddpm_noise_map`, include/dcamd.h, on the cosine schedules); nothing is copied to the host inside the loop.
 """
 from collections import namedtuple
 
 import torch
 
-from . import _lib as L
-from . import discrete as DG
+from . import ancestral as AN
 from . import solver as S
 from . import trajectory as TJ
 
@@ -42,62 +41,9 @@ def max_bytes_of(config):
     return v
 
 
-def grid(dc, from_t):
-    """(g, scal, alsg): the `trajectory.Grid` of the n + 1 points, (c, alpha_t, sigma_t, alpha_s, sd) of pass i = 0 .. n - 1 and
-    (alpha_i, sigma_i) of every point as 0-dim fp32 tensors on the host."""
-    g = TJ.grid(dc, from_t, 0.0)
-    lams = g.lam
-    scal = [dc._sampler_step_scalars(lams[i], lams[i + 1]) for i in range(len(lams) - 1)]
-    lam = [v.detach().float().cpu().reshape(()) for v in lams]
-    alsg = [(torch.sqrt(torch.sigmoid(v)), torch.sqrt(torch.sigmoid(-v))) for v in lam]
-    return g, scal, alsg
-
-
 def run_eager(dc, x, lab, from_t, w):
-    """The statement on any backbone: -> (start, noise).  The draws are `randn_like(x)` in the order i = 0 .. n."""
-    if dc.discrete:
-        return DG.noise_maps_eager(dc, x, lab, TJ.grid(dc, from_t, 0.0), w)
-    dev = x.device
-    g, _, alsg = grid(dc, from_t)
-    lams = g.lam
-    n = len(lams) - 1
-    lab_dev = dc.encoder.weight.device if dc.encoder is not None else dev
-    cond, null, lens = S.contexts(dc, lab.to(lab_dev), dev, dc.ema.ema_model)
-    kc = {"encoder_lengths": lens["cond"]} if lens else {}
-    kn = {"encoder_lengths": lens["null"]} if lens else {}
-    latent = lambda i: alsg[i][0].to(dev) * x + alsg[i][1].to(dev) * torch.randn_like(x)      # noqa: E731
-    noise = torch.empty((n,) + tuple(x.shape), dtype=torch.float32, device=dev)
-    start = z = latent(0)
-    for i in range(n):
-        z_next = latent(i + 1)
-        lam_t, lam_s = lams[i].to(dev).unsqueeze(0), lams[i + 1].to(dev).unsqueeze(0)
-        label = g.label[i].to(dev).unsqueeze(0)
-        pred = dc.ema(z, label, encoder_hidden_states=cond, **kc)
-        u_pred = dc.ema(z, label, encoder_hidden_states=null, **kn)
-        mu, var = dc.ddpm_sampler_step(z, pred, u_pred, lam_t.clone().detach(), lam_s.clone().detach(), w=w)
-        noise[i] = (z_next - mu) / torch.sqrt(var)
-        z = z_next
-    return start.to(torch.float32), noise
-
-
-def run_hip(walk, x, scal, alsg, noise):
-    """The same on a HIP backbone: image b is the one trajectory of its unit pair in `walk` (trajectory.py), pass i is one session step
-    at (x_i, lam_i) and one `dc_ddpm_noise_map` per chunk that writes noise[i] in place.  The latents take draws i = 0 .. n of `noise`."""
-    dev = x.device
-    n = len(scal)
-    alsg = [(a.to(dev), s.to(dev)) for a, s in alsg]
-    xf = x.detach().to(torch.float32).contiguous()
-    latent = lambda i: (alsg[i][0] * xf + alsg[i][1] * noise(i)).contiguous()              # noqa: E731
-    maps = torch.empty((n,) + tuple(x.shape), dtype=torch.float32, device=dev)
-    start = z = latent(0)
-    for i in range(n):                                                        # no device -> host copy
-        z_next = latent(i + 1)
-        c, alpha_t, sigma_t, alpha_s, sd = scal[i]
-        for _, imgs, f in walk.run(i, z):
-            TJ.launch("dc_ddpm_noise_map", L.DdpmNoiseMapParams(
-                x_next=z_next[imgs].data_ptr(), out=maps[i, imgs].data_ptr(), alpha_t=alpha_t, sigma_t=sigma_t, alpha_s=alpha_s, c=c, sd=sd, **f))
-        z = z_next
-    return start, maps
+    """The eager statement under its earlier name: `ancestral.noise_maps_eager` on the grid from `from_t` -> (start, noise)."""
+    return AN.noise_maps_eager(AN.step_kind(dc, TJ.grid(dc, from_t, 0.0), w), x, lab)
 
 
 @torch.no_grad()
@@ -111,12 +57,10 @@ def invert(dc, x, text, from_t, guidance, rng, seed, name="text"):
     if size > cap:
         raise ValueError(f"invert_ddpm stores one noise map per step: {n} x {tuple(x.shape)} f32 = {size} bytes, more than "
                          f"config.ddpm_invert_max_bytes = {cap} (fewer sampling_steps, a smaller batch, or raise the key)")
+    kind = AN.step_kind(dc, TJ.grid(dc, from_t, 0.0), w)
     if hip:
-        g, scal, alsg = grid(dc, from_t)
-        walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), g, w, who="invert_ddpm", noun="fused noise map")
-        draws = TJ.NoiseSource(x, rng, seed, n + 1)
-        # the discrete grid: the unclipped mean by dc_solver_step and the map in torch (discrete.py); otherwise the fused kernel
-        start, noise = DG.noise_maps_hip(walk, x, g, draws) if dc.discrete else run_hip(walk, x, scal, alsg, draws)
+        walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), kind.g, w, who="invert_ddpm", noun="fused noise map")
+        start, noise = AN.noise_maps_hip(kind, walk, x, TJ.NoiseSource(x, rng, seed, n + 1))
     else:
-        start, noise = run_eager(dc, x, lab, from_t, w)
+        start, noise = AN.noise_maps_eager(kind, x, lab)
     return DdpmInversion(start, noise, from_t, w)

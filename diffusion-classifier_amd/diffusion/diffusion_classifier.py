@@ -86,10 +86,10 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import ancestral as AN
 from .. import dist as D
 from .. import counterfactual as CF
 from .. import ddpm_invert as DI
-from .. import discrete as DG
 from .. import posterior as P
 from .. import evidence as EV
 from .. import solver as S
@@ -681,6 +681,7 @@ class DiffusionClassifier(nn.Module):
     # HIP backbones: ONE batch-2 plan launch per step (class token || null token, the class-independent layers once per
     # image) and ONE fused sampler-step kernel (`dc_ddpm_step`); a foreign nn.Module takes the reference's two eager calls
     # and its elementwise torch expressions (`ddpm_sampler_step`, kept for that path and as the fused kernel's statement).
+    # The loops are ancestral.py's; `clip` and `ddpm_sampler_step` stay here as the reference's surface.
     def clip(self, x):
         return torch.clamp(x, -1, 1)
 
@@ -697,28 +698,7 @@ class DiffusionClassifier(nn.Module):
         mu = alpha_s * (z_t * (1 - c) / alpha_t + c * x_pred)
         return mu, (sigma_s ** 2) * c
 
-    @staticmethod
-    def _sampler_step_scalars(lam_t, lam_s):
-        """(c, alpha_t, sigma_t, alpha_s, sd) of one sampler step as Python floats, from fp32 torch ops on the host: the expressions of
-        `ddpm_sampler_step` on 0-dim tensors, sd = sqrt(sigma_s^2 c)."""
-        lt, ls = lam_t.detach().float().cpu().reshape(()), lam_s.detach().float().cpu().reshape(())
-        c = -torch.special.expm1(lt - ls)
-        alpha_t, alpha_s = torch.sqrt(torch.sigmoid(lt)), torch.sqrt(torch.sigmoid(ls))
-        sigma_t, sigma_s = torch.sqrt(torch.sigmoid(-lt)), torch.sqrt(torch.sigmoid(-ls))
-        sd = torch.sqrt((sigma_s ** 2) * c)
-        return float(c), float(alpha_t), float(sigma_t), float(alpha_s), float(sd)
-
-    def _fused_sampler_step(self, backbone, z_t, pair, lam_t, lam_s, noise):
-        """`ddpm_sampler_step` + the update `z = mu + noise * sqrt(var)` (noise None: the clipped mean of the last pass) on the
-        prediction pair of `forward_pair`, as one kernel.  The step's scalars are formed by the same fp32 torch ops as above."""
-        c, alpha_t, sigma_t, alpha_s, sd = self._sampler_step_scalars(lam_t, lam_s)
-        z = z_t.detach().to(torch.float32).contiguous()
-        out = torch.empty_like(z)
-        p = L.DdpmStepParams(z=z.data_ptr(), pred=pair.data_ptr(), noise=None if noise is None else noise.data_ptr(), out=out.data_ptr(),
-                             n=z.shape[0], ld=pair.shape[-1], alpha_t=alpha_t, sigma_t=sigma_t, alpha_s=alpha_s, c=c, sd=sd,
-                             **TJ.step_fields(self, backbone, z.shape, self.cfg_w))
-        L.check(L.lib().dc_ddpm_step(p, L.stream_ptr()), "dc_ddpm_step")
-        return out
+    _sampler_step_scalars = staticmethod(AN.Clipped.scalars)                  # the earlier name of the clipped step's host scalars
 
     @torch.no_grad()
     def sample(self, x, text=None, from_t=1, decode=False):
@@ -730,37 +710,12 @@ class DiffusionClassifier(nn.Module):
         config.vae_path): the result is then `decode_latents` of those latents, images [BS, out_channels, f H, f W].
         schedule='scaled_linear' (needs config.timestep_spacing): the grid is the integer steps of `trajectory.discrete_steps`, x is
         diffused to its first point k_0, the backbone is fed float(k_i), and nothing is clipped — the ancestral mean is a z + b x
-        (discrete.py), the last deterministic pass returns the data prediction as it is."""
+        (ancestral.py), the last deterministic pass returns the data prediction as it is."""
         self._refuse_discrete("sample", from_t)
         TJ.check_decode(self, decode)
-        z = self._sample_latents(x, text, from_t)
-        return self.decode_latents(z) if decode else z
-
-    def _sample_latents(self, x, text, from_t):
-        """`sample` before any decoding: the solver's loop under a deterministic config.sampler, else the ancestral loop below."""
         sampler = S.sampler_of(self.config)
-        if sampler is not None:
-            return S.sample(self, x, text, from_t, sampler)
-        dev = x.device
-        z_t = TJ.initial_latent(self, x, from_t)
-        backbone = self.ema.ema_model
-        cond, null, lens = TJ.contexts(self, text, dev, backbone)             # lens: the rows' token counts of a ragged prompt table
-        if not (hasattr(backbone, "forward_pair") and cond is not None and z_t.is_cuda):
-            if self.discrete:
-                return DG.ancestral_eager(self, z_t, [cond], null, TJ.grid(self, from_t, 0.0), lens)[0]
-            return TJ.ancestral_eager(self, z_t, [cond], null, from_t, lens)[0]
-        kw = {"cond_lengths": lens["cond"], "null_lengths": lens["null"]} if lens else {}
-        g = TJ.grid(self, from_t, 0.0)
-        if self.discrete:                                                     # unclipped: the mean by dc_solver_step, the add in torch
-            return DG.sample_pair(self, backbone, z_t, cond, null, kw, g)
-        n = len(g.lam) - 1
-        for i in range(n + 1):                                                # the last pass repeats step n-1 and keeps the mean
-            t = min(i, n - 1)
-            lam_t, lam_s = g.lam[t].to(dev).unsqueeze(0), g.lam[t + 1].to(dev).unsqueeze(0)
-            pair = backbone.forward_pair(z_t, g.label[t].to(dev).unsqueeze(0), cond, null, **kw)
-            noise = torch.randn_like(z_t).to(torch.float32).contiguous() if i < n else None
-            z_t = self._fused_sampler_step(backbone, z_t, pair, lam_t, lam_s, noise).to(z_t.dtype)
-        return z_t
+        z = AN.sample(self, x, text, from_t) if sampler is None else S.sample(self, x, text, from_t, sampler)
+        return self.decode_latents(z) if decode else z
 
     @torch.no_grad()
     def counterfactual(self, x, classes=None, from_t=0.5, *, against="input", rng="reference", seed=0, pixel_space=False,
@@ -808,7 +763,7 @@ class DiffusionClassifier(nn.Module):
                        holds no reconstruction error; class ids: the base is that class's decoded trajectory.  False: nothing changes
         schedule='scaled_linear' (needs config.timestep_spacing): all of the above on the integer grid of `sample`, unclipped — the
         ancestral passes are one unclamped `dc_solver_step` (the posterior mean) and one torch add of the shared noise per pass and
-        chunk (discrete.py)"""
+        chunk (ancestral.py)"""
         self._refuse_discrete("counterfactual", from_t)
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class, decode=decode)
 

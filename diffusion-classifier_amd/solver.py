@@ -56,8 +56,7 @@ def step_scalars(lams, sampler, direction, clip=True):
     out, h_prev = [], None
     for i in range(n):
         lt, ls = lam[i], lam[i + 1]
-        alpha_t, alpha_s = torch.sqrt(torch.sigmoid(lt)), torch.sqrt(torch.sigmoid(ls))
-        sigma_t, sigma_s = torch.sqrt(torch.sigmoid(-lt)), torch.sqrt(torch.sigmoid(-ls))
+        (alpha_t, sigma_t), (alpha_s, sigma_s) = TJ.point_scalars(lt), TJ.point_scalars(ls)
         h = (ls - lt) / 2
         k1 = sigma_s / sigma_t
         k2 = -alpha_s * torch.special.expm1(-h)
@@ -70,6 +69,11 @@ def step_scalars(lams, sampler, direction, clip=True):
         out.append((float(alpha_t), float(sigma_t), float(k1), float(k2), k3, final))
         h_prev = h
     return out
+
+
+def denoise_scalars(dc, g, sampler):
+    """`step_scalars` of a decode down the grid `g`: the one place that says the discrete grid clips nothing."""
+    return step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete)
 
 
 def eager_pass(dc, z, pred, u_pred, w, sc, x_prev, clamp=True):
@@ -85,14 +89,9 @@ def eager_pass(dc, z, pred, u_pred, w, sc, x_prev, clamp=True):
 
 def run_eager(dc, z, g, scal, w, cond, null, lens=None):
     """The passes `scal` from z on the grid `g`: per pass one conditional and one null backbone call at z's batch, fed g.label."""
-    dev = z.device
-    kc = {"encoder_lengths": lens["cond"]} if lens else {}
-    kn = {"encoder_lengths": lens["null"]} if lens else {}
     x_prev = None
     for i, sc in enumerate(scal):
-        label = g.label[i].to(dev).unsqueeze(0)
-        pred = dc.ema(z, label, encoder_hidden_states=cond, **kc)
-        u_pred = dc.ema(z, label, encoder_hidden_states=null, **kn)
+        pred, u_pred = TJ.guided_pair(dc, z, g.label[i].to(z.device).unsqueeze(0), cond, null, lens)
         z, x_prev = eager_pass(dc, z, pred, u_pred, w, sc, x_prev, clamp=not dc.discrete)
     return z
 
@@ -102,7 +101,7 @@ def decode_eager(dc, z, text, from_t, sampler):
     down to 0 with config.cfg_w."""
     cond, null, lens = contexts(dc, text, z.device, dc.ema.ema_model)
     g = TJ.grid(dc, from_t, 0.0)
-    return run_eager(dc, z, g, step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete), dc.cfg_w, cond, null, lens)
+    return run_eager(dc, z, g, denoise_scalars(dc, g, sampler), dc.cfg_w, cond, null, lens)
 
 
 def sample_eager(dc, x, text, from_t, sampler):
@@ -134,7 +133,7 @@ def sample(dc, x, text, from_t, sampler):
     if hasattr(backbone, "pair_session") and text is not None and dc.encoder_type is not None and x.is_cuda:
         g = TJ.grid(dc, from_t, 0.0)
         walk = TJ.Walk(dc, backbone, x, text.detach().cpu().reshape(-1, 1).to(torch.int64), g, dc.cfg_w)
-        return run_walk(walk, initial_latent(dc, x, from_t), step_scalars(g.lam, sampler, "denoise", clip=not dc.discrete))[:, 0]
+        return run_walk(walk, initial_latent(dc, x, from_t), denoise_scalars(dc, g, sampler))[:, 0]
     return sample_eager(dc, x, text, from_t, sampler)
 
 
@@ -157,8 +156,7 @@ def invert_eager(dc, x, lab, to_t, guidance):
     g = TJ.grid(dc, 0.0, to_t)
     lams = g.lam
     z = torch.sqrt(torch.sigmoid(lams[0])).to(dev) * x
-    lab_dev = dc.encoder.weight.device if dc.encoder is not None else dev
-    cond, null, lens = contexts(dc, lab.to(lab_dev), dev, dc.ema.ema_model)
+    cond, null, lens = contexts(dc, lab.to(TJ.label_device(dc, dev)), dev, dc.ema.ema_model)
     return run_eager(dc, z, g, step_scalars(lams, "ddim", "invert"), float(guidance), cond, null, lens)
 
 

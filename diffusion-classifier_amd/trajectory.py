@@ -1,12 +1,12 @@
 """What `sample`, `counterfactual`, `invert` and `invert_ddpm` share: the entry checks, the grid of a call (`Grid`: the log-SNR of every
-point and what the backbone is fed there; `discrete_steps`: the integer DDPM grid), the start latent, the contexts, the step kernels'
-geometry, the noise of a call, and the walk of all trajectories of a call over a HIP backbone.
+point and what the backbone is fed there; `discrete_steps`: the integer DDPM grid), alpha and sigma of a grid point, the start latent,
+the contexts, the eager guided prediction pair, the step kernels' geometry, the noise of a call, and the walk of all trajectories of a
+call over a HIP backbone.
 
-The loops themselves live with their arithmetic and none takes a mode flag: the ancestral decode in counterfactual.py (`decode_hip`),
-the solver walk in solver.py (`run_walk`: the deterministic decode and, on the upward grid, DDIM inversion), the noise-map inversion in
-ddpm_invert.py (`run_hip`).  Each is `for pass: for chunk in walk.run(t, z): one step kernel`.  `ancestral_eager` is the reference's
-ancestral loop in eager torch, the path of a foreign nn.Module and the written statement of the kernels.  The ancestral loops of the
-discrete grid (unclipped, the mean by `dc_solver_step`) are their own functions in discrete.py.
+The loops themselves live with their arithmetic and none takes a mode flag: the solver walk in solver.py (`run_walk`: the deterministic
+decode and, on the upward grid, DDIM inversion) and the ancestral loops in ancestral.py (decode, `sample`'s pair loop, noise maps; each
+once in eager torch and once on HIP).  A HIP loop is `for pass: for chunk in walk.run(t, z): one step`.  What the cosine schedules and
+the discrete grid do differently in an ancestral step is an `ancestral.step_kind`, chosen once per call; the loops never ask which.
 """
 import ctypes as C
 from collections import namedtuple
@@ -111,6 +111,13 @@ def grid(dc, u_from, u_to):
     return Grid([dc.ddpm_logsnr[k] for k in ks], [torch.tensor(float(k), dtype=torch.float32) for k in ks], ks)
 
 
+def point_scalars(lam):
+    """(alpha, sigma) of the grid point with log-SNR `lam`: 0-dim fp32 tensors on the host, the fp32 torch ops every step scalar and
+    every latent alpha_i x + sigma_i e_i is formed from."""
+    v = lam.detach().float().cpu().reshape(())
+    return torch.sqrt(torch.sigmoid(v)), torch.sqrt(torch.sigmoid(-v))
+
+
 def initial_latent(dc, x, from_t, noise=None):
     """`sample`'s start: randn for from_t == 1, else diffuse(x) to from_t — one draw from torch's generator, or draw 0 of a Philox
     `NoiseSource` (cloned out of its buffer when it is the start itself).  On the discrete grid x is diffused to grid point 0, which
@@ -142,30 +149,17 @@ def contexts(dc, text, dev, backbone):
     return cond, null, lens
 
 
-def ancestral_eager(dc, z0, conds, null, from_t, lens=None, noise_maps=None):
-    """The reference's ancestral loop from z0 under the K label columns `conds`: per step and column one conditional and one null call
-    at z0's batch and `ddpm_sampler_step`, every column adding the step's one `randn_like` (or noise_maps[i] in its place) — op for op
-    what K calls of `sample` with the seed reset in front of each compute -> the K clipped means of the last pass.
-    lens: `contexts`' token counts for a ragged table (K = 1).  (schedule='scaled_linear': the callers take `discrete.ancestral_eager`.)"""
-    dev = z0.device
+def label_device(dc, dev):
+    """Where class ids must live to be encoded: the prompt table's device, else `dev`."""
+    return dc.encoder.weight.device if dc.encoder is not None else dev
+
+
+def guided_pair(dc, z, label, cond, null, lens=None):
+    """(pred, u_pred) in eager torch: one conditional and one null backbone call at (z, label), in that order.
+    lens: `contexts`' token counts for a ragged table."""
     kc = {"encoder_lengths": lens["cond"]} if lens else {}
     kn = {"encoder_lengths": lens["null"]} if lens else {}
-    g = grid(dc, from_t, 0.0)
-    n = len(g.lam) - 1
-    zs = [z0] * len(conds)
-    for i in range(n + 1):                                                    # the last pass repeats step n-1 and keeps the mean
-        t = min(i, n - 1)
-        lam_t, lam_s, label = g.lam[t].to(dev).unsqueeze(0), g.lam[t + 1].to(dev).unsqueeze(0), g.label[t].to(dev).unsqueeze(0)
-        mus, var = [], None
-        for z, cond in zip(zs, conds):
-            pred = dc.ema(z, label, encoder_hidden_states=cond, **kc)
-            u_pred = dc.ema(z, label, encoder_hidden_states=null, **kn)
-            mu, var = dc.ddpm_sampler_step(z, pred, u_pred, lam_t.clone().detach(), lam_s.clone().detach())
-            mus.append(mu)
-        if i == n:
-            return [dc.clip(mu) for mu in mus]
-        noise = torch.randn_like(mus[0]) if noise_maps is None else noise_maps[i]
-        zs = [mu + noise * torch.sqrt(var) for mu in mus]
+    return dc.ema(z, label, encoder_hidden_states=cond, **kc), dc.ema(z, label, encoder_hidden_states=null, **kn)
 
 
 def step_fields(dc, backbone, shape, w, noun="fused sampler step"):
@@ -213,8 +207,7 @@ def image_chunks(BS, K, units):
 def pair_sessions(dc, backbone, cl, chunks, dev):
     """One pair session per chunk (b0, b1) of images for the labels cl [BS, K]: unit pair b * K + k is class token cl[b, k] || null
     token; contexts, lengths and the context plan once per call and chunk, session ci in slot ci."""
-    table = dc.encoder is not None
-    lab_dev = dc.encoder.weight.device if table else dev
+    lab_dev = label_device(dc, dev)
     ln = dc.encoder.lengths.cpu() if dc._ragged_table() else None
     sessions = []
     for ci, (b0, b1) in enumerate(chunks):
