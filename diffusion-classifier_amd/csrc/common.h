@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "dcamd.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -148,6 +149,28 @@ template <typename F> static inline int dc_by_dtype16(int dtype, const char* wha
 template <typename F> static inline int dc_by_dtype(int dtype, const char* what, F&& f) {
   if (dtype == DC_F32) return f(float{});
   return dc_by_dtype16(dtype, what, f);
+}
+
+// ---- the scoring loss (include/dcamd.h DC_LOSS_*): one per-element term for dc_eps_mse and dc_err_map ---------------------------
+// The kind is a template parameter of both kernels: the l2 instance holds d * d and nothing of the other two.  NaN in is NaN out for
+// every kind (|NaN| <= delta is false, and delta * (NaN - ...) is NaN).
+template <int LOSS> __device__ __forceinline__ float loss_term(float d, float delta) {
+  if constexpr (LOSS == DC_LOSS_L1) return fabsf(d);
+  if constexpr (LOSS == DC_LOSS_HUBER) {
+    const float a = fabsf(d);
+    return a <= delta ? 0.5f * d * d : delta * (a - 0.5f * delta);
+  }
+  return d * d;
+}
+// dc_by_loss(p->loss, p->huber_delta, "dc_eps_mse", [&](auto kind) { ...launch<decltype(kind)::value>...; return DC_OK; }); an unknown
+// kind, or Huber with a delta that is not finite and > 0: DC_ERR_ARG.
+template <typename F> static inline int dc_by_loss(int loss, float huber_delta, const char* who, F&& f) {
+  if (loss == DC_LOSS_L2) return f(std::integral_constant<int, DC_LOSS_L2>{});
+  if (loss == DC_LOSS_L1) return f(std::integral_constant<int, DC_LOSS_L1>{});
+  DC_REQUIRE(loss == DC_LOSS_HUBER, DC_ERR_ARG, "%s: loss=%d (DC_LOSS_L2 = 0, DC_LOSS_L1 = 1, DC_LOSS_HUBER = 2)", who, loss);
+  DC_REQUIRE(huber_delta > 0.f && huber_delta < __builtin_huge_valf(), DC_ERR_ARG,        // NaN fails both comparisons
+             "%s: huber_delta=%g must be finite and > 0", who, (double)huber_delta);
+  return f(std::integral_constant<int, DC_LOSS_HUBER>{});
 }
 
 // ---- asynchronous LDS fragment reads with hand-counted waits -------------------------------------------------

@@ -151,8 +151,12 @@ struct MseArgs {
   const float* pred; const float* eps; const float* x; const float* alpha; const float* sigma;
   const int32_t* bj_of_unit; const int32_t* img_of_bj; const int32_t* out_index; float* out;
   int C, HW, ld, v_param, W, patch;
+  float huber_delta;       // read by the DC_LOSS_HUBER instance only
 };
 
+// LOSS: the per-element term (common.h loss_term), a compile-time kind on all three read paths; the accumulation order is the same for
+// every kind.  DC_LOSS_L2 ends in sqrt then square, the other two store the sum.
+template <int LOSS>
 __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
   __shared__ float part[4];
   const int u = blockIdx.x, t = threadIdx.x;
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
             v = sg * z + al * v;
           }
           const float d = v - e;
-          s += d * d;
+          s += loss_term<LOSS>(d, a.huber_delta);
         }
     }
   } else
@@ -202,7 +206,7 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
       pv = sg * z + al * pv;
     }
     const float d = pv - e;
-    s += d * d;
+    s += loss_term<LOSS>(d, a.huber_delta);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -210,8 +214,12 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
   __syncthreads();
   if (t == 0) {
     const float tot = ((part[0] + part[1]) + part[2]) + part[3];
-    const float r = sqrtf(tot);   // reference takes torch.norm(...)**2: sqrt, then square
-    a.out[a.out_index ? a.out_index[u] : u] = r * r;
+    float r = tot;
+    if constexpr (LOSS == DC_LOSS_L2) {
+      r = sqrtf(tot);             // reference takes torch.norm(...)**2: sqrt, then square
+      r = r * r;
+    }
+    a.out[a.out_index ? a.out_index[u] : u] = r;
   }
 }
 
@@ -222,9 +230,12 @@ extern "C" int dc_eps_mse(const dc_eps_mse_params* p, dc_stream stream) {
   DC_REQUIRE(p->H % pp == 0 && p->W % pp == 0, DC_ERR_SHAPE, "dc_eps_mse: patch=%d does not tile %dx%d", pp, p->H, p->W);
   if (p->v_param) DC_REQUIRE(p->x && p->alpha && p->sigma, DC_ERR_ARG, "dc_eps_mse: v-param needs x/alpha/sigma");
   MseArgs a{p->pred, p->eps, p->x, p->alpha, p->sigma, p->bj_of_unit, p->img_of_bj, p->out_index, p->out,
-            p->C, p->H * p->W, p->ld, p->v_param, p->W, pp};
-  hipLaunchKernelGGL(eps_mse_kernel, dim3(p->n_units), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  return dc_check_launch("dc_eps_mse");
+            p->C, p->H * p->W, p->ld, p->v_param, p->W, pp, p->huber_delta};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return dc_by_loss(p->loss, p->huber_delta, "dc_eps_mse", [&](auto kind) {
+    hipLaunchKernelGGL((eps_mse_kernel<decltype(kind)::value>), dim3(p->n_units), dim3(256), 0, s, a);
+    return dc_check_launch("dc_eps_mse");
+  });
 }
 
 // ------------------------------------------------------------------ sampler step ---

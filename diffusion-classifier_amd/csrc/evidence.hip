@@ -1,5 +1,5 @@
 // evidence.hip — per-pixel class evidence from the scoring loop (include/dcamd.h "class evidence maps").
-// dc_err_map: per (unit, pixel) the channel sum of (eps_hat - eps)^2, quantised to fixed point and added to the cell's int64 plane.
+// dc_err_map: per (unit, pixel) the channel sum of the scoring loss's term ((eps_hat - eps)^2 for l2), quantised to fixed point and added to the cell's int64 plane.
 // Integer adds are associative, so the result does not depend on arrival order, launch shape or how the grid was cut.
 // dc_evidence_maps: the per-stage planes -> mean map, paired difference map to the winner, invalid counts.
 #include <math.h>
@@ -11,11 +11,13 @@ struct ErrMapArgs {
   const int32_t* bj_of_unit; const int32_t* img_of_bj; const int32_t* out_index;
   unsigned long long* acc; int32_t* bad;
   int C, HW, ld, v_param, W, patch, T, cells, nblk;
+  float huber_delta;       // read by the DC_LOSS_HUBER instance only
 };
 
 // One workgroup per (unit, 256 consecutive pixels); a lane owns one pixel and walks its channels in ascending order, so the C reads of
 // an NHWC prediction row are back to back, the planes of eps / x are read coalesced across the wave, and a wave's 64 adds are one
-// 512-byte run of the cell's plane.
+// 512-byte run of the cell's plane.  LOSS: the per-element term (common.h loss_term), dc_eps_mse's, a compile-time kind.
+template <int LOSS>
 __global__ __launch_bounds__(256) void err_map_kernel(const ErrMapArgs a) {
   const int u = blockIdx.x / a.nblk;
   const int p = (blockIdx.x - u * a.nblk) * 256 + threadIdx.x;
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(256) void err_map_kernel(const ErrMapArgs a) {
       pv = sg * z + al * pv;
     }
     const float d = pv - e;
-    v += d * d;
+    v += loss_term<LOSS>(d, a.huber_delta);
   }
   if (v >= 0.f && v <= DC_EVIDENCE_VMAX) {         // false for NaN
     const long long q = (long long)rint((double)v * (double)(1ll << DC_EVIDENCE_FRAC_BITS));
@@ -67,9 +69,13 @@ extern "C" int dc_err_map(const dc_err_map_params* p, dc_stream stream) {
   const int HW = p->H * p->W, nblk = (HW + 255) / 256;
   DC_REQUIRE((long long)p->n_units * nblk < (1ll << 31), DC_ERR_SHAPE, "dc_err_map: %d units x %d pixel blocks", p->n_units, nblk);
   ErrMapArgs a{p->pred, p->eps, p->x, p->alpha, p->sigma, p->bj_of_unit, p->img_of_bj, p->out_index,
-               reinterpret_cast<unsigned long long*>(p->acc), p->bad, p->C, HW, p->ld, p->v_param, p->W, pp, p->T, p->cells, nblk};
-  hipLaunchKernelGGL(err_map_kernel, dim3((unsigned)(p->n_units * nblk)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  return dc_check_launch("dc_err_map");
+               reinterpret_cast<unsigned long long*>(p->acc), p->bad, p->C, HW, p->ld, p->v_param, p->W, pp, p->T, p->cells, nblk,
+               p->huber_delta};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return dc_by_loss(p->loss, p->huber_delta, "dc_err_map", [&](auto kind) {
+    hipLaunchKernelGGL((err_map_kernel<decltype(kind)::value>), dim3((unsigned)(p->n_units * nblk)), dim3(256), 0, s, a);
+    return dc_check_launch("dc_err_map");
+  });
 }
 
 // ------------------------------------------------------------------ evidence maps --

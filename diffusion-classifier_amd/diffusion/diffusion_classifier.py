@@ -25,6 +25,8 @@ prefetch stream), `shard_grid` (opt-in: True
 shards the (trial, image) grid of ONE replicated batch over the default process group),
 `simulate_rank` ((r, N), bench.py only: time rank r's share of an N-rank sharded call on one GPU),
 `stop_margin_z` (opt-in per-image early stopping, see below; None: off, none of its code runs),
+`score_loss` (None | "l2" | "l1" | "huber": the per-element term summed into classify's errors and evidence maps, with `huber_delta`
+(default 1.0) for "huber"; read once at construction; None / "l2": the reference's squared error, bit for bit; loss.py),
 `vae_path` (a LOCAL diffusers AutoencoderKL directory: `classify` encodes images to latents on the device first, nets/vae.py;
 `vae_dtype` its compute dtype, default the backbone's; `encode_latents(x)`; `classify(..., latents=True)` takes latents as they are;
 `decode_latents(z)` is the way back through the same directory's decoder, loaded at its first call, at most `vae_decode_batch` (default 8)
@@ -92,6 +94,7 @@ from .. import counterfactual as CF
 from .. import ddpm_invert as DI
 from .. import posterior as P
 from .. import evidence as EV
+from .. import loss as LS
 from .. import solver as S
 from .. import trajectory as TJ
 from ..scoring import _ForeignRunner, _HipRunner      # (tests and tools reach the runners through this module)
@@ -175,6 +178,7 @@ class DiffusionClassifier(nn.Module):
         pred_param = self.config.pred_param
         assert pred_param in ['v', 'eps'], "Invalid prediction parameterization. Must be 'v' or 'eps'"
         self.pred_param = pred_param
+        self.score_loss = LS.score_loss_of(self.config)      # (kind, huber delta) of classify's errors and maps; ValueError for bad keys
         schedule = self.config.schedule
         assert schedule in ['cosine', 'shifted_cosine', 'scaled_linear'], "Invalid schedule. Must be 'cosine', 'shifted_cosine' or 'scaled_linear'"
         self.discrete = schedule == 'scaled_linear'      # the backbone's time input is then the DDPM step, not the log-SNR (noise_labels)

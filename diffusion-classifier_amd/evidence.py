@@ -5,7 +5,8 @@ reduction throws away.  For pixel (y, x) of the model's [H, W] grid
 
     v[u, y, x] = sum_ch (eps_hat_u[ch, y, x] - eps_bj[ch, y, x])^2          fp32, ch ascending,
 
-eps_hat formed exactly as the eps-MSE forms it (the v-param conversion, DiT's un-patchified read).  All classes of a trial share
+eps_hat formed exactly as the eps-MSE forms it (the v-param conversion, DiT's un-patchified read); under `config.score_loss` "l1" /
+"huber" the square is that loss's per-element term (loss.py), so the maps follow the loss the errors use.  All classes of a trial share
 (t, eps), so differences between classes are paired by construction, and no backbone forward is added.
 
 Accumulation over trials is FIXED-POINT, hence associative: the same bits for every micro-batch split, launch shape, arrival order
@@ -39,6 +40,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from . import loss as LS
 
 F = L.EVIDENCE_FRAC_BITS          # include/dcamd.h DC_EVIDENCE_FRAC_BITS
 VMAX = L.EVIDENCE_VMAX            # include/dcamd.h DC_EVIDENCE_VMAX
@@ -63,10 +65,11 @@ def new_slabs(n_stages, cells, HW, device):
             torch.zeros((n_stages, cells + 1), dtype=torch.int32, device=device))
 
 
-def err_map_torch(eps_pred, e, cell, acc, bad):
+def err_map_torch(eps_pred, e, cell, acc, bad, loss=L.LOSS_L2, huber_delta=1.0):
     """One batch of units: eps_pred / e [n, C, H, W], cell [n] int64 (the flat (b, class) cell of each unit); adds into acc
-    [cells + 1, HW] int64 and bad [cells + 1] int32 of the stage, in place."""
-    v = ((eps_pred.float() - e.float()) ** 2).sum(1)                       # [n, H, W] fp32
+    [cells + 1, HW] int64 and bad [cells + 1] int32 of the stage, in place.  loss / huber_delta: the scoring loss (loss.py; a L.LOSS_*
+    kind), whose per-element term is summed over the channels."""
+    v = LS.term_torch(eps_pred.float() - e.float(), loss, huber_delta).sum(1)      # [n, H, W] fp32
     ok = torch.isfinite(v) & (v >= 0) & (v <= VMAX)
     q = torch.round(torch.where(ok, v, torch.zeros_like(v)).double() * 2.0 ** F).to(torch.int64)
     acc.index_add_(0, cell, q.reshape(q.shape[0], -1))

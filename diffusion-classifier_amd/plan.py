@@ -538,7 +538,7 @@ class PlanBuilder:
 
     # ---- the two ends of a scoring plan (UNetPlan, DiTPlan) -------------------------------------
     def score_head(self, score, Cin, H, W, ld, dt, im2col, patch=0):
-        """score = dict(x=[B,C,H,W] f32 buffer, eps=[n_bj,C,H,W], alpha, sigma, img_of_bj, out_index, errors, v_param).  Emits q_sample,
+        """score = dict(x=[B,C,H,W] f32 buffer, eps=[n_bj,C,H,W], alpha, sigma, img_of_bj, out_index, errors, v_param, loss, huber_delta).  Emits q_sample,
         which writes the first GEMM's operand: returns (that operand, the (eps, alpha, sigma) externals score_tail takes back)."""
         noise = tuple(self.external(k, score[k], "bj", 1, 1, 1, L.DC_F32) for k in ("eps", "alpha", "sigma"))
         a0 = self.qsample("a0", self.const(score["x"]), *noise, self.const(score["img_of_bj"]), Cin, H, W, ld, dt, im2col=im2col, patch=patch)
@@ -551,7 +551,8 @@ class PlanBuilder:
         px = self.n["unit"] * pred.H * g * pred.W * g
         f = dict(pred=pred, eps=noise[0], x=self.const(score["x"]), alpha=noise[1], sigma=noise[2], bj_of_unit=self.const(bj_of_unit),
                  img_of_bj=self.const(score["img_of_bj"]), out_index=self.const(score["out_index"]), n_units=self.n["unit"], C=Cin,
-                 H=pred.H * g, W=pred.W * g, ld=pred.ld, v_param=int(score["v_param"]), patch=int(patch))
+                 H=pred.H * g, W=pred.W * g, ld=pred.ld, v_param=int(score["v_param"]), patch=int(patch),
+                 loss=int(score["loss"]), huber_delta=float(score["huber_delta"]))      # the scoring loss (loss.py), for both ops
         self.emit(L.OP_EPS_MSE, dict(f, out=self.const(score["errors"])), [pred, *noise], [],
                   dict(name="eps_mse", family="eps_mse", flops=0.0, bytes=8.0 * Cin * px))
         if score.get("emap_acc") is not None:

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from . import evidence as EV
+from . import loss as LS
 from . import posterior as P
 from . import trajectory as TJ
 
@@ -178,10 +179,11 @@ class _ForeignRunner(_Runner):
                 emb = dc.encode_text_prompt(lab)
                 pred = self.bb(x=z, noise_labels=lam, encoder_hidden_states=emb)
                 eps_pred = sg * z + al * pred if dc.pred_param == 'v' else pred
-                err = torch.norm((eps_pred - e).view(len(bl), -1), dim=1, p=2) ** 2
+                err = LS.error_torch(eps_pred, e, *dc.score_loss)      # l2: torch.norm(...) ** 2, the reference's statement
                 self.err[bs.to(x.device), lab, j] = err
                 if self.ev is not None:
-                    EV.err_map_torch(eps_pred, e, bs.to(x.device) * dc.config.classes + lab, self.ev[0][self.ev_stage], self.ev[1][self.ev_stage])
+                    EV.err_map_torch(eps_pred, e, bs.to(x.device) * dc.config.classes + lab, self.ev[0][self.ev_stage], self.ev[1][self.ev_stage],
+                                     *dc.score_loss)
 
 
 class _HipRunner(_Runner):
@@ -210,7 +212,11 @@ class _HipRunner(_Runner):
         S = int(dc.encoder.weight.shape[1]) if dc._table_mode() else 1                 # tokens per context
         varlen = dc._ragged_table()                                                    # prompts of different lengths: a plan with ctx_len
         key = (BS, n_bj, k, self.dt, str(dev), (Cc, H, W), bool(getattr(self.bb, "share_trunk", True)), id(self.bb),
-               self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ()) + (("evidence",) if self.ev is not None else ())
+               self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ())
+        if dc.score_loss[0] != L.LOSS_L2:                # the loss is baked into the plan's two scoring ops: never serve another loss's plan
+            key += (("loss",) + dc.score_loss,)
+        if self.ev is not None:
+            key += ("evidence",)
         sp = dc._score_plans.get(key)
         if sp is not None:
             dc._score_plans[key] = dc._score_plans.pop(key)      # most recently used last
@@ -226,7 +232,7 @@ class _HipRunner(_Runner):
             eps=torch.zeros((n_bj, Cc, H, W), dtype=torch.float32, device=dev),
             errors=torch.full((BS * cfg.classes * T + 1,), float("inf"), dtype=torch.float32, device=dev),
             **{f: layout.view(ctl, f) for f in ("lam", "alpha", "sigma", "img_of_bj", "ctx_of_unit", "out_index")},
-            v_param=dc.pred_param == 'v')
+            v_param=dc.pred_param == 'v', loss=dc.score_loss[0], huber_delta=dc.score_loss[1])
         if self.ev is not None:          # such plans own the accumulators their map op adds into (one stage at a time: run_stage)
             score["emap_acc"], score["emap_bad"] = (v[0] for v in EV.new_slabs(1, BS * cfg.classes, H * W, dev))
             score["emap_T"] = T

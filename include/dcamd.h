@@ -32,7 +32,7 @@
  *   dc_latent_im2col    nothing in the reference: the decoder half of the same AutoencoderKL (decode_latents, sample / counterfactual with
  *                       decode=True) — post_quant_conv and the un-scaling of the latents in fp32, written as the A operand of the
  *                       decoder's conv_in; every other layer of the decoder is dc_igemm / dc_groupnorm / dc_attention(_wide)
- *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2)
+ *   dc_eps_mse          diffusion_classifier.py:706-711 (v->eps, torch.norm(...)**2); additive: DC_LOSS_L1 / DC_LOSS_HUBER sums
  *   dc_haar_dwt2/idwt2  utils/wavelet.py:4-35 / :37-68
  *   dc_ddpm_step        diffusion_classifier.py:175-208 (ddpm_sampler_step) + :262-266, one fused pass per sampling step
  *   dc_ddpm_step_shared / dc_abs_diff_map
@@ -90,7 +90,10 @@ extern "C" {
  *  DC_OP_ATTENTION_WIDE / DC_OP_IM2COL_S2 — likewise)
  * (dc_conv3_pn_tail, dc_conv3_pn_tail_ok, dc_conv3_pn_tail_variant, dc_conv3_pn_tail_ring_floats, dc_pn_tail_params, dc_conv3_pn_tail_op
  *  and DC_OP_CONV3_PN_TAIL — likewise)
- * (the AutoencoderKL decoder's head — dc_latent_im2col, dc_latent_im2col_params and DC_OP_LATENT_IM2COL — likewise) */
+ * (the AutoencoderKL decoder's head — dc_latent_im2col, dc_latent_im2col_params and DC_OP_LATENT_IM2COL — likewise)
+ * (the scoring loss — `loss` and `huber_delta`, the LAST two fields of dc_eps_mse_params and dc_err_map_params, with DC_LOSS_* — is
+ *  additive within 5: no symbol, struct name or op kind changed, and a caller that zero-initialises the structs gets DC_LOSS_L2, the
+ *  bits it got before) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -571,13 +574,23 @@ int32_t dc_tblock_front_ok(const dc_tblock_front_params* p);     /* 1: the shape
 /* err[u] = (|| eps_hat_u - eps_{bj(u)} ||_2)^2 over C*H*W   (reference :706-711)
  * pred [n_units, H, W, ld] f32 NHWC; eps [n_bj,C,H,W], x [n_img,C,H,W] f32 NCHW.
  * v_param: eps_hat = sigma*z + alpha*pred with z = alpha*x + sigma*eps (fp32), else pred.
- * out_index: err is stored at out[out_index[u]] (NULL: out[u]). Deterministic reduction. */
+ * out_index: err is stored at out[out_index[u]] (NULL: out[u]). Deterministic reduction.
+ * loss: the per-element term summed over C*H*W, with d = eps_hat - eps in fp32 (Li et al. evaluate l1, l2 and Huber):
+ *   DC_LOSS_L2     d^2, and the sum goes through sqrt then square as above (the zero value: what every caller got before the field)
+ *   DC_LOSS_L1     |d|
+ *   DC_LOSS_HUBER  |d| <= huber_delta ? 0.5 d^2 : huber_delta (|d| - 0.5 huber_delta)      torch's huber_loss, summed
+ * l1 and Huber store the sum as it is.  Sums, not means.  huber_delta is read for DC_LOSS_HUBER only and must then be finite and > 0;
+ * an unknown kind or such a delta is DC_ERR_ARG.  A NaN element makes its unit's error NaN for every kind. */
+#define DC_LOSS_L2 0
+#define DC_LOSS_L1 1
+#define DC_LOSS_HUBER 2
 typedef struct {
   const float* pred; const float* eps; const float* x; const float* alpha; const float* sigma;
   const int32_t* bj_of_unit; const int32_t* img_of_bj; const int32_t* out_index;
   float* out; int32_t n_units, C, H, W, ld, v_param;
   int32_t patch;            /* >1: pred is DiT's un-patchified projection [n_units, H/p, W/p, ld] with
                                k = (py*p+px)*C + c (nets/dit.py un-patchify folded into the read) */
+  int32_t loss; float huber_delta;
 } dc_eps_mse_params;
 int dc_eps_mse(const dc_eps_mse_params* p, dc_stream s);
 
@@ -736,7 +749,9 @@ int dc_class_posterior(const dc_class_posterior_params* p, dc_stream s);
  * dc_err_map takes dc_eps_mse's inputs and adds q to acc[cell, y, x], cell = out_index[u] / T (out_index NULL: u / T); an index outside
  * [0, cells * T) — the errors dump cell of padded slots — goes to the extra plane `cells`.  acc int64 [cells + 1, H * W], bad int32
  * [cells + 1]; both are accumulated into (the caller zeroes them).  A lane owns a pixel and loops over the channels; the adds are
- * 64-bit integer global atomics, one wave adding 512 contiguous bytes.  It runs right after DC_OP_EPS_MSE, which it leaves alone. */
+ * 64-bit integer global atomics, one wave adding 512 contiguous bytes.  It runs right after DC_OP_EPS_MSE, which it leaves alone.
+ * loss / huber_delta: as in dc_eps_mse_params — v is the channel sum of the same per-element term (DC_LOSS_L2, zero: the square
+ * above), under the same fixed-point rule; the same values are refused. */
 #define DC_EVIDENCE_FRAC_BITS 30
 #define DC_EVIDENCE_VMAX 16384.0f
 typedef struct {
@@ -745,6 +760,7 @@ typedef struct {
   int64_t* acc; int32_t* bad;
   int32_t n_units, C, H, W, ld, v_param, patch;
   int32_t T, cells, pad_;
+  int32_t loss; float huber_delta;
 } dc_err_map_params;
 int dc_err_map(const dc_err_map_params* p, dc_stream s);
 
