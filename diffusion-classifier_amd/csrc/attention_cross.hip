@@ -77,14 +77,19 @@ __global__ __launch_bounds__(256) void attn_cross_f32_kernel(const CrossArgs a) 
   attn_exact_run<T, SW>(w, PlainMode{{w.nk}}, a.scale, a.d, a.KB, kv);
 }
 
-// `fn`: the entry point's name in front of every message (dc_cross_attention / dc_cross_attention_len validate alike)
-static int cross_validate(const dc_cross_attention_params* p, const char* fn) {
+// `fn`: the entry point's name in front of every message (dc_cross_attention / dc_cross_attention_len validate alike); kv_len: the
+// length array of dc_cross_attention_len (null elsewhere)
+static int cross_validate(const dc_cross_attention_params* p, const char* fn, const int32_t* kv_len = nullptr) {
   DC_REQUIRE(p && p->q && p->k && p->v && p->out, DC_ERR_ARG, "%s: null pointer", fn);
   DC_REQUIRE(p->dtype == DC_F32 || p->dtype == DC_BF16 || p->dtype == DC_F16, DC_ERR_DTYPE, "%s: dtype %d", fn, p->dtype);
   DC_REQUIRE(p->d == 16 || p->d == 32 || p->d == 64 || p->d == 96 || p->d == 128 || p->d == 160, DC_ERR_SHAPE, "%s: head dim %d (16/32/64/96/128/160)", fn, p->d);
   DC_REQUIRE(p->n > 0 && p->Lq > 0 && p->heads > 0, DC_ERR_SHAPE, "%s: n/Lq/heads", fn);
   DC_REQUIRE(p->S >= 1, DC_ERR_SHAPE, "%s: S=%d (at least one key)", fn, p->S);
   DC_REQUIRE(p->ld_q >= p->heads * p->d && p->ld_kv >= p->heads * p->d && p->ld_out >= p->heads * p->d, DC_ERR_SHAPE, "%s: ld", fn);
+  // as seq_attn_validate: the kernels index q / k / v / out by element and the maps and lengths as int32
+  DC_REQUIRE((((uintptr_t)p->q_map | (uintptr_t)p->kv_map | (uintptr_t)kv_len) & 3) == 0, DC_ERR_ALIGN, "%s: q_map / kv_map / kv_len must be 4-byte aligned", fn);
+  const uintptr_t es = (uintptr_t)dc_dtype_size(p->dtype) - 1;
+  DC_REQUIRE((((uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->out) & es) == 0, DC_ERR_ALIGN, "%s: q/k/v/out must be element aligned", fn);
   // the matrix-core kernel keeps the running max of the RAW scores and folds the scale into the exponent's FMA: valid for scale > 0 only
   DC_REQUIRE(p->scale > 0.f, DC_ERR_ARG, "%s: scale must be positive (got %g)", fn, (double)p->scale);
   return DC_OK;
@@ -144,14 +149,14 @@ static dc_cross_attention_params cross_base(const dc_cross_attention_len_params*
 extern "C" const char* dc_cross_attention_len_variant(const dc_cross_attention_len_params* p) {
   if (!p) return "invalid";
   const dc_cross_attention_params b = cross_base(p);
-  if (cross_validate(&b, "dc_cross_attention_len") != DC_OK) return "invalid";
+  if (cross_validate(&b, "dc_cross_attention_len", p->kv_len) != DC_OK) return "invalid";
   return cross_mfma_ok(&b) ? "mfma" : "fp32";
 }
 
 extern "C" int dc_cross_attention_len(const dc_cross_attention_len_params* p, dc_stream stream) {
   DC_REQUIRE(p, DC_ERR_ARG, "dc_cross_attention_len: null pointer");
   const dc_cross_attention_params b = cross_base(p);
-  const int rc = cross_validate(&b, "dc_cross_attention_len");
+  const int rc = cross_validate(&b, "dc_cross_attention_len", p->kv_len);
   if (rc != DC_OK) return rc;
   // no lengths: every context has S keys, which is dc_cross_attention's launch
   if (!p->kv_len) return cross_launch<false>(&b, nullptr, stream, "dc_cross_attention_len");

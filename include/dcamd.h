@@ -405,6 +405,7 @@ int dc_latent_im2col(const dc_latent_im2col_params* p, dc_stream s);
  * of a context are never read.
  * scale must be > 0 and S >= 1 (DC_ERR_ARG / DC_ERR_SHAPE); head dims d = 16, 32, 64, 96, 128, 160 (DC_ERR_SHAPE otherwise), narrower
  * heads zero-padded by the caller exactly as for dc_attention (scale of the true width; the pad columns of the output are zero).
+ * q / k / v / out must be aligned to their element and q_map / kv_map (and kv_len below) to 4 bytes (DC_ERR_ALIGN).
  * 160 is Stable Diffusion 1.x's 1280-channel level in 8 heads; its self-attention is this function too: q / k / v the three column
  * offsets of the fused QKV tensor, Lq = S = L, ld_q = ld_kv, both maps NULL (dc_attention serves no 160).
  * 16-bit with d = 32 / 64 / 96 / 128 / 160 and 16-byte aligned rows: the matrix-core kernel (one wave per 32 queries of a (sample, head),

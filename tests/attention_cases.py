@@ -20,8 +20,8 @@ A case is a dict of dc_attention_params' plain fields (dtype, n, L, heads, d, ld
     why       one line
 Plain Python and CPU torch only: nothing here opens a device.
 
-Largest err / bound on an MI355X per route and dtype (tests/test_gpu_attention.py prints it per case): not recorded yet — the module has
-not run on a device; fill in from its first run."""
+Largest err / bound on an MI355X per route and dtype (tests/test_gpu_attention.py prints it per case): wave 0.44 (bf16) / 0.33 (f16), mfma
+0.42 / 0.34, flash 0.48 / 0.27, fp32 0.0092 (f32) / 0.95 (bf16) / 0.84 (f16)."""
 
 import torch
 
