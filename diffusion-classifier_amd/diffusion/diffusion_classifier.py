@@ -12,7 +12,9 @@ per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text
 'clip' (additive, with `config.clip_path` and `config.prompt_tokens = S`) does the same with a CLIP text transformer (nets/clip.py).
 `config.schedule`: 'cosine' and 'shifted_cosine' as in the reference; 'scaled_linear' (additive) is the discrete DDPM schedule a Stable
 Diffusion UNet is trained on — `train_timesteps` (1000) steps, `beta_start` / `beta_end` (0.00085 / 0.012), optionally read from
-`scheduler_path` (a local diffusers scheduler_config.json).  `schedule(t)` is then the log-SNR of the step t falls into, and the backbone
+`scheduler_path` (a local diffusers scheduler_config.json); 'ddpm_linear' (additive) is the DDPM paper's grid a published DiT is trained
+on, betas = linspace(beta_start, beta_end) (1e-4 / 0.02), diffusers' beta_schedule = "linear", and everything below holds for it as for
+'scaled_linear'.  `schedule(t)` is then the log-SNR of the step t falls into, and the backbone
 is fed `noise_labels(t)`, that step as a float, instead of the log-SNR.  Generation on that grid is opt-in: with
 `config.timestep_spacing` = "trailing" | "leading" (additive; diffusers' two integer spacings, `steps_offset` an additive int read from
 `scheduler_path` too) `sample`, `counterfactual`, `invert` and `invert_ddpm` walk the integer steps k_0 > ... > k_n = 0 of
@@ -180,18 +182,19 @@ class DiffusionClassifier(nn.Module):
         self.pred_param = pred_param
         self.score_loss = LS.score_loss_of(self.config)      # (kind, huber delta) of classify's errors and maps; ValueError for bad keys
         schedule = self.config.schedule
-        assert schedule in ['cosine', 'shifted_cosine', 'scaled_linear'], "Invalid schedule. Must be 'cosine', 'shifted_cosine' or 'scaled_linear'"
-        self.discrete = schedule == 'scaled_linear'      # the backbone's time input is then the DDPM step, not the log-SNR (noise_labels)
+        assert schedule in ['cosine', 'shifted_cosine', 'scaled_linear', 'ddpm_linear'], \
+            "Invalid schedule. Must be 'cosine', 'shifted_cosine', 'scaled_linear' or 'ddpm_linear'"
+        self.discrete = schedule in self.DISCRETE      # the backbone's time input is then the DDPM step, not the log-SNR (noise_labels)
         spacing = self.config.timestep_spacing
         if spacing not in (None, "trailing", "leading"):
             raise ValueError(f"config.timestep_spacing must be None, 'trailing' or 'leading', got {spacing!r}")
         if spacing is not None and not self.discrete:
-            raise ValueError(f"config.timestep_spacing = {spacing!r} belongs to the discrete grid of schedule='scaled_linear', "
+            raise ValueError(f"config.timestep_spacing = {spacing!r} belongs to the discrete grid of schedule='scaled_linear' / 'ddpm_linear', "
                              f"not to schedule={schedule!r}: the cosine schedules generate on linspace(from_t, 0, sampling_steps + 1)")
         self.timestep_spacing = spacing
         if self.discrete:
-            self._init_scaled_linear()
-            self.schedule = self.logsnr_schedule_scaled_linear
+            self._init_discrete(schedule)
+            self.schedule = self.logsnr_schedule_discrete
         else:
             self.schedule = self.logsnr_schedule_cosine if schedule == 'cosine' else self.logsnr_schedule_cosine_shifted
         self.noise_d = self.config.noise_d
@@ -347,13 +350,22 @@ class DiffusionClassifier(nn.Module):
     def logsnr_schedule_cosine_shifted(self, t):
         return self.logsnr_schedule_cosine(t) + 2 * math.log(self.noise_d / self.image_d)
 
-    # ---- the discrete DDPM schedule of Stable Diffusion (additive: config.schedule = 'scaled_linear') ----
-    def _init_scaled_linear(self):
-        """N = config.train_timesteps (1000) steps of betas = linspace(sqrt(beta_start), sqrt(beta_end), N)^2 (0.00085, 0.012) ->
+    # ---- the discrete DDPM schedules (additive: config.schedule = 'scaled_linear' | 'ddpm_linear') ----
+    # name -> (diffusers' beta_schedule, default beta_start, default beta_end, the betas of N steps in fp64)
+    DISCRETE = {
+        "scaled_linear": ("scaled_linear", 0.00085, 0.012, lambda b0, b1, N: torch.linspace(b0 ** 0.5, b1 ** 0.5, N, dtype=torch.float64) ** 2),
+        "ddpm_linear": ("linear", 1e-4, 0.02, lambda b0, b1, N: torch.linspace(b0, b1, N, dtype=torch.float64)),
+    }
+
+    def _init_discrete(self, schedule):
+        """N = config.train_timesteps (1000) steps of betas — 'scaled_linear' (Stable Diffusion): linspace(sqrt(beta_start),
+        sqrt(beta_end), N)^2 (0.00085, 0.012); 'ddpm_linear' (DiT, the DDPM paper's grid): linspace(beta_start, beta_end, N) (1e-4, 0.02) ->
         `self.ddpm_logsnr` [N] fp32, log(abar_k / (1 - abar_k)) with abar = cumprod(1 - betas) in fp64, once, on the host.
         config.scheduler_path: a local diffusers scheduler_config.json that supplies num_train_timesteps / beta_start / beta_end (keys of
-        the config win over it where both are given), must say beta_schedule = scaled_linear and must agree with config.pred_param."""
+        the config win over it where both are given), must name the schedule's own beta_schedule ("scaled_linear", and "linear" for
+        'ddpm_linear') and must agree with config.pred_param."""
         cfg = self.config
+        beta_schedule, d0, d1, betas_of = self.DISCRETE[schedule]
         sched = {}
         if cfg.scheduler_path is not None:
             import json
@@ -362,17 +374,20 @@ class DiffusionClassifier(nn.Module):
                 path = os.path.join(path, "scheduler_config.json")
             with open(path) as fh:
                 sched = json.load(fh)
-            if sched.get("beta_schedule", "scaled_linear") != "scaled_linear":
-                raise ValueError(f"{path}: beta_schedule = {sched['beta_schedule']!r}, but schedule='scaled_linear' is the only discrete schedule built here")
+            if sched.get("beta_schedule", beta_schedule) != beta_schedule:
+                other = [k for k, v in self.DISCRETE.items() if v[0] == sched["beta_schedule"]]
+                raise ValueError(f"{path}: beta_schedule = {sched['beta_schedule']!r}, but schedule={schedule!r} is built from beta_schedule = "
+                                 f"{beta_schedule!r}" + (f" (that file belongs to schedule={other[0]!r})" if other else
+                                                         f" (the discrete schedules built here: {sorted(self.DISCRETE)})"))
             want = {"epsilon": "eps", "v_prediction": "v"}.get(sched.get("prediction_type", "epsilon"))
             if want != self.pred_param:
                 raise ValueError(f"{path}: prediction_type = {sched.get('prediction_type')!r} but config.pred_param = {self.pred_param!r}")
         pick = lambda own, key, default: own if own is not None else sched.get(key, default)
         N = int(pick(cfg.train_timesteps, "num_train_timesteps", 1000))
-        b0, b1 = float(pick(cfg.beta_start, "beta_start", 0.00085)), float(pick(cfg.beta_end, "beta_end", 0.012))
+        b0, b1 = float(pick(cfg.beta_start, "beta_start", d0)), float(pick(cfg.beta_end, "beta_end", d1))
         if N < 1 or not 0.0 < b0 <= b1 < 1.0:
-            raise ValueError(f"schedule='scaled_linear' needs train_timesteps >= 1 and 0 < beta_start <= beta_end < 1, got {N}, {b0}, {b1}")
-        betas = torch.linspace(b0 ** 0.5, b1 ** 0.5, N, dtype=torch.float64) ** 2
+            raise ValueError(f"schedule={schedule!r} needs train_timesteps >= 1 and 0 < beta_start <= beta_end < 1, got {N}, {b0}, {b1}")
+        betas = betas_of(b0, b1, N)
         abar = torch.cumprod(1.0 - betas, 0)
         self.train_timesteps = N
         off = pick(cfg.steps_offset, "steps_offset", 0)
@@ -387,25 +402,27 @@ class DiffusionClassifier(nn.Module):
         t = torch.as_tensor(t)
         return torch.clamp(torch.floor(t.detach().to("cpu", torch.float64) * N), 0, N - 1).to(torch.int64)
 
-    def logsnr_schedule_scaled_linear(self, t):
+    def logsnr_schedule_discrete(self, t):
         """log-SNR of the step t falls into, fp32 (on t's device)."""
         return self.ddpm_logsnr[self.ddpm_step(t)].to(torch.as_tensor(t).device)
 
+    logsnr_schedule_scaled_linear = logsnr_schedule_discrete      # the earlier name
+
     def noise_labels(self, t):
         """What the backbone is fed as its time input at t: the log-SNR `schedule(t)` for the cosine schedules (the reference's
-        models), the DDPM step as fp32 for 'scaled_linear' (a Stable Diffusion UNet embeds the integer step)."""
+        models), the DDPM step as fp32 for the discrete schedules (a Stable Diffusion UNet and a published DiT embed the integer step)."""
         if self.discrete:
             return self.ddpm_step(t).to(torch.float32).to(torch.as_tensor(t).device)
         return self.schedule(t)
 
     def _refuse_discrete(self, what, from_t):
-        """Generation under schedule='scaled_linear' is opt-in: without config.timestep_spacing there is no map from
+        """Generation under a discrete schedule ('scaled_linear', 'ddpm_linear') is opt-in: without config.timestep_spacing there is no map from
         linspace(from_t, 0, sampling_steps + 1) to DDPM steps.  With the key, the grid of this call is built once here so that an
         impossible one (trajectory.discrete_steps) is refused before any draw."""
         if not self.discrete:
             return
         if self.timestep_spacing is None:
-            raise NotImplementedError(f"{what} under schedule='scaled_linear' needs config.timestep_spacing = 'trailing' | 'leading': "
+            raise NotImplementedError(f"{what} under schedule={self.config.schedule!r} needs config.timestep_spacing = 'trailing' | 'leading': "
                                       "how sampling_steps are laid on the discrete DDPM grid is the caller's choice (unset: classify only)")
         TJ.discrete_steps(self, from_t)
 

@@ -8,7 +8,7 @@ the per-class part of the conditioning is a table row added in a GEMM epilogue.
 import torch
 
 from . import _lib as L
-from .packing import f32c, pack_matrix, pad_head_cols, pad_head_rows, padded_head_dim
+from .packing import eps_rows, f32c, pack_matrix, pad_head_cols, pad_head_rows, padded_head_dim
 from .plan import TORCH_DT, Plan, PlanBuilder, bke, round_up
 
 
@@ -50,16 +50,29 @@ class DiTWeights:
             P[k + ".ff2.b"] = f32c(sd[k + ".ff.net.2.bias"], device)
         P["po1.w"], P["po1.b"] = pack_matrix(sd["proj_out_1.weight"], L.DC_F32, device), f32c(sd["proj_out_1.bias"], device)
         P["po2.w"], P["po2.b"] = pack_matrix(sd["proj_out_2.weight"], dt, device), f32c(sd["proj_out_2.bias"], device)
+        if cfg.out_channels == 2 * cin:
+            # learned variance: the eps rows of proj_out_2 as a projection of their own, [p * p * cin, D] — what the plans that feed a
+            # scoring tail or a step kernel run instead of the full one (DiTPlan, eps_only)
+            rows = eps_rows(p, cin, cfg.out_channels)
+            P["po2e.w"], P["po2e.b"] = pack_matrix(sd["proj_out_2.weight"][rows], dt, device), f32c(sd["proj_out_2.bias"][rows], device)
         self.P = P
 
 
 class DiTPlan(Plan):
     """inputs: lam [n_bj]; ctx_of_unit [U] = class label per unit (row of the embedding tables);
     a0 = patch tokens [n_bj, g, g, kin].  output: pred [U, g, g, p*p*out_ch] f32 (un-patchify is
-    folded into dc_eps_mse / done by the caller)."""
+    folded into dc_eps_mse / done by the caller).
+    eps_only (always with a score): the prediction feeds a kernel that indexes it with the latent's channel count C as the feature
+    stride (the scoring tail, the step kernels behind forward_pair / a pair session), so it must hold eps alone:
+    pred [U, g, g, p*p*C].  With out_channels == C that is the plan as ever; with out_channels == 2 C (learned variance) proj_out_2
+    runs on its eps rows only (DiTWeights "po2e"); any other width is refused (packing.eps_rows)."""
 
-    def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, score=None, device=None, share_trunk=True):
+    def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, score=None, device=None, share_trunk=True, eps_only=False):
         cfg = model.config
+        eps_only = eps_only or score is not None
+        po2, oc = "po2", cfg.out_channels
+        if eps_only and eps_rows(cfg.patch_size, cfg.in_channels, oc, type(model).__name__) is not None:
+            po2, oc = "po2e", cfg.in_channels
         dev = device or weights.dev
         dt = weights.dt
         P = weights.P
@@ -117,8 +130,7 @@ class DiTPlan(Plan):
             h = pb.igemm(k + ".ff2", f, pb.const(P[k + ".ff2.w"]), D, bias=pb.const(P[k + ".ff2.b"]),
                          gate=m.view(5 * D, D), residual=h)
         hn = pb.layernorm("final.ln", h, None, None, 1e-6, scale=fin.view(D, D), shift=fin.view(0, D))
-        oc = cfg.out_channels
-        pred = pb.igemm("proj_out_2", hn, pb.const(P["po2.w"]), p * p * oc, bias=pb.const(P["po2.b"]), out_dt=L.DC_F32,
+        pred = pb.igemm("proj_out_2", hn, pb.const(P[po2 + ".w"]), p * p * oc, bias=pb.const(P[po2 + ".b"]), out_dt=L.DC_F32,
                         tile_n=32 if p * p * oc <= 32 else 128)
         self.pred = pred
         if score is not None:

@@ -7,6 +7,8 @@ in the reference, which passes its third argument positionally into diffusers'
 (`encoder_type='DiT'`, diffusion_classifier.py:90-92).  Parameter names are diffusers'
 `DiTTransformer2DModel`'s.  Modules only hold parameters; arithmetic runs in libdcamd.
 """
+import json
+import os
 from types import SimpleNamespace
 from typing import Optional
 
@@ -17,6 +19,7 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import engine as E
 from .. import engine_dit as ED
+from ..packing import eps_rows
 from .unet import PairSession, _Bag, _HipBackbone
 
 
@@ -99,25 +102,34 @@ class DiT(_HipBackbone):
 
     weights_class, im2col = ED.DiTWeights, 2                   # `patch` is the instance's patch_size
 
-    def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None):
+    eps_rows_only = True       # trajectory.step_fields: forward_pair / a pair session hand out eps alone, at feature stride in_channels
+
+    def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None, eps_only=False):
+        """eps_only (implied by a score): the plan's prediction holds eps alone, [U, g, g, p*p*in_channels] — with learned-variance
+        outputs (out_channels == 2 * in_channels) proj_out_2 is cut to its eps rows; another out_channels != in_channels is refused
+        here, before anything is packed (engine_dit.DiTPlan)."""
+        if eps_only or score is not None:
+            eps_rows(self.patch, self.config.in_channels, self.config.out_channels, type(self).__name__)
         dt = E.DT[self.compute_dtype]
-        return ED.DiTPlan(self, self.packed_weights(dt, device), n_bj, n_cls, n_ctx, score=score, device=device)
+        return ED.DiTPlan(self, self.packed_weights(dt, device), n_bj, n_cls, n_ctx, score=score, device=device, eps_only=eps_only)
 
     def _label_plan(self, kind, N, dev, labels):
         """What `forward`, `forward_pair` and `pair_session` share: the plan cached under kind + (N, device, dtype) (built on first use)
-        with the labels — one int tensor of N per unit of an image, unit n_cls * b + u = labels[u][b] — copied into its `ctx_of_unit`."""
+        with the labels — one int tensor of N per unit of an image, unit n_cls * b + u = labels[u][b] — copied into its `ctx_of_unit`.
+        `forward`'s plan predicts all out_channels, the pair plans eps alone."""
         key = kind + (N, str(dev), self.compute_dtype)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = self.make_plan(N, len(labels), None, dev)
+            plan = self._plans[key] = self.make_plan(N, len(labels), None, dev, eps_only=kind[0] != "fwd")
         plan.ctx_of_unit.copy_(torch.stack([lab.reshape(-1) for lab in labels], dim=1).reshape(-1).to(dev, torch.int32))
         return plan
 
     @torch.no_grad()
     def forward_pair(self, x, noise_labels, cond, null):
         """Classifier-free-guidance pair as ONE batch-2 plan launch: unit 2b = image b under label `cond[b]`, unit 2b+1 under the
-        null label `null[b]` (reference `sample`, :255-266, calls the backbone twice per step).  Returns the plan's un-patchified
-        projection [2N, H/p, W/p, ld] fp32 (the layout `dc_ddpm_step` reads with patch = p) — a view the next call overwrites."""
+        null label `null[b]` (reference `sample`, :255-266, calls the backbone twice per step).  Returns the plan's patch-major
+        projection [2N, H/p, W/p, p*p*in_channels] fp32, eps alone — a learned variance (out_channels == 2 * in_channels) is dropped, as
+        diffusers' DiTPipeline drops it (the layout `dc_ddpm_step` reads with patch = p) — a view the next call overwrites."""
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError("DiT.forward_pair needs CUDA/HIP tensors (no CPU fallback)")
@@ -149,3 +161,43 @@ class DiT(_HipBackbone):
         g = H // p
         out = plan.pred_view().reshape(N, g, g, p, p, oc)          # un-patchify: nhwpqc -> nchpwq
         return out.permute(0, 5, 1, 3, 2, 4).reshape(N, oc, g * p, g * p).contiguous().to(x.dtype)
+
+    # ---- loading --------------------------------------------------------------------------------
+    REQUIRED_KEYS = ("num_attention_heads", "attention_head_dim", "in_channels", "num_layers", "sample_size", "patch_size",
+                     "num_embeds_ada_norm")
+    # keys of diffusers' Transformer2DModel / DiTTransformer2DModel config that the constructor does not take: accepted at the value the
+    # published DiT checkpoints carry (the class-conditional adaLN-Zero transformer on continuous latents), refused by name at another
+    FIXED_KEYS = dict(cross_attention_dim=None, num_vector_embeds=None, only_cross_attention=False, use_linear_projection=False,
+                      double_self_attention=False, attention_type="default", caption_channels=None, interpolation_scale=None)
+    WEIGHTS = "diffusion_pytorch_model.safetensors"
+
+    @classmethod
+    def from_directory(cls, path, **overrides):
+        """A local diffusers `transformer/` directory (config.json + diffusion_pytorch_model.safetensors) of a published DiT.  Config keys
+        that start with `_` are ignored; `overrides` replace keys of the file; the keys of FIXED_KEYS must carry the value given there;
+        every other key goes to the constructor, which refuses what is outside the envelope by name — as is a key neither knows.  The
+        weights load strictly (the parameter names are diffusers') and the model is frozen.  Never touches the network."""
+        cfg_path, st_path = os.path.join(path, "config.json"), os.path.join(path, cls.WEIGHTS)
+        for f in (cfg_path, st_path):
+            if not os.path.isfile(f):
+                raise FileNotFoundError(f"{f} is missing: {cls.__name__}.from_directory needs a local diffusers DiTTransformer2DModel / "
+                                        f"Transformer2DModel directory with config.json and {cls.WEIGHTS} (nothing is fetched)")
+        with open(cfg_path) as fh:
+            raw = json.load(fh)
+        missing = [k for k in cls.REQUIRED_KEYS if k not in raw]
+        if missing:
+            raise ValueError(f"{cfg_path} lacks {missing}")
+        kw = {k: v for k, v in raw.items() if not k.startswith("_")}
+        kw.update(overrides)
+        for k, want in cls.FIXED_KEYS.items():
+            got = kw.pop(k, want)
+            if got != want:
+                raise NotImplementedError(f"{cls.__name__}({k}={got!r}) is outside the scoring path built here (supported: {want!r})")
+        try:
+            model = cls(**kw)
+        except TypeError as e:
+            raise NotImplementedError(f"{cfg_path}: {e} (a config key this envelope does not know)") from None
+        from safetensors.torch import load_file
+        model.load_state_dict(load_file(st_path), strict=True)
+        model.requires_grad_(False)
+        return model

@@ -143,6 +143,20 @@ def pad_head_cols(w, d, dp):
     return out.reshape(w.shape[0], -1)
 
 
+def eps_rows(p, C, oc, who="DiT"):
+    """Learned-variance outputs (out_channels = 2 * in_channels: eps, then the variance interpolation): the rows of a patch projection
+    [p * p * oc, D] that hold eps, row (py * p + px) * oc + c for c < C, in (py, px, c) order — the projection cut to them writes
+    features k = (py * p + px) * C + c, what a model with out_channels = C writes and every elementwise kernel reads.
+    oc == C: None (every row is one).  Any other width is refused, naming both numbers: nothing here reads such a prediction."""
+    if oc == C:
+        return None
+    if oc != 2 * C:
+        raise NotImplementedError(f"{who}: out_channels = {oc} with in_channels = {C} is not served by the scoring and generation plans: "
+                                  f"out_channels must be in_channels (eps) or 2 * in_channels = {2 * C} (eps, then a learned variance "
+                                  "that is dropped)")
+    return (torch.arange(p * p).reshape(-1, 1) * oc + torch.arange(C).reshape(1, -1)).reshape(-1)
+
+
 class LazyPacks:
     """Base of a weights object whose plans ask for further packed forms on first use.  The object has `P` (key -> packed device
     tensor), `_sd` (the state dict, references only), `dt` and `dev`."""

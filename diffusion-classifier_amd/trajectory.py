@@ -164,10 +164,12 @@ def guided_pair(dc, z, label, cond, null, lens=None):
 
 def step_fields(dc, backbone, shape, w, noun="fused sampler step"):
     """The fields every step struct shares but n and ld, for latents of `shape` [*, C, H, W] under guidance weight w.  `patch` is the
-    backbone's; the kernels index the prediction with z's channel count as the feature stride, so out_channels must equal C."""
+    backbone's; the kernels index the prediction with z's channel count as the feature stride, so the prediction must hold C channels:
+    out_channels == C, or a backbone whose pair plans project the eps rows only (`eps_rows_only`: DiT) with out_channels == 2 C — the
+    learned variance is dropped, as diffusers' DiTPipeline drops it."""
     _, Cc, H, W = shape
     oc = int(getattr(backbone.config, "out_channels", Cc) or Cc)
-    if oc != Cc:
+    if oc != Cc and not (oc == 2 * Cc and getattr(backbone, "eps_rows_only", False)):
         raise L.DcamdError(f"{noun} needs out_channels == in_channels (got {oc} vs {Cc})")
     w = float(w)
     return dict(C=Cc, H=H, W=W, patch=int(getattr(backbone.config, "patch_size", 0) or 0), v_param=int(dc.pred_param == 'v'),

@@ -590,7 +590,8 @@ typedef struct {
   const int32_t* bj_of_unit; const int32_t* img_of_bj; const int32_t* out_index;
   float* out; int32_t n_units, C, H, W, ld, v_param;
   int32_t patch;            /* >1: pred is DiT's un-patchified projection [n_units, H/p, W/p, ld] with
-                               k = (py*p+px)*C + c (nets/dit.py un-patchify folded into the read) */
+                               k = (py*p+px)*C + c (nets/dit.py un-patchify folded into the read; the feature stride is C:
+                               the caller projects the eps rows only) */
   int32_t loss; float huber_delta;
 } dc_eps_mse_params;
 int dc_eps_mse(const dc_eps_mse_params* p, dc_stream s);
@@ -601,7 +602,7 @@ int dc_eps_mse(const dc_eps_mse_params* p, dc_stream s);
  *   mu = alpha_s * (z * (1 - c) / alpha_t + c * x);   out = noise ? mu + noise * sd : clip(mu, -1, 1)      (sd = sqrt(sigma_s^2 c))
  * z / noise / out [n, C, H, W] f32 NCHW; pred [2n, H, W, ld] f32 NHWC, rows 2b (class token) and 2b+1 (null token) of image b —
  * the output of ONE batch-2 backbone plan (patch > 1: DiT's un-patchified projection as in dc_eps_mse, whose feature stride is C:
- * the backbone's out_channels must equal C).  Same operation order as the reference's torch expressions, no contraction: equal to
+ * the caller projects the eps rows only, also of a backbone whose out_channels is 2C).  Same operation order as the reference's torch expressions, no contraction: equal to
  * them bit for bit for the same fp32 scalars (w, one_plus_w, alpha_*, sigma_t, c, sd — formed by the caller). */
 typedef struct {
   const float* z; const float* pred; const float* noise; float* out;
