@@ -11,7 +11,7 @@ All arithmetic of the scoring path runs in `libdcamd.so` (HIP kernels + C-ABI, c
 """
 from . import _lib  # noqa: F401
 from .nets.unet import UNetCondition2D, UNet2D  # noqa: F401
-from .nets.sd_unet import StableDiffusionUNet  # noqa: F401
+from .nets.sd_unet import StableDiffusionUNet, StableDiffusionXLUNet  # noqa: F401
 from .nets.dit import DiT  # noqa: F401
 from .nets.vae import VAEEncoder, VAEDecoder  # noqa: F401
 from .diffusion.diffusion_classifier import DiffusionClassifier  # noqa: F401
@@ -150,6 +150,19 @@ def sd21_unet_kwargs():
     # the published Stable Diffusion 2.1 UNet (2.1-base: 64x64 latents; the 768-pixel model differs in sample_size = 96 alone): heads
     # (5, 10, 20, 20), i.e. 64 channels per head everywhere, the OpenCLIP ViT-H context of 1024 channels, linear projections
     return dict(sd15_unet_kwargs(), cross_attention_dim=1024, attention_head_dim=(5, 10, 20, 20), use_linear_projection=True)
+
+
+def sdxl_unet_kwargs():
+    # the published Stable Diffusion XL base UNet (`unet/config.json` of stable-diffusion-xl-base-1.0): 128x128 latents, three levels,
+    # 1 / 2 / 10 transformer blocks per site (none at the first level), 64 channels per head everywhere, the 768 + 1280 context of its two
+    # CLIP text encoders, linear projections, the text_time embedding over a 1280-wide pooled row and six size numbers at 256 each;
+    # StableDiffusionXLUNet takes it
+    return dict(sample_size=128, in_channels=4, out_channels=4, layers_per_block=2, block_out_channels=(320, 640, 1280),
+                down_block_types=("DownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D"),
+                up_block_types=("CrossAttnUpBlock2D", "CrossAttnUpBlock2D", "UpBlock2D"),
+                mid_block_type="UNetMidBlock2DCrossAttn", norm_num_groups=32, cross_attention_dim=2048, attention_head_dim=(5, 10, 20),
+                transformer_layers_per_block=(1, 2, 10), use_linear_projection=True, addition_embed_type="text_time",
+                addition_time_embed_dim=256, projection_class_embeddings_input_dim=2816)
 
 
 def chexpert_dit_b4_kwargs(wavelet_transform=True):

@@ -10,6 +10,11 @@ per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text
 't5' (with `config.t5_path`, a LOCAL Hugging Face directory, and `config.prompt_tokens = S`) runs the T5 encoder on the device
 (nets/t5.py) and fills the same table: `set_class_prompts(input_ids, attention_mask)`, then everything is the 'prompt' path.
 'clip' (additive, with `config.clip_path` and `config.prompt_tokens = S`) does the same with a CLIP text transformer (nets/clip.py).
+'clip_dual' (additive, with `config.clip_path`, `config.clip2_path`, optionally `config.clip2_variant` and `config.add_time_ids`) is the
+conditioning of a StableDiffusionXLUNet: both CLIP text encoders read at their penultimate layer fill the table side by side, the second
+one's projected pooled output fills `pooled_table` next to it, and six size numbers shared by all classes go with them
+(`set_class_prompts(ids, mask, input_ids_2=, attention_mask_2=)`, `set_pooled`); scoring only — `sample`, `counterfactual`, `invert` and
+`invert_ddpm` raise NotImplementedError under it.
 `config.schedule`: 'cosine' and 'shifted_cosine' as in the reference; 'scaled_linear' (additive) is the discrete DDPM schedule a Stable
 Diffusion UNet is trained on — `train_timesteps` (1000) steps, `beta_start` / `beta_end` (0.00085 / 0.012), optionally read from
 `scheduler_path` (a local diffusers scheduler_config.json); 'ddpm_linear' (additive) is the DDPM paper's grid a published DiT is trained
@@ -248,6 +253,8 @@ class DiffusionClassifier(nn.Module):
             self.tokenizer = None
             self.null_token = self.config.classes
             self._prompts_set = False
+        elif self.encoder_type == 'clip_dual':
+            self._init_clip_dual(backbone)
         elif self.encoder_type == 'prompt':
             S = self.config.prompt_tokens
             assert isinstance(S, int) and S >= 1, "encoder_type='prompt' needs config.prompt_tokens = S >= 1"
@@ -280,6 +287,77 @@ class DiffusionClassifier(nn.Module):
         self._score_plans = {}
         self._timed_sink = None      # bench.py: list collecting (plan, per-op event ms) instead of plain runs
 
+    # ---- encoder_type='clip_dual' (additive): the conditioning of a Stable Diffusion XL UNet ----
+    def _init_clip_dual(self, backbone):
+        """Two CLIP text encoders from LOCAL directories: config.clip_path (SDXL's text_encoder/, a CLIPTextEncoder) and
+        config.clip2_path (text_encoder_2/, a CLIPTextEncoderWithProjection; config.clip2_variant = "fp16" reads model.fp16.safetensors),
+        both read at layer=-2, the second also pooled.  The prompt table [classes + 1, S, hidden_1 + hidden_2] holds the two
+        penultimate states side by side, encoder 1 first, as diffusers concatenates them; next to it `pooled_table`
+        [classes + 1, projection_dim], a buffer registered under this encoder type only.  config.add_time_ids: diffusers' six numbers
+        (original_h, original_w, crop_top, crop_left, target_h, target_w), one set for all classes and images; None: (s, s, 0, 0, s, s)
+        with s = config.image_size."""
+        cfg = self.config
+        for key in ("clip_path", "clip2_path"):
+            if getattr(cfg, key) is None:
+                raise NotImplementedError(f"encoder_type='clip_dual' needs config.{key}: LOCAL Hugging Face directories of the two CLIP text "
+                                          "models of a Stable Diffusion XL pipeline (clip_path: text_encoder/, clip2_path: text_encoder_2/; "
+                                          "nothing is fetched)")
+        from ..nets.clip import CLIPTextEncoder, CLIPTextEncoderWithProjection
+        S = cfg.prompt_tokens
+        assert isinstance(S, int) and S >= 2, "encoder_type='clip_dual' needs config.prompt_tokens = S >= 2"
+        self.text_encoder = CLIPTextEncoder.from_directory(cfg.clip_path)
+        self.text_encoder_2 = CLIPTextEncoderWithProjection.from_directory(cfg.clip2_path, variant=cfg.clip2_variant)
+        h1, h2, P_ = self.text_encoder.config.hidden_size, self.text_encoder_2.config.hidden_size, self.text_encoder_2.config.projection_dim
+        bc = backbone.config
+        xdim = getattr(bc, "cross_attention_dim", None)
+        if h1 + h2 != xdim:
+            raise ValueError(f"the two CLIP text encoders are {h1} + {h2} = {h1 + h2} wide but backbone.config.cross_attention_dim = {xdim}")
+        dim, pcid = getattr(bc, "addition_time_embed_dim", None), getattr(bc, "projection_class_embeddings_input_dim", None)
+        if dim is None or pcid is None or P_ + 6 * dim != pcid:
+            raise ValueError(f"projection_dim + 6 * addition_time_embed_dim = {P_} + 6 * {dim} but "
+                             f"backbone.config.projection_class_embeddings_input_dim = {pcid}")
+        ids = cfg.add_time_ids
+        if ids is None:
+            s = float(cfg.image_size)
+            ids = (s, s, 0.0, 0.0, s, s)
+        ids = torch.as_tensor(ids, dtype=torch.float32).reshape(-1)
+        if ids.numel() != 6:
+            raise ValueError(f"config.add_time_ids must be six numbers (original_h, original_w, crop_top, crop_left, target_h, target_w), "
+                             f"got {ids.numel()}")
+        self.add_time_ids = ids                          # plain attribute: host data, one set for every class and image
+        self.encoder = PromptTable(cfg.classes + 1, S, h1 + h2)
+        self.register_buffer("pooled_table", torch.zeros(cfg.classes + 1, P_))
+        self.tokenizer = None
+        self.null_token = cfg.classes
+        self._prompts_set = False
+        self._pooled_rows = set()                        # rows given through set_pooled: a table filled by hand needs all of them
+
+    @torch.no_grad()
+    def set_pooled(self, row, vec):
+        """encoder_type='clip_dual': pooled row `row` := vec [projection_dim], the way PromptTable.set_prompt sets a prompt row (for
+        text embeddings computed offline; `set_class_prompts` fills both tables from token ids)."""
+        if self.encoder_type != 'clip_dual':
+            raise RuntimeError(f"set_pooled belongs to encoder_type='clip_dual' (this classifier has {self.encoder_type!r})")
+        vec = torch.as_tensor(vec)
+        P_ = self.pooled_table.shape[1]
+        if vec.dim() != 1 or vec.shape[0] != P_:
+            raise ValueError(f"the pooled vector of row {row} must be [{P_}], got {tuple(vec.shape)}")
+        self.pooled_table[row] = vec.to(self.pooled_table.device, self.pooled_table.dtype)
+        self._pooled_rows.add(int(row) % self.pooled_table.shape[0])
+
+    def added_cond(self, labels):
+        """What a foreign backbone is called with next to encoder_hidden_states: {} unless encoder_type='clip_dual', then
+        added_cond_kwargs = {"text_embeds": the pooled rows of `labels`, "time_ids": config.add_time_ids per row} (diffusers' names)."""
+        if self.encoder_type != 'clip_dual':
+            return {}
+        te = self.pooled_table[labels.to(self.pooled_table.device)]
+        return {"added_cond_kwargs": {"text_embeds": te, "time_ids": self.add_time_ids.to(te.device).expand(te.shape[0], 6)}}
+
+    def _refuse_sdxl_generation(self, what):
+        if self.encoder_type == 'clip_dual':
+            raise NotImplementedError(f"{what}: generation with an SDXL backbone (encoder_type='clip_dual') is not built: scoring only — "
+                                      "classify, evaluate / inference in classification mode, and the backbone's forward")
+
     # ---- small reference-identical helpers (host side, fp32 torch like the reference) -------
     def encode_text_prompt(self, text):
         if self.encoder_type == 'nn':
@@ -296,22 +374,34 @@ class DiffusionClassifier(nn.Module):
 
     def _table_mode(self):
         """Is the conditioning a PromptTable row per class ('prompt', and 't5' / 'clip' whose encoder fills the same table)?"""
-        return self.encoder_type in ('prompt', 't5', 'clip')
+        return self.encoder_type in ('prompt', 't5', 'clip', 'clip_dual')
 
     def _ragged_table(self):
         return self._table_mode() and self.encoder.varlen
 
     def _require_prompts(self):
+        if self.encoder_type == 'clip_dual' and not self._prompts_set and len(self._pooled_rows) < self.pooled_table.shape[0]:
+            raise RuntimeError("encoder_type='clip_dual': call set_class_prompts(input_ids, attention_mask, input_ids_2=..., "
+                               "attention_mask_2=...) before classify, or fill both tables by hand (encoder.set_prompt and set_pooled for "
+                               "every row)")
         if self.encoder_type in ('t5', 'clip') and not self._prompts_set:
             raise RuntimeError(f"encoder_type={self.encoder_type!r}: call set_class_prompts(input_ids, attention_mask) before classify / "
                                "sample (the prompt table is still empty)")
 
     @torch.no_grad()
-    def set_class_prompts(self, input_ids, attention_mask=None):
+    def set_class_prompts(self, input_ids, attention_mask=None, *, input_ids_2=None, attention_mask_2=None):
         """encoder_type='t5' / 'clip': token ids [classes + 1, L <= S] of one prompt per class, the last row the null prompt (tokenising
         is the caller's job), and their right-padded attention mask.  Runs the text encoder on the device (its compute dtype is
         config.compute_dtype), writes weight[:, :L], zeroes the rest and records the token counts as the table's lengths (without a
-        mask every row is a real state and the lengths are L: what Stable Diffusion feeds its UNet from CLIP)."""
+        mask every row is a real state and the lengths are L: what Stable Diffusion feeds its UNet from CLIP).
+        encoder_type='clip_dual': input_ids / attention_mask are the first tokenizer's, input_ids_2 / attention_mask_2 (required) the
+        second's — the two differ in their pad token and may differ in L, but the token counts must agree row by row (the table has
+        one length per row; ValueError naming the first row that differs).  Both encoders are read at layer=-2, their states written
+        side by side (encoder 1 first), the second's pooled output into `pooled_table`.  The null row is encoded like any other."""
+        if self.encoder_type == 'clip_dual':
+            return self._set_class_prompts_dual(input_ids, attention_mask, input_ids_2, attention_mask_2)
+        if input_ids_2 is not None or attention_mask_2 is not None:
+            raise ValueError(f"input_ids_2 / attention_mask_2 belong to encoder_type='clip_dual' (this classifier has {self.encoder_type!r})")
         if self.encoder_type not in ('t5', 'clip'):
             raise RuntimeError(f"set_class_prompts belongs to encoder_type='t5' / 'clip' (this classifier has {self.encoder_type!r})")
         rows, S = self.encoder.weight.shape[0], self.encoder.weight.shape[1]
@@ -328,6 +418,37 @@ class DiffusionClassifier(nn.Module):
         self.encoder.weight.zero_()
         self.encoder.weight[:, :ids.shape[1]] = emb.to(self.encoder.weight.dtype)
         self.encoder.set_lengths(lens)
+        self._prompts_set = True
+
+    def _set_class_prompts_dual(self, ids1, mask1, ids2, mask2):
+        if ids2 is None:
+            raise ValueError("encoder_type='clip_dual' needs input_ids_2 (and attention_mask_2): the token ids of the second tokenizer")
+        rows, S = self.encoder.weight.shape[0], self.encoder.weight.shape[1]
+        ids1, ids2 = torch.as_tensor(ids1), torch.as_tensor(ids2)
+        for name, ids in (("input_ids", ids1), ("input_ids_2", ids2)):
+            if ids.dim() != 2 or ids.shape[0] != rows or not 1 <= ids.shape[1] <= S:
+                raise ValueError(f"{name} must be [{rows}, L <= {S}] (one prompt per class and the null prompt), got {tuple(ids.shape)}")
+        from ..engine_t5 import lengths_of_mask
+        len1, len2 = lengths_of_mask(mask1, ids1.shape), lengths_of_mask(mask2, ids2.shape)
+        differ = (len1 != len2).nonzero().reshape(-1).tolist()
+        if differ:
+            b = differ[0]
+            raise ValueError(f"the two tokenizers' token counts must agree row by row: row {b} has {int(len1[b])} tokens for the first "
+                             f"encoder and {int(len2[b])} for the second")
+        dev = self.encoder.weight.device
+        dt = self.config.compute_dtype or "bf16"
+        for enc in (self.text_encoder, self.text_encoder_2):
+            if enc.compute_dtype != dt:
+                enc.set_compute_dtype(dt)
+        on = lambda t: None if t is None else torch.as_tensor(t).to(dev)
+        h1 = self.text_encoder.hidden_state(ids1.to(dev), on(mask1), layer=-2)
+        h2, pooled = self.text_encoder_2(ids2.to(dev), on(mask2), layer=-2, pooled=True)
+        L1, L2, H1 = ids1.shape[1], ids2.shape[1], h1.shape[2]
+        self.encoder.weight.zero_()
+        self.encoder.weight[:, :L1, :H1] = h1.to(self.encoder.weight.dtype)
+        self.encoder.weight[:, :L2, H1:] = h2.to(self.encoder.weight.dtype)
+        self.encoder.set_lengths(len1)
+        self.pooled_table.copy_(pooled.to(self.pooled_table.dtype))
         self._prompts_set = True
 
     def _refuse_ragged_on_foreign(self):
@@ -732,6 +853,7 @@ class DiffusionClassifier(nn.Module):
         schedule='scaled_linear' (needs config.timestep_spacing): the grid is the integer steps of `trajectory.discrete_steps`, x is
         diffused to its first point k_0, the backbone is fed float(k_i), and nothing is clipped — the ancestral mean is a z + b x
         (ancestral.py), the last deterministic pass returns the data prediction as it is."""
+        self._refuse_sdxl_generation("sample")
         self._refuse_discrete("sample", from_t)
         TJ.check_decode(self, decode)
         sampler = S.sampler_of(self.config)
@@ -785,6 +907,7 @@ class DiffusionClassifier(nn.Module):
         schedule='scaled_linear' (needs config.timestep_spacing): all of the above on the integer grid of `sample`, unclipped — the
         ancestral passes are one unclamped `dc_solver_step` (the posterior mean) and one torch add of the shared noise per pass and
         chunk (ancestral.py)"""
+        self._refuse_sdxl_generation("counterfactual")
         self._refuse_discrete("counterfactual", from_t)
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class, decode=decode)
 
@@ -801,6 +924,7 @@ class DiffusionClassifier(nn.Module):
         With config.vae_path, x and the result are LATENTS (`encode_latents` / `decode_latents`).
         schedule='scaled_linear' (needs config.timestep_spacing): the grid is `sample`'s integer steps from to_t in reverse, so inversion
         and decode visit the same points; the data prediction is not clipped."""
+        self._refuse_sdxl_generation("invert")
         self._refuse_discrete("invert", to_t)
         return S.invert(self, x, text, to_t, guidance)
 
@@ -826,6 +950,7 @@ class DiffusionClassifier(nn.Module):
         With config.vae_path, x, start and noise are LATENTS (`encode_latents` / `decode_latents`).
         schedule='scaled_linear' (needs config.timestep_spacing): the same on `sample`'s integer grid with the unclipped mean
         mu_i = a z + b x — one unclamped `dc_solver_step` per pass and chunk, the map (x_{i+1} - mu_i) / sd_i in torch on that mean."""
+        self._refuse_sdxl_generation("invert_ddpm")
         self._refuse_discrete("invert_ddpm", from_t)
         return DI.invert(self, x, text, from_t, guidance, rng, seed)
 

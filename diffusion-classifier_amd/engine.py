@@ -1,5 +1,6 @@
 """UNet scoring-step engine: the packed weights (`UNetWeights`) and the launch plan (`UNetPlan`) of a UNetCondition2D or a
-StableDiffusionUNet (nets/sd_unet.py: heads per attention site, no `encoder_hid_proj`, heads of 160 channels).
+StableDiffusionUNet (nets/sd_unet.py: heads per attention site, no `encoder_hid_proj`, heads of 160 channels) or a StableDiffusionXLUNet
+(several transformer blocks per site; the text_time side path, which makes the ResNet time vector per unit).
 
 The plan model — ops, domains, the arena, `PlanBuilder`, the route switches — is plan.py; the weight packers are packing.py.  Their
 names that tests, tools and nets/ have always reached through this module are imported below.
@@ -67,6 +68,9 @@ class UNetWeights(LazyPacks):
         lin("time_embedding.linear_2", L.DC_F32)
         if "encoder_hid_proj.weight" in sd:      # (a StableDiffusionUNet has none: the context is attn2's input as it is)
             lin("encoder_hid_proj", L.DC_F32)
+        if "add_embedding.linear_1.weight" in sd:      # StableDiffusionXLUNet: the text_time side path, fp32 like the time embedding
+            lin("add_embedding.linear_1", L.DC_F32)
+            lin("add_embedding.linear_2", L.DC_F32)
         norm("conv_norm_out")
         conv3("conv_out", tile_n=32 if cfg.out_channels <= 32 else 128)
         self.resnets, self.attns, self.heads = [], [], {}      # heads: per attention site
@@ -88,23 +92,37 @@ class UNetWeights(LazyPacks):
         self.tproj_total = o
         P["tproj.w"] = pack_matrix(tw, L.DC_F32, device)
         P["tproj.b"] = f32c(tb, device)
+        # a site is one Transformer2DModel (`...attentions.j`); its blocks `<site>.transformer_blocks.{k}` run in sequence between one
+        # proj_in and one proj_out.  depth[site]: their number (1 everywhere but in a StableDiffusionXLUNet); tblocks: every (site, block key)
+        self.depth, self.tblocks = {}, []
+        # the one-token plan (S = 1, the class-vector path) is refused for a text_time model (UNetPlan): its fp32 matrices are not packed
+        one_token = getattr(cfg, "addition_embed_type", None) != "text_time"
         for key in sorted({k[: -len(".proj_in.weight")] for k in sd if k.endswith(".proj_in.weight")}):
             self.attns.append(key)
             norm(key + ".norm"); conv1(key + ".proj_in"); conv1(key + ".proj_out")
-            tb_ = key + ".transformer_blocks.0"
-            norm(tb_ + ".norm1"); norm(tb_ + ".norm3")
             heads = self.heads[key] = site_heads(cfg, key)
             d = sd[key + ".proj_in.weight"].shape[0] // heads
             dp = site_head_dim(d)
-            qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0), d, dp)
-            P[tb_ + ".qkv.w"] = pack_matrix(qkv, dt, device)
-            P[tb_ + ".attn1.to_out.0.w"] = pack_matrix(pad_head_cols(sd[tb_ + ".attn1.to_out.0.weight"], d, dp), dt, device)
-            P[tb_ + ".attn1.to_out.0.b"] = f32c(sd[tb_ + ".attn1.to_out.0.bias"], device)
-            P[tb_ + ".ff.net.0.proj.w"], P[tb_ + ".ff.net.0.proj.b"] = pack_geglu(
-                sd[tb_ + ".ff.net.0.proj.weight"], sd[tb_ + ".ff.net.0.proj.bias"], dt, device)
-            lin(tb_ + ".ff.net.2")
-            # class-token side path (fp32): to_v then to_out of attn2 (to_q/to_k never matter for 1 key)
-            lin(tb_ + ".attn2.to_out.0", L.DC_F32)
+            pre = key + ".transformer_blocks."
+            self.depth[key] = 1 + max(int(k[len(pre):].split(".")[0]) for k in sd if k.startswith(pre))
+            for kb in range(self.depth[key]):
+                tb_ = pre + str(kb)
+                self.tblocks.append((key, tb_))
+                norm(tb_ + ".norm1"); norm(tb_ + ".norm3")
+                qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0), d, dp)
+                P[tb_ + ".qkv.w"] = pack_matrix(qkv, dt, device)
+                P[tb_ + ".attn1.to_out.0.w"] = pack_matrix(pad_head_cols(sd[tb_ + ".attn1.to_out.0.weight"], d, dp), dt, device)
+                P[tb_ + ".attn1.to_out.0.b"] = f32c(sd[tb_ + ".attn1.to_out.0.bias"], device)
+                P[tb_ + ".ff.net.0.proj.w"], P[tb_ + ".ff.net.0.proj.b"] = pack_geglu(
+                    sd[tb_ + ".ff.net.0.proj.weight"], sd[tb_ + ".ff.net.0.proj.bias"], dt, device)
+                lin(tb_ + ".ff.net.2")
+                # class-token side path (fp32): to_v then to_out of attn2 (to_q/to_k never matter for 1 key)
+                if one_token:
+                    lin(tb_ + ".attn2.to_out.0", L.DC_F32)
+        self.P = P
+        self._sd = sd              # references only (no copy): split packing of skip-connection convs is lazy
+        if not one_token:
+            return
         vw = torch.cat([sd[k + ".transformer_blocks.0.attn2.to_v.weight"] for k in self.attns], 0)
         self.cv_off, o = {}, 0
         for k in self.attns:
@@ -112,8 +130,6 @@ class UNetWeights(LazyPacks):
             o += sd[k + ".transformer_blocks.0.attn2.to_v.weight"].shape[0]
         self.cv_total = o
         P["attn2v.w"] = pack_matrix(vw, L.DC_F32, device)
-        self.P = P
-        self._sd = sd              # references only (no copy): split packing of skip-connection convs is lazy
 
     def split_resnet(self, key, C0):
         """Packed halves of a skip-connection ResNet's input convs: `.conv1.wa/.wb` ([Cout, 9*C0] / [Cout, 9*C1], same
@@ -149,7 +165,7 @@ class UNetWeights(LazyPacks):
         sd = self._sd
 
         def make():
-            d = sd[tb_ + ".norm1.weight"].shape[0] // self.heads[tb_[: -len(".transformer_blocks.0")]]
+            d = sd[tb_ + ".norm1.weight"].shape[0] // self.heads[tb_.rsplit(".transformer_blocks.", 1)[0]]
             qkv = pad_head_rows(torch.cat([sd[tb_ + f".attn1.to_{n}.weight"] for n in "qkv"], 0).float(), d, site_head_dim(d))
             wf, bf = pack_geglu(sd[tb_ + ".ff.net.0.proj.weight"], sd[tb_ + ".ff.net.0.proj.bias"], self.dt, self.dev,
                                 ln_gamma=sd[tb_ + ".norm3.weight"], ln_beta=sd[tb_ + ".norm3.bias"])
@@ -159,49 +175,49 @@ class UNetWeights(LazyPacks):
         self.once(tb_ + ".qkv.wf", make)
 
     def pack_cross(self, fold_ln):
-        """attn2 as attention (a context of several tokens; the one-token plan never needs these): per transformer `<tb>.norm2.g/.b`,
+        """attn2 as attention (a context of several tokens; the one-token plan never needs these): per transformer block `<tb>.norm2.g/.b`,
         `<tb>.attn2.to_q.w` and `<tb>.attn2.to_out.0.wc` in the compute dtype with attn1's head padding, and ONE fp32 matrix
-        `attn2kv.w` that stacks [to_k ; to_v] of every site (rows `ckv_off[key]` ... + 2 Cq: K | V of that site), so the context side
-        path produces K | V of all sites with one GEMM, as `attn2v.w` stacks to_v for the one-token plan.  fold_ln: also
+        `attn2kv.w` that stacks [to_k ; to_v] of every block of every site (rows `ckv_off[tb]` ... + 2 Cq: K | V of that block), so the
+        context side path produces K | V of all of them with one GEMM, as `attn2v.w` stacks to_v for the one-token plan.  fold_ln: also
         `<tb>.attn2.to_q.wf/.bf`, norm2 folded into to_q for the row-standardising GEMM."""
         sd = self._sd
 
-        def site(key):
+        def widths(key):
             d = sd[key + ".proj_in.weight"].shape[0] // self.heads[key]
-            return key + ".transformer_blocks.0", d, site_head_dim(d)
+            return d, site_head_dim(d)
 
         def make():
             new, kv, self.ckv_off, o = {}, [], {}, 0
-            for key in self.attns:
-                tb_, d, dp = site(key)
+            for key, tb_ in self.tblocks:
+                d, dp = widths(key)
                 new[tb_ + ".norm2.g"], new[tb_ + ".norm2.b"] = f32c(sd[tb_ + ".norm2.weight"], self.dev), f32c(sd[tb_ + ".norm2.bias"], self.dev)
                 new[tb_ + ".attn2.to_q.w"] = pack_matrix(pad_head_rows(sd[tb_ + ".attn2.to_q.weight"], d, dp), self.dt, self.dev)
                 new[tb_ + ".attn2.to_out.0.wc"] = pack_matrix(pad_head_cols(sd[tb_ + ".attn2.to_out.0.weight"], d, dp), self.dt, self.dev)
                 new[tb_ + ".attn2.to_out.0.bc"] = f32c(sd[tb_ + ".attn2.to_out.0.bias"], self.dev)
                 kv += [pad_head_rows(sd[tb_ + ".attn2.to_k.weight"], d, dp), pad_head_rows(sd[tb_ + ".attn2.to_v.weight"], d, dp)]
-                self.ckv_off[key] = o
+                self.ckv_off[tb_] = o
                 o += 2 * self.heads[key] * dp
             self.ckv_total = o
             return dict(new, **{"attn2kv.w": pack_matrix(torch.cat(kv, 0), L.DC_F32, self.dev)})
 
-        def make_folded(key):
-            tb_, d, dp = site(key)
+        def make_folded(key, tb_):
+            d, dp = widths(key)
             wq = pad_head_rows(sd[tb_ + ".attn2.to_q.weight"].float(), d, dp)
             return {tb_ + ".attn2.to_q.wf": pack_matrix(wq, self.dt, self.dev, col_scale=sd[tb_ + ".norm2.weight"]),
                     tb_ + ".attn2.to_q.bf": fold_layernorm_bias(wq, None, sd[tb_ + ".norm2.bias"], self.dev)}
         self.once("attn2kv.w", make)
-        for key in self.attns if fold_ln else ():
-            self.once(key + ".transformer_blocks.0.attn2.to_q.wf", lambda: make_folded(key))
+        for key, tb_ in self.tblocks if fold_ln else ():
+            self.once(tb_ + ".attn2.to_q.wf", lambda: make_folded(key, tb_))
 
     def fold_proj_out(self, key):
         """proj_out folded into the feed-forward's second linear: with h3 = W2 f + b2 + h2 (ff.net.2 + residual) the block's output
         x + Wpo h3 + bpo equals x + [Wpo W2 | Wpo] [f ; h2] + (Wpo b2 + bpo) — ONE GEMM over K = 4C + C with x as its residual instead of
         two (h3 never exists).  Exact algebra; the product matrix is formed in fp64 and rounded once to the compute dtype.
-        Packs `<key>.ffpo.w` [C, 5C] and `<key>.ffpo.b`."""
+        Packs `<key>.ffpo.w` [C, 5C] and `<key>.ffpo.b`.  The ff.net.2 is the site's LAST block's: proj_out follows that one alone."""
         sd = self._sd
 
         def make():
-            tb_ = key + ".transformer_blocks.0"
+            tb_ = f"{key}.transformer_blocks.{self.depth[key] - 1}"
             w2, b2 = sd[tb_ + ".ff.net.2.weight"].double(), sd[tb_ + ".ff.net.2.bias"].double()
             wpo = sd[key + ".proj_out.weight"].double()
             wpo = wpo.reshape(wpo.shape[0], -1)
@@ -241,6 +257,11 @@ class UNetPlan(Plan):
         self.dt, self.n_bj, self.n_cls, self.n_ctx, self.S, self.varlen = dt, n_bj, n_cls, n_ctx, S, bool(varlen)
         self.weights, self.P, self.sw = weights, weights.P, switches()
         self.G, self.eps = cfg.norm_num_groups, cfg.norm_eps
+        # StableDiffusionXLUNet: the text_time side path (`aug`, a row per context, added to the time embedding) and sites of several blocks
+        text_time = getattr(cfg, "addition_embed_type", None) == "text_time"
+        if S == 1 and (text_time or max(weights.depth.values(), default=1) > 1):
+            raise L.DcamdError(f"{type(model).__name__}: a context of one token (the class-vector path) is not built for text_time "
+                               "conditioning or for sites of several transformer blocks: hand the backbone a prompt of S > 1 tokens")
         U = n_bj * n_cls
         pb = self.pb = PlanBuilder(dev, n_bj, n_cls, n_ctx)
         H = W = cfg.sample_size
@@ -259,6 +280,9 @@ class UNetPlan(Plan):
         # its K | V.  The context plan is the same: the pad rows of a prompt are projected and never read
         self.ctx_len = torch.full((n_ctx,), S, **i32) if varlen else None
         self.ctx_len_ptr = pb.const(self.ctx_len)
+        # text_time: pooled [n_ctx, pooled_dim] and time_ids [n_ctx, 6] f32, inputs of the context plan like ctx (None otherwise)
+        self.pooled = torch.zeros(n_ctx, cfg.pooled_dim, **f32) if text_time else None
+        self.time_ids = torch.zeros(n_ctx, 6, **f32) if text_time else None
         kin = weights.kin
         if score is not None:
             self.score = score
@@ -268,11 +292,15 @@ class UNetPlan(Plan):
             a0 = pb.external("a0", self.a0_buf, "bj", H, W, kin, dt)
         # ---- fp32 side path: time embedding, stacked time_emb_proj; the class-token vectors / prompt K | V are the context plan's ----
         c, C0 = self.c, cfg.block_out_channels[0]
+        self.context_plan(dev)          # (emits into its own builder: the main plan's op order does not depend on where this stands)
         te = pb.sinusoid("temb.sin", lam, C0, cfg.flip_sin_to_cos, cfg.freq_shift)
         te = pb.igemm("temb.l1", te, c("time_embedding.linear_1.w"), 4 * C0, bias=c("time_embedding.linear_1.b"), act=L.ACT_SILU)
-        te = pb.igemm("temb.l2", te, c("time_embedding.linear_2.w"), 4 * C0, bias=c("time_embedding.linear_2.b"), act=L.ACT_SILU)   # = SiLU(temb)
+        # text_time: temb.l2 runs in the UNIT domain with `aug` as its row vector — the epilogue is act((acc + bias) + rowvec), rows read
+        # through bj_of_unit, the vector through ctx_of_unit: SiLU(temb[bj] + aug[ctx]) with no new op.  tproj then has U rows, and every
+        # ResNet, whose time vector it is, becomes a per-unit layer: the class-shared trunk ends behind conv_in (inherent to the model)
+        te = pb.igemm("temb.l2", te, c("time_embedding.linear_2.w"), 4 * C0, bias=c("time_embedding.linear_2.b"), rowvec=self.aug,
+                      act=L.ACT_SILU)                                                                                 # = SiLU(temb (+ aug))
         self.tproj = pb.igemm("tproj", te, c("tproj.w"), weights.tproj_total, bias=c("tproj.b"))
-        self.context_plan(dev)
         pred = self.pred = self.walk(a0, share_trunk)
         if pred.dom != "unit":
             raise L.DcamdError("backbone has no class-conditioned layer: nothing to score per class")
@@ -298,7 +326,22 @@ class UNetPlan(Plan):
                           bias=pc.const(P["encoder_hid_proj.b"]))
         else:
             hp = cctx                  # no projection (StableDiffusionUNet): the context rows are the side path's input themselves
-        self.cvec, self.ckv = {}, {}
+        self.cvec, self.ckv, self.aug = {}, {}, None
+        aug = None
+        if self.pooled is not None:
+            # text_time (diffusers, restated): the six size numbers of a context through the sinusoid of width addition_time_embed_dim,
+            # [n_ctx, 6 * dim] concatenated BEHIND text_embeds (the GEMM's second K range), add_embedding.linear_1 -> SiLU -> linear_2.
+            # It depends on the context row alone: once per call, n_ctx rows, fp32
+            dim, T4 = cfg.addition_time_embed_dim, 4 * cfg.block_out_channels[0]
+            tid = pc.external("time_ids", self.time_ids, "ctx", 1, 1, 6, L.DC_F32)
+            sin = pc.tensor("add.sin", "ctx", 1, 1, 6 * dim, L.DC_F32)
+            pc.emit(L.OP_SINUSOID, dict(lam=tid, out=sin, n=6 * n_ctx, dim=dim, flip_sin_to_cos=int(cfg.flip_sin_to_cos),
+                                        freq_shift=float(cfg.freq_shift)),
+                    [tid], [sin], dict(name="add.sin", family="sinusoid", flops=0.0, bytes=0.0))
+            pooled = pc.external("pooled", self.pooled, "ctx", 1, 1, cfg.pooled_dim, L.DC_F32)
+            a1 = pc.igemm("add.l1", pooled, pc.const(P["add_embedding.linear_1.w"]), T4, src1=sin,
+                          bias=pc.const(P["add_embedding.linear_1.b"]), act=L.ACT_SILU)
+            aug = pc.igemm("add.l2", a1, pc.const(P["add_embedding.linear_2.w"]), T4, bias=pc.const(P["add_embedding.linear_2.b"]))
         if S == 1:
             # one key: softmax = 1, attn2 is to_out(to_v(ctx)), a row vector of the attn1.to_out epilogue
             vall = pc.igemm("ctx.to_v", hp, pc.const(P["attn2v.w"]), weights.cv_total)
@@ -315,12 +358,14 @@ class UNetPlan(Plan):
             # the compute dtype); the main plan reads them as 'ctx'-domain tensors of 1 x S tokens
             weights.pack_cross(self.sw.ln_fold)
             kvall = pc.igemm("ctx.to_kv", hp, pc.const(P["attn2kv.w"]), weights.ckv_total, out_dt=self.dt)
-            pc.finalize(keep_alive=[kvall])
+            pc.finalize(keep_alive=[kvall] + ([aug] if aug is not None else []))
             kvx = pb.external("ctx.kv", pc.tensor_view(kvall), "ctx", 1, S, weights.ckv_total, self.dt)
-            for k in weights.attns:
+            for k, tb_ in weights.tblocks:
                 heads = weights.heads[k]
                 Cq = heads * site_head_dim(P[k + ".norm.g"].shape[0] // heads)
-                self.ckv[k] = (kvx.view(weights.ckv_off[k], Cq), kvx.view(weights.ckv_off[k] + Cq, Cq))
+                self.ckv[tb_] = (kvx.view(weights.ckv_off[tb_], Cq), kvx.view(weights.ckv_off[tb_] + Cq, Cq))
+            if aug is not None:
+                self.aug = pb.external("add.aug", pc.tensor_view(aug).view(n_ctx, -1), "ctx", 1, 1, aug.C, L.DC_F32)
 
     def walk(self, a0, share_trunk):
         """The main path, conv_in to conv_out; returns the prediction tensor."""
@@ -437,7 +482,13 @@ class UNetPlan(Plan):
         if h is None:
             h = pb.groupnorm(key + ".gn", x, c(key + ".norm.g"), c(key + ".norm.b"), self.G, 1e-6, False)
         if self.S > 1:
-            h = self.prompt_attention(key, tbk, self.self_attention(key, tbk, h, None, heads, d, Cq), heads, d, Cq)
+            # the blocks of the site in sequence between one proj_in and one proj_out (one block everywhere but in a StableDiffusionXLUNet)
+            depth = self.weights.depth[key]
+            for kb in range(depth):
+                tbk = f"{key}.transformer_blocks.{kb}"
+                h = self.prompt_attention(key, tbk, self.self_attention(key, tbk, h, None, heads, d, Cq, proj_in=kb == 0), heads, d, Cq)
+                h = self.feed_forward(key, tbk, x, h, last=kb == depth - 1)
+            return h
         elif self.sw.tblock and h.dom == pb.dom(h, self.cvec[key]) and pb.tblock_front_ok(h, heads):
             # proj_in -> LayerNorm -> q/k/v -> attention -> to_out + class vector + residual in ONE launch, the sample on chip
             assert Cq == x.C, "dc_tblock_front takes unpadded heads only"
@@ -447,11 +498,13 @@ class UNetPlan(Plan):
             h = self.self_attention(key, tbk, h, self.cvec[key], heads, d, Cq)
         return self.feed_forward(key, tbk, x, h)
 
-    def self_attention(self, key, tbk, h, rowvec, heads, d, Cq):
+    def self_attention(self, key, tbk, h, rowvec, heads, d, Cq, proj_in=True):
         """proj_in -> LayerNorm -> q/k/v -> attention -> to_out + residual as a chain of launches.  rowvec: the class vector of a
-        one-token context (attn2 of one key is a row vector of this epilogue); None in a prompt plan."""
+        one-token context (attn2 of one key is a row vector of this epilogue); None in a prompt plan.  proj_in False: h is the output
+        of the site's previous block."""
         pb, c, Cc = self.pb, self.c, h.C
-        h = pb.igemm(key + ".proj_in", h, c(key + ".proj_in.w"), Cc, bias=c(key + ".proj_in.b"))
+        if proj_in:
+            h = pb.igemm(key + ".proj_in", h, c(key + ".proj_in.w"), Cc, bias=c(key + ".proj_in.b"))
         # (q/k/v keeps its LayerNorm launch: measured faster on the 256x256 tile + LayerNorm than on the row-standardising GEMM)
         hn = pb.layernorm(tbk + ".ln1", h, c(tbk + ".norm1.g"), c(tbk + ".norm1.b"), 1e-5)
         qkv = pb.igemm(tbk + ".qkv", hn, c(tbk + ".qkv.w"), 3 * Cq)
@@ -472,11 +525,12 @@ class UNetPlan(Plan):
         else:
             hn = pb.layernorm(tbk + ".ln2", h, c(tbk + ".norm2.g"), c(tbk + ".norm2.b"), 1e-5)
             q2 = pb.igemm(tbk + ".attn2.to_q", hn, c(tbk + ".attn2.to_q.w"), Cq)
-        o2 = pb.cross_attention(tbk + ".attn2", q2, self.ckv[key][0], self.ckv[key][1], heads, d, kv_len=self.ctx_len_ptr)
+        o2 = pb.cross_attention(tbk + ".attn2", q2, self.ckv[tbk][0], self.ckv[tbk][1], heads, d, kv_len=self.ctx_len_ptr)
         return pb.igemm(tbk + ".attn2_out", o2, c(tbk + ".attn2.to_out.0.wc"), h.C, bias=c(tbk + ".attn2.to_out.0.bc"), residual=h)
 
-    def feed_forward(self, key, tbk, x, h):
-        """norm3 -> GEGLU -> ff.net.2 + residual -> proj_out + the block input x."""
+    def feed_forward(self, key, tbk, x, h, last=True):
+        """norm3 -> GEGLU -> ff.net.2 + residual -> proj_out + the site's input x.  last False (a block with another one behind it):
+        it ends at ff.net.2 + residual; proj_out, and its fold into ff.net.2, belong to the site's last block."""
         pb, c, Cc = self.pb, self.c, h.C
         # LayerNorm folded into the consuming GEMM where the activation-stationary kernel can standardise the rows itself
         # (gamma into W's columns, beta into the bias: UNetWeights.fold_layernorms): no LayerNorm launch, no normalised tensor
@@ -486,6 +540,8 @@ class UNetPlan(Plan):
         else:
             hn = pb.layernorm(tbk + ".ln3", h, c(tbk + ".norm3.g"), c(tbk + ".norm3.b"), 1e-5)
             f = pb.igemm(tbk + ".geglu", hn, c(tbk + ".ff.net.0.proj.w"), 8 * Cc, bias=c(tbk + ".ff.net.0.proj.b"), act=L.ACT_GEGLU)
+        if not last:
+            return pb.igemm(tbk + ".ff_out", f, c(tbk + ".ff.net.2.w"), Cc, bias=c(tbk + ".ff.net.2.b"), residual=h)
         if self.sw.po_fold:
             # ff.net.2 and proj_out as one GEMM over [f | h] (UNetWeights.fold_proj_out): no ff_out tensor, one launch fewer
             self.weights.fold_proj_out(key)

@@ -5,6 +5,9 @@ Restated: transformers' `CLIPTextModel.last_hidden_state`: token + position embe
 bias + residual] -> final LayerNorm.  The residual stream is fp32; what the GEMMs read is the compute dtype.  The attention mask must be
 right-padded, so it is a token count per prompt; causality already hides every pad key from every valid query, so the count only decides
 which rows are computed (dc_attention_causal's / dc_layernorm_rows' row_len) and how many keys the UNet's cross-attention sees downstream.
+On request the same plan also keeps the penultimate residual stream (`hidden_states[-2]`) and computes the projected pooled row
+(`CLIPTextModelWithProjection.text_embeds`) with ops the library already has: DC_OP_EMBED_ROWS over the stream as a table,
+DC_OP_LAYERNORM_ROWS over the B gathered rows and an fp32 dc_igemm.
 """
 import torch
 
@@ -40,14 +43,21 @@ class ClipWeights:
                 P[k + n + ".g"], P[k + n + ".b"] = f32c(sd[k + n + ".weight"], device), f32c(sd[k + n + ".bias"], device)
         P["final.g"] = f32c(sd[PREFIX + "final_layer_norm.weight"], device)
         P["final.b"] = f32c(sd[PREFIX + "final_layer_norm.bias"], device)
+        if "text_projection.weight" in sd:        # CLIPTextEncoderWithProjection: the pooled row's fp32 GEMM (no bias)
+            P["proj.w"] = pack_matrix(sd["text_projection.weight"], L.DC_F32, device)
         self.P = P
 
 
 class ClipPlan(Plan):
     """inputs: ids [B, L] int64 and lens [B] int32 (device buffers of the plan: copy into them, then run()).
-    output: out [B, L, hidden] fp32, rows at or past a prompt's length zero.  8 * layers + 2 ops."""
+    output: out [B, L, hidden] fp32, rows at or past a prompt's length zero.  8 * layers + 2 ops.
+    penultimate: `hs2`, the fp32 residual stream after layers - 1 layers (transformers' hidden_states[-2], no final LayerNorm), is kept
+    alive to the end of the plan; its rows at or past a prompt's length are whatever the residual adds left there (the caller zeroes
+    them).  pooled: three more ops — DC_OP_EMBED_ROWS gathers row `eos[b]` (int64 [B], b * L + the EOS position, a device buffer of the
+    plan) of the last stream read as a table of B * L rows, DC_OP_LAYERNORM_ROWS applies the final LayerNorm to those B rows, and an
+    fp32 dc_igemm multiplies them by text_projection -> `pooled` [B, projection_dim] fp32.  One run yields all of them."""
 
-    def __init__(self, model, weights, B, Lq):
+    def __init__(self, model, weights, B, Lq, penultimate=False, pooled=False):
         cfg = model.config
         dev, dt, P = weights.dev, weights.dt, weights.P
         D, heads, dff = cfg.hidden_size, cfg.num_attention_heads, cfg.intermediate_size
@@ -101,8 +111,31 @@ class ClipPlan(Plan):
             pb.emit(L.OP_ACT_PASS, dict(x=ff, n=rows * dff, dtype=dt, kind=kind), [ff], [ff],
                     dict(name=k + "act", family="act_pass", flops=0.0, bytes=2.0 * rows * dff * es))
             h = gemm(k + "fc2", ff, k + "fc2.w", k + "fc2.b", D, residual=h, out_dt=L.DC_F32)
+            if penultimate and i == cfg.num_hidden_layers - 2:
+                self.hs2 = h
         self.out = layernorm("final.ln", h, P["final.g"], P["final.b"], L.DC_F32)
-        pb.finalize(keep_alive=[self.out])
+        keep = [self.out] + ([self.hs2] if penultimate else [])
+        if pooled:
+            self.eos = torch.zeros(B, dtype=torch.int64, device=dev)
+            row = pb.tensor("pooled.row", "bj", 1, 1, D, L.DC_F32)
+            pb.emit(L.OP_EMBED_ROWS, dict(table=h, ids=pb.const(self.eos), out=row, out_dtype=L.DC_F32, rows=B, C=D, vocab=rows),
+                    [h], [row], dict(name="pooled.row", family="embed_rows", flops=0.0, bytes=8.0 * B * D))
+            pn = pb.tensor("pooled.ln", "bj", 1, 1, D, L.DC_F32)
+            pb.emit(L.OP_LAYERNORM_ROWS,
+                    dict(x=row, y=pn, gamma=pb.const(P["final.g"]), beta=pb.const(P["final.b"]), row_len=None, dtype=L.DC_F32,
+                         out_dtype=L.DC_F32, rows=B, C=D, rows_per_sample=1, eps=eps),
+                    [row], [pn], dict(name="pooled.ln", family="layernorm_rows", flops=0.0, bytes=8.0 * B * D))
+            self.pooled = pb.igemm("text_projection", pn, pb.const(P["proj.w"]), cfg.projection_dim)
+            keep.append(self.pooled)
+        pb.finalize(keep_alive=keep)
+        if pooled:
+            pb.check_served(type(model).__name__, f"the pooled output of {B} prompts of {Lq} tokens")
 
     def out_view(self):
         return super().out_view().view(self.B, self.L, -1)
+
+    def hs2_view(self):
+        return self.pb.tensor_view(self.hs2).view(self.B, self.L, -1)
+
+    def pooled_view(self):
+        return self.pb.tensor_view(self.pooled).view(self.B, -1)

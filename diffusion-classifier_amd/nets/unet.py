@@ -44,12 +44,7 @@ def _attention(qdim, ctx_dim, inner):
     return a
 
 
-def _transformer2d(ch, xdim, groups, linear=False):
-    """linear: proj_in / proj_out as nn.Linear [C, C] (diffusers' use_linear_projection) instead of 1x1 convs [C, C, 1, 1]: the same
-    arithmetic under another weight shape."""
-    t = _Bag()
-    t.norm = nn.GroupNorm(groups, ch, eps=1e-6)
-    t.proj_in = nn.Linear(ch, ch) if linear else nn.Conv2d(ch, ch, 1)
+def _tblock(ch, xdim):
     b = _Bag()
     b.norm1 = nn.LayerNorm(ch)
     b.attn1 = _attention(ch, None, ch)
@@ -60,7 +55,17 @@ def _transformer2d(ch, xdim, groups, linear=False):
     proj = _Bag()
     proj.proj = nn.Linear(ch, 8 * ch)
     b.ff.net = nn.ModuleList([proj, nn.Identity(), nn.Linear(4 * ch, ch)])
-    t.transformer_blocks = nn.ModuleList([b])
+    return b
+
+
+def _transformer2d(ch, xdim, groups, linear=False, depth=1):
+    """linear: proj_in / proj_out as nn.Linear [C, C] (diffusers' use_linear_projection) instead of 1x1 convs [C, C, 1, 1]: the same
+    arithmetic under another weight shape.  depth: `transformer_blocks.{k}` for k < depth, run in sequence between proj_in and proj_out
+    (diffusers' transformer_layers_per_block; more than 1: StableDiffusionXLUNet only)."""
+    t = _Bag()
+    t.norm = nn.GroupNorm(groups, ch, eps=1e-6)
+    t.proj_in = nn.Linear(ch, ch) if linear else nn.Conv2d(ch, ch, 1)
+    t.transformer_blocks = nn.ModuleList([_tblock(ch, xdim) for _ in range(depth)])
     t.proj_out = nn.Linear(ch, ch) if linear else nn.Conv2d(ch, ch, 1)
     return t
 
@@ -265,6 +270,9 @@ class UNetCondition2D(_HipBackbone):
         boc, lpb, G, eps, xdim = cfg.block_out_channels, cfg.layers_per_block, cfg.norm_num_groups, cfg.norm_eps, cfg.cross_attention_dim
         down_block_types, up_block_types = cfg.down_block_types, cfg.up_block_types
         nb, rboc = len(boc), boc[::-1]
+        # transformer blocks per site: one entry per down block (the up blocks read it reversed, the mid block takes the last), as for
+        # attention_head_dim; only StableDiffusionXLUNet's config carries the key
+        tlpb = getattr(cfg, "transformer_layers_per_block", None) or (1,) * nb
         temb = boc[0] * 4
         self.conv_in = nn.Conv2d(in_channels, boc[0], 3, padding=1)
         self.time_embedding = _Bag()
@@ -281,12 +289,12 @@ class UNetCondition2D(_HipBackbone):
             blk = _Bag()
             blk.resnets = nn.ModuleList([_resnet(cin if j == 0 else out, out, temb, G, eps) for j in range(lpb[i])])
             if kind == "CrossAttnDownBlock2D":
-                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G, linear) for _ in range(lpb[i])])
+                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G, linear, tlpb[i]) for _ in range(lpb[i])])
             if i != nb - 1:
                 blk.downsamplers = nn.ModuleList([_sampler(out, 2)])
             self.down_blocks.append(blk)
         self.mid_block = _Bag()
-        self.mid_block.attentions = nn.ModuleList([_transformer2d(boc[-1], xdim, G, linear)])
+        self.mid_block.attentions = nn.ModuleList([_transformer2d(boc[-1], xdim, G, linear, tlpb[-1])])
         self.mid_block.resnets = nn.ModuleList([_resnet(boc[-1], boc[-1], temb, G, eps) for _ in range(2)])
         self.up_blocks = nn.ModuleList()
         rlpb = lpb[::-1]
@@ -301,7 +309,7 @@ class UNetCondition2D(_HipBackbone):
             blk.resnets = nn.ModuleList(
                 [_resnet((prev if j == 0 else out) + (cin if j == n - 1 else out), out, temb, G, eps) for j in range(n)])
             if kind == "CrossAttnUpBlock2D":
-                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G, linear) for _ in range(n)])
+                blk.attentions = nn.ModuleList([_transformer2d(out, xdim, G, linear, tlpb[::-1][i]) for _ in range(n)])
             if i != nb - 1:
                 blk.upsamplers = nn.ModuleList([_sampler(out, 1)])
             self.up_blocks.append(blk)
@@ -345,10 +353,11 @@ class UNetCondition2D(_HipBackbone):
             raise L.DcamdError(f"prompt lengths must lie in [1, {S}], got {ln.tolist()}")
         return ln.to(torch.int32)
 
-    def _ctx_plan(self, kind, N, dev, S, ctxs, lengths):
+    def _ctx_plan(self, kind, N, dev, S, ctxs, lengths, fill=None):
         """What `forward`, `forward_pair` and `pair_session` share: the plan cached under kind + (N, device, dtype, share_trunk, S[,
         "varlen"]) (built on first use), the contexts `ctxs` — one [N, S, hid] per unit of an image, context n_cls * b + u = ctxs[u][b]
-        — and their `lengths` (any of them given: a "varlen" plan; None on a side: all S) copied in, the context plan run."""
+        — and their `lengths` (any of them given: a "varlen" plan; None on a side: all S) copied in, the context plan run.
+        fill(plan): copies whatever else the context plan reads (StableDiffusionXLUNet: the pooled rows and size ids), before it runs."""
         key = kind + (N, str(dev), self.compute_dtype, self.share_trunk, S)
         varlen = any(ln is not None for ln in lengths)
         if varlen:
@@ -360,6 +369,8 @@ class UNetCondition2D(_HipBackbone):
         plan.ctx.copy_(torch.stack(ctxs, dim=1).to(dev, torch.float32).reshape(plan.ctx.shape))
         if varlen:
             plan.ctx_len.copy_(lens.reshape(-1))                              # interleaved as the contexts
+        if fill is not None:
+            fill(plan)
         plan.run_ctx()
         return plan
 

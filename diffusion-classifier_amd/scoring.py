@@ -177,7 +177,8 @@ class _ForeignRunner(_Runner):
             for c in range(classes.shape[1]):
                 lab = classes[bs, c].to(x.device)
                 emb = dc.encode_text_prompt(lab)
-                pred = self.bb(x=z, noise_labels=lam, encoder_hidden_states=emb)
+                # (encoder_type='clip_dual': also added_cond_kwargs = {text_embeds, time_ids}, diffusers' names; {} otherwise)
+                pred = self.bb(x=z, noise_labels=lam, encoder_hidden_states=emb, **dc.added_cond(lab))
                 eps_pred = sg * z + al * pred if dc.pred_param == 'v' else pred
                 err = LS.error_torch(eps_pred, e, *dc.score_loss)      # l2: torch.norm(...) ** 2, the reference's statement
                 self.err[bs.to(x.device), lab, j] = err
@@ -308,6 +309,12 @@ class _HipRunner(_Runner):
             plan.ctx.copy_(self.dc.encoder.weight[:ncls].detach().to(self.dev, torch.float32).reshape(plan.ctx.shape))
             if plan.varlen:                              # the same on every rank: grid sharding needs nothing else
                 plan.ctx_len.copy_(self.dc.encoder.lengths[:ncls].to(self.dev, torch.int32))
+        if getattr(plan, "pooled", None) is not None:    # a StableDiffusionXLUNet: the pooled row of every class and the shared size ids
+            if self.dc.encoder_type != 'clip_dual':
+                raise L.DcamdError(f"{type(self.bb).__name__} needs encoder_type='clip_dual' (the pooled text rows and the size ids of its "
+                                   f"text_time embedding), this classifier has {self.dc.encoder_type!r}")
+            plan.pooled.copy_(self.dc.pooled_table[:ncls].detach().to(self.dev, torch.float32))
+            plan.time_ids.copy_(self.dc.add_time_ids.to(self.dev, torch.float32).expand(ncls, 6))
         plan.run_ctx()                                   # per-class vectors: once per stage, not per micro-batch
 
     def _stage_blocks(self, sp, pairs, classes, stage, rows, dump):
