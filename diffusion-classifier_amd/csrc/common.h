@@ -163,14 +163,54 @@ template <int LOSS> __device__ __forceinline__ float loss_term(float d, float de
   return d * d;
 }
 // dc_by_loss(p->loss, p->huber_delta, "dc_eps_mse", [&](auto kind) { ...launch<decltype(kind)::value>...; return DC_OK; }); an unknown
-// kind, or Huber with a delta that is not finite and > 0: DC_ERR_ARG.
-template <typename F> static inline int dc_by_loss(int loss, float huber_delta, const char* who, F&& f) {
+// kind, or Huber with a delta that is not finite and > 0: DC_ERR_ARG.  The flag DC_LOSS_WEIGHTED is dc_by_weights' and is masked here.
+template <typename F> static inline int dc_by_loss(int loss_field, float huber_delta, const char* who, F&& f) {
+  const int loss = loss_field & ~DC_LOSS_WEIGHTED;
   if (loss == DC_LOSS_L2) return f(std::integral_constant<int, DC_LOSS_L2>{});
   if (loss == DC_LOSS_L1) return f(std::integral_constant<int, DC_LOSS_L1>{});
-  DC_REQUIRE(loss == DC_LOSS_HUBER, DC_ERR_ARG, "%s: loss=%d (DC_LOSS_L2 = 0, DC_LOSS_L1 = 1, DC_LOSS_HUBER = 2)", who, loss);
+  DC_REQUIRE(loss == DC_LOSS_HUBER, DC_ERR_ARG, "%s: loss=%d (DC_LOSS_L2 = 0, DC_LOSS_L1 = 1, DC_LOSS_HUBER = 2)", who, loss_field);
   DC_REQUIRE(huber_delta > 0.f && huber_delta < __builtin_huge_valf(), DC_ERR_ARG,        // NaN fails both comparisons
              "%s: huber_delta=%g must be finite and > 0", who, (double)huber_delta);
   return f(std::integral_constant<int, DC_LOSS_HUBER>{});
+}
+
+// ---- the loss weights (include/dcamd.h dc_eps_mse_params pixel_w / trial_w): what the weighted instances of both kernels share -------
+struct LossWeights { const float* pixel_w; const float* trial_w; int T, cells; };
+// s + m t(d), one multiply per element.  DC_LOSS_L2: (m d) d with the second product fused into the sum — the unweighted instance's
+// s += d * d compiles to one fma as well, so m = 1 gives its bits; the other kinds add a rounded term there, as fma(1, t, s) does.
+// (A compiler dependence: the unweighted instances leave the contraction to hipcc's default -ffp-contract — d * d into the add for l2,
+// no product of the Huber branches into it — and the gfx950 listings show exactly that; the GPU tests compare the bits.  Spelling the
+// unweighted l2 accumulation as an explicit fma would remove the dependence but touches an existing instance.)
+template <int LOSS> __device__ __forceinline__ float loss_acc_weighted(float s, float d, float m, float delta) {
+  if constexpr (LOSS == DC_LOSS_L2) return __builtin_fmaf(m * d, d, s);
+  return __builtin_fmaf(m, loss_term<LOSS>(d, delta), s);
+}
+// w of a unit: trial_w[img, oi % T] with oi the unit's out_index; an oi outside [0, cells T) (the dump slot of padded units) and a NULL
+// table: 1.
+__device__ __forceinline__ float trial_weight(const LossWeights& w, long long oi, int img) {
+  if (!w.trial_w || oi < 0 || oi >= (long long)w.cells * w.T) return 1.f;
+  return w.trial_w[(size_t)img * w.T + (int)(oi % w.T)];
+}
+// The weights block a caller puts behind its params struct when `loss` carries DC_LOSS_WEIGHTED (dcamd.h, dc_eps_mse_params).
+struct dc_loss_weights_block { const float* pixel_w; const float* trial_w; int32_t w_T, w_cells; };
+// dc_by_weights(p, "dc_eps_mse", [&](auto weighted, const LossWeights& wt) { ...launch<..., decltype(weighted)::value>...; }): without
+// the flag nothing behind *p is read and the unweighted instance runs; trial_w without the maps it is read through, or without
+// T / cells (dc_err_map: its own fields, else the block's): DC_ERR_ARG.
+template <typename P, typename F> static inline int dc_by_weights(const P* p, const char* who, F&& f) {
+  if (!(p->loss & DC_LOSS_WEIGHTED)) return f(std::false_type{}, LossWeights{nullptr, nullptr, 0, 0});
+  static_assert(sizeof(P) % alignof(dc_loss_weights_block) == 0, "the block stands at sizeof of the params struct");
+  const dc_loss_weights_block* b = reinterpret_cast<const dc_loss_weights_block*>(p + 1);
+  LossWeights wt{b->pixel_w, b->trial_w, b->w_T, b->w_cells};
+  // a guard against a stray flag bit: the block must look like one whether or not trial_w is set (dc_err_map: agree with its own fields)
+  DC_REQUIRE(wt.T > 0 && wt.cells > 0, DC_ERR_ARG,
+             "%s: the weights block (pixel_w, trial_w, w_T, w_cells) behind the struct needs w_T > 0 and w_cells > 0 (w_T=%d w_cells=%d)",
+             who, wt.T, wt.cells);
+  if constexpr (std::is_same_v<P, dc_err_map_params>)
+    DC_REQUIRE(wt.T == p->T && wt.cells == p->cells, DC_ERR_ARG, "%s: the weights block's w_T=%d w_cells=%d differ from T=%d cells=%d",
+               who, wt.T, wt.cells, p->T, p->cells);
+  if (wt.trial_w)
+    DC_REQUIRE(p->out_index && p->img_of_bj, DC_ERR_ARG, "%s: trial_w needs out_index and img_of_bj", who);
+  return f(std::true_type{}, wt);
 }
 
 // ---- asynchronous LDS fragment reads with hand-counted waits -------------------------------------------------

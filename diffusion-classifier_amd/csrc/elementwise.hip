@@ -153,11 +153,14 @@ struct MseArgs {
   int C, HW, ld, v_param, W, patch;
   float huber_delta;       // read by the DC_LOSS_HUBER instance only
 };
+struct MseWeightedArgs : MseArgs { LossWeights wt; };      // the weighted instances' argument: the unweighted ones keep theirs
 
 // LOSS: the per-element term (common.h loss_term), a compile-time kind on all three read paths; the accumulation order is the same for
 // every kind.  DC_LOSS_L2 ends in sqrt then square, the other two store the sum.
-template <int LOSS>
-__global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
+// WGT: the pixel / trial weights of the loss (dcamd.h dc_eps_mse_params), compile-time as well — the instances without them hold none
+// of it.  m multiplies each term (loss_acc_weighted; the pixel-owner path loads it once per pixel), w the stored result.
+template <int LOSS, bool WGT>
+__global__ __launch_bounds__(256) void eps_mse_kernel(const std::conditional_t<WGT, MseWeightedArgs, MseArgs> a) {
   __shared__ float part[4];
   const int u = blockIdx.x, t = threadIdx.x;
   const int bj = a.bj_of_unit ? a.bj_of_unit[u] : u;
@@ -167,6 +170,8 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
   const float* pr = a.pred + (size_t)u * (a.patch > 1 ? a.HW / (a.patch * a.patch) : a.HW) * a.ld;
   const float* ep = a.eps + (size_t)bj * CHW;
   const float* xx = a.x ? a.x + (size_t)img * CHW : nullptr;
+  const float* pw = nullptr;                       // WGT: the image's weight plane (NULL: ones)
+  if constexpr (WGT) pw = a.wt.pixel_w ? a.wt.pixel_w + (size_t)img * a.HW : nullptr;
   float s = 0.f;
   if (a.patch <= 1 && a.C <= 16) {
     // image-shaped prediction with a few channels (UNets: C = 3..12): a lane owns whole pixels, so the C reads of an NHWC
@@ -175,6 +180,7 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
     // paid a 64-bit division per element — 0.6 TB/s on the 256x256 workloads.)
     for (int p = t; p < a.HW; p += 256) {
       const float* row = pr + (size_t)p * a.ld;
+      const float m = pw ? pw[p] : 1.f;
 #pragma unroll
       for (int c = 0; c < 16; ++c)
         if (c < a.C) {
@@ -186,7 +192,8 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
             v = sg * z + al * v;
           }
           const float d = v - e;
-          s += loss_term<LOSS>(d, a.huber_delta);
+          if constexpr (WGT) s = loss_acc_weighted<LOSS>(s, d, m, a.huber_delta);
+          else s += loss_term<LOSS>(d, a.huber_delta);
         }
     }
   } else
@@ -206,7 +213,8 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
       pv = sg * z + al * pv;
     }
     const float d = pv - e;
-    s += loss_term<LOSS>(d, a.huber_delta);
+    if constexpr (WGT) s = loss_acc_weighted<LOSS>(s, d, pw ? pw[p] : 1.f, a.huber_delta);
+    else s += loss_term<LOSS>(d, a.huber_delta);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -219,6 +227,7 @@ __global__ __launch_bounds__(256) void eps_mse_kernel(const MseArgs a) {
       r = sqrtf(tot);             // reference takes torch.norm(...)**2: sqrt, then square
       r = r * r;
     }
+    if constexpr (WGT) r *= trial_weight(a.wt, a.out_index ? a.out_index[u] : u, img);
     a.out[a.out_index ? a.out_index[u] : u] = r;
   }
 }
@@ -233,8 +242,16 @@ extern "C" int dc_eps_mse(const dc_eps_mse_params* p, dc_stream stream) {
             p->C, p->H * p->W, p->ld, p->v_param, p->W, pp, p->huber_delta};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return dc_by_loss(p->loss, p->huber_delta, "dc_eps_mse", [&](auto kind) {
-    hipLaunchKernelGGL((eps_mse_kernel<decltype(kind)::value>), dim3(p->n_units), dim3(256), 0, s, a);
-    return dc_check_launch("dc_eps_mse");
+    return dc_by_weights(p, "dc_eps_mse", [&](auto weighted, const LossWeights& wt) {
+      constexpr int LOSS = decltype(kind)::value;
+      if constexpr (decltype(weighted)::value) {
+        const MseWeightedArgs aw{a, wt};
+        hipLaunchKernelGGL((eps_mse_kernel<LOSS, true>), dim3(p->n_units), dim3(256), 0, s, aw);
+      } else {
+        hipLaunchKernelGGL((eps_mse_kernel<LOSS, false>), dim3(p->n_units), dim3(256), 0, s, a);
+      }
+      return dc_check_launch("dc_eps_mse");
+    });
   });
 }
 

@@ -13,12 +13,14 @@ struct ErrMapArgs {
   int C, HW, ld, v_param, W, patch, T, cells, nblk;
   float huber_delta;       // read by the DC_LOSS_HUBER instance only
 };
+struct ErrMapWeightedArgs : ErrMapArgs { LossWeights wt; };      // the weighted instances' argument: the unweighted ones keep theirs
 
 // One workgroup per (unit, 256 consecutive pixels); a lane owns one pixel and walks its channels in ascending order, so the C reads of
 // an NHWC prediction row are back to back, the planes of eps / x are read coalesced across the wave, and a wave's 64 adds are one
 // 512-byte run of the cell's plane.  LOSS: the per-element term (common.h loss_term), dc_eps_mse's, a compile-time kind.
-template <int LOSS>
-__global__ __launch_bounds__(256) void err_map_kernel(const ErrMapArgs a) {
+// WGT: the loss weights (dcamd.h dc_err_map_params), compile-time too: v = ((channel sum) m[y, x]) w behind the unchanged channel loop.
+template <int LOSS, bool WGT>
+__global__ __launch_bounds__(256) void err_map_kernel(const std::conditional_t<WGT, ErrMapWeightedArgs, ErrMapArgs> a) {
   const int u = blockIdx.x / a.nblk;
   const int p = (blockIdx.x - u * a.nblk) * 256 + threadIdx.x;
   if (p >= a.HW) return;
@@ -50,6 +52,10 @@ __global__ __launch_bounds__(256) void err_map_kernel(const ErrMapArgs a) {
     const float d = pv - e;
     v += loss_term<LOSS>(d, a.huber_delta);
   }
+  if constexpr (WGT) {
+    if (a.wt.pixel_w) v *= a.wt.pixel_w[(size_t)img * a.HW + p];
+    v *= trial_weight(a.wt, oi, img);
+  }
   if (v >= 0.f && v <= DC_EVIDENCE_VMAX) {         // false for NaN
     const long long q = (long long)rint((double)v * (double)(1ll << DC_EVIDENCE_FRAC_BITS));
     atomicAdd(a.acc + (size_t)cell * a.HW + p, (unsigned long long)q);
@@ -73,8 +79,17 @@ extern "C" int dc_err_map(const dc_err_map_params* p, dc_stream stream) {
                p->huber_delta};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return dc_by_loss(p->loss, p->huber_delta, "dc_err_map", [&](auto kind) {
-    hipLaunchKernelGGL((err_map_kernel<decltype(kind)::value>), dim3((unsigned)(p->n_units * nblk)), dim3(256), 0, s, a);
-    return dc_check_launch("dc_err_map");
+    return dc_by_weights(p, "dc_err_map", [&](auto weighted, const LossWeights& wt) {
+      constexpr int LOSS = decltype(kind)::value;
+      const dim3 grid((unsigned)(p->n_units * nblk));
+      if constexpr (decltype(weighted)::value) {
+        const ErrMapWeightedArgs aw{a, wt};
+        hipLaunchKernelGGL((err_map_kernel<LOSS, true>), grid, dim3(256), 0, s, aw);
+      } else {
+        hipLaunchKernelGGL((err_map_kernel<LOSS, false>), grid, dim3(256), 0, s, a);
+      }
+      return dc_check_launch("dc_err_map");
+    });
   });
 }
 

@@ -4,6 +4,7 @@ Kept surface (same names, argument meaning, assertions and return types):
   DiffusionClassifier(backbone, config)                         reference :17-81
   .classify(x, text=None, fast=False) -> LongTensor[BS]         reference :657-725
   .evaluate(val_dataloader, stop_idx, metrics, classification)  reference :532-578
+  .loss(x, text=None)                                           reference :295-344, forward only (training is not part of this project)
   .encode_text_prompt / .diffuse / .logsnr_schedule_cosine(_shifted)  :83-161
 `config.encoder_type`: 'nn' and 'DiT' as in the reference; 'prompt' (additive, with `config.prompt_tokens = S`) conditions on a table of
 per-class prompts [classes + 1, S, hid] — the [B, S, hid] the reference's text encoder hands to the backbone (:93-98), without fetching one.
@@ -34,6 +35,11 @@ shards the (trial, image) grid of ONE replicated batch over the default process 
 `stop_margin_z` (opt-in per-image early stopping, see below; None: off, none of its code runs),
 `score_loss` (None | "l2" | "l1" | "huber": the per-element term summed into classify's errors and evidence maps, with `huber_delta`
 (default 1.0) for "huber"; read once at construction; None / "l2": the reference's squared error, bit for bit; loss.py),
+`trial_weighting` (None | "uniform" | "train" | a callable f(logsnr [T, BS]) -> weights | under the discrete schedules a 1-D sequence of
+`train_timesteps` weights: a weight per (trial, image) on classify's errors and evidence maps, "train" being the truncated-SNR weight of
+the reference's training loss with its clamp `min_snr_gamma`, default 5.0; read once at construction; with `simulate_rank` ValueError;
+None / "uniform": nothing changes, bit for bit; loss.py), `pixel_weight_key` (`evaluate` / `inference` in classification mode hand
+batch[key] to `classify(..., pixel_weight=)`),
 `vae_path` (a LOCAL diffusers AutoencoderKL directory: `classify` encodes images to latents on the device first, nets/vae.py;
 `vae_dtype` its compute dtype, default the backbone's; `encode_latents(x)`; `classify(..., latents=True)` takes latents as they are;
 `decode_latents(z)` is the way back through the same directory's decoder, loaded at its first call, at most `vae_decode_batch` (default 8)
@@ -70,6 +76,8 @@ Extra keyword-only arguments (defaults keep the reference behaviour):
                  and, under grid sharding, one int64 all-reduce per call; no backbone forward is added.  Placed after the posterior and
                  before t_done in the returned tuple.  T <= 2^18; with `simulate_rank` ValueError.  Models trained on
                  `wavelet_dec_2(image) / 2`: the maps live on the wavelet grid
+  pixel_weight   a float tensor [BS, H, W] or [BS, 1, H, W] on the model's grid: the per-pixel weight of every term in the errors and the
+                 evidence maps (a 0/1 mask scores a region; loss.py); None: nothing changes, bit for bit
   return_trials  also return t_done, int32 [BS] on the scoring device, as the LAST element of the tuple: the trials each image was
                  scored on (T everywhere when stop_margin_z is unset)
   rng            "reference": draw rand(BS) / randn_like(x) per trial in the reference's order;
@@ -202,6 +210,8 @@ class DiffusionClassifier(nn.Module):
             self.schedule = self.logsnr_schedule_discrete
         else:
             self.schedule = self.logsnr_schedule_cosine if schedule == 'cosine' else self.logsnr_schedule_cosine_shifted
+        # the per-trial weights of classify's errors and maps (loss.py): None, or what `trial_weights` turns into `weight` per call
+        self.trial_weighting = LS.trial_weighting_of(self.config, self.train_timesteps if self.discrete else None)
         self.noise_d = self.config.noise_d
         self.image_d = self.config.image_size
         self.cfg_w = self.config.cfg_w
@@ -588,15 +598,24 @@ class DiffusionClassifier(nn.Module):
     # ---- the hot path ---------------------------------------------------------------------
     @torch.no_grad()
     def classify(self, x, text=None, fast=False, *, t=None, eps=None, fast_select=None, return_errors=False,
-                 rng="reference", seed=0, group=None, return_posterior=False, return_trials=False, return_evidence=False, latents=False):
+                 rng="reference", seed=0, group=None, return_posterior=False, return_trials=False, return_evidence=False, latents=False,
+                 pixel_weight=None):
         """latents (additive; config.vae_path only): True says x already holds latents (`encode_latents`); otherwise x is an image
-        batch and is encoded first — t / eps, the evidence maps and everything else then live on the latent grid."""
+        batch and is encoded first — t / eps, the evidence maps and everything else then live on the latent grid.
+        pixel_weight (additive): a float tensor [BS, H, W] or [BS, 1, H, W] on the model's grid (x's own after the VAE encoder: the latent
+        grid under config.vae_path, the wavelet grid of a DWT model, DiT's un-patchified [H, W]) that weights every pixel's term in the
+        errors and the evidence maps (loss.py); a 0/1 mask scores a region.  Its values are data (NaN propagates and is counted by the
+        posterior's `invalid`); under grid sharding every rank passes the identical tensor."""
         if self.vae is not None and not latents:
             x = self.encode_latents(x)
         cfg = self.config
+        if pixel_weight is not None:
+            pixel_weight = LS.pixel_weight_of(pixel_weight, x.shape[0], x.shape[2], x.shape[3])
         z_stop = P.stop_margin_of(cfg)           # None: no per-image early stopping, none of its code runs
         if z_stop is not None and cfg.simulate_rank:
             raise ValueError("stop_margin_z cannot be combined with simulate_rank: one rank's share of the errors decides nothing")
+        if self.trial_weighting is not None and cfg.simulate_rank:
+            raise ValueError("trial_weighting cannot be combined with simulate_rank: the measurement key times the unweighted kernels")
         tau = P.temperature_of(cfg) if return_posterior else None
         if return_evidence and cfg.simulate_rank:
             raise ValueError("return_evidence cannot be combined with simulate_rank: one rank's share of the grid explains nothing")
@@ -623,14 +642,15 @@ class DiffusionClassifier(nn.Module):
         if sim:
             rank, ws = int(sim[0]), int(sim[1])
         elif ws > 1:
-            D.assert_replicated(x, group)
+            D.assert_replicated(x, group, also=pixel_weight)
 
         classes = self._candidate_classes(text, fast, fast_select, BS)
         draws = self._trial_draws(x, T, t, eps, rng, seed)
+        weights = {} if pixel_weight is None else {"pixel_w": pixel_weight}      # (the trial weights travel in the draws)
         if hasattr(backbone, "make_plan"):
-            runner = _HipRunner(self, backbone, x, T, draws)           # libdcamd; raises without GPU / library
+            runner = _HipRunner(self, backbone, x, T, draws, **weights)           # libdcamd; raises without GPU / library
         else:
-            runner = _ForeignRunner(self, backbone, x, T, draws)       # user-supplied nn.Module, eager torch
+            runner = _ForeignRunner(self, backbone, x, T, draws, **weights)       # user-supplied nn.Module, eager torch
         # per-image early stopping (config.stop_margin_z): t_done[b] = 0 while image b is undecided, else the trials it was decided on;
         # `rows` = the undecided images (ascending ids; None: all of them, the plain path), the same list on every rank
         t_done = frozen = rows = None
@@ -734,8 +754,60 @@ class DiffusionClassifier(nn.Module):
             sigma_all = torch.stack([torch.sqrt(torch.sigmoid(-logsnr[j].clone())) for j in range(T)])
         # `label`: the backbone's time input per (trial, image) — the log-SNR tensor itself unless the schedule is discrete
         label = torch.stack([self.noise_labels(t_all[j].clone()) for j in range(T)]) if self.discrete else logsnr
-        return dict(logsnr=logsnr, alpha=alpha_all, sigma=sigma_all, label=label,
-                    eps_of=eps_of, philox=(rng == "philox" and eps is None), seed=int(seed))
+        draws = dict(logsnr=logsnr, alpha=alpha_all, sigma=sigma_all, label=label,
+                     eps_of=eps_of, philox=(rng == "philox" and eps is None), seed=int(seed))
+        if self.trial_weighting is not None:     # config.trial_weighting: `weight` [T, BS] fp32 on the host (loss.py); absent otherwise
+            steps = self.ddpm_step(t_all) if self.discrete else None
+            draws["weight"] = LS.trial_weights(self.trial_weighting, self.pred_param, logsnr, steps)
+        return draws
+
+    @torch.no_grad()
+    def loss(self, x, text=None, *, t=None, eps=None, ema=False):
+        """The reference's `loss` (:295-344) as a forward-only evaluation — the validation loss people log; TRAINING IS NOT PART OF THIS
+        PROJECT, no autograd graph is built and nothing can be back-propagated through the result.  mean over the batch and C * H * W of
+        w(logsnr) (eps_hat - eps)^2 with the truncated-SNR weight of :331-337 (loss.py `train_weight`: config.trial_weighting = "train"'s
+        weight with its min_snr_gamma, whatever trial_weighting is set to), at one draw per image in the reference's order (t = rand(BS),
+        then eps = randn_like(x)); `t` [BS] and `eps` (x's shape) inject the draws.  Returns a 0-dim fp32 tensor on the scoring device.
+        HIP backbones: one trial and one class column (`text`, class ids [BS]; None raises ValueError) through the scoring plans — the
+        weighted dc_eps_mse, so the per-image sums go through its sqrt-then-square; ema=False scores `self.model` as the reference does,
+        True the EMA model `classify` scores.  A foreign backbone: the reference's statements in eager torch."""
+        if self.vae is not None:
+            x = self.encode_latents(x)
+        BS = x.shape[0]
+        tw = self.trial_weighting
+        gamma = tw[1] if tw is not None and tw[0] == "train" else LS.MIN_SNR_GAMMA
+        backbone = self.ema.ema_model if ema else self.model
+        t = torch.rand(BS) if t is None else torch.as_tensor(t, dtype=torch.float32).cpu().reshape(BS)
+        if not hasattr(backbone, "make_plan"):
+            text_embeddings = None
+            if text is not None and self.encoder_type is not None:
+                text_embeddings = self.encode_text_prompt(text).to(x.device)
+            logsnr_t = self.schedule(t).to(x.device)
+            alpha_t = torch.sqrt(torch.sigmoid(logsnr_t)).view(-1, 1, 1, 1).to(x.device)
+            sigma_t = torch.sqrt(torch.sigmoid(-logsnr_t)).view(-1, 1, 1, 1).to(x.device)
+            eps_t = torch.randn_like(x) if eps is None else eps.to(x.device).reshape(x.shape)
+            z_t = alpha_t * x + sigma_t * eps_t
+            pred = backbone(x=z_t, noise_labels=self.noise_labels(t).to(x.device), encoder_hidden_states=text_embeddings,
+                            **({} if text is None else self.added_cond(text)))
+            eps_pred = sigma_t * z_t + alpha_t * pred if self.pred_param == 'v' else pred
+            minsnr_weight = LS.train_weight(logsnr_t, self.pred_param, gamma).view(-1, 1, 1, 1)
+            return torch.mean(minsnr_weight * (eps_pred - eps_t) ** 2).to(torch.float32)
+        if text is None:
+            raise ValueError("loss on a HIP backbone scores one class column: pass text, the class id of every image ([BS])")
+        self._require_prompts()
+        labels = torch.as_tensor(text).detach().cpu().reshape(-1).to(torch.int64)
+        if labels.numel() != BS or int(labels.min()) < 0 or int(labels.max()) >= self.config.classes:
+            raise ValueError(f"loss: text must hold one class id in [0, {self.config.classes}) per image, got {labels.tolist()}")
+        eps_t = torch.randn_like(x) if eps is None else eps.reshape(x.shape)
+        logsnr = self.schedule(t.clone()).reshape(1, BS)
+        draws = dict(logsnr=logsnr, alpha=torch.sqrt(torch.sigmoid(logsnr.clone())), sigma=torch.sqrt(torch.sigmoid(-logsnr.clone())),
+                     label=self.noise_labels(t.clone()).reshape(1, BS), eps_of={0: eps_t}, philox=False, seed=0,
+                     weight=LS.trial_weights(("train", gamma), self.pred_param, logsnr))
+        runner = _HipRunner(self, backbone, x, 1, draws)
+        runner.score_loss = (L.LOSS_L2, 1.0)             # the training loss is the squared error, whatever config.score_loss scores with
+        runner.run_stage(D.local_pairs(0, 1, BS, 0, 1), labels.view(BS, 1), stage=(0, 0, 1))
+        err = runner.errors()[torch.arange(BS, device=runner.dev), labels.to(runner.dev), 0]      # w_b * sum over C H W, per image
+        return err.sum() / float(BS * x.shape[1] * x.shape[2] * x.shape[3])
 
     def check_device_errors(self):
         """Raise if a producer-side-GroupNorm launch (csrc/epi_pn.h) gave up waiting for the other workgroups of a sample since the last
@@ -757,10 +829,14 @@ class DiffusionClassifier(nn.Module):
             # a metric with `wants_posterior = True` (utils/metrics.py AUROC, SelectiveAccuracy) is fed (labels, batch, ClassPosterior)
             want_post = classification and metrics is not None and any(getattr(m, "wants_posterior", False) for m in metrics)
             post = None
+            # config.pixel_weight_key (additive): batch[key] is the call's pixel_weight, on the model's grid as it is (dwt_on_device
+            # transforms "images" only)
+            key = self.config.pixel_weight_key if classification else None      # (sampling mode never looks for the mask)
+            pw = {} if key is None else {"pixel_weight": batch[key]}
             if want_post:
-                sample, post = self.classify(x, p, fast=self.config.fast_classification, return_posterior=True)
+                sample, post = self.classify(x, p, fast=self.config.fast_classification, return_posterior=True, **pw)
             else:
-                sample = self.classify(x, p, fast=self.config.fast_classification) if classification else self.sample(x, p, from_t)
+                sample = self.classify(x, p, fast=self.config.fast_classification, **pw) if classification else self.sample(x, p, from_t)
             if metrics is not None:
                 for metric in metrics:
                     if post is not None and getattr(metric, "wants_posterior", False):

@@ -28,8 +28,9 @@ REPLICATED_CHECK_FIRST = 2       # the first calls on a group are always compare
 REPLICATED_CHECK_EVERY = 64      # ... and every 64th after that
 
 
-def assert_replicated(x, group=None):
-    """Grid sharding splits the (trial, image) pairs of ONE batch over the ranks: every rank must hold the same x.
+def assert_replicated(x, group=None, also=None):
+    """Grid sharding splits the (trial, image) pairs of ONE batch over the ranks: every rank must hold the same x (and the same
+    `also`, classify's pixel_weight, when the call has one).
     Compares a cheap fingerprint (shape, sum, sum of squares, a strided sample) across the group, bit for bit (the fp64 words are
     compared as int64, so a replicated batch that contains NaN still passes).  The check costs a pass over x, a small all-gather and
     a host sync, so it is not made on every call — but WHETHER it is made must be the same decision on every rank, or one rank's
@@ -45,8 +46,14 @@ def assert_replicated(x, group=None):
         return False
     xf = x.detach().reshape(-1).to(torch.float64)
     step = max(1, xf.numel() // 61)
+    # (the pixel weights of the call, when it has any: three words on every rank either way, so the gather's sizes always agree)
+    if also is None:
+        mf = torch.zeros(3, dtype=torch.float64, device=xf.device)
+    else:
+        m = also.detach().reshape(-1).to(xf.device, torch.float64)
+        mf = torch.stack([torch.ones((), dtype=torch.float64, device=xf.device), m.sum(), (m * m).sum()])
     fp = torch.cat([torch.tensor([float(x.shape[0]), float(xf.numel())], dtype=torch.float64, device=xf.device),
-                    xf.sum().reshape(1), (xf * xf).sum().reshape(1), xf[::step][:61]]).contiguous().view(torch.int64)
+                    xf.sum().reshape(1), (xf * xf).sum().reshape(1), xf[::step][:61], mf]).contiguous().view(torch.int64)
     ws = dist.get_world_size(group)
     if fp.is_cuda and dist.get_backend(group) == "gloo":
         fp = fp.cpu()                    # gloo has no device all-gather

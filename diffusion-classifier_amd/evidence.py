@@ -65,11 +65,16 @@ def new_slabs(n_stages, cells, HW, device):
             torch.zeros((n_stages, cells + 1), dtype=torch.int32, device=device))
 
 
-def err_map_torch(eps_pred, e, cell, acc, bad, loss=L.LOSS_L2, huber_delta=1.0):
+def err_map_torch(eps_pred, e, cell, acc, bad, loss=L.LOSS_L2, huber_delta=1.0, pixel_w=None, trial_w=None):
     """One batch of units: eps_pred / e [n, C, H, W], cell [n] int64 (the flat (b, class) cell of each unit); adds into acc
     [cells + 1, HW] int64 and bad [cells + 1] int32 of the stage, in place.  loss / huber_delta: the scoring loss (loss.py; a L.LOSS_*
-    kind), whose per-element term is summed over the channels."""
+    kind), whose per-element term is summed over the channels.  pixel_w [n, H, W] / trial_w [n] (fp32, the units' own rows; None: no
+    such weight): v = ((channel sum) m) w, loss.py's weights, in front of the fixed-point rule."""
     v = LS.term_torch(eps_pred.float() - e.float(), loss, huber_delta).sum(1)      # [n, H, W] fp32
+    if pixel_w is not None:
+        v = v * pixel_w
+    if trial_w is not None:
+        v = v * trial_w[:, None, None]
     ok = torch.isfinite(v) & (v >= 0) & (v <= VMAX)
     q = torch.round(torch.where(ok, v, torch.zeros_like(v)).double() * 2.0 ** F).to(torch.int64)
     acc.index_add_(0, cell, q.reshape(q.shape[0], -1))

@@ -28,6 +28,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from . import loss as LS
 
 DT = {"f32": L.DC_F32, "fp32": L.DC_F32, "float32": L.DC_F32, "bf16": L.DC_BF16, "bfloat16": L.DC_BF16,
       "f16": L.DC_F16, "fp16": L.DC_F16, "float16": L.DC_F16}
@@ -184,7 +185,9 @@ class PlanBuilder:
             return "unit"
         return doms.pop()
 
-    def emit(self, kind, fields, reads, writes, meta=None):
+    def emit(self, kind, fields, reads, writes, meta=None, cls=None):
+        """cls: the ctypes class of the op's record when it is not the op's own params struct (a weighted scoring op: the struct with
+        the weights block behind it, loss.weighted_params)."""
         idx = len(self.ops)
         self.meta.append(dict(meta or {}, kind=kind))
         for t in reads + writes:
@@ -195,7 +198,7 @@ class PlanBuilder:
                 if b.first is None:
                     b.first = idx
                 b.last = idx
-        self.ops.append((kind, L.OP_PARAMS[kind], fields))
+        self.ops.append((kind, cls or L.OP_PARAMS[kind], fields))
 
     # ---- ops -----------------------------------------------------------------------
     def igemm(self, name, src0, W, Cout, *, taps=1, stride=1, upsample=0, src1=None, bias=None, rowvec=None,
@@ -538,7 +541,7 @@ class PlanBuilder:
 
     # ---- the two ends of a scoring plan (UNetPlan, DiTPlan) -------------------------------------
     def score_head(self, score, Cin, H, W, ld, dt, im2col, patch=0):
-        """score = dict(x=[B,C,H,W] f32 buffer, eps=[n_bj,C,H,W], alpha, sigma, img_of_bj, out_index, errors, v_param, loss, huber_delta).  Emits q_sample,
+        """score = dict(x=[B,C,H,W] f32 buffer, eps=[n_bj,C,H,W], alpha, sigma, img_of_bj, out_index, errors, v_param, loss, huber_delta; optionally pixel_w, trial_w, T, cells: the loss weights).  Emits q_sample,
         which writes the first GEMM's operand: returns (that operand, the (eps, alpha, sigma) externals score_tail takes back)."""
         noise = tuple(self.external(k, score[k], "bj", 1, 1, 1, L.DC_F32) for k in ("eps", "alpha", "sigma"))
         a0 = self.qsample("a0", self.const(score["x"]), *noise, self.const(score["img_of_bj"]), Cin, H, W, ld, dt, im2col=im2col, patch=patch)
@@ -553,12 +556,18 @@ class PlanBuilder:
                  img_of_bj=self.const(score["img_of_bj"]), out_index=self.const(score["out_index"]), n_units=self.n["unit"], C=Cin,
                  H=pred.H * g, W=pred.W * g, ld=pred.ld, v_param=int(score["v_param"]), patch=int(patch),
                  loss=int(score["loss"]), huber_delta=float(score["huber_delta"]))      # the scoring loss (loss.py), for both ops
+        weighted = score.get("pixel_w") is not None or score.get("trial_w") is not None
+        if weighted:       # the loss weights: the flag in `loss` and the block behind both structs (dcamd.h DC_LOSS_WEIGHTED)
+            f.update(loss=f["loss"] | L.LOSS_WEIGHTED, pixel_w=self.const(score.get("pixel_w")), trial_w=self.const(score.get("trial_w")),
+                     w_T=int(score["T"]), w_cells=int(score["cells"]))
+        cls_of = (lambda kind: LS.weighted_params(L.OP_PARAMS[kind])) if weighted else (lambda kind: None)
         self.emit(L.OP_EPS_MSE, dict(f, out=self.const(score["errors"])), [pred, *noise], [],
-                  dict(name="eps_mse", family="eps_mse", flops=0.0, bytes=8.0 * Cin * px))
+                  dict(name="eps_mse", family="eps_mse", flops=0.0, bytes=8.0 * Cin * px), cls=cls_of(L.OP_EPS_MSE))
         if score.get("emap_acc") is not None:
             acc = score["emap_acc"]
             self.emit(L.OP_ERR_MAP, dict(f, acc=self.const(acc), bad=self.const(score["emap_bad"]), T=int(score["emap_T"]), cells=acc.shape[0] - 1),
-                      [pred, *noise], [], dict(name="err_map", family="err_map", flops=0.0, bytes=(8.0 * Cin + 8.0) * px))
+                      [pred, *noise], [], dict(name="err_map", family="err_map", flops=0.0, bytes=(8.0 * Cin + 8.0) * px),
+                      cls=cls_of(L.OP_ERR_MAP))
 
     # ---- finalize: liveness-based arena + ctypes records ----------------------------
     def finalize(self, keep_alive=()):

@@ -110,8 +110,13 @@ class _Runner:
 
     ev = None            # (acc, bad) per-stage evidence accumulators of a return_evidence call (evidence.py), `ev_stage` the running stage
 
-    def __init__(self, dc, backbone, x, T, draws, dev):
+    def __init__(self, dc, backbone, x, T, draws, dev, pixel_w=None):
         self.dc, self.bb, self.x, self.T, self.d, self.dev = dc, backbone, x, T, draws, dev
+        self.score_loss = dc.score_loss      # (kind, huber delta) of this call (DiffusionClassifier.loss sets l2 whatever the config says)
+        # the loss weights of this call (loss.py), both None on the plain path: pixel_w fp32 [BS, H, W] on the runner's device,
+        # trial_w fp32 [T, BS] on the host, where the draws live
+        self.pixel_w = None if pixel_w is None else pixel_w.to(dev)
+        self.trial_w = draws.get("weight")
         # what the backbone is fed as its time input: the log-SNR itself, unless the draws carry a `label` of their own (the
         # 'scaled_linear' schedule: the DDPM step; DiffusionClassifier.noise_labels)
         self.label = draws.get("label", draws["logsnr"])
@@ -136,11 +141,11 @@ class _ForeignRunner(_Runner):
 
     posterior, _evidence = staticmethod(P.class_posterior_torch), staticmethod(EV.evidence_maps_torch)
 
-    def __init__(self, dc, backbone, x, T, draws):
+    def __init__(self, dc, backbone, x, T, draws, pixel_w=None):
         if draws["philox"]:
             raise L.DcamdError("rng='philox' needs a HIP backbone (UNetCondition2D / DiT)")
         dc._refuse_ragged_on_foreign()
-        super().__init__(dc, backbone, x, T, draws, x.device)
+        super().__init__(dc, backbone, x, T, draws, x.device, pixel_w)
         self.err = torch.full((x.shape[0], dc.config.classes, T), float("inf"), device=x.device)
 
     def errors(self):
@@ -174,17 +179,19 @@ class _ForeignRunner(_Runner):
             e = d["eps_of"][j]
             e = (e if full else e[bs.to(e.device)]).to(x.device)
             z = al * (x if full else x[bs.to(x.device)]) + sg * e
+            wt = dict(pixel_w=None if self.pixel_w is None else self.pixel_w[bs.to(x.device)],
+                      trial_w=None if self.trial_w is None else self.trial_w[j, bs].to(x.device))
             for c in range(classes.shape[1]):
                 lab = classes[bs, c].to(x.device)
                 emb = dc.encode_text_prompt(lab)
                 # (encoder_type='clip_dual': also added_cond_kwargs = {text_embeds, time_ids}, diffusers' names; {} otherwise)
                 pred = self.bb(x=z, noise_labels=lam, encoder_hidden_states=emb, **dc.added_cond(lab))
                 eps_pred = sg * z + al * pred if dc.pred_param == 'v' else pred
-                err = LS.error_torch(eps_pred, e, *dc.score_loss)      # l2: torch.norm(...) ** 2, the reference's statement
+                err = LS.error_torch(eps_pred, e, *self.score_loss, **wt)      # l2: torch.norm(...) ** 2, the reference's statement
                 self.err[bs.to(x.device), lab, j] = err
                 if self.ev is not None:
                     EV.err_map_torch(eps_pred, e, bs.to(x.device) * dc.config.classes + lab, self.ev[0][self.ev_stage], self.ev[1][self.ev_stage],
-                                     *dc.score_loss)
+                                     *self.score_loss, **wt)
 
 
 class _HipRunner(_Runner):
@@ -192,10 +199,12 @@ class _HipRunner(_Runner):
 
     posterior, _evidence = staticmethod(P.class_posterior_hip), staticmethod(EV.evidence_maps_hip)
 
-    def __init__(self, dc, backbone, x, T, draws):
+    def __init__(self, dc, backbone, x, T, draws, pixel_w=None):
         self.lib = L.require_gpu()
-        super().__init__(dc, backbone, x, T, draws, x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        super().__init__(dc, backbone, x, T, draws, x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device()), pixel_w)
         self.x_dev = x.detach().to(self.dev, torch.float32).contiguous()
+        # the call's trial weights in the kernels' layout [BS, T]: ONE host-to-device copy per call (like x), the stages copy on the device
+        self.trial_w_dev = None if self.trial_w is None else self.trial_w.t().contiguous().to(self.dev)
         self.err_dev = None
         dt = dc.config.compute_dtype or "bf16"
         if getattr(backbone, "compute_dtype", None) != dt:
@@ -214,8 +223,11 @@ class _HipRunner(_Runner):
         varlen = dc._ragged_table()                                                    # prompts of different lengths: a plan with ctx_len
         key = (BS, n_bj, k, self.dt, str(dev), (Cc, H, W), bool(getattr(self.bb, "share_trunk", True)), id(self.bb),
                self.T, cfg.classes, wver, S) + (("varlen",) if varlen else ())
-        if dc.score_loss[0] != L.LOSS_L2:                # the loss is baked into the plan's two scoring ops: never serve another loss's plan
-            key += (("loss",) + dc.score_loss,)
+        if self.score_loss[0] != L.LOSS_L2:                # the loss is baked into the plan's two scoring ops: never serve another loss's plan
+            key += (("loss",) + self.score_loss,)
+        weighted = (self.pixel_w is not None, self.trial_w is not None)
+        if any(weighted):                                # such plans own the weight buffers and launch the weighted kernel instances
+            key += (("weights",) + weighted,)
         if self.ev is not None:
             key += ("evidence",)
         sp = dc._score_plans.get(key)
@@ -233,7 +245,11 @@ class _HipRunner(_Runner):
             eps=torch.zeros((n_bj, Cc, H, W), dtype=torch.float32, device=dev),
             errors=torch.full((BS * cfg.classes * T + 1,), float("inf"), dtype=torch.float32, device=dev),
             **{f: layout.view(ctl, f) for f in ("lam", "alpha", "sigma", "img_of_bj", "ctx_of_unit", "out_index")},
-            v_param=dc.pred_param == 'v', loss=dc.score_loss[0], huber_delta=dc.score_loss[1])
+            v_param=dc.pred_param == 'v', loss=self.score_loss[0], huber_delta=self.score_loss[1])
+        if any(weighted):                # per-call buffers, filled in _feed: switching the weights' values never needs another plan
+            score["pixel_w"] = torch.ones((BS, H, W), dtype=torch.float32, device=dev) if weighted[0] else None
+            score["trial_w"] = torch.ones((BS, T), dtype=torch.float32, device=dev) if weighted[1] else None
+            score["T"], score["cells"] = T, BS * cfg.classes
         if self.ev is not None:          # such plans own the accumulators their map op adds into (one stage at a time: run_stage)
             score["emap_acc"], score["emap_bad"] = (v[0] for v in EV.new_slabs(1, BS * cfg.classes, H * W, dev))
             score["emap_T"] = T
@@ -305,6 +321,10 @@ class _HipRunner(_Runner):
             score["emap_acc"].zero_()
             score["emap_bad"].zero_()
         score["x"].copy_(self.x_dev)
+        if self.pixel_w is not None:
+            score["pixel_w"].copy_(self.pixel_w)
+        if self.trial_w is not None:
+            score["trial_w"].copy_(self.trial_w_dev)
         if self.dc.encoder is not None:
             plan.ctx.copy_(self.dc.encoder.weight[:ncls].detach().to(self.dev, torch.float32).reshape(plan.ctx.shape))
             if plan.varlen:                              # the same on every rank: grid sharding needs nothing else

@@ -93,7 +93,9 @@ extern "C" {
  * (the AutoencoderKL decoder's head — dc_latent_im2col, dc_latent_im2col_params and DC_OP_LATENT_IM2COL — likewise)
  * (the scoring loss — `loss` and `huber_delta`, the LAST two fields of dc_eps_mse_params and dc_err_map_params, with DC_LOSS_* — is
  *  additive within 5: no symbol, struct name or op kind changed, and a caller that zero-initialises the structs gets DC_LOSS_L2, the
- *  bits it got before) */
+ *  bits it got before)
+ * (the loss weights — DC_LOSS_WEIGHTED, a flag bit of `loss`, announces a weights block BEHIND the struct in the caller's memory — are
+ *  additive within 5 likewise: no struct, field, symbol or op kind changed, and without the bit nothing behind the struct is read) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -581,7 +583,23 @@ int32_t dc_tblock_front_ok(const dc_tblock_front_params* p);     /* 1: the shape
  *   DC_LOSS_L1     |d|
  *   DC_LOSS_HUBER  |d| <= huber_delta ? 0.5 d^2 : huber_delta (|d| - 0.5 huber_delta)      torch's huber_loss, summed
  * l1 and Huber store the sum as it is.  Sums, not means.  huber_delta is read for DC_LOSS_HUBER only and must then be finite and > 0;
- * an unknown kind or such a delta is DC_ERR_ARG.  A NaN element makes its unit's error NaN for every kind. */
+ * an unknown kind or such a delta is DC_ERR_ARG.  A NaN element makes its unit's error NaN for every kind.
+ * Weights of the loss.  `loss` may carry the flag DC_LOSS_WEIGHTED next to the kind (loss = DC_LOSS_L1 | DC_LOSS_WEIGHTED); any other
+ * bit is DC_ERR_ARG.  The caller then passes the struct as the head of a larger object: directly behind it (at sizeof of the struct,
+ * which is a multiple of 8) stand, in this order,
+ *     const float* pixel_w;  const float* trial_w;  int32_t w_T, w_cells;
+ * — the same block behind a dc_err_map_params.  It is no struct of this header on purpose: the structs and their fields are frozen
+ * within version 5, and a caller that never sets the bit never has anything read behind its struct.  Without the bit: the kernels above,
+ * untouched.  With t the term above,
+ *   s = sum over C*H*W of m[y, x] * t(d)      m = pixel_w[img, y, x], pixel_w f32 [n_img, H, W], img = img_of_bj[bj(u)] (NULL: bj(u));
+ *                                             one fp32 multiply per element, the accumulation order of the unweighted kernel
+ *                                             (DC_LOSS_L2: (m d) d, the second product fused into the sum as the unweighted d d is)
+ *   r = sqrt(s), r = r * r for DC_LOSS_L2, r = s otherwise;   err[u] = r * w, one fp32 multiply
+ *   w = trial_w[img * T + j], trial_w f32 [n_img, T], j = out_index[u] % T, with T = w_T and cells = w_cells (dc_err_map: its own T and
+ *   cells fields, which w_T / w_cells must equal); w_T > 0 and w_cells > 0 are required whenever the flag is set, a guard against a
+ *   stray bit; an out_index outside [0, cells * T) — the dump slot of padded units — takes w = 1.A NULL pointer of the two is a weight of 1.  All ones give the bits of the unweighted call.
+ * trial_w needs out_index, img_of_bj, T > 0 and cells > 0: DC_ERR_ARG otherwise.  Weights are data: a NaN weight makes its units NaN. */
+#define DC_LOSS_WEIGHTED 256
 #define DC_LOSS_L2 0
 #define DC_LOSS_L1 1
 #define DC_LOSS_HUBER 2
@@ -753,7 +771,11 @@ int dc_class_posterior(const dc_class_posterior_params* p, dc_stream s);
  * [cells + 1]; both are accumulated into (the caller zeroes them).  A lane owns a pixel and loops over the channels; the adds are
  * 64-bit integer global atomics, one wave adding 512 contiguous bytes.  It runs right after DC_OP_EPS_MSE, which it leaves alone.
  * loss / huber_delta: as in dc_eps_mse_params — v is the channel sum of the same per-element term (DC_LOSS_L2, zero: the square
- * above), under the same fixed-point rule; the same values are refused. */
+ * above), under the same fixed-point rule; the same values are refused.
+ * DC_LOSS_WEIGHTED in `loss`: dc_eps_mse's weights block behind the struct; without the bit the kernel above, untouched — v =
+ * ((channel sum) * m[y, x]) * w, two fp32
+ * multiplies behind the channel loop, then the same fixed-point rule: a weighted v above DC_EVIDENCE_VMAX, or a NaN one, is counted in
+ * bad like any other.  The dump plane's units take w = 1. */
 #define DC_EVIDENCE_FRAC_BITS 30
 #define DC_EVIDENCE_VMAX 16384.0f
 typedef struct {
