@@ -16,7 +16,10 @@ object, a step kind, chosen once per call by `step_kind`; the loops below take i
              b = sqrt(abar_s) beta / (1 - abar_t), sd^2 = (1 - abar_s) / (1 - abar_t) beta with beta = 1 - abar_t / abar_s: the DDPM
              posterior.  On the device the mean is one non-final first-order `dc_solver_step` with clamp = 0, k1 = a, k2 = b, the
              update and the map one in-place torch op on the walk's buffers: the C ABI has no unclipped ancestral entry.
-The two are not harmonised: each keeps its own operation order and its own spelling of the update, bit for bit.
+  `LearnedRange`  the discrete grid under config.variance = "learned": `Linear`'s mean, and the deviation of every element from the
+             variance channels the model predicts next to eps, sde = exp(0.5 (fr log beta + (1 - fr) log beta~)), fr = (v + 1) / 2.  On
+             the device step and map are one kernel each, `dc_ddpm_step_shared` / `dc_ddpm_noise_map` in DC_STEP_LEARNED_RANGE.
+The kinds are not harmonised: each keeps its own operation order and its own spelling of the update, bit for bit.
 
 A kind holds the `trajectory.Grid` of the call, the guidance weight, and the host scalars of the n steps (`scalars`: fp32 torch ops on
 0-dim host tensors, handed to the kernels as Python floats).  Its eager statement is `mean` / `update` / `last` / `noise_map`, its HIP
@@ -48,9 +51,14 @@ def linear_mean(dc, z, pred, u_pred, sc, w):
 
 
 class _Kind:
+    variance = False          # does the kind read the backbone's variance channels (pair plans with the full projection)?
+
     def __init__(self, dc, g, w):
         self.dc, self.g, self.w, self.n = dc, g, w, len(g.lam) - 1
-        self.scal = [self.scalars(g.lam[t], g.lam[t + 1]) for t in range(self.n)]
+        self.scal = [self.scalars_at(t) for t in range(self.n)]
+
+    def scalars_at(self, t):
+        return self.scalars(self.g.lam[t], self.g.lam[t + 1])
 
 
 class Clipped(_Kind):
@@ -128,8 +136,72 @@ class Linear(_Kind):
         torch.sub(x_next, out, out=out).div_(self.scal[t][4])
 
 
+class LearnedRange(_Kind):
+    """The discrete grid's step of a model that predicts its variance (config.variance = "learned"; diffusers' "learned_range", the
+    improved-DDPM sampler of a published DiT): `Linear`'s mean on the eps channels, and per element
+    sde = exp(0.5 (fr log_hi + (1 - fr) log_lo)), fr = (v + 1) / 2 on the CONDITIONAL call's variance channels v (guidance mixes eps
+    only), log_hi = log beta, log_lo = log of the posterior variance.  On the device step and map are one kernel each:
+    `dc_ddpm_step_shared` / `dc_ddpm_noise_map` in DC_STEP_LEARNED_RANGE, on pair plans that keep the variance features."""
+    variance = True
+
+    @staticmethod
+    def scalars(lam_t, lam_s, abar_t, abar_s):
+        """(alpha_t, sigma_t, a, b, log_hi, log_lo) as Python floats: the first four are `Linear.scalars`'; the two logs are formed in
+        fp64 from the fp64 abar of the two integer steps and rounded to fp32 once — 1 - abar_t / abar_s cancels at neighbouring steps,
+        which the fp32 log-SNRs cannot carry.  The posterior variance is clamped below at 1e-20, as diffusers clamps it."""
+        alpha_t, sigma_t, a, b, _ = Linear.scalars(lam_t, lam_s)
+        at, as_ = torch.as_tensor(abar_t, dtype=torch.float64), torch.as_tensor(abar_s, dtype=torch.float64)
+        beta = 1.0 - at / as_
+        post = torch.clamp((1.0 - as_) / (1.0 - at) * beta, min=1e-20)
+        return alpha_t, sigma_t, a, b, float(torch.log(beta).to(torch.float32)), float(torch.log(post).to(torch.float32))
+
+    def scalars_at(self, t):
+        g, abar = self.g, self.dc.abar
+        return self.scalars(g.lam[t], g.lam[t + 1], abar[g.steps[t]], abar[g.steps[t + 1]])
+
+    def mean(self, z, pred, u_pred, t):
+        """(mu, sde) at step t from the two calls' 2C-channel outputs: `linear_mean` on their eps halves, sde [BS, C, H, W] from the
+        conditional call's variance half."""
+        Cc = z.shape[1]
+        if pred.shape[1] != 2 * Cc or u_pred.shape[1] != 2 * Cc:
+            raise ValueError(f"config.variance = 'learned' needs a backbone that returns {2 * Cc} channels (eps and variance) for "
+                             f"{Cc}-channel latents, got {pred.shape[1]}")
+        alpha_t, sigma_t, a, b, log_hi, log_lo = self.scal[t]
+        mu = linear_mean(self.dc, z, pred[:, :Cc], u_pred[:, :Cc], (alpha_t, sigma_t, a, b, None), self.w)
+        fr = 0.5 * pred[:, Cc:] + 0.5
+        return mu, torch.exp(0.5 * (fr * log_hi + (1.0 - fr) * log_lo))
+
+    def update(self, mu, noise, sde):
+        return mu + noise * sde
+
+    def last(self, mu):
+        return mu
+
+    def noise_map(self, x_next, mu, sde):
+        return (x_next - mu) / sde
+
+    def _step_scalars(self, t):
+        """The scalar fields of both structs at step t; alpha_s, c and sd are not read in this mode."""
+        alpha_t, sigma_t, a, b, log_hi, log_lo = self.scal[t]
+        return dict(alpha_t=alpha_t, sigma_t=sigma_t, alpha_s=0.0, c=0.0, sd=0.0, k1=a, k2=b, log_hi=log_hi, log_lo=log_lo)
+
+    def step_hip(self, f, out, t, e, K=None):
+        """One `dc_ddpm_step_shared` on the step fields `f` (which carry the mode block's flag, mode and fstride), the block behind
+        the struct: unshared noise is noise_div = 1."""
+        p = TJ.mode_params(L.DdpmStepSharedParams)(noise=None if e is None else e.data_ptr(), out=out.data_ptr(),
+                                                   noise_div=1 if K is None else K, pad_=0, **self._step_scalars(t), **f)
+        TJ.launch("dc_ddpm_step_shared", p, L.DdpmStepSharedParams)
+
+    def map_hip(self, f, x_next, out, t):
+        p = TJ.mode_params(L.DdpmNoiseMapParams)(x_next=x_next.data_ptr(), out=out.data_ptr(), **self._step_scalars(t), **f)
+        TJ.launch("dc_ddpm_noise_map", p, L.DdpmNoiseMapParams)
+
+
 def step_kind(dc, g, w):
-    """The step kind of a call on the grid `g` under guidance weight w: the one place that asks which schedule the classifier has."""
+    """The step kind of a call on the grid `g` under guidance weight w: the one place that asks which schedule the classifier has and
+    whether its variance is learned (config.variance, refused at construction off the discrete grid)."""
+    if getattr(dc, "variance", None) == "learned":
+        return LearnedRange(dc, g, w)
     return (Linear if dc.discrete else Clipped)(dc, g, w)
 
 
@@ -170,7 +242,9 @@ def sample_pair(kind, backbone, z_t, cond, null, lens):
     `kind.step_hip` per pass, one `randn_like` per pass but the last, in the reference's order."""
     dc, g, n = kind.dc, kind.g, kind.n
     kw = {"cond_lengths": lens["cond"], "null_lengths": lens["null"]} if lens else {}
-    fields = TJ.step_fields(dc, backbone, z_t.shape, dc.cfg_w)
+    if kind.variance:
+        kw["variance"] = True                                                 # the pair plan that keeps the variance features
+    fields = TJ.step_fields(dc, backbone, z_t.shape, dc.cfg_w, variance=kind.variance)
     for i in range(n + 1):
         t = min(i, n - 1)
         pair = backbone.forward_pair(z_t, g.label[t].to(z_t.device).unsqueeze(0), cond, null, **kw)

@@ -145,7 +145,8 @@ def run(dc, x, classes, from_t, against, rng, seed, pixel_space, start="noise", 
     if hip:
         # the walk's refusals before the first draw here; its sessions open at its first pass, after the inversions' (the same slots)
         g = TJ.grid(dc, from_t, 0.0)
-        walk = TJ.Walk(dc, dc.ema.ema_model, x, cl, g, dc.cfg_w)
+        kind = None if sampler is not None else AN.step_kind(dc, g, dc.cfg_w)
+        walk = TJ.Walk(dc, dc.ema.ema_model, x, cl, g, dc.cfg_w, variance=kind is not None and kind.variance)
         noise = TJ.NoiseSource(x, rng, seed, len(g.lam))
         if z0 is None:
             z0 = S.initial_latent(dc, x, from_t, noise)
@@ -154,7 +155,7 @@ def run(dc, x, classes, from_t, against, rng, seed, pixel_space, start="noise", 
         else:
             noise.like = z0                                              # the steps draw in the start's dtype, as `sample` does
             draw = nmaps.__getitem__ if nmaps is not None else lambda i: noise(i + 1)
-            samples = AN.decode_hip(AN.step_kind(dc, g, dc.cfg_w), walk, z0, draw)
+            samples = AN.decode_hip(kind, walk, z0, draw)
     else:
         z0 = S.initial_latent(dc, x, from_t) if z0 is None else z0
         samples = run_foreign(dc, z0, cl, from_t, nmaps) if sampler is None else run_foreign_solver(dc, z0, cl, from_t, sampler)

@@ -265,25 +265,34 @@ extern "C" int dc_eps_mse(const dc_eps_mse_params* p, dc_stream stream) {
 struct StepArgs {
   const float* z; const float* pred; float* out;
   int C, HW, W, ld, patch, v_param, n;
+  int fs;                 // feature stride of a patch's pixels in pred: C (eps alone), or the learned-range step's fstride
   float w, one_plus_w, alpha_t, sigma_t;
 };
 
-// Element i = (b, r) of z: the indexing of the prediction pair, the guidance mix and the data prediction (clipped when `clip`) -> x;
-// zt = z[i].  One body for every step kernel, so the mean a noise map is solved against is the mean the step adds it to and the
-// solvers' x is the ancestral sampler's.
-__device__ __forceinline__ float step_xpred(const StepArgs& a, size_t i, size_t CHW, size_t rows, bool clip, int& b, size_t& r, float& zt) {
-#pragma clang fp contract(off)
+// Element i = (b, r) of z -> its feature in image b's conditional rows of the prediction pair; the null rows' lies rows * ld behind
+// it, the learned-range step's variance feature C behind it.
+__device__ __forceinline__ const float* step_pair(const StepArgs& a, size_t i, size_t CHW, size_t rows, int& b, size_t& r) {
   b = (int)(i / CHW);
   r = i - (size_t)b * CHW;
   const int c = (int)(r / a.HW), p = (int)(r - (size_t)c * a.HW);
   size_t pi;
   if (a.patch > 1) {
     const int y = p / a.W, xw = p - y * a.W, pp = a.patch;
-    pi = ((size_t)(y / pp) * (a.W / pp) + xw / pp) * a.ld + (size_t)((y % pp) * pp + xw % pp) * a.C + c;
+    pi = ((size_t)(y / pp) * (a.W / pp) + xw / pp) * a.ld + (size_t)((y % pp) * pp + xw % pp) * a.fs + c;
   } else {
     pi = (size_t)p * a.ld + c;
   }
-  const float* pair = a.pred + (size_t)(2 * b) * rows * a.ld + pi;               // image b's conditional rows, then its null rows
+  return a.pred + (size_t)(2 * b) * rows * a.ld + pi;                             // image b's conditional rows, then its null rows
+}
+
+// Element i = (b, r) of z: the indexing of the prediction pair, the guidance mix and the data prediction (clipped when `clip`) -> x;
+// zt = z[i].  One body for every step kernel, so the mean a noise map is solved against is the mean the step adds it to and the
+// solvers' x is the ancestral sampler's.  pair: the element's conditional feature, for a kernel that reads more behind it.
+__device__ __forceinline__ float step_xpred(const StepArgs& a, size_t i, size_t CHW, size_t rows, bool clip, int& b, size_t& r, float& zt,
+                                            const float** pair_out = nullptr) {
+#pragma clang fp contract(off)
+  const float* pair = step_pair(a, i, CHW, rows, b, r);
+  if (pair_out) *pair_out = pair;
   const float pc = pair[0], pu = pair[rows * a.ld];
   zt = a.z[i];
   const float pr = a.one_plus_w * pc - a.w * pu;                                 // pred = (1 + w) * pred - w * u_pred
@@ -299,7 +308,8 @@ static int step_args(const char* who, const P* p, StepArgs& a, unsigned& grid) {
   const int pp = p->patch > 1 ? p->patch : 1;
   DC_REQUIRE(p->n > 0 && p->C > 0 && p->H > 0 && p->W > 0 && p->ld >= p->C * pp * pp, DC_ERR_SHAPE, "%s: extents", who);
   DC_REQUIRE(p->H % pp == 0 && p->W % pp == 0, DC_ERR_SHAPE, "%s: patch=%d does not tile %dx%d", who, pp, p->H, p->W);
-  a = StepArgs{p->z, p->pred, p->out, p->C, p->H * p->W, p->W, p->ld, pp, p->v_param, p->n, p->w, p->one_plus_w, p->alpha_t, p->sigma_t};
+  a = StepArgs{p->z, p->pred, p->out, p->C, p->H * p->W, p->W, p->ld, pp, p->v_param, p->n, p->C, p->w, p->one_plus_w, p->alpha_t,
+               p->sigma_t};
   const size_t total = (size_t)p->n * p->C * a.HW;
   grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
   return DC_OK;
@@ -310,16 +320,37 @@ struct DdpmArgs {
   const float* noise;
   float alpha_s, c, sd;
   int noise_div;          // trajectory b adds noise row b / noise_div (dc_ddpm_step: 1, a row per trajectory)
+  float k1, k2, log_hi, log_lo;      // DC_STEP_LEARNED_RANGE only (the fixed instance reads none of them)
 };
 
-// The posterior mean of element i on the clipped data prediction.
-__device__ __forceinline__ float ddpm_mean(const DdpmArgs& a, size_t i, size_t CHW, size_t rows, int& b, size_t& r) {
+// The learned-range deviation of one element from its variance feature vc (include/dcamd.h dc_ddpm_step_shared): the step and its
+// noise map call this one function, so the map divides by the bits the step multiplies with.
+__device__ __forceinline__ float learned_sde(float vc, float log_hi, float log_lo) {
 #pragma clang fp contract(off)
-  float zt;
-  const float xp = step_xpred(a.s, i, CHW, rows, true, b, r, zt);
-  return a.alpha_s * (zt * (1.f - a.c) / a.s.alpha_t + a.c * xp);
+  const float fr = 0.5f * vc + 0.5f;
+  return expf(0.5f * (fr * log_hi + (1.f - fr) * log_lo));
 }
 
+// Mean and deviation of element i.  DC_STEP_FIXED: the posterior mean on the clipped data prediction, sde = sd.
+// DC_STEP_LEARNED_RANGE: mu = k1 z + k2 x on the unclipped one (solver_step_kernel's first-order update), sde from the conditional
+// row's variance feature, C behind its eps feature.
+template <int MODE>
+__device__ __forceinline__ float ddpm_mean(const DdpmArgs& a, size_t i, size_t CHW, size_t rows, int& b, size_t& r, float& sde) {
+#pragma clang fp contract(off)
+  float zt;
+  if constexpr (MODE == DC_STEP_LEARNED_RANGE) {
+    const float* pair;
+    const float xp = step_xpred(a.s, i, CHW, rows, false, b, r, zt, &pair);
+    sde = learned_sde(pair[a.s.C], a.log_hi, a.log_lo);
+    return a.k1 * zt + a.k2 * xp;
+  } else {
+    const float xp = step_xpred(a.s, i, CHW, rows, true, b, r, zt);
+    sde = a.sd;
+    return a.alpha_s * (zt * (1.f - a.c) / a.s.alpha_t + a.c * xp);
+  }
+}
+
+template <int MODE>
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
 #pragma clang fp contract(off)
   const size_t CHW = (size_t)a.s.C * a.s.HW, total = CHW * a.s.n;
@@ -327,10 +358,13 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     int b;
     size_t r;
-    const float mu = ddpm_mean(a, i, CHW, rows, b, r);
+    float sde;
+    const float mu = ddpm_mean<MODE>(a, i, CHW, rows, b, r, sde);
     if (a.noise) {
       const size_t ni = a.noise_div == 1 ? i : (size_t)(b / a.noise_div) * CHW + r;
-      a.s.out[i] = mu + a.noise[ni] * a.sd;
+      a.s.out[i] = mu + a.noise[ni] * sde;
+    } else if constexpr (MODE == DC_STEP_LEARNED_RANGE) {
+      a.s.out[i] = mu;                                                           // last pass: the mean, nothing is clipped
     } else {
       a.s.out[i] = fminf(fmaxf(mu, -1.f), 1.f);                                  // last pass: the clipped mean
     }
@@ -339,6 +373,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const DdpmArgs a) {
 
 // The noise map of the same step (include/dcamd.h dc_ddpm_noise_map): out = (x_next - mu) / sd on ddpm_step_kernel's mean.  out may be
 // x_next's buffer: a thread reads its element before it writes it, and no other thread touches that element.
+template <int MODE>
 __global__ __launch_bounds__(256) void ddpm_noise_map_kernel(const DdpmArgs a, const float* x_next) {
 #pragma clang fp contract(off)
   const size_t CHW = (size_t)a.s.C * a.s.HW, total = CHW * a.s.n;
@@ -346,9 +381,39 @@ __global__ __launch_bounds__(256) void ddpm_noise_map_kernel(const DdpmArgs a, c
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     int b;
     size_t r;
-    const float mu = ddpm_mean(a, i, CHW, rows, b, r);
-    a.s.out[i] = (x_next[i] - mu) / a.sd;
+    float sde;
+    const float mu = ddpm_mean<MODE>(a, i, CHW, rows, b, r, sde);
+    a.s.out[i] = (x_next[i] - mu) / sde;
   }
+}
+
+// The mode block a caller puts behind dc_ddpm_step_shared_params / dc_ddpm_noise_map_params when `v_param` carries DC_STEP_MODE_BLOCK
+// (dcamd.h); without the flag nothing behind the struct is read.  dc_ddpm_step_params has no such flag: the fixed step, v_param as ever.
+struct StepMode { int32_t mode, fstride; float k1, k2, log_hi, log_lo; };
+static StepMode step_mode(const dc_ddpm_step_params*, bool& flagged) { flagged = false; return StepMode{DC_STEP_FIXED, 0, 0.f, 0.f, 0.f, 0.f}; }
+template <typename P>
+static StepMode step_mode(const P* p, bool& flagged) {
+  static_assert(sizeof(P) % 8 == 0, "the mode block lies at sizeof of the struct");
+  flagged = (p->v_param & DC_STEP_MODE_BLOCK) != 0;
+  if (!flagged) return StepMode{DC_STEP_FIXED, 0, 0.f, 0.f, 0.f, 0.f};
+  return *reinterpret_cast<const StepMode*>(reinterpret_cast<const char*>(p) + sizeof(P));
+}
+
+// The mode's checks (after step_args) and kernel arguments.  DC_STEP_FIXED reads nothing of the block but `mode`.
+static int ddpm_mode_args(const char* who, const StepMode& m, bool flagged, DdpmArgs& a) {
+  if (flagged) a.s.v_param &= ~DC_STEP_MODE_BLOCK;                                // the parametrisation next to the flag
+  DC_REQUIRE(m.mode == DC_STEP_FIXED || m.mode == DC_STEP_LEARNED_RANGE, DC_ERR_ARG,
+             "%s: mode=%d (DC_STEP_FIXED = 0, DC_STEP_LEARNED_RANGE = 1)", who, m.mode);
+  a.k1 = a.k2 = a.log_hi = a.log_lo = 0.f;
+  if (m.mode == DC_STEP_FIXED) return DC_OK;
+  const long long pp = a.s.patch, C2 = 2ll * a.s.C, need = a.s.patch > 1 ? pp * pp * m.fstride : C2;
+  DC_REQUIRE(m.fstride >= C2 && a.s.ld >= need, DC_ERR_SHAPE,
+             "%s: the learned-range step needs fstride=%d >= 2C=%lld and ld=%d >= %lld (2C features per pixel)", who, m.fstride, C2, a.s.ld, need);
+  const float inf = __builtin_huge_valf();
+  DC_REQUIRE(m.log_lo > -inf && m.log_lo <= m.log_hi && m.log_hi <= 0.f, DC_ERR_ARG,      // NaN fails the comparisons
+             "%s: log_lo=%g and log_hi=%g must be finite with log_lo <= log_hi <= 0", who, (double)m.log_lo, (double)m.log_hi);
+  a.s.fs = m.fstride, a.k1 = m.k1, a.k2 = m.k2, a.log_hi = m.log_hi, a.log_lo = m.log_lo;
+  return DC_OK;
 }
 
 template <typename P>
@@ -357,8 +422,13 @@ static int ddpm_step_entry(const char* who, const P* p, int noise_div, dc_stream
   unsigned grid;
   if (const int rc = step_args(who, p, a.s, grid)) return rc;
   DC_REQUIRE(noise_div >= 1 && p->n % noise_div == 0, DC_ERR_ARG, "%s: noise_div=%d must be >= 1 and divide n=%d", who, noise_div, p->n);
+  bool flagged;
+  const StepMode m = step_mode(p, flagged);
+  if (const int rc = ddpm_mode_args(who, m, flagged, a)) return rc;
   a.noise = p->noise, a.alpha_s = p->alpha_s, a.c = p->c, a.sd = p->sd, a.noise_div = noise_div;
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (m.mode == DC_STEP_LEARNED_RANGE) hipLaunchKernelGGL(ddpm_step_kernel<DC_STEP_LEARNED_RANGE>, dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(ddpm_step_kernel<DC_STEP_FIXED>, dim3(grid), dim3(256), 0, s, a);
   return dc_check_launch(who);
 }
 
@@ -373,10 +443,18 @@ extern "C" int dc_ddpm_noise_map(const dc_ddpm_noise_map_params* p, dc_stream st
   unsigned grid;
   if (const int rc = step_args("dc_ddpm_noise_map", p, a.s, grid)) return rc;
   DC_REQUIRE(p->x_next, DC_ERR_ARG, "dc_ddpm_noise_map: null pointer");
-  DC_REQUIRE(p->sd > 0.f && p->sd < __builtin_huge_valf(), DC_ERR_ARG,      // NaN fails both comparisons
-             "dc_ddpm_noise_map: sd=%g must be finite and > 0", (double)p->sd);
+  bool flagged;
+  const StepMode m = step_mode(p, flagged);
+  if (const int rc = ddpm_mode_args("dc_ddpm_noise_map", m, flagged, a)) return rc;
+  if (m.mode == DC_STEP_FIXED)
+    DC_REQUIRE(p->sd > 0.f && p->sd < __builtin_huge_valf(), DC_ERR_ARG,    // NaN fails both comparisons
+               "dc_ddpm_noise_map: sd=%g must be finite and > 0", (double)p->sd);
   a.noise = nullptr, a.alpha_s = p->alpha_s, a.c = p->c, a.sd = p->sd, a.noise_div = 1;
-  hipLaunchKernelGGL(ddpm_noise_map_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, p->x_next);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (m.mode == DC_STEP_LEARNED_RANGE)
+    hipLaunchKernelGGL(ddpm_noise_map_kernel<DC_STEP_LEARNED_RANGE>, dim3(grid), dim3(256), 0, s, a, p->x_next);
+  else
+    hipLaunchKernelGGL(ddpm_noise_map_kernel<DC_STEP_FIXED>, dim3(grid), dim3(256), 0, s, a, p->x_next);
   return dc_check_launch("dc_ddpm_noise_map");
 }
 

@@ -59,7 +59,8 @@ def invert(dc, x, text, from_t, guidance, rng, seed, name="text"):
                          f"config.ddpm_invert_max_bytes = {cap} (fewer sampling_steps, a smaller batch, or raise the key)")
     kind = AN.step_kind(dc, TJ.grid(dc, from_t, 0.0), w)
     if hip:
-        walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), kind.g, w, who="invert_ddpm", noun="fused noise map")
+        walk = TJ.Walk(dc, dc.ema.ema_model, x, lab.view(-1, 1), kind.g, w, who="invert_ddpm", noun="fused noise map",
+                       variance=kind.variance)
         start, noise = AN.noise_maps_hip(kind, walk, x, TJ.NoiseSource(x, rng, seed, n + 1))
     else:
         start, noise = AN.noise_maps_eager(kind, x, lab)

@@ -95,6 +95,10 @@ ancestral sampler) makes `sample` and `counterfactual` deterministic after their
 `.invert_ddpm(x, text, from_t)` is the edit-friendly DDPM inversion — a start and one noise map per step under which the ancestral sampler
 decodes the image back exactly — and `counterfactual(..., start="ddpm_invert")` decodes every class from it (ddpm_invert.py;
 `ddpm_invert_max_bytes` caps the maps' buffer, default 2 GiB).
+`config.variance` (None | "fixed" | "learned"; read once at construction) chooses the deviation of an ancestral step on the discrete
+grid: "learned" takes it, per element, from the variance channels a model with out_channels = 2 * in_channels predicts next to eps
+(a published DiT; diffusers' variance_type = "learned_range") in `sample`, `counterfactual` and `invert_ddpm`; `classify` and `invert`
+do not read it.  None / "fixed": the fixed posterior variance, everything as before, bit for bit.
 """
 import math
 import os
@@ -216,6 +220,7 @@ class DiffusionClassifier(nn.Module):
         self.image_d = self.config.image_size
         self.cfg_w = self.config.cfg_w
         assert isinstance(backbone, nn.Module), "Model must be an instance of torch.nn.Module."
+        self.variance = self._variance_of(backbone)      # None | "learned": which ancestral step kind generation takes (ancestral.py)
         self.model = backbone
         self.ema = EMA(self.model, beta=config.ema_beta, update_after_step=config.ema_warmup,
                        update_every=config.ema_update_freq)
@@ -526,6 +531,7 @@ class DiffusionClassifier(nn.Module):
             raise ValueError(f"steps_offset must be an int, got {off!r}")
         self.steps_offset = off                                                  # added to every 'leading' step of the generation grid
         self.ddpm_logsnr = torch.log(abar / (1.0 - abar)).to(torch.float32)      # plain attribute: host data, never part of a checkpoint
+        self.abar = abar                                 # the fp64 table itself, likewise: the learned-range step's two log variances
 
     def ddpm_step(self, t):
         """t in [0, 1] as the reference draws it -> the DDPM step k = min(floor(t N), N - 1) (int64; the product in fp64)."""
@@ -556,6 +562,36 @@ class DiffusionClassifier(nn.Module):
             raise NotImplementedError(f"{what} under schedule={self.config.schedule!r} needs config.timestep_spacing = 'trailing' | 'leading': "
                                       "how sampling_steps are laid on the discrete DDPM grid is the caller's choice (unset: classify only)")
         TJ.discrete_steps(self, from_t)
+
+    def _variance_of(self, backbone):
+        """config.variance (additive, read once here): None / "fixed" -> None, every ancestral step adds the fixed posterior deviation
+        as ever; "learned" -> "learned", the step takes its deviation from the variance channels the backbone predicts next to eps
+        (diffusers' variance_type = "learned_range", the improved-DDPM sampler a published DiT is trained for; ancestral.LearnedRange).
+        "learned" needs a discrete schedule, a backbone with out_channels == 2 * in_channels and the ancestral sampler: ValueError
+        otherwise, as for any other value."""
+        v = getattr(self.config, "variance", None)
+        if v is None or v == "fixed":
+            return None
+        if v != "learned":
+            raise ValueError(f"config.variance must be None, 'fixed' or 'learned', got {v!r}")
+        if not self.discrete:
+            raise ValueError(f"config.variance = 'learned' belongs to the discrete DDPM grid (schedule='scaled_linear' / 'ddpm_linear'): "
+                             f"its two bounds are log beta and the log posterior variance of integer steps, which "
+                             f"schedule={self.config.schedule!r} does not have")
+        ic, oc = getattr(backbone.config, "in_channels", None), getattr(backbone.config, "out_channels", None)
+        if ic is None or oc is None or oc != 2 * ic:
+            raise ValueError(f"config.variance = 'learned' needs a backbone that predicts the variance next to eps: "
+                             f"out_channels == 2 * in_channels, got out_channels = {oc} and in_channels = {ic}")
+        self._refuse_learned_under_solver()
+        return v
+
+    def _refuse_learned_under_solver(self):
+        """config.sampler is read per call, so `sample` and `counterfactual` ask again: a deterministic sampler adds no noise, the
+        learned variance would do nothing there."""
+        sampler = S.sampler_of(self.config)
+        if sampler is not None:
+            raise ValueError(f"config.variance = 'learned' needs the ancestral sampler (config.sampler unset or 'ddpm'), got "
+                             f"config.sampler = {sampler!r}: a deterministic sampler adds no noise, the key would do nothing there")
 
     @torch.no_grad()
     def encode_latents(self, x):
@@ -605,7 +641,8 @@ class DiffusionClassifier(nn.Module):
         pixel_weight (additive): a float tensor [BS, H, W] or [BS, 1, H, W] on the model's grid (x's own after the VAE encoder: the latent
         grid under config.vae_path, the wavelet grid of a DWT model, DiT's un-patchified [H, W]) that weights every pixel's term in the
         errors and the evidence maps (loss.py); a 0/1 mask scores a region.  Its values are data (NaN propagates and is counted by the
-        posterior's `invalid`); under grid sharding every rank passes the identical tensor."""
+        posterior's `invalid`); under grid sharding every rank passes the identical tensor.
+        config.variance is not read: scoring compares eps alone."""
         if self.vae is not None and not latents:
             x = self.encode_latents(x)
         cfg = self.config
@@ -928,9 +965,16 @@ class DiffusionClassifier(nn.Module):
         config.vae_path): the result is then `decode_latents` of those latents, images [BS, out_channels, f H, f W].
         schedule='scaled_linear' (needs config.timestep_spacing): the grid is the integer steps of `trajectory.discrete_steps`, x is
         diffused to its first point k_0, the backbone is fed float(k_i), and nothing is clipped — the ancestral mean is a z + b x
-        (ancestral.py), the last deterministic pass returns the data prediction as it is."""
+        (ancestral.py), the last deterministic pass returns the data prediction as it is.
+        config.variance = "learned" (additive; a discrete schedule, out_channels == 2 * in_channels, the ancestral sampler): every pass but
+        the last adds noise * exp(0.5 (fr log beta + (1 - fr) log beta~)) per element, fr = (v + 1) / 2 from the variance channels of the
+        CONDITIONAL prediction — diffusers' "learned_range" — in place of the fixed posterior deviation; the mean is unchanged.  HIP DiT:
+        one pair plan that keeps the variance features and one `dc_ddpm_step_shared` in DC_STEP_LEARNED_RANGE per pass; a foreign
+        nn.Module: the same expressions in torch on its 2C-channel outputs.  Under a deterministic config.sampler ValueError."""
         self._refuse_sdxl_generation("sample")
         self._refuse_discrete("sample", from_t)
+        if self.variance is not None:
+            self._refuse_learned_under_solver()
         TJ.check_decode(self, decode)
         sampler = S.sampler_of(self.config)
         z = AN.sample(self, x, text, from_t) if sampler is None else S.sample(self, x, text, from_t, sampler)
@@ -982,9 +1026,15 @@ class DiffusionClassifier(nn.Module):
                        holds no reconstruction error; class ids: the base is that class's decoded trajectory.  False: nothing changes
         schedule='scaled_linear' (needs config.timestep_spacing): all of the above on the integer grid of `sample`, unclipped — the
         ancestral passes are one unclamped `dc_solver_step` (the posterior mean) and one torch add of the shared noise per pass and
-        chunk (ancestral.py)"""
+        chunk (ancestral.py)
+        config.variance = "learned" (see `sample`): the ancestral passes add the learned deviation — the K trajectories of an image share
+        their noise draw, each scales it by its own per-element deviation (its own class's variance channels); one `dc_ddpm_step_shared`
+        in DC_STEP_LEARNED_RANGE per pass and chunk, starts "noise" and "ddpm_invert", `against` and decode=True as ever; start="invert"
+        needs a deterministic sampler, which the key refuses (ValueError)"""
         self._refuse_sdxl_generation("counterfactual")
         self._refuse_discrete("counterfactual", from_t)
+        if self.variance is not None:
+            self._refuse_learned_under_solver()
         return CF.run(self, x, classes, from_t, against, rng, seed, pixel_space, start=start, invert_class=invert_class, decode=decode)
 
     @torch.no_grad()
@@ -999,7 +1049,8 @@ class DiffusionClassifier(nn.Module):
         per step and chunk; a foreign nn.Module takes the eager form (solver.py).
         With config.vae_path, x and the result are LATENTS (`encode_latents` / `decode_latents`).
         schedule='scaled_linear' (needs config.timestep_spacing): the grid is `sample`'s integer steps from to_t in reverse, so inversion
-        and decode visit the same points; the data prediction is not clipped."""
+        and decode visit the same points; the data prediction is not clipped.
+        config.variance is not read: DDIM inversion adds no noise (a HIP DiT runs its eps-only pair plans here as ever)."""
         self._refuse_sdxl_generation("invert")
         self._refuse_discrete("invert", to_t)
         return S.invert(self, x, text, to_t, guidance)
@@ -1025,7 +1076,10 @@ class DiffusionClassifier(nn.Module):
         eager form (ddpm_invert.py).  Needs the ancestral sampler only when decoded: `counterfactual(..., start="ddpm_invert")`.
         With config.vae_path, x, start and noise are LATENTS (`encode_latents` / `decode_latents`).
         schedule='scaled_linear' (needs config.timestep_spacing): the same on `sample`'s integer grid with the unclipped mean
-        mu_i = a z + b x — one unclamped `dc_solver_step` per pass and chunk, the map (x_{i+1} - mu_i) / sd_i in torch on that mean."""
+        mu_i = a z + b x — one unclamped `dc_solver_step` per pass and chunk, the map (x_{i+1} - mu_i) / sd_i in torch on that mean.
+        config.variance = "learned" (see `sample`): sd_i is per element, the learned deviation at (x_i, text) — noise[i] =
+        (x_{i+1} - mu_i) / sde_i, one `dc_ddpm_noise_map` in DC_STEP_LEARNED_RANGE per pass and chunk, by the device code the step
+        multiplies with, so the decode under the same class lands on x_{i+1} again."""
         self._refuse_sdxl_generation("invert_ddpm")
         self._refuse_discrete("invert_ddpm", from_t)
         return DI.invert(self, x, text, from_t, guidance, rng, seed)

@@ -65,7 +65,9 @@ class DiTPlan(Plan):
     eps_only (always with a score): the prediction feeds a kernel that indexes it with the latent's channel count C as the feature
     stride (the scoring tail, the step kernels behind forward_pair / a pair session), so it must hold eps alone:
     pred [U, g, g, p*p*C].  With out_channels == C that is the plan as ever; with out_channels == 2 C (learned variance) proj_out_2
-    runs on its eps rows only (DiTWeights "po2e"); any other width is refused (packing.eps_rows)."""
+    runs on its eps rows only (DiTWeights "po2e"); any other width is refused (packing.eps_rows).
+    Without eps_only the full proj_out_2 runs, pred [U, g, g, p*p*out_ch]: `forward`'s plan, and the pair plans of `variance=True`,
+    whose step kernel (dc_ddpm_step_shared / dc_ddpm_noise_map in DC_STEP_LEARNED_RANGE) is told out_ch as the feature stride."""
 
     def __init__(self, model, weights, n_bj, n_cls, n_ctx, *, score=None, device=None, share_trunk=True, eps_only=False):
         cfg = model.config

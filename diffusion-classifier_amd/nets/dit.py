@@ -103,6 +103,7 @@ class DiT(_HipBackbone):
     weights_class, im2col = ED.DiTWeights, 2                   # `patch` is the instance's patch_size
 
     eps_rows_only = True       # trajectory.step_fields: forward_pair / a pair session hand out eps alone, at feature stride in_channels
+    variance_pair_plans = True      # ... and with variance=True all out_channels, at feature stride out_channels (the learned-range step)
 
     def make_plan(self, n_bj, n_cls, n_ctx, device, score=None, share_trunk=None, eps_only=False):
         """eps_only (implied by a score): the plan's prediction holds eps alone, [U, g, g, p*p*in_channels] — with learned-variance
@@ -116,37 +117,50 @@ class DiT(_HipBackbone):
     def _label_plan(self, kind, N, dev, labels):
         """What `forward`, `forward_pair` and `pair_session` share: the plan cached under kind + (N, device, dtype) (built on first use)
         with the labels — one int tensor of N per unit of an image, unit n_cls * b + u = labels[u][b] — copied into its `ctx_of_unit`.
-        `forward`'s plan predicts all out_channels, the pair plans eps alone."""
+        `forward`'s plan predicts all out_channels, the pair plans eps alone — but the "pair_var" / "pair_session_var" kinds of
+        `variance=True`, plans of their own that run the full proj_out_2."""
         key = kind + (N, str(dev), self.compute_dtype)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = self.make_plan(N, len(labels), None, dev, eps_only=kind[0] != "fwd")
+            plan = self._plans[key] = self.make_plan(N, len(labels), None, dev, eps_only=kind[0] in ("pair", "pair_session"))
         plan.ctx_of_unit.copy_(torch.stack([lab.reshape(-1) for lab in labels], dim=1).reshape(-1).to(dev, torch.int32))
         return plan
 
+    def _pair_kind(self, kind, variance):
+        """The plan-key kind of a pair plan: `kind`, or kind + "_var" for the plans that keep the variance features."""
+        if not variance:
+            return kind
+        C, oc = self.config.in_channels, self.config.out_channels
+        if oc != 2 * C:
+            raise L.DcamdError(f"variance=True needs learned-variance outputs, out_channels == 2 * in_channels (got {oc} vs 2 * {C} = {2 * C})")
+        return kind + "_var"
+
     @torch.no_grad()
-    def forward_pair(self, x, noise_labels, cond, null):
+    def forward_pair(self, x, noise_labels, cond, null, variance=False):
         """Classifier-free-guidance pair as ONE batch-2 plan launch: unit 2b = image b under label `cond[b]`, unit 2b+1 under the
         null label `null[b]` (reference `sample`, :255-266, calls the backbone twice per step).  Returns the plan's patch-major
         projection [2N, H/p, W/p, p*p*in_channels] fp32, eps alone — a learned variance (out_channels == 2 * in_channels) is dropped, as
-        diffusers' DiTPipeline drops it (the layout `dc_ddpm_step` reads with patch = p) — a view the next call overwrites."""
+        the fixed-variance samplers never read it (the layout `dc_ddpm_step` reads with patch = p) — a view the next call overwrites.
+        variance=True (out_channels == 2 * in_channels only): a plan of its own with the full proj_out_2, the prediction
+        [2N, H/p, W/p, p*p*out_channels] — per pixel eps then the variance interpolation, feature stride out_channels, the layout
+        `dc_ddpm_step_shared` reads in DC_STEP_LEARNED_RANGE."""
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError("DiT.forward_pair needs CUDA/HIP tensors (no CPU fallback)")
-        plan = self._label_plan(("pair",), x.shape[0], x.device, (cond, null))
+        plan = self._label_plan((self._pair_kind("pair", variance),), x.shape[0], x.device, (cond, null))
         self._feed(plan, x, noise_labels)
         plan.run()
         return plan.pred_view()
 
     @torch.no_grad()
-    def pair_session(self, N, device, cond, null, slot=0):
+    def pair_session(self, N, device, cond, null, slot=0, variance=False):
         """The once-per-call half of `forward_pair` for N images on `device`: the label pairs copied into the `ctx_of_unit` of a plan that
         belongs to `slot`.  Returns a `PairSession` (nets/unet.py) whose `step(x, lam)` gives what `forward_pair(x, lam, cond, null)`
-        gives."""
+        gives.  variance: as `forward_pair`'s, a plan of its own per slot."""
         L.require_gpu()
         if cond.numel() != N or null.numel() != N:
             raise L.DcamdError(f"a pair session of {N} images needs {N} labels per side, got {cond.numel()} and {null.numel()}")
-        return PairSession(self, self._label_plan(("pair_session", slot), N, torch.device(device), (cond, null)), N)
+        return PairSession(self, self._label_plan((self._pair_kind("pair_session", variance), slot), N, torch.device(device), (cond, null)), N)
 
     @torch.no_grad()
     def forward(self, x, noise_labels, encoder_hidden_states=None):

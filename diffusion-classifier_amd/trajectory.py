@@ -6,7 +6,9 @@ call over a HIP backbone.
 The loops themselves live with their arithmetic and none takes a mode flag: the solver walk in solver.py (`run_walk`: the deterministic
 decode and, on the upward grid, DDIM inversion) and the ancestral loops in ancestral.py (decode, `sample`'s pair loop, noise maps; each
 once in eager torch and once on HIP).  A HIP loop is `for pass: for chunk in walk.run(t, z): one step`.  What the cosine schedules and
-the discrete grid do differently in an ancestral step is an `ancestral.step_kind`, chosen once per call; the loops never ask which.
+the discrete grid do differently in an ancestral step — and a learned variance from a fixed one — is an `ancestral.step_kind`, chosen
+once per call; the loops never ask which.  A kind that reads the variance channels says so (`kind.variance`), and the `Walk` then opens
+pair sessions whose plans keep them.
 """
 import ctypes as C
 from collections import namedtuple
@@ -162,18 +164,29 @@ def guided_pair(dc, z, label, cond, null, lens=None):
     return dc.ema(z, label, encoder_hidden_states=cond, **kc), dc.ema(z, label, encoder_hidden_states=null, **kn)
 
 
-def step_fields(dc, backbone, shape, w, noun="fused sampler step"):
+def step_fields(dc, backbone, shape, w, noun="fused sampler step", variance=False):
     """The fields every step struct shares but n and ld, for latents of `shape` [*, C, H, W] under guidance weight w.  `patch` is the
     backbone's; the kernels index the prediction with z's channel count as the feature stride, so the prediction must hold C channels:
     out_channels == C, or a backbone whose pair plans project the eps rows only (`eps_rows_only`: DiT) with out_channels == 2 C — the
-    learned variance is dropped, as diffusers' DiTPipeline drops it."""
+    learned variance is then not computed at all: these kinds step with the fixed posterior variance.
+    variance (the step kind's: `ancestral.LearnedRange`): the kernels read the variance features too, from pair plans that keep the full
+    projection (`variance_pair_plans`: DiT) — the fields gain the mode block's mode = DC_STEP_LEARNED_RANGE and fstride =
+    out_channels, which must be 2 C, and `v_param` the flag that announces the block (DC_STEP_MODE_BLOCK)."""
     _, Cc, H, W = shape
     oc = int(getattr(backbone.config, "out_channels", Cc) or Cc)
+    w = float(w)
+    f = dict(C=Cc, H=H, W=W, patch=int(getattr(backbone.config, "patch_size", 0) or 0), v_param=int(dc.pred_param == 'v'),
+             w=w, one_plus_w=float(1.0 + w))
+    if variance:
+        if oc != 2 * Cc:
+            raise L.DcamdError(f"{noun} with a learned variance needs out_channels == 2 * in_channels (got {oc} vs 2 * {Cc} = {2 * Cc})")
+        if not getattr(backbone, "variance_pair_plans", False):
+            raise L.DcamdError(f"{noun} with a learned variance needs a backbone whose pair plans keep the variance features (DiT); "
+                               f"{type(backbone).__name__} has none")
+        return dict(f, v_param=f["v_param"] | L.STEP_MODE_BLOCK, mode=L.STEP_LEARNED_RANGE, fstride=oc)
     if oc != Cc and not (oc == 2 * Cc and getattr(backbone, "eps_rows_only", False)):
         raise L.DcamdError(f"{noun} needs out_channels == in_channels (got {oc} vs {Cc})")
-    w = float(w)
-    return dict(C=Cc, H=H, W=W, patch=int(getattr(backbone.config, "patch_size", 0) or 0), v_param=int(dc.pred_param == 'v'),
-                w=w, one_plus_w=float(1.0 + w))
+    return f
 
 
 class NoiseSource:
@@ -206,9 +219,10 @@ def image_chunks(BS, K, units):
     return [(b0, min(BS, b0 + per)) for b0 in range(0, BS, per)]
 
 
-def pair_sessions(dc, backbone, cl, chunks, dev):
+def pair_sessions(dc, backbone, cl, chunks, dev, variance=False):
     """One pair session per chunk (b0, b1) of images for the labels cl [BS, K]: unit pair b * K + k is class token cl[b, k] || null
-    token; contexts, lengths and the context plan once per call and chunk, session ci in slot ci."""
+    token; contexts, lengths and the context plan once per call and chunk, session ci in slot ci.
+    variance: the sessions' plans keep the variance features (the backbone's `pair_session(..., variance=True)`)."""
     lab_dev = label_device(dc, dev)
     ln = dc.encoder.lengths.cpu() if dc._ragged_table() else None
     sessions = []
@@ -217,6 +231,8 @@ def pair_sessions(dc, backbone, cl, chunks, dev):
         nul = torch.full_like(lab, dc.null_token)
         cond, null = dc.encode_text_prompt(lab.to(lab_dev)).to(dev), dc.encode_text_prompt(nul.to(lab_dev)).to(dev)
         kw = dict(cond_lengths=ln[lab], null_lengths=ln[nul]) if ln is not None else {}
+        if variance:
+            kw["variance"] = True
         sessions.append(backbone.pair_session(lab.numel(), dev, cond, null, slot=ci, **kw))
     return sessions
 
@@ -227,15 +243,16 @@ class Walk:
     one pair session per chunk (the prompts projected once), lambda and the backbone's time input of the `Grid` on the device, the
     step structs' common fields
     — and walked step-major, chunk-minor by the caller's loop; nothing is copied to the host inside it.
-    who / noun: the caller's words in the two refusals."""
+    who / noun: the caller's words in the two refusals.  variance: the step kind's `variance` — the sessions' plans then keep the
+    variance features and the step fields carry mode and fstride (`step_fields`)."""
 
-    def __init__(self, dc, backbone, x, cl, grid, w, who="counterfactual", noun="fused sampler step"):
+    def __init__(self, dc, backbone, x, cl, grid, w, who="counterfactual", noun="fused sampler step", variance=False):
         L.require_gpu()
         if not x.is_cuda:
             raise L.DcamdError(f"{who} on a HIP backbone needs a CUDA/HIP tensor (as sample does; no CPU fallback)")
         self.BS, self.K = cl.shape
         self.shape = tuple(x.shape[1:])
-        self.fields = step_fields(dc, backbone, x.shape, w, noun)
+        self.fields = step_fields(dc, backbone, x.shape, w, noun, variance=variance)
         self.chunks = image_chunks(self.BS, self.K, units_per_launch(dc.config, x.shape[2], x.shape[3], 2 * self.K))
         self.lam = torch.stack([v.detach().float().reshape(()) for v in grid.lam]).to(x.device)
         # the cosine schedules feed the backbone the log-SNR itself: one tensor, as ever
@@ -243,7 +260,7 @@ class Walk:
         self.clamp = int(not dc.discrete)                                     # dc_solver_step's clamp: nothing is clipped on the discrete grid
         # opened at the first pass, behind the caller's draws and blocking host-to-device copies: the context plans then run on the
         # device while the host prepares pass 0, instead of being waited for by the next such copy
-        self.sessions, self._open = None, lambda: pair_sessions(dc, backbone, cl, self.chunks, x.device)
+        self.sessions, self._open = None, lambda: pair_sessions(dc, backbone, cl, self.chunks, x.device, variance)
 
     def buffers(self, z0):
         """(za, zb): the trajectories' latents, trajectory b * K + k starting from z0[b], and the buffer the first pass writes."""
@@ -264,6 +281,24 @@ class Walk:
             yield rows, slice(b0, b1), dict(self.fields, z=z[rows].data_ptr(), pred=pair.data_ptr(), n=(b1 - b0) * self.K, ld=pair.shape[-1])
 
 
-def launch(entry, params):
-    """One step kernel on the current stream: entry "dc_solver_step" | "dc_ddpm_step_shared" | "dc_ddpm_noise_map"."""
-    L.check(getattr(L.lib(), entry)(C.byref(params), L.stream_ptr()), entry)
+# ---- the C ABI of the step mode (include/dcamd.h DC_STEP_MODE_BLOCK) ------------------------------------------------------------------
+MODE_BLOCK = [("mode", L.i32), ("fstride", L.i32), ("k1", L.f32), ("k2", L.f32), ("log_hi", L.f32), ("log_lo", L.f32)]
+_with_mode = {}
+
+
+def mode_params(cls):
+    """L.DdpmStepSharedParams / L.DdpmNoiseMapParams -> the ctypes class of the struct WITH the mode block behind it, as the two entries
+    read it when `v_param` carries L.STEP_MODE_BLOCK: the struct's own fields, then mode, fstride, k1, k2, log_hi, log_lo at sizeof of
+    the struct.  The header declares no such struct (its structs are frozen); this flat class has the same layout, checked here."""
+    if cls not in _with_mode:
+        ext = type(cls.__name__ + "Mode", (C.Structure,), {"_fields_": list(cls._fields_) + MODE_BLOCK})
+        assert C.sizeof(cls) % 8 == 0 and ext.mode.offset == C.sizeof(cls) and C.sizeof(ext) == C.sizeof(cls) + 24, cls
+        _with_mode[cls] = ext
+    return _with_mode[cls]
+
+
+def launch(entry, params, base=None):
+    """One step kernel on the current stream: entry "dc_solver_step" | "dc_ddpm_step_shared" | "dc_ddpm_noise_map".
+    base: the entry's own struct class when `params` is that struct with the mode block behind it (`mode_params`)."""
+    ref = C.byref(params) if base is None else C.cast(C.pointer(params), C.POINTER(base))
+    L.check(getattr(L.lib(), entry)(ref, L.stream_ptr()), entry)

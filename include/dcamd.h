@@ -95,7 +95,10 @@ extern "C" {
  *  additive within 5: no symbol, struct name or op kind changed, and a caller that zero-initialises the structs gets DC_LOSS_L2, the
  *  bits it got before)
  * (the loss weights — DC_LOSS_WEIGHTED, a flag bit of `loss`, announces a weights block BEHIND the struct in the caller's memory — are
- *  additive within 5 likewise: no struct, field, symbol or op kind changed, and without the bit nothing behind the struct is read) */
+ *  additive within 5 likewise: no struct, field, symbol or op kind changed, and without the bit nothing behind the struct is read)
+ * (the learned-range step — DC_STEP_MODE_BLOCK, a flag bit of `v_param` in dc_ddpm_step_shared_params and dc_ddpm_noise_map_params,
+ *  announces a mode block BEHIND the struct in the caller's memory, with DC_STEP_* — is additive within 5 likewise: no struct, field,
+ *  symbol or op kind changed, and without the bit nothing behind the struct is read: the kernel instance and the bits as before) */
 #define DC_ABI_VERSION 5
 
 typedef void* dc_stream; /* hipStream_t */
@@ -634,7 +637,32 @@ int dc_ddpm_step(const dc_ddpm_step_params* p, dc_stream s);
  * one z_{from_t} and one noise draw per step).  z / out [n, C, H, W], pred [2n, ...] as above; trajectory u adds row u / noise_div of
  * noise [n / noise_div, C, H, W] (noise NULL: the clipped mean).  The arithmetic, its order and the kernel body are dc_ddpm_step's:
  * with noise_div = 1, or on noise repeated noise_div times, the two agree bit for bit.  noise_div < 1 or n % noise_div != 0:
- * DC_ERR_ARG. */
+ * DC_ERR_ARG.
+ *
+ * The step mode.  `v_param` may carry the flag DC_STEP_MODE_BLOCK next to the parametrisation (v_param = 1 | DC_STEP_MODE_BLOCK); it
+ * announces a mode block in the caller's memory directly behind the struct, at sizeof(dc_ddpm_step_shared_params) (a multiple of 8):
+ *     int32_t mode, fstride;  float k1, k2, log_hi, log_lo;
+ * (the structs of this header are frozen: the layout is that of `struct { dc_ddpm_step_shared_params base; int32_t mode, fstride;
+ * float k1, k2, log_hi, log_lo; }`).  Without the flag nothing behind the struct is read.  mode = DC_STEP_FIXED: all of the above, the
+ * same kernel instance and bits, the other five block fields ignored; an unknown mode: DC_ERR_ARG.  DC_STEP_LEARNED_RANGE is the improved-DDPM step of a model that predicts its variance next to eps
+ * (diffusers' variance_type = "learned_range"; a published DiT): pred holds, per pixel, 2C features — eps in 0 .. C-1 and the variance
+ * interpolation v in C .. 2C-1 — at feature stride fstride: feature (py*p+px)*fstride + c for patch p > 1, p*ld + c for patch <= 1.
+ * Per element, in this order, no contraction:
+ *   pr  = one_plus_w * pc - w * pu                        (pc, pu: the eps features of rows 2b and 2b+1)
+ *   x   = v_param ? alpha_t * z - sigma_t * pr : (z - sigma_t * pr) / alpha_t                          (never clipped)
+ *   mu  = k1 * z + k2 * x                                 (dc_solver_step's first-order update: the same bits)
+ *   fr  = 0.5f * vc + 0.5f                                (vc: the CONDITIONAL row's feature at the same index + C; guidance mixes
+ *                                                          eps only, as diffusers' DiTPipeline steps the conditional half)
+ *   sde = expf(0.5f * (fr * log_hi + (1.f - fr) * log_lo))
+ *   out = noise ? mu + noise * sde : mu                   (no clip on the last pass; v is not clamped)
+ * with k1 = sqrt(abar_t / abar_s) (1 - abar_s) / (1 - abar_t), k2 = sqrt(abar_s) beta / (1 - abar_t), log_hi = log beta and
+ * log_lo = log of the posterior variance (1 - abar_s) / (1 - abar_t) beta, beta = 1 - abar_t / abar_s, formed by the caller.  alpha_s, c
+ * and sd are ignored.  fstride >= 2C and ld >= p*p*fstride (patch <= 1: ld >= 2C) or DC_ERR_SHAPE; log_hi and log_lo finite with
+ * log_lo <= log_hi <= 0 or DC_ERR_ARG.  dc_ddpm_step keeps its struct: the learned-range step of unshared noise is this entry with
+ * noise_div = 1. */
+#define DC_STEP_MODE_BLOCK 256
+#define DC_STEP_FIXED 0
+#define DC_STEP_LEARNED_RANGE 1
 typedef struct {
   const float* z; const float* pred; const float* noise; float* out;
   int32_t n, C, H, W, ld, patch, v_param;
@@ -675,7 +703,17 @@ int dc_solver_step(const dc_solver_step_params* p, dc_stream s);
  *   out = (x_next - mu) / sd
  * so that dc_ddpm_step on (z, pred) with noise = out gives mu + out * sd = x_next up to the rounding of the last two operations.  The
  * kernel equals the torch evaluation of the same expressions bit for bit for the same fp32 scalars.  out may be the buffer of x_next
- * (every thread reads its element before it writes it).  NULL pointers, or an sd that is not finite and > 0: DC_ERR_ARG. */
+ * (every thread reads its element before it writes it).  NULL pointers, or an sd that is not finite and > 0: DC_ERR_ARG.
+ *
+ * DC_STEP_MODE_BLOCK in `v_param`: dc_ddpm_step_shared's mode block (mode, fstride, k1, k2, log_hi, log_lo) behind THIS struct, at
+ * sizeof(dc_ddpm_noise_map_params); without the bit nothing behind the struct is read.  mode = DC_STEP_FIXED: all of the above, the same
+ * kernel instance and bits, the other five ignored; an unknown mode: DC_ERR_ARG.  DC_STEP_LEARNED_RANGE: the map of
+ * dc_ddpm_step_shared's learned-range step, in its layout (2C features per pixel at feature stride fstride) — pr, x (unclipped), mu = k1 * z + k2 * x, fr and sde exactly as written there, by the same
+ * device code, then
+ *   out = (x_next - mu) / sde
+ * so that the learned-range step on (z, pred) with noise = out lands on x_next up to the rounding of a division and a multiply-add on
+ * the same sde bits.  alpha_s, c and sd are ignored (sd is not checked); the requirements on fstride, ld, log_hi and log_lo and their
+ * codes are that entry's. */
 typedef struct {
   const float* z; const float* pred; const float* x_next; float* out;
   int32_t n, C, H, W, ld, patch, v_param;
